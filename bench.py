@@ -73,12 +73,35 @@ def parse_args(argv=None):
                     help="self-check of the launch path without a GPU: the ranks meet over gloo, sum their ranks, rank 0 prints a JSON line")
     ap.add_argument("--single-process-leg", type=int, default=0, metavar="N",
                     help="(internal) run ONLY the multi-device-context measurement over N devices and print its JSON")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image the last timed step produced to DIR/*.npy (float32; a fixed pixel sample above 48 MB)")
     ap.add_argument("--share-device", action="store_true",
                     help="single-process leg: all N shares on device 0 (one-GPU box rehearsal; peer-copy transport)")
     return ap.parse_args(argv)
 
 
 # ------------------------------------------------------------------------------------------------ self-launch -----
+DUMP_FULL_BYTES = 48 << 20      # a larger image is dumped as a fixed sample of pixels (the whole dump stays under 64 MB)
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_image(img, out_dir):
+    """img: the (H, W, 4) float32 frame a caller of dispatch_compute receives.  Whole as image.npy when small enough, else
+    DUMP_SAMPLE_PIXELS pixels drawn by a fixed seed (image_sample.npy, (n, 4) float32) and their flat indices y * W + x
+    (image_sample_pixels.npy, float64: exact).  Returns the file names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_FULL_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return ["image.npy"]
+    h, w = img.shape[:2]
+    idx = np.sort(np.random.default_rng(0).choice(h * w, size=min(DUMP_SAMPLE_PIXELS, h * w), replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(h * w, -1)[idx])
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
+    return ["image_sample.npy", "image_sample_pixels.npy"]
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -689,6 +712,8 @@ def main():
     fresh = not args.replay and not progressive
     sec, total_pixels = wl.run(args.steps, args.warmup, fresh)
     ms_per_step = sec * 1e3
+    # what the last timed step left in the image (run() has synchronised the device): copied now, before any later frame
+    last_image = wl.full.cpu().numpy() if (args.dump_outputs and wl.full is not None) else None
     samples_per_step = total_pixels * spp * args.passes
     value = samples_per_step / sec / 1e6
     frame_kernel_ms = Workload.mean_ms(wl.trace_events)
@@ -785,6 +810,9 @@ def main():
     if not args.no_single_process and not progressive:
         torch.cuda.synchronize()
         single = run_single_process_child(args, world)
+
+    if last_image is not None:
+        dump_image(last_image, args.dump_outputs)
 
     desc = wl.desc
     out = {

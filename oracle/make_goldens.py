@@ -4,6 +4,7 @@ $REF_DIR at run time) on Mesa llvmpipe through oracle/_ref/libglref.so.
 
 Run in the build container only (needs /root/reference and the swrast DRI driver):
     make -C oracle && python oracle/make_goldens.py
+    python oracle/make_goldens.py --live     (only the fixtures of the formerly live comparisons)
 Fixtures are data: scene parameters, camera uniforms and the RGBA32F image the reference wrote.
 Scenes are regenerated from their parameters by libtdthost.so (byte-identical everywhere; a
 sha256 of every payload is stored and re-checked by the tests).
@@ -229,7 +230,108 @@ def present():
     print("present:", out.shape, out2.shape, "distinct bytes", len(np.unique(out2)))
 
 
+# tests/test_reference_live.py, tests/test_octree_update.py and tests/test_ply_ingest.py: the reference's answers for the cases
+# those tests build themselves (fresh scenes, other cell counts, turned cameras, fresh presentation frames, a pile of edits, the
+# shader's work-group size and buffer layout, the reference's two PLY models), so that they run without the reference checkout
+LIVE_FRESH = [(0, 3, 11), (0, 4, 12), (1, 5, 13), (2, 6, 14)]
+LIVE_CELL_COUNTS = [(1, 5, 21, 100000), (2, 6, 22, 99999), (0, 7, 23, 100000), (1, 6, 24, 3000)]
+LIVE_CC_ORIGINS = (None, (0.0, 0.0, -0.5))
+LIVE_TURNED = [(0, (0.2, -0.1, 0.25), -17.0, 8.0, 60.0), (2, (0.62, 0.3, 0.7), 43.0, -20.0, 60.0), (1, (-0.7, 0.9, 0.6), -57.0, -40.0, 60.0)]
+LIVE_PRESENT_SHAPES = ((33, 70), (64, 64), (5, 257))
+LIVE_LAYOUT_NAMES = ["indirect_cells[0].value", "indirect_cells[0].type", "octree_floats[0].scale", "octree_floats[0].inv_scale",
+                     "octree_floats[0].inv_cell_count", "octree_ints[0].max_iter", "octree_ints[0].cell_count",
+                     "materials[0].albedo_index", "albedos[0].z"]
+
+
+def live_cc_camera(origin):
+    if origin is None:
+        return host.camera_reference_pose(96, 64, 2, 5)
+    return host.camera_build(90.0, 96, aspect_ratio=1.5, viewport_height=2.0, origin=origin, samples_per_pixel=2, max_bounce=5)
+
+
+def live_turned_camera(origin, yaw, pitch, fov):
+    c = host.Camera(fov, 96, aspect_ratio=1.5, viewport_height=2.0, origin=origin, samples_per_pixel=3, max_bounce=5)
+    c.turn_yaw(float(np.radians(yaw)) / 0.05)
+    c.turn_pitch(float(np.radians(pitch)) / 0.05)
+    return c.uniforms()
+
+
+def live_present_frames():
+    rng = np.random.default_rng(99)
+    frames = {}
+    for shape in LIVE_PRESENT_SHAPES:
+        img = rng.uniform(-0.2, 1.2, shape + (4,)).astype(np.float32)
+        img[rng.random(shape) < 0.05] = np.float32("nan")
+        frames[shape] = img
+    return frames
+
+
+def live_edit_deltas():
+    rng = np.random.default_rng(11)
+    out = []
+    for _ in range(6):
+        delta = np.zeros((1, 8), np.float32)
+        delta[0, :3] = rng.random(3)
+        delta[0, 3], delta[0, 4] = float(rng.integers(0, 3)), float(rng.integers(0, 4))
+        out.append(delta)
+    return out
+
+
+def live():
+    import ctypes
+    gl = oracle_py.GLRef.get()
+    arrays, meta = {}, {"renderer": gl.renderer()}
+    for kind, depth, seed in LIVE_FRESH:
+        scene = host.Scene.generate(kind, depth, 1 << 14, 100, seed)
+        arrays[f"fresh_{kind}_{depth}_{seed}"] = gl.render(scene, host.camera_reference_pose(96, 64, 2, 5))
+    for kind, depth, seed, cc in LIVE_CELL_COUNTS:
+        scene = host.scene_with_cell_count(host.Scene.generate(kind, depth, 1 << 20, 100, seed), cc, 1000)
+        for i, origin in enumerate(LIVE_CC_ORIGINS):
+            arrays[f"cc_{kind}_{depth}_{seed}_{cc}_{i}"] = gl.render(scene, live_cc_camera(origin))
+    for cfg, origin, yaw, pitch, fov in LIVE_TURNED:
+        arrays[f"turned_{cfg}"] = gl.render(host.Scene.config(cfg), live_turned_camera(origin, yaw, pitch, fov))
+    for (h, w), img in live_present_frames().items():
+        arrays[f"present_{h}x{w}"] = oracle_py.glref_present(img)
+    # six edits piled up on one tree: after each, the dwords that changed and the counter
+    scene = host.Scene.config(1)
+    scene.blobs[0] = np.concatenate([scene.blobs[0], np.zeros(16 * 32, np.uint32)])
+    counter, counters = 70, []
+    for i, delta in enumerate(live_edit_deltas()):
+        before = scene.blobs[0]
+        cells, counter = oracle_py.glref_octree_update(scene, delta, counter, (0, 1, 0))
+        changed = np.nonzero(cells != before)[0].astype(np.uint32)
+        arrays[f"edit_{i}_changed_index"], arrays[f"edit_{i}_changed_value"] = changed, cells[changed]
+        counters.append(counter)
+        scene.blobs[0] = cells
+    meta["edit_counters"] = counters
+    gl.program()
+    gs = (ctypes.c_int * 3)()
+    gl.L.glref_group_size(gs)
+    meta["group_size"] = list(gs)
+    layout = {}
+    for name in LIVE_LAYOUT_NAMES:
+        v = (ctypes.c_int * 2)()
+        assert gl.L.glref_buffer_variable(name.encode(), v) == 0, name
+        layout[name] = list(v)
+    meta["buffer_variables"] = layout                                     # [offset, array stride]
+    models = os.path.join(oracle_py.REF_DIR, "assets", "models")
+    meta["models_sha256"] = {f: hashlib.sha256(open(os.path.join(models, f), "rb").read()).hexdigest()
+                             for f in ("3x3x3_point.ply", "monu1_point.ply")}
+    os.makedirs(os.path.join(OUT, "live"), exist_ok=True)
+    np.savez_compressed(os.path.join(OUT, "live", "reference_live.npz"), meta=json.dumps(meta), **arrays)
+    print("reference_live:", len(arrays), "arrays")
+    # monu1_point.ply as data: its vertex lines (x y z red green blue) and the reference's render of the octree built from it
+    rows = np.loadtxt(os.path.join(models, "monu1_point.ply"), skiprows=11, dtype=np.int32, ndmin=2)
+    scene = host.Ply(open(os.path.join(models, "monu1_point.ply"), "rb").read(), strict_crlf=False).to_scene(max_iter=256)
+    np.savez_compressed(os.path.join(OUT, "live", "monu1_point.npz"), xyz=rows[:, :3].astype(np.int16), rgb=rows[:, 3:].astype(np.uint8),
+                        image=gl.render(scene, host.camera_reference_pose(128, 96, 2, 4)))
+    print("monu1_point:", rows.shape)
+
+
 if __name__ == "__main__":
+    if "--live" in sys.argv[1:]:
+        live()
+        sys.exit(0)
     main()
     if not any(a.startswith("--only=") for a in sys.argv[1:]):
         math_table()

@@ -25,13 +25,3 @@ def oracle():
     import oracle_py
     return oracle_py.Oracle()
 
-
-@pytest.fixture(scope="session")
-def glref():
-    import oracle_py
-    if not oracle_py.glref_available():
-        pytest.skip("reference checkout / llvmpipe harness not present (only in the build container)")
-    try:
-        return oracle_py.GLRef.get()
-    except Exception as e:  # llvmpipe missing
-        pytest.skip(f"llvmpipe unavailable: {e}")

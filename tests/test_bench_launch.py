@@ -31,6 +31,29 @@ def test_arguments_and_workloads():
     assert r == 80 + 48 + 28 + 16 + 40 and w == 64
 
 
+def test_dump_outputs_argument_and_files(tmp_path):
+    """--dump-outputs DIR: a frame up to 48 MB is written whole; a larger one as the same fixed pixel sample every time."""
+    import numpy as np
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    assert bench.parse_args([]).dump_outputs is None
+    small = np.random.default_rng(1).random((1080, 1920, 4), dtype=np.float32)
+    assert bench.dump_image(small, str(tmp_path / "a")) == ["image.npy"]
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and (got.view(np.uint32) == small.view(np.uint32)).all()
+    big = np.arange(2160 * 3840 * 4, dtype=np.float32).reshape(2160, 3840, 4)
+    for d in ("b", "c"):
+        assert bench.dump_image(big, str(tmp_path / d)) == ["image_sample.npy", "image_sample_pixels.npy"]
+    total = 0
+    for name in ("image_sample.npy", "image_sample_pixels.npy"):
+        b, c = np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name)
+        assert b.dtype in (np.float32, np.float64) and np.array_equal(b, c)
+        total += os.path.getsize(tmp_path / "b" / name)
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "b" / "image_sample_pixels.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE_PIXELS and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "image_sample.npy"), big.reshape(-1, 4)[idx])
+
+
 def test_self_launch_spawns_ranks_that_meet():
     """The driver's shape of command: no torchrun, --gpus 3 — three child processes rendezvous over gloo on 127.0.0.1."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -106,3 +129,33 @@ def test_bench_gpus_2_self_launched_on_one_gpu():
     sp = j["single_process"]
     assert "error" not in sp, sp
     assert sp["devices"] == [0, 0] and sp["written_pixels"] == 7680 * 4320 and sp["transport"] == "copy" and sp["rccl_ranks"] == 0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_frame(tmp_path, oracle):
+    """`--steps 3 --dump-outputs DIR`: three timed steps, and DIR/image.npy is the frame the hot path rendered — bit for bit the
+    oracle's on bands of rows — and the same frame from a second run."""
+    import numpy as np
+    from tdt4230_project_raytracing_amd import host
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    quick = ["--gpus", "1", "--warmup", "1", "--spp", "2", "--no-cpu-baseline", "--no-strong", "--no-target",
+             "--no-reference-default", "--no-single-process"]
+    imgs = []
+    for steps, d in ((3, "a"), (1, "b")):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--dump-outputs", str(tmp_path / d)]
+                           + quick, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        imgs.append(np.load(tmp_path / d / "image.npy"))
+    a, b = imgs
+    assert a.shape == (1080, 1920, 4) and a.dtype == np.float32
+    assert (a.view(np.uint32) == b.view(np.uint32)).all()
+    W, H, _, bounce, _, scene_cfg = bench.WORKLOADS[2]
+    scene, cam = host.Scene.config(scene_cfg), host.camera_reference_pose(W, H, 2, bounce)
+    want = np.zeros_like(a)
+    for y0 in (0, 512, 1048):
+        oracle.render(scene, cam, (W + 1, H + 1), rows=(y0, y0 + 8), threads=8, image=want)
+        assert (a[y0:y0 + 8].view(np.uint32) == want[y0:y0 + 8].view(np.uint32)).all(), y0

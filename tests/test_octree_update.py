@@ -46,19 +46,21 @@ def test_oracle_edit_equals_reference(oracle, name):
     assert (img.view(np.uint32) == z["image"].view(np.uint32)).all()        # the trace on the edited tree
 
 
-def test_oracle_edit_vs_reference_shader_live(oracle, glref):
-    rng = np.random.default_rng(11)
+def test_oracle_edit_vs_reference_shader_live(oracle):
+    """Six edits piled up on one tree, against what the reference shader did to it (tests/golden/live/reference_live.npz, recorded on
+    llvmpipe by oracle/make_goldens.py --live: after every edit, the dwords that changed and the atomic counter)."""
+    import make_goldens as mg
+    z = np.load(os.path.join(GOLDEN, "live", "reference_live.npz"))
+    counters = json.loads(str(z["meta"]))["edit_counters"]
     scene = host.Scene.config(1)
     scene.blobs[0] = np.concatenate([scene.blobs[0], np.zeros(16 * 32, np.uint32)])
     counter = 70
-    for _ in range(6):                                                        # edits pile up on one tree
-        delta = np.zeros((1, 8), np.float32)
-        delta[0, :3] = rng.random(3)
-        delta[0, 3], delta[0, 4] = float(rng.integers(0, 3)), float(rng.integers(0, 4))
-        ref = oracle_py.glref_octree_update(scene, delta, counter, (0, 1, 0))
+    for i, delta in enumerate(mg.live_edit_deltas()):                        # edits pile up on one tree
+        ref = scene.blobs[0].copy()
+        ref[z[f"edit_{i}_changed_index"]] = z[f"edit_{i}_changed_value"]
         got = oracle_py.oracle_octree_update(oracle, scene, delta, counter, (0, 1, 0))
-        assert got[1] == ref[1] and np.array_equal(got[0], ref[0])
-        scene.blobs[0], counter = ref
+        assert got[1] == counters[i] and np.array_equal(got[0], ref)
+        scene.blobs[0], counter = ref, counters[i]
 
 
 @pytest.mark.gpu

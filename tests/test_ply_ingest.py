@@ -1,6 +1,9 @@
 """Next row §8f-1: the PLY point loader (ply_point_loader.rs:102-319) restated, and the octree build
 the reference never wrote.  PARITY UNPINNED for the loader (no Rust toolchain to run it): expected
-values below are derived by hand from the reference source for its own 3x3x3 model."""
+values below are derived by hand from the reference source for its own 3x3x3 model.  The reference's two model files are pinned
+by their SHA-256 and its render of the large one, both recorded by oracle/make_goldens.py --live (tests/golden/live/)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -8,7 +11,14 @@ import pytest
 
 from tdt4230_project_raytracing_amd import host
 
-REF_MODELS = os.path.join(os.environ.get("REF_DIR", "/root/reference"), "assets", "models")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def model_sha256(name):
+    z = np.load(os.path.join(GOLDEN, "live", "reference_live.npz"))
+    return json.loads(str(z["meta"]))["models_sha256"][name]
+
+
 HEADER = ["ply", "format ascii 1.0", "comment : MagicaVoxel @ Ephtracy", "element vertex {n}", "property float x",
           "property float y", "property float z", "property uchar red", "property uchar green", "property uchar blue",
           "end_header"]
@@ -23,10 +33,7 @@ def cube_edges_ply(eol):
 
 
 def test_regenerated_model_is_the_reference_file():
-    path = os.path.join(REF_MODELS, "3x3x3_point.ply")
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    assert open(path, "rb").read() == cube_edges_ply("\n")[0]
+    assert hashlib.sha256(cube_edges_ply("\n")[0]).hexdigest() == model_sha256("3x3x3_point.ply")
 
 
 def test_loader_content():
@@ -86,18 +93,25 @@ def test_octree_from_ply(oracle):
     assert (img[..., 3] == 1).all() and (img[..., :3] != img[0, 0, :3]).any()    # the model is in view
 
 
-def test_reference_monument_model(oracle, glref):
+def monument_ply():
+    """The reference's assets/models/monu1_point.ply rebuilt from its vertex lines (tests/golden/live/monu1_point.npz) under the
+    header of the 3x3x3 model; the render the reference shader made of it rides along."""
+    z = np.load(os.path.join(GOLDEN, "live", "monu1_point.npz"))
+    xyz, rgb = z["xyz"], z["rgb"]
+    lines = [h.format(n=len(xyz)) for h in HEADER] + [f"{x} {y} {z_} {r} {g} {b}" for (x, y, z_), (r, g, b) in zip(xyz.tolist(), rgb.tolist())]
+    return ("\n".join(lines) + "\n").encode(), z["image"]
+
+
+def test_reference_monument_model(oracle):
     """The reference's large model (156 942 voxels): parsed, built, and the resulting octree rendered
     identically by the reference shader and the oracle."""
-    path = os.path.join(REF_MODELS, "monu1_point.ply")
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    p = host.Ply(open(path, "rb").read(), strict_crlf=False)
+    data, ref = monument_ply()
+    assert hashlib.sha256(data).hexdigest() == model_sha256("monu1_point.ply")
+    p = host.Ply(data, strict_crlf=False)
     assert p.header_vertex == 156942 and len(p.positions) == 156942
     assert p.min_point == [-29, -52, 0]
     scene = p.to_scene(max_iter=256)
     assert scene.max_depth == 7 and scene.counts["voxels"] == 156942 and scene.counts["materials"] == 8
     cam = host.camera_reference_pose(128, 96, 2, 4)
-    ref = glref.render(scene, cam)
     got = oracle.render(scene, cam, threads=8)
     assert (got.view(np.uint32) == ref.view(np.uint32)).all()
