@@ -175,6 +175,14 @@ class ComputeShader {
     ctx_->check(tdt_dispatch_compute(program.id(), width, height, depth));
   }
   const int *group_size() const { return group_size_; }
+  // NEW (the reference has no ray query): what the primary ray of each pixel (x, y) and sample `sample` hits first, traced from
+  // this program's camera uniforms with the bits the renderer traces (tdt_pick_pixels); `rays` (may be null) receives the rays
+  std::vector<tdt_ray_hit> pick(const std::vector<std::array<int32_t, 2>> &xy, int sample = 0, std::vector<float> *rays = nullptr) const {
+    std::vector<tdt_ray_hit> out(xy.size());
+    if (rays) rays->assign(xy.size() * 6, 0.0f);
+    ctx_->check(tdt_pick_pixels(program.id(), xy.empty() ? nullptr : xy[0].data(), xy.size(), sample, rays ? rays->data() : nullptr, out.data()));
+    return out;
+  }
  private:
   Context *ctx_ = nullptr;
   int group_size_[3] = {0, 0, 0};
@@ -220,6 +228,26 @@ class Octree {
     else update_compute.dispatch_compute(dispatch_count, 1, 1);
   }
   const VertexBufferObject &counter() const { return counter_; }
+  // NEW: rays {origin, direction} (6 floats each, normalised directions) through the bound octree (tdt_raycast)
+  std::vector<tdt_ray_hit> raycast(const Context &ctx, const std::vector<float> &rays) const {
+    std::vector<tdt_ray_hit> out(rays.size() / 6);
+    ctx.check(tdt_raycast(ctx.raw(), rays.data(), out.size(), out.data()));
+    return out;
+  }
+  // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
+  // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
+  // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.
+  bool click(const ComputeShader &raytracer, int x, int y, bool place, float material, const ComputeShader &update_compute,
+             tdt_ray_hit *hit = nullptr) const {
+    const tdt_ray_hit h = raytracer.pick({{{x, y}}}, 0)[0];
+    if (hit) *hit = h;
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    std::vector<float> delta(8, 0.0f);
+    if (tdt_pick_edit_delta(&h, floats, ints, place ? 1 : 0, material, delta.data()) != 0) return false;    // miss / stale record / outside
+    update_vbo(delta, 5, update_compute);
+    return true;
+  }
  private:
   Vector3f min_point_{};
   float scale_ = 1, block_distance_ = 0;

@@ -151,6 +151,19 @@ int64_t tdt_ply_albedos(const tdt_ply *p, uint32_t *keys, uint8_t *rgb, int64_t 
  * the far (z = 0) side of the octree so that the reference camera (main.rs:165-168) looks at it. */
 int tdt_scene_from_ply(const tdt_ply *p, int max_iter, int z_up, tdt_scene **out);
 
+/* ---------------------------------------------------------------- pick-to-edit --------------- */
+/* The DeltaNode (8 floats: the 32-byte std430 stride of octree_update.comp:41-48) for a click on the voxel face a ray query found
+ * (tdt_ray_hit, include/tdt_rt.h) — what the reference's click handler (main.rs:551-568) hands Octree::update_vbo, aimed at the
+ * face under the cursor instead of a point at a fixed distance.  place = 1: ClickEvent::Left, type 2.0 (LEAF); place = 0:
+ * ClickEvent::Right, type 0.0 (EMPTY); value = the active material.  Position: the centre, in unit octree coordinates, of the
+ * finest-level cell (2^-max_depth) just outside (place) or just inside (remove) the hit face,
+ *     snap((point - min_point) / scale +- normal * 0.5 * 2^-max_depth).
+ * octree_floats / octree_ints: the payloads of slots 6 / 7.  Returns 0, or TDT_ERR_INVALID_VALUE (0x0501) when status is not
+ * TDT_RAY_HIT, fresh_record == 0, or the position falls outside [0,1)^3 (octree.rs:165-168) — message in tdt_host_last_error. */
+typedef struct tdt_ray_hit tdt_ray_hit;
+int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, float value,
+                        float delta_out[8]);
+
 #ifdef __cplusplus
 }
 #endif

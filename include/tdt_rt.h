@@ -243,6 +243,45 @@ int tdt_octree_build_from_points(tdt_ctx *ctx, const int32_t *voxels_xyzk, size_
 int tdt_debug_edit_mode(tdt_ctx *ctx, int mode);
 /* which path the last edit dispatch of the context took: 0 none yet, 1 ordered walk, 2 parallel.  Synchronises. */
 int tdt_debug_last_edit_path(tdt_ctx *ctx);
+/* ---- ray queries ------------------------------------------------------------------------------------------------------
+ * "What is under this pixel?": one query ray per lane through OctreeHit (raytracer.comp:397-450) exactly as the trace runs
+ * it for a fresh invocation (zeroed loop-carried temporaries): root slab test with t_min = 0.0003, t_max = +inf, the
+ * restart-from-root loop with its `adv` step, the in-octree test, the literal treeLookup, the padded empty-cell exit, and
+ * the i > 0 leaf slab test — a pick answers with the bits the renderer traces for that pixel and sample.  Reads slots 0, 6
+ * and 7 only; the image, the cost history, the hand-out order and the frame carry are left as they were.  Directions are
+ * used as given: the shader's step `adv` is in units of t, so pass normalised directions.  A multi-device context answers
+ * from device_ids[0] (device pointers must live there).  n == 0 is a no-op; NULL pointers with n > 0:
+ * TDT_ERR_INVALID_VALUE; slots 0 / 6 / 7 unbound: TDT_ERR_INCOMPLETE. */
+enum { TDT_RAY_MISS = 0, TDT_RAY_HIT = 1, TDT_RAY_ITER_LIMIT = 2 /* max_iter ran out inside the octree */ };
+typedef struct tdt_ray_hit {
+  int32_t  status;        /* TDT_RAY_MISS / TDT_RAY_HIT / TDT_RAY_ITER_LIMIT */
+  uint32_t material;      /* leaf Node.value: index into slot 1 (hit only) */
+  float    t;             /* t_enter of the CubeHit call whose record is returned (the root call site's when found on
+                             iteration 0); 0 when that record is a zeroed temporary */
+  int32_t  iterations;    /* OctreeHit loop iterations that reached treeLookup */
+  float    point[3];      /* hit.point exactly as OctreeHit hands it back */
+  float    normal[3];     /* hit.normal (oriented against the ray) */
+  int32_t  front_face;
+  int32_t  fresh_record;  /* 0: the call site's slab test missed, point / normal / front_face are the zeroed temporaries
+                             a fresh invocation hands back (raytracer.comp:426-433) */
+  float    cell_min[3];   /* leaf cube's lower corner, the shader's own expression grid_uv * scale + min_point */
+  float    cell_size;     /* scale * inv_pow_depth */
+} tdt_ray_hit;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_ray_hit) == 64, "tdt_ray_hit is 64 bytes");
+#else
+_Static_assert(sizeof(tdt_ray_hit) == 64, "tdt_ray_hit is 64 bytes");
+#endif
+/* rays: n x {ox, oy, oz, dx, dy, dz} in host memory; synchronous (finishes the context's stream). */
+int tdt_raycast(tdt_ctx *ctx, const float *rays, size_t n, tdt_ray_hit *out);
+/* the same over device memory (n x 6 floats in, 4-byte aligned; n tdt_ray_hit out, 16-byte aligned), asynchronous on the
+ * context's stream */
+int tdt_raycast_device(tdt_ctx *ctx, const void *rays_dev, size_t n, void *hits_dev);
+/* the primary ray of pixel (x, y) (xy: n pairs, non-negative), sample `sample` >= 0, from the program's camera uniforms
+ * (raytracer.comp:240-245), traced as above; rays_out (n x 6 floats, may be NULL) receives the rays themselves.  Synchronous.
+ * A TDT_PROGRAM_OCTREE_UPDATE program: TDT_ERR_INVALID_OPERATION. */
+int tdt_pick_pixels(tdt_compute *c, const int32_t *xy, size_t n, int sample, float *rays_out, tdt_ray_hit *out);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -9,6 +9,9 @@
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
 //   w a s d = translate Front / Left / Back / Rigth, u j = Up / Down, q e = turn_yaw(-/+ 1), r f = turn_pitch(-/+ 1),
 //   S / N = sprint / normal speed.  --png writes the frame as the quad pass would present it (main.rs:582-600).
+// --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
+//   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
+//   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +26,8 @@ int main(int argc, char **argv) {
   int W = 1280, H = 720, spp = 4, bounce = 6, device = 0;
   std::string out, png, settings_path, moves;
   std::vector<float> edit;
+  int pick_x = -1, pick_y = -1, material = 1;
+  bool place = true;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -35,6 +40,9 @@ int main(int argc, char **argv) {
     else if (a == "--settings") settings_path = next();
     else if (a == "--move") moves = next();
     else if (a == "--edit") { float v[5]; if (std::sscanf(next(), "%f,%f,%f,%f,%f", v, v + 1, v + 2, v + 3, v + 4) != 5) { std::fprintf(stderr, "--edit x,y,z,type,value\n"); return 2; } edit.assign(v, v + 5); }
+    else if (a == "--pick") { if (std::sscanf(next(), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
+    else if (a == "--click") { const std::string v = next(); if (v != "left" && v != "right") { std::fprintf(stderr, "--click left|right\n"); return 2; } place = v == "left"; }
+    else if (a == "--material") material = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   try {
@@ -100,6 +108,13 @@ int main(int argc, char **argv) {
       std::vector<float> delta(500, 0.0f);
       std::copy(edit.begin(), edit.end(), delta.begin());
       octree.update_vbo(delta, 5, octree_update_program);
+    }
+    if (pick_x >= 0) {                                                                   // main.rs:551-568, aimed at the pixel
+      tdt_ray_hit h;
+      const bool edited = octree.click(raytrace_program, pick_x, pick_y, place, (float)material, octree_update_program, &h);
+      std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
+                  pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
+                  h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
     }
     // main.rs:578-580
     octree.vao.bind();

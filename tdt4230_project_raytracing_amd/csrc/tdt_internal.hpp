@@ -23,6 +23,7 @@ struct CostSig {
 };
 
 namespace tdt { struct Multi; struct EditScratch; }
+struct TraceParams;
 
 struct tdt_buffer {
   tdt_ctx *ctx;
@@ -89,6 +90,7 @@ struct tdt_ctx {
   bool no_specialise;   // TDT_NO_SPECIALISE=1: never pick a scene-specialised kernel (A/B testing)
   tdt::Multi *multi;            // non-null: this is a multi-device context (tdt_ctx_create_multi); see tdt_multi.hip
   tdt::EditScratch *edit;       // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
+  void *query; size_t query_bytes;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
   std::vector<tdt_buffer *> buffers;
   std::vector<tdt_image *> images;
   std::vector<tdt_compute *> computes;
@@ -125,6 +127,9 @@ Tiles tiles_of(const tdt_compute *c, const Cover &k);
 // 16 bytes of slack zeroed, and belongs to the buffer from here on (tdt_rt.hip)
 int adopt_device_buffer(tdt_ctx *ctx, void *dev, size_t bytes, tdt_buffer **out);
 
+// OctreeFloats / OctreeInts from the shadows of the buffers bound to slots 6 / 7 (both must be bound) into P
+int octree_uniforms(tdt_ctx *ctx, TraceParams &P);
+
 // ---- tdt_multi.hip: every public entry point forwards here when the handle belongs to a multi-device context ----
 void multi_destroy(tdt_ctx *ctx);
 int multi_finish(tdt_ctx *ctx);
@@ -148,5 +153,8 @@ tdt_ctx *multi_first_member(tdt_ctx *front);
 // ---- tdt_edit.hip ----
 int launch_update(tdt_compute *c, int width, int height, int depth);
 void edit_scratch_destroy(tdt_ctx *ctx);
+
+// ---- tdt_query.hip ----
+void query_scratch_destroy(tdt_ctx *ctx);
 
 }  // namespace tdt

@@ -1339,6 +1339,21 @@ TraceFn find_variant(int form, int depth, bool resident, bool full, bool brick, 
   return nullptr;
 }
 
+}  // namespace
+
+// OctreeFloats / OctreeInts (slots 6 / 7) as the dispatch sees them: read from the host shadows of the bound buffers
+int tdt::octree_uniforms(tdt_ctx *ctx, TraceParams &P) {
+  if (ctx->ssbo[TDT_SLOT_OCTREE_FLOATS]->bytes < 28 || ctx->ssbo[TDT_SLOT_OCTREE_INTS]->bytes < 12)
+    return fail(ctx, TDT_ERR_INVALID_VALUE, "octree uniform buffers are too small (need 28 / 12 bytes)");
+  float of[7]; int32_t oi[3];
+  std::memcpy(of, ctx->ssbo[TDT_SLOT_OCTREE_FLOATS]->shadow, sizeof of);
+  std::memcpy(oi, ctx->ssbo[TDT_SLOT_OCTREE_INTS]->shadow, sizeof oi);
+  P.min_x = of[0]; P.min_y = of[1]; P.min_z = of[2]; P.scale = of[4]; P.inv_scale = of[5]; P.inv_cell_count = of[6];
+  P.max_depth = oi[0]; P.max_iter = oi[1]; P.cell_count = oi[2];
+  return TDT_OK;
+}
+
+namespace {
 int launch(tdt_compute *c, int width, int height, int depth, int mode, int spp_begin, int spp_count, void *carry,
            int total_spp, unsigned long long *counts_out) {
   tdt_ctx *ctx = c->ctx;
@@ -1348,22 +1363,16 @@ int launch(tdt_compute *c, int width, int height, int depth, int mode, int spp_b
   for (int s : required)
     if (!ctx->ssbo[s]) return fail(ctx, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot " + std::to_string(s));
   if (!ctx->image0) return fail(ctx, TDT_ERR_INCOMPLETE, "no image bound to unit 0");
-  if (ctx->ssbo[TDT_SLOT_OCTREE_FLOATS]->bytes < 28 || ctx->ssbo[TDT_SLOT_OCTREE_INTS]->bytes < 12)
-    return fail(ctx, TDT_ERR_INVALID_VALUE, "octree uniform buffers are too small (need 28 / 12 bytes)");
   tdt_image *img = ctx->image0;
 
   TraceParams P;
   std::memset(&P, 0, sizeof P);
+  if (int rc = tdt::octree_uniforms(ctx, P)) return rc;
   P.image_width = c->image_width; P.image_height = c->image_height;
   for (int i = 0; i < 3; i++) {
     P.hor[i] = c->horizontal[i]; P.ver[i] = c->vertical[i]; P.llc[i] = c->lower_left_corner[i]; P.org[i] = c->origin[i];
   }
   P.samples_per_pixel = c->samples_per_pixel; P.max_bounce = c->max_bounce;
-  float of[7]; int32_t oi[3];
-  std::memcpy(of, ctx->ssbo[TDT_SLOT_OCTREE_FLOATS]->shadow, sizeof of);
-  std::memcpy(oi, ctx->ssbo[TDT_SLOT_OCTREE_INTS]->shadow, sizeof oi);
-  P.min_x = of[0]; P.min_y = of[1]; P.min_z = of[2]; P.scale = of[4]; P.inv_scale = of[5]; P.inv_cell_count = of[6];
-  P.max_depth = oi[0]; P.max_iter = oi[1]; P.cell_count = oi[2];
   auto dwords = [](const tdt_buffer *b) { size_t d = b->bytes >> 2; return (uint32_t)(d > 0xFFFFFFFFull ? 0xFFFFFFFFull : d); };
   P.cells = (const uint32_t *)ctx->ssbo[TDT_SLOT_CELLS]->dev; P.cells_dwords = dwords(ctx->ssbo[TDT_SLOT_CELLS]);
   P.materials = (const uint32_t *)ctx->ssbo[TDT_SLOT_MATERIALS]->dev; P.materials_dwords = dwords(ctx->ssbo[TDT_SLOT_MATERIALS]);
@@ -1803,6 +1812,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   if (ctx->bricks) (void)hipFree(ctx->bricks);
   if (ctx->phase_timing) for (auto &e : ctx->phase_ev) (void)hipEventDestroy(e);
   tdt::edit_scratch_destroy(ctx);
+  tdt::query_scratch_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

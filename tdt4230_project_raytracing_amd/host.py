@@ -266,6 +266,26 @@ class Scene:
         return sum(a.nbytes for a in self.blobs.values())
 
 
+def pick_edit_delta(hit, scene, place, value):
+    """tdt_pick_edit_delta: the 8-float DeltaNode {pos, type, value, padding} for a click on the face `hit` found (one record of
+    rt.RAY_HIT_DTYPE); place = 1 puts a LEAF of material `value` in the finest cell in front of the face, 0 empties the one
+    behind it.  `scene`: a Scene (its slot 6 / 7 payloads) or a (floats[7], ints[3]) pair.  Raises ValueError when the hit
+    cannot be edited at (miss, stale record, position outside the octree)."""
+    L = lib()
+    L.tdt_pick_edit_delta.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
+    rec = np.ascontiguousarray(np.asarray(hit).reshape(-1)[:1])
+    if rec.dtype.itemsize != 64:
+        raise TypeError("hit must be a tdt_ray_hit record (rt.RAY_HIT_DTYPE)")
+    floats, ints = (scene.blobs[6], scene.blobs[7]) if isinstance(scene, Scene) else scene
+    of = np.ascontiguousarray(np.asarray(floats).view(np.float32).reshape(-1)[:7], np.float32)
+    oi = np.ascontiguousarray(np.asarray(ints).view(np.int32).reshape(-1)[:3], np.int32)
+    out = np.zeros(8, np.float32)
+    rc = L.tdt_pick_edit_delta(rec.ctypes.data, of.ctypes.data, oi.ctypes.data, int(place), float(value), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return out
+
+
 def scene_with_cell_count(scene, cell_count, zero_tail_nodes=0):
     """The same tree as a host with other conventions uploads it: Octree::init_global_buffers writes floats[6] = 1.0 / cell_count as
     f32 and ints[2] = cell_count (octree.rs:49, 79) — the reference's main.rs passes 100000 — and a pre-allocated cells buffer ends in

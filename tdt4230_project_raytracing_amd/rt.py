@@ -23,6 +23,21 @@ ERR_INVALID_ENUM, ERR_INVALID_VALUE, ERR_INVALID_OPERATION = 0x0500, 0x0501, 0x0
 PROGRAM_RAYTRACER, PROGRAM_OCTREE_UPDATE = 0, 1
 SHADER_STORAGE_BUFFER, ATOMIC_COUNTER_BUFFER = 0x90D2, 0x92C0
 
+RAY_MISS, RAY_HIT, RAY_ITER_LIMIT = 0, 1, 2
+# tdt_ray_hit (include/tdt_rt.h), field for field
+RAY_HIT_DTYPE = np.dtype([("status", "<i4"), ("material", "<u4"), ("t", "<f4"), ("iterations", "<i4"),
+                          ("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("front_face", "<i4"), ("fresh_record", "<i4"),
+                          ("cell_min", "<f4", (3,)), ("cell_size", "<f4")])
+assert RAY_HIT_DTYPE.itemsize == 64
+
+
+def hits_from_bytes(b):
+    """(n, 64) uint8 (numpy, or a torch tensor on any device) -> numpy array of RAY_HIT_DTYPE, shape (n,)."""
+    if hasattr(b, "detach"):
+        b = b.detach().cpu().numpy()
+    return np.ascontiguousarray(b, np.uint8).reshape(-1, 64).view(RAY_HIT_DTYPE).reshape(-1)
+
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -80,6 +95,9 @@ SYMBOLS = [
     ("tdt_debug_stats", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _I, _I]),
     ("tdt_debug_wave_ends", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _I]),
     ("tdt_debug_pixel_log", _I, [_P, ctypes.c_void_p, ctypes.c_size_t]),
+    ("tdt_raycast", _I, [_P, _P, _S, _P]),
+    ("tdt_raycast_device", _I, [_P, _P, _S, _P]),
+    ("tdt_pick_pixels", _I, [_P, _P, _S, _I, _P, _P]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -185,6 +203,24 @@ class Context:
 
     def finish(self):
         self.check(lib().tdt_finish(self.h))
+
+    def raycast(self, rays):
+        """tdt_raycast: (n, 6) rays {origin, direction} (normalised directions: the traversal step is in units of t) through the
+        bound octree (slots 0, 6, 7).  A numpy array -> numpy array of RAY_HIT_DTYPE; a torch tensor on the GPU (float32, (n, 6),
+        on the context's first device) -> a (n, 64) uint8 tensor on that device (tdt_raycast_device; hits_from_bytes reads
+        it), after torch's pending work on the device and the query have finished."""
+        if hasattr(rays, "data_ptr") and getattr(rays, "is_cuda", False):
+            import torch
+            r = rays.detach().to(torch.float32).contiguous().reshape(-1, 6)
+            out = torch.empty((r.shape[0], 64), dtype=torch.uint8, device=r.device)
+            torch.cuda.synchronize(r.device)
+            self.check(lib().tdt_raycast_device(self.h, ctypes.c_void_p(r.data_ptr()), r.shape[0], ctypes.c_void_p(out.data_ptr())))
+            self.finish()
+            return out
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros(r.shape[0], RAY_HIT_DTYPE)
+        self.check(lib().tdt_raycast(self.h, r.ctypes.data, r.shape[0], out.ctypes.data))
+        return out
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
@@ -343,6 +379,16 @@ class ComputeShader:
     def dispatch_compute(self, width, height, depth):
         self.ctx.check(lib().tdt_dispatch_compute(self.h, width, height, depth))
 
+    def pick(self, xy, sample=0, return_rays=False):
+        """tdt_pick_pixels: what the primary ray of each pixel (x, y) — texture coordinates, row 0 at the bottom — and sample
+        `sample` hits first, from this program's camera uniforms: numpy array of RAY_HIT_DTYPE (and the (n, 6) rays)."""
+        p = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        out = np.zeros(p.shape[0], RAY_HIT_DTYPE)
+        rays = np.zeros((p.shape[0], 6), np.float32) if return_rays else None
+        self.ctx.check(lib().tdt_pick_pixels(self.h, p.ctypes.data, p.shape[0], int(sample),
+                                             rays.ctypes.data if return_rays else None, out.ctypes.data))
+        return (out, rays) if return_rays else out
+
     # --- extensions (no reference counterpart) ---
     def set_partition(self, rank, world):
         self.ctx.check(lib().tdt_set_partition(self.h, rank, world))
@@ -498,6 +544,10 @@ class Renderer:
     def render(self, width=None, height=None):
         self.dispatch(width, height)
         return self.texture.read()
+
+    def pick(self, xy, sample=0, return_rays=False):
+        """ComputeShader.pick with this renderer's camera: what is under each pixel."""
+        return self.shader.pick(xy, sample, return_rays)
 
     def close(self):
         self.ctx.close()

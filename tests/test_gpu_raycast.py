@@ -1,0 +1,444 @@
+"""Ray queries on the GPU (csrc/tdt_query.hip): a pick returns what the renderer's primary ray of that pixel and sample hits
+first — bit for bit the oracle's first hit —, random rays find the voxel a float64 brute-force search finds, the device
+form agrees with the host form, pick-to-edit round-trips through the edit program, and queries leave render state alone."""
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from octree_util import expand_cells
+from oracle_py import oracle_octree_update
+from tdt4230_project_raytracing_amd import build, host, rt
+
+pytestmark = pytest.mark.gpu
+
+W, H = 64, 48
+POSES = [                                            # (origin, yaw, pitch, fov): outside and inside the octrees
+    ((0.0, 0.2, 0.9), 0.0, -8.0, 90.0),
+    ((1.3, 1.0, 0.7), -48.0, -28.0, 40.0),
+    ((-0.5005, 0.1, 0.4), 1.5, 0.0, 90.0),
+    ((0.0, -0.1, -0.3), 0.0, 0.0, 90.0),
+    ((0.1, 0.05, -0.6), 135.0, 10.0, 70.0),
+]
+
+
+def _cam(origin, yaw, pitch, fov, w=W, h=H, spp=4, bounce=1):
+    c = host.Camera(fov, w, aspect_ratio=np.float32(w) / np.float32(h), origin=origin, viewport_height=2.0, samples_per_pixel=spp,
+                    max_bounce=bounce)
+    if yaw:
+        c.turn_yaw(yaw)
+    if pitch:
+        c.turn_pitch(pitch)
+    return c.uniforms()
+
+
+def _lambertian(scene):
+    """Every material Lambertian with its own albedo (blue 0.25: never the sky's 1.0)."""
+    n = len(scene.blobs[1]) // 3
+    mats = np.zeros((n, 3), np.uint32)
+    mats[:, 2] = np.arange(n)
+    i = np.arange(n, dtype=np.float32)
+    alb = np.stack([(i + 1) / np.float32(n + 2), np.float32(1) - (i + 1) / np.float32(n + 3), np.full(n, 0.25, np.float32)], 1)
+    blobs = dict(scene.blobs)
+    blobs[1] = mats.reshape(-1)
+    blobs[2] = alb.astype(np.float32).reshape(-1)
+    return host.Scene(blobs, name=scene.name + "_lamb"), alb.astype(np.float32)
+
+
+def _scenes():
+    return [host.Scene.demo()] + [host.Scene.config(i) for i in range(4)] + [host.Scene.generate(host.SCENE_TERRAIN, 8, 1 << 20, 100, 0x9A1C4)]
+
+
+def _sky(dy):
+    yp = (dy + np.float32(1.0)).astype(np.float32)
+    w = (np.float32(1.0) + -(np.float32(0.5) * yp)).astype(np.float32)
+    return np.stack([w + np.float32(0.25) * yp, w + np.float32(0.35) * yp, np.ones_like(w)], -1).astype(np.float32)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.parametrize("si", range(6))
+def test_pick_is_the_reference_first_hit(oracle, si):
+    scene, alb = _lambertian(_scenes()[si])
+    xy = np.stack(np.meshgrid(np.arange(W), np.arange(H)), -1).reshape(-1, 2).astype(np.int32)     # row-major: y outer, x inner
+    hits_seen = 0
+    for pose in POSES:
+        cam = _cam(*pose)
+        r = rt.Renderer(scene, cam)
+        try:
+            for s in (0, 3):
+                hits, rays = r.pick(xy, sample=s, return_rays=True)
+                again = r.ctx.raycast(rays)                          # the same rays through tdt_raycast: the same bytes
+                assert again.tobytes() == hits.tobytes()
+                accum = np.zeros((H, W, 4), np.float32)
+                carry = np.zeros((H, W, 16), np.float32)
+                oracle.accumulate(scene, cam, accum, carry, s, 1, dispatch=(W, 2 * H))    # (covers the whole 64 x 48)
+                hits = hits.reshape(H, W)
+                col = accum[..., :3]
+                hit = hits["status"] == rt.RAY_HIT
+                hits_seen += int(hit.sum())
+                assert not (hits["status"] > rt.RAY_ITER_LIMIT).any()
+                mat = np.where(hit, hits["material"], 0)
+                assert (_bits(col[hit]) == _bits(alb[mat[hit]])).all()
+                sky = _sky(rays[:, 4].reshape(H, W))
+                assert (_bits(col[~hit]) == _bits(sky[~hit])).all()
+                root = hit & (hits["iterations"] == 1)
+                leaf = hit & (hits["iterations"] > 1)
+                cv = carry.view(np.uint32)
+                for sel, n_off, ff_off, p_off in ((root, 0, 3, 4), (leaf, 8, 11, 12)):
+                    assert (_bits(hits["normal"][sel]) == cv[sel][:, n_off:n_off + 3]).all()
+                    assert (_bits(hits["point"][sel]) == cv[sel][:, p_off:p_off + 3]).all()
+                    assert (hits["front_face"][sel].astype(np.uint32) == cv[sel][:, ff_off]).all()
+                assert (_bits(hits["t"][root]) == cv[root][:, 7]).all()
+        finally:
+            r.close()
+    assert hits_seen > 0
+
+
+# ---- geometry against a float64 brute-force search ------------------------------------------------------------------------
+def _random_scene(rng, depth):
+    """A few solid boxes (uniform subtrees: LEAFs above the finest level) and scattered single voxels, materials 1..6."""
+    g = 1 << depth
+    parts = []
+    for _ in range(int(rng.integers(3, 8))):
+        lo = rng.integers(0, g, 3)
+        hi = np.minimum(lo + rng.integers(1, max(2, g // 4) + 1, 3), g)
+        xs, ys, zs = np.meshgrid(*[np.arange(a, b) for a, b in zip(lo, hi)], indexing="ij")
+        box = np.stack([xs.ravel(), ys.ravel(), zs.ravel()], 1)
+        parts.append(np.concatenate([box, np.full((len(box), 1), rng.integers(1, 7))], 1))
+    n = int(rng.integers(40, 400))
+    parts.append(np.concatenate([rng.integers(0, g, (n, 3)), rng.integers(1, 7, (n, 1))], 1))
+    return np.concatenate(parts).astype(np.int32)
+
+
+def _brute(occ, depth, o, d, scale, mn, margin):
+    """First occupied finest cell along each ray (float64 3-D DDA): (kept, t, cell, material index + 1)."""
+    g = 1 << depth
+    og = (o - mn) / scale * g
+    dg = d / scale * g
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / dg
+        t0s, t1s = (0.0 - og) * inv, (g - og) * inv
+    lo, hi = np.fmin(t0s, t1s), np.fmax(t0s, t1s)
+    lo = np.where(dg == 0, np.where((og >= 0) & (og < g), -np.inf, np.inf), lo)
+    hi = np.where(dg == 0, np.where((og >= 0) & (og < g), np.inf, -np.inf), hi)
+    tin, tout = np.maximum(lo.max(1), 0.0), hi.min(1)
+    n = len(o)
+    alive = tin < tout
+    p = og + np.where(alive, tin, 0.0)[:, None] * dg
+    cell = np.clip(np.floor(p), 0, g - 1).astype(np.int64)
+    step = np.sign(dg).astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tnext = np.where(dg > 0, (cell + 1 - og) * inv, np.where(dg < 0, (cell - og) * inv, np.inf))
+        tdelta = np.where(dg != 0, np.abs(inv), np.inf)
+    t_enter = tin.copy()
+    t_prev = np.full(n, -np.inf)
+    axis = np.argmax(lo, 1)                          # the box face a ray enters through (outside origins)
+    inside0 = lo.max(1) < 0                          # origin inside the box
+    # the first step lands only adv |d_axis| past the box face; treeLookup's x index (rc:376-378) rounds a coordinate that close
+    # below a cell's upper edge into the NEXT cell (fl(v + f) = v + 1): the reference's own artefact, kept bit for bit — and not
+    # the geometry this test checks
+    entry_ok = inside0 | (np.abs(d[np.arange(len(o)), axis]) >= 0.2)
+    found = np.zeros(n, bool)
+    res_cell = np.zeros((n, 3), np.int64)
+    res_t = np.zeros(n)
+    res_axis = np.zeros(n, np.int64)
+    res_prev = np.zeros(n)
+    first = np.ones(n, bool)
+    rows = np.arange(n)
+    min_gap = np.full(n, np.inf)                     # the closest two successive crossings of the path (t)
+    for _ in range(3 * g + 3):
+        if not alive.any():
+            break
+        idx = rows[alive]
+        c = cell[idx]
+        occ_here = occ[c[:, 0], c[:, 1], c[:, 2]]
+        hit_now = occ_here > 0
+        if hit_now.any():
+            h = idx[hit_now]
+            found[h] = True
+            res_cell[h] = cell[h]
+            res_t[h] = t_enter[h]
+            res_axis[h] = axis[h]
+            res_prev[h] = t_prev[h]
+            alive[h] = False
+        # origin inside a voxel: not a ray this test keeps
+        bad = idx[hit_now & first[idx] & inside0[idx]]
+        found[bad] = False
+        idx = idx[~hit_now]
+        first[idx] = False
+        a = np.argmin(tnext[idx], 1)
+        tn = tnext[idx, a]
+        t_prev[idx] = t_enter[idx]
+        min_gap[idx] = np.minimum(min_gap[idx], tn - t_enter[idx])
+        t_enter[idx] = tn
+        axis[idx] = a
+        cell[idx, a] += step[idx, a]
+        tnext[idx, a] += tdelta[idx, a]
+        out = (cell[idx, a] < 0) | (cell[idx, a] >= g) | (tn > tout[idx])
+        alive[idx[out]] = False
+    # margins (in finest cells along the ray): entry away from the face's edges, the previous crossing and the exit far away,
+    # not grazing, and far from the origin
+    speed = np.linalg.norm(dg, axis=1)
+    pe = og + res_t[:, None] * dg
+    mask_other = np.ones((n, 3), bool)
+    mask_other[rows, res_axis] = False
+    edge = np.where(mask_other, np.minimum(np.abs(pe - res_cell), np.abs(res_cell + 1 - pe)), np.inf).min(1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_exit_cell = np.where(dg > 0, (res_cell + 1 - og) * inv, np.where(dg < 0, (res_cell - og) * inv, np.inf)).min(1)
+    dn = np.abs(dg[rows, res_axis]) / speed
+    # the traversal leaves an empty cell through its box padded by 1e-5 and then steps `adv` (<= 6e-5) further: it can overshoot a
+    # voxel by up to 1e-5 / |d_axis| + 6e-5 along the ray — the margin covers that, and never falls below `margin` cells
+    with np.errstate(divide="ignore"):
+        dmin = np.where(d != 0, np.abs(d), np.inf).min(1)
+    m = np.maximum(margin, (1e-4 + 1e-5 / dmin) * 2.0 / scale * g)
+    # (every crossing of the path, not only the last: a sample that lands where two planes cross can sit exactly on the second plane,
+    # and treeLookup's round-half-even then takes the lower child — another artefact of the reference's index arithmetic)
+    kept = found & (edge >= m) & ((res_t - res_prev) * speed >= m) & (min_gap * speed >= m) & ((t_exit_cell - res_t) * speed >= m) \
+        & (dn >= 0.1) & (res_t >= 1e-3) & entry_ok
+    return kept, res_t, res_cell, found
+
+
+@pytest.mark.parametrize("depth", [3, 4, 5, 6, 7, 8])
+def test_random_rays_find_the_brute_force_voxel(depth):
+    rng = np.random.default_rng(1000 + depth)
+    vox = _random_scene(rng, depth)
+    scale, mn = (1.0, np.array([-0.5, -0.5, -1.0], np.float32)) if depth % 2 else (2.5, np.array([-1.25, 0.5, -3.0], np.float32))
+    ctx = rt.Context(0)
+    try:
+        cells, n_cells = rt.octree_build_cells(ctx, vox, depth)
+        cc = 1 << 16
+        floats = rt.VertexBufferObject(ctx, np.array([mn[0], mn[1], mn[2], 0.0, scale, 1.0 / scale, 1.0 / cc], np.float32))
+        ints = rt.VertexBufferObject(ctx, np.array([depth, 4096, cc], np.int32))
+        for slot, b in ((0, cells), (6, floats), (7, ints)):
+            ctx.bind_buffer_base(rt.SHADER_STORAGE_BUFFER, slot, b)
+        tree = expand_cells(cells.read(np.uint32), depth)
+        g = 1 << depth
+        occ = np.zeros((g, g, g), np.uint8)
+        occ[tree[:, 0], tree[:, 1], tree[:, 2]] = tree[:, 3]
+        n = 20000
+        o_unit = rng.uniform(-0.3, 1.3, (n, 3))
+        target = rng.uniform(0.0, 1.0, (n, 3))
+        aim = rng.random(n) < 0.5                       # half the rays aimed at a random voxel (deep sparse trees are mostly empty)
+        target[aim] = (vox[rng.integers(0, len(vox), int(aim.sum())), :3] + rng.uniform(0.0, 1.0, (int(aim.sum()), 3))) / (1 << depth)
+        d = target - o_unit
+        axis_par = rng.random(n) < 0.1                  # some axis-parallel rays
+        ax = rng.integers(0, 3, n)
+        d[axis_par] = 0.0
+        d[axis_par, ax[axis_par]] = rng.choice([-1.0, 1.0], int(axis_par.sum()))
+        d /= np.linalg.norm(d, axis=1)[:, None]
+        o = (o_unit * scale + mn).astype(np.float32)
+        d = d.astype(np.float32)
+        hits = ctx.raycast(np.concatenate([o, d], 1))
+        kept, t64, cell, _ = _brute(occ, depth, o.astype(np.float64), d.astype(np.float64), scale, mn.astype(np.float64), 1e-3)
+        assert kept.sum() > 300, kept.sum()
+        h = hits[kept]
+        bad = np.flatnonzero(kept)[h["status"] != rt.RAY_HIT]
+        assert bad.size == 0, [(o[i].tolist(), d[i].tolist(), float(t64[i]), cell[i].tolist(), int(hits[i]["status"]), int(hits[i]["iterations"]),
+                                float(hits[i]["t"])) for i in bad[:4]]
+        c = cell[kept]
+        assert (h["material"] + 1 == occ[c[:, 0], c[:, 1], c[:, 2]]).all()
+        lo = (c / g) * scale + mn
+        hi = ((c + 1) / g) * scale + mn
+        tol = 1e-6 * scale
+        assert (h["cell_min"] <= lo + tol).all() and (h["cell_min"] + h["cell_size"][:, None] >= hi - tol).all()
+        assert (np.abs(h["t"] - t64[kept]) <= 1e-4 * scale).all()
+        assert not (hits["status"] == rt.RAY_ITER_LIMIT).any()
+    finally:
+        ctx.close()
+
+
+def test_device_batches_equal_the_host_form():
+    import torch
+    scene = host.Scene.demo()
+    cam = host.camera_reference_pose(64, 64, 1, 2)
+    r = rt.Renderer(scene, cam)
+    try:
+        g = torch.Generator(device="cpu").manual_seed(7)
+        n = 1 << 20
+        o = torch.rand((n, 3), generator=g) * 1.6 - 0.8 + torch.tensor([0.0, 0.0, -0.5])
+        d = torch.randn((n, 3), generator=g)
+        d = d / d.norm(dim=1, keepdim=True)
+        rays = torch.cat([o, d], 1).to(torch.float32)
+        dev = rays.to("cuda:0")
+        full = r.ctx.raycast(dev)
+        assert full.shape == (n, 64) and full.is_cuda
+        k = 300000
+        split = torch.cat([r.ctx.raycast(dev[:k]), r.ctx.raycast(dev[k:])])
+        assert torch.equal(full, split)
+        sub = rays[::97].numpy()
+        host_hits = r.ctx.raycast(sub)
+        assert host_hits.tobytes() == full[::97].cpu().numpy().tobytes()
+        assert (rt.hits_from_bytes(full)["status"] == rt.RAY_HIT).sum() > 0
+    finally:
+        r.close()
+
+
+def _edit_rig(scene, cam, counter0):
+    r = rt.Renderer(scene, cam)
+    upd = rt.ComputeShader(r.ctx, rt.PROGRAM_OCTREE_UPDATE)
+    counter = rt.VertexBufferObject(r.ctx, np.array([counter0], np.uint32))
+    r.ctx.bind_buffer_base(rt.ATOMIC_COUNTER_BUFFER, 0, counter)
+    dv = rt.VertexBufferObject(r.ctx, np.zeros(1000, np.float32))
+    r.ctx.bind_buffer_base(rt.SHADER_STORAGE_BUFFER, 5, dv)
+    return r, upd, counter, dv
+
+
+def _node_at(cells, q, depth):
+    """(type, value) of the first node that is not a PARENT on the path to finest cell q (binary digits: q is a cell centre)."""
+    v = 0
+    for level in range(1, depth + 1):
+        sh = depth - level
+        i = (((2 * v + ((q[0] >> sh) & 1)) << 1) + ((q[1] >> sh) & 1) << 1) + ((q[2] >> sh) & 1)
+        t, v = int(cells[2 * i + 1]), int(cells[2 * i])
+        if t != 1:
+            return t, v
+    return 1, v
+
+
+def test_pick_to_edit_round_trip(oracle):
+    scene = host.Scene.config(2)
+    depth = scene.max_depth
+    cam = host.camera_reference_pose(96, 64, 1, 2)
+    c0 = int(scene.counts["cells"])
+    r, upd, counter, dv = _edit_rig(scene, cam, c0)
+    try:
+        original = r.vbos[0].read(np.uint32)
+        cand = [(x, y) for y in range(2, 64, 3) for x in range(2, 96, 3)]
+        picks = r.pick(np.array(cand, np.int32))
+        chosen = None
+        # a face whose placement writes one node that was EMPTY: octree_update.comp turns it into a PARENT of a freshly counted cell on
+        # the way and then overwrites it with the delta, so removing writes the zero node back (the counted cell stays counted)
+        for (x, y), h in zip(cand, picks):
+            if h["status"] != rt.RAY_HIT or not h["fresh_record"]:
+                continue
+            try:
+                delta = host.pick_edit_delta(h, scene, 1, 3.0)
+            except ValueError:
+                continue
+            after, cnt = oracle_octree_update(oracle, scene, delta[:5], c0, (0, 1, 0))
+            changed = np.flatnonzero(after != original)
+            if changed.size and changed.max() - changed.min() <= 1 and not original[changed.min() & ~1:(changed.min() & ~1) + 2].any():
+                chosen = (x, y, h, delta, after, cnt)
+                break
+        assert chosen is not None
+        x, y, h0, delta, expect, c1 = chosen
+        rt.update_vbo(r.ctx, dv, delta, 5, upd)
+        cells = r.vbos[0].read(np.uint32)
+        assert np.array_equal(cells, expect)
+        assert int(counter.read(np.uint32)[0]) == c1
+        want = np.floor(delta[:3].astype(np.float64) * (1 << depth)).astype(np.int64)
+        assert _node_at(cells, want, depth) == (2, 3)           # a LEAF of material 3 where the helper aimed
+        assert _node_at(original, want, depth)[0] == 0
+        h1 = r.pick(np.array([[x, y]], np.int32))[0]
+        assert h1["status"] == rt.RAY_HIT and h1["material"] == 3 and h1["t"] < h0["t"]
+        removal = host.pick_edit_delta(h1, scene, 0, 0.0)
+        edited = host.Scene({**scene.blobs, 0: cells})
+        expect2, _ = oracle_octree_update(oracle, edited, removal[:5], c1, (0, 1, 0))
+        rt.update_vbo(r.ctx, dv, removal, 5, upd)
+        back = r.vbos[0].read(np.uint32)
+        assert np.array_equal(back, expect2) and np.array_equal(back, original)
+    finally:
+        r.close()
+
+
+def test_multi_device_and_render_state(oracle):
+    scene = host.Scene.config(1)
+    cam = _cam((0.0, 0.2, 0.9), 0.0, -8.0, 90.0, w=96, h=64, spp=4, bounce=3)
+    xy = np.stack(np.meshgrid(np.arange(0, 96, 3), np.arange(0, 64, 3)), -1).reshape(-1, 2).astype(np.int32)
+    ref = oracle.render(scene, cam, threads=8)
+    single = rt.Renderer(scene, cam)
+    multi = rt.Renderer(scene, cam, devices=[0, 0])
+    try:
+        assert (single.render().view(np.uint32) == ref.view(np.uint32)).all()
+        a, rays = single.pick(xy, 2, return_rays=True)
+        b = multi.pick(xy, 2)
+        assert a.tobytes() == b.tobytes()
+        assert multi.ctx.raycast(rays).tobytes() == a.tobytes()
+        for _ in range(3):
+            single.pick(xy, 0)
+        assert (single.render().view(np.uint32) == ref.view(np.uint32)).all()
+        assert (multi.render().view(np.uint32) == ref.view(np.uint32)).all()
+    finally:
+        single.close()
+        multi.close()
+
+
+def test_error_codes():
+    L = rt.lib()
+    ctx = rt.Context(0)
+    try:
+        rays = np.zeros((4, 6), np.float32)
+        rays[:, 5] = 1.0
+        out = np.zeros(4, rt.RAY_HIT_DTYPE)
+        assert L.tdt_raycast(ctx.h, rays.ctypes.data, 4, out.ctypes.data) == rt.ERR_INCOMPLETE
+        scene = host.Scene.config(0)
+        vbos = rt.upload_scene(ctx, scene)
+        assert L.tdt_raycast(ctx.h, None, 4, out.ctypes.data) == rt.ERR_INVALID_VALUE
+        assert L.tdt_raycast(ctx.h, rays.ctypes.data, 4, None) == rt.ERR_INVALID_VALUE
+        assert L.tdt_raycast_device(ctx.h, None, 4, None) == rt.ERR_INVALID_VALUE
+        assert L.tdt_raycast(ctx.h, None, 0, None) == rt.OK
+        assert L.tdt_raycast_device(ctx.h, None, 0, None) == rt.OK
+        assert L.tdt_raycast(ctx.h, rays.ctypes.data, 4, out.ctypes.data) == rt.OK
+        tracer = rt.ComputeShader(ctx)
+        xy = np.zeros((1, 2), np.int32)
+        assert L.tdt_pick_pixels(tracer.h, None, 1, 0, None, out.ctypes.data) == rt.ERR_INVALID_VALUE
+        assert L.tdt_pick_pixels(tracer.h, xy.ctypes.data, 0, 0, None, None) == rt.OK
+        upd = rt.ComputeShader(ctx, rt.PROGRAM_OCTREE_UPDATE)
+        assert L.tdt_pick_pixels(upd.h, xy.ctypes.data, 1, 0, None, out.ctypes.data) == rt.ERR_INVALID_OPERATION
+        del vbos
+    finally:
+        ctx.close()
+
+
+def test_demo_pick_and_click_equals_the_oracle(oracle, tmp_path):
+    exe = build.build_demo()
+    out = str(tmp_path / "frame.pfm")
+    w, h = 128, 96
+    scene = host.Scene.demo()
+    cam = host.camera_reference_pose(w, h, 2, 6)
+    # the pixel nearest the centre whose pick can be placed at (the centre itself looks past the demo's voxels)
+    r = rt.Renderer(scene, cam)
+    try:
+        xy = np.stack(np.meshgrid(np.arange(w), np.arange(h)), -1).reshape(-1, 2).astype(np.int32)
+        picks = r.pick(xy)
+    finally:
+        r.close()
+    order = np.argsort(np.abs(xy[:, 0] - w // 2) + np.abs(xy[:, 1] - h // 2), kind="stable")
+    px = None
+    for i in order:
+        if picks[i]["status"] == rt.RAY_HIT and picks[i]["fresh_record"]:
+            try:
+                host.pick_edit_delta(picks[i], scene, 1, 3.0)
+            except ValueError:
+                continue
+            px = xy[i]
+            break
+    assert px is not None
+    p = subprocess.run([exe, "--size", f"{w}x{h}", "--spp", "2", "--bounce", "6", "--pick", f"{px[0]},{px[1]}", "--click", "left",
+                        "--material", "3", "--out", out], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    m = re.search(r"pick (\d+),(\d+) status (\d+) material (\d+) t (\S+) iterations (\d+) point (\S+),(\S+),(\S+) "
+                  r"normal (\S+),(\S+),(\S+) fresh (\d+) edit (\w+)", p.stdout)
+    assert m and m.group(14) == "place", p.stdout
+    hit = np.zeros(1, rt.RAY_HIT_DTYPE)
+    hit["status"], hit["material"], hit["t"], hit["iterations"] = int(m.group(3)), int(m.group(4)), float(m.group(5)), int(m.group(6))
+    hit["point"] = [float(m.group(i)) for i in (7, 8, 9)]
+    hit["normal"] = [float(m.group(i)) for i in (10, 11, 12)]
+    hit["fresh_record"] = int(m.group(13))
+    mine = picks[int(px[1]) * w + int(px[0])]           # the demo's pick is the library's pick of that pixel
+    assert mine["status"] == hit["status"][0] and mine["material"] == hit["material"][0]
+    assert _bits(mine["point"]).tolist() == _bits(hit["point"][0]).tolist()
+    delta = host.pick_edit_delta(hit, scene, 1, 3.0)
+    cells, _ = oracle_octree_update(oracle, scene, delta[:5], 19, (0, 1, 0))
+    ref = oracle.render(host.Scene({**scene.blobs, 0: cells}), cam, threads=8)
+    with open(out, "rb") as f:
+        assert f.readline().strip() == b"PF4"
+        fw, fh = map(int, f.readline().split())
+        f.readline()
+        img = np.frombuffer(f.read(), "<f4").reshape(fh, fw, 4)
+    assert (img.view(np.uint32) == ref.view(np.uint32)).all()
+    assert not (ref.view(np.uint32) == oracle.render(scene, cam, threads=8).view(np.uint32)).all()
