@@ -3,7 +3,7 @@
 synthetic scene already resident in HBM (plus, for N > 1 GPUs, the single RCCL gather of per-rank tile buffers and their
 de-interleave on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--spp S] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--spp S] [--scaling weak|strong] [--full]
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its N ranks itself (child processes,
 started before this process touches a GPU); under `python -m torch.distributed.run --nproc-per-node N` it is one of the ranks.
@@ -11,11 +11,17 @@ started before this process touches a GPU); under `python -m torch.distributed.r
 N = 1 workload (default): BASELINE.json's metric configuration — 1920x1080, 64 spp, max_bounce 8, the 64^3-octree synthetic
 scene of configs[1] — dispatched exactly as the reference does (main.rs:579), so 1056 of the 1080 rows are written
 (compute_shader.rs:30-32) and only written pixels are counted.  Every timed step is a frame the scheduler has NOT seen
-(tdt_forget_costs before it: two-phase schedule, probe in image order); the replay of an identical frame is reported beside
-it as config.replay_ms.  N > 1: weak scaling of that frame (N x the pixel rows over the same frustum).  Every line also
-carries a `strong` block — BASELINE configs[3]: ONE 7680x4320 / 64 spp / 256^3 frame sharded over the N ranks, per-rank trace,
-gather and assemble times separated — and a `single_process` block: the same 8K frame driven through the C ABI's
-multi-device context (tdt_ctx_create_multi) from one process.  Prints ONE JSON line on rank 0.
+(tdt_forget_costs before it: two-phase schedule, probe in image order).  N > 1: strong scaling of that frame (one image sharded
+over the ranks; --scaling weak: N x the pixel rows over the same frustum).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line; the blocks that measure
+anything else are null in it.  --full adds them: the replay of an identical frame (config.replay_ms), the probe / main / resolve
+phases and the `roofline` of the dominant launch, the CPU oracle baseline, `target_4k` (BASELINE configs[2]) and
+`reference_default` (the reference's own frame), `strong` — BASELINE configs[3]: ONE 7680x4320 / 64 spp / 256^3 frame sharded
+over the N ranks, per-rank trace, gather and assemble times separated — and `single_process`: the same 8K frame driven through
+the C ABI's multi-device context (tdt_ctx_create_multi) from one process; at N > 1 also the same frame on one GPU
+(`headline_scaling`) and the weak-scaled side block (`weak`).  The --no-* switches drop single blocks of a --full run.
+Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -54,6 +60,9 @@ def parse_args(argv=None):
     ap.add_argument("--passes", type=int, default=1,
                     help="N=1 only: a step = one PROGRESSIVE frame of passes x spp samples per pixel (configs[4] is 16 x 64): "
                          "running sums and hit-record carry through HBM, one resolve at the end (bit-identical to one pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: replay, phases and roofline, CPU baseline, the other "
+                         "configurations (target_4k, reference_default, strong, single_process) and, N > 1, the one-GPU and weak figures")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the weak-scaled side block (N x the pixel rows)")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaled 8K block (BASELINE configs[3])")
@@ -723,7 +732,7 @@ def main():
 
     # ---- N > 1, strong headline: the same frame on ONE GPU in this run (rank 0 alone), and the weak-scaled figure as a side block ----
     headline_scaling = weak = None
-    if world > 1 and scaling == "strong" and args.config != 4 and not progressive:
+    if args.full and world > 1 and scaling == "strong" and args.config != 4 and not progressive:
         one_sec = None
         if rank == 0:
             ow = Workload(R, args.config, spp=args.spp, alone=True)
@@ -742,21 +751,21 @@ def main():
             ww.close()
 
     # phases of a history-free frame (probe / main / resolve) from events recorded inside the library, a few more frames
-    phase = measure_phases(wl, 5) if (fresh and rank == 0 and not R.sharded) else None
+    phase = measure_phases(wl, 5) if (args.full and fresh and rank == 0 and not R.sharded) else None
 
     # ---- the other schedule, for the record -----------------------------------------------------------------------------
     other_ms = None
-    if not progressive:
+    if args.full and not progressive:
         wl.step(False, False)                                # (a replay needs a recorded frame)
         other_sec, _ = wl.run(args.steps, 1, not fresh)
         other_ms = other_sec * 1e3
 
     # ---- roofline of the dominant kernel: the main launch of the frame, measured on rank 0 ------------------------------
-    roofline = nominal_roofline(R, wl, args.config, phase, frame_kernel_ms) if rank == 0 else None
+    roofline = nominal_roofline(R, wl, args.config, phase, frame_kernel_ms) if (args.full and rank == 0) else None
 
     # ---- CPU baseline: the oracle (a port, not the product) on a bounded sample; the reference's own llvmpipe figure quoted ----
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores = min(os.cpu_count() or 1, 32)
         bands, band_rows = 96, 8
         tc, px, bad = oracle_bands(wl, bands, band_rows, cores)
@@ -769,7 +778,7 @@ def main():
 
     # ---- BASELINE configs[2] (the north-star roofline configuration) and the reference's own workload: N = 1 lines only ------
     target_4k = reference_default = None
-    if world == 1 and not R.sharded and not progressive and args.config == 2:
+    if args.full and world == 1 and not R.sharded and not progressive and args.config == 2:
         if not args.no_target:
             target_4k = target_block(R, args)
         if not args.no_reference_default:
@@ -777,7 +786,7 @@ def main():
 
     # ---- BASELINE configs[3]: ONE 8K frame, strong-sharded over the ranks -------------------------------------------------
     strong = None
-    if not args.no_strong and args.config != 4 and not progressive:
+    if args.full and not args.no_strong and args.config != 4 and not progressive:
         sw = Workload(R, 4, rows_factor=1)
         ssec, spx = sw.run(args.strong_steps, 1, True)
         strace = R.gather_floats(Workload.mean_ms(sw.trace_events))
@@ -807,7 +816,7 @@ def main():
 
     # ---- the same 8K frame through the C ABI's multi-device context, one process (a fresh one) ------------------------------
     single = None
-    if not args.no_single_process and not progressive:
+    if args.full and not args.no_single_process and not progressive:
         torch.cuda.synchronize()
         single = run_single_process_child(args, world)
 

@@ -31,6 +31,13 @@ def test_arguments_and_workloads():
     assert r == 80 + 48 + 28 + 16 + 40 and w == 64
 
 
+def test_full_is_off_by_default():
+    """A plain run measures the headline alone; --full adds the side blocks, and --no-* still drop single ones from it."""
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-strong"])
+    assert a.full and a.no_strong and not a.no_cpu_baseline
+
+
 def test_dump_outputs_argument_and_files(tmp_path):
     """--dump-outputs DIR: a frame up to 48 MB is written whole; a larger one as the same fixed pixel sample every time."""
     import numpy as np
@@ -109,11 +116,11 @@ def test_a_failing_rank_fails_the_launch():
 
 @pytest.mark.gpu
 def test_bench_gpus_2_self_launched_on_one_gpu():
-    """`python bench.py --gpus 2 --backend gloo --steps 1 --warmup 1` as a fresh child: rc 0 and one JSON line that carries the
+    """`python bench.py --gpus 2 --backend gloo --steps 1 --warmup 1 --full` as a fresh child: rc 0 and one JSON line that carries the
     strong-scaled headline (the metric's frame sharded over the ranks) with the weak-scaled side block, the strong 8K block with its per-rank times, and the single-process (multi-device context) block."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1",
-                        "--strong-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--strong-steps", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -129,6 +136,23 @@ def test_bench_gpus_2_self_launched_on_one_gpu():
     sp = j["single_process"]
     assert "error" not in sp, sp
     assert sp["devices"] == [0, 0] and sp["written_pixels"] == 7680 * 4320 and sp["transport"] == "copy" and sp["rccl_ranks"] == 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the line carries the headline and its configuration, and every side block is null (none was measured)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "2"],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "Mray-samples/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert (j["steps"], j["warmup"], j["n_gpus"]) == (2, 1, 1) and j["config"]["image"] == [1920, 1080] and j["config"]["spp"] == 2
+    assert j["config"]["first_dispatch_ms"] > 0 and j["config"]["replay_ms"] is None
+    for k in ("headline_scaling", "weak", "roofline", "cpu_baseline", "target_4k", "reference_default", "strong", "single_process"):
+        assert j[k] is None, k
 
 
 @pytest.mark.gpu

@@ -6,7 +6,8 @@
 Each variant is `label|environment|library` (library `-` = the product build; environment may be empty).  Every (config, rep) runs
 all variants back to back, so box-to-box and time drift hit them alike; the table gives the median history-free / replay frame time
 per variant and config and its ratio to the FIRST variant.  A variant is one `python bench.py` child (TDT_LIB selects the library at
-import time), so a speed proxy that writes garbage pixels can be timed too (the children run with --no-cpu-baseline)."""
+import time), so a speed proxy that writes garbage pixels can be timed too (the children run --full for the replay and phases, with
+--no-cpu-baseline and the other configurations off)."""
 import argparse, json, os, statistics, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +21,7 @@ def run_variant(env_s, lib, config, steps):
     for kv in env_s.split():
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "2", "--config", str(config), "--no-cpu-baseline", "--no-strong",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "2", "--config", str(config), "--no-cpu-baseline", "--no-strong",
            "--no-single-process", "--no-target", "--no-reference-default"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -20,13 +20,13 @@ for C in 2 3 5; do
   python3 tools/pmc_summary.py $O/tcc_c${C}/FETCH_SIZE $O/tcc_c${C}/WRITE_SIZE $O/tcc_c${C}/TCC_HIT_sum > $O/tcc_c${C}.summary.txt
   echo "tcc c$C done"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c2.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -- python3 bench.py --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c3.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c5 -- python3 bench.py --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c5.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -- python3 bench.py --full --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c3.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c5 -- python3 bench.py --full --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c5.log 2>&1
 echo "stats done"
-python3 bench.py --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench.err
-python3 bench.py --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c3.json 2>> $O/bench.err
-python3 bench.py --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c5.json 2>> $O/bench.err
-python3 bench.py --steps 2 --warmup 1 --config 5 --passes 16 --no-strong --no-single-process > $O/bench_c5_progressive.json 2>> $O/bench.err
-python3 bench.py --steps 4 --warmup 1 --config 4 --no-cpu-baseline --no-single-process > $O/bench_c4_8k.json 2>> $O/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench.err
+python3 bench.py --full --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c3.json 2>> $O/bench.err
+python3 bench.py --full --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c5.json 2>> $O/bench.err
+python3 bench.py --full --steps 2 --warmup 1 --config 5 --passes 16 --no-strong --no-single-process > $O/bench_c5_progressive.json 2>> $O/bench.err
+python3 bench.py --full --steps 4 --warmup 1 --config 4 --no-cpu-baseline --no-single-process > $O/bench_c4_8k.json 2>> $O/bench.err
 ls $O

@@ -26,16 +26,16 @@ for C in 2 3 5 0; do
 done
 fi
 if [ $PART = all ] || [ $PART = bench ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-strong --no-single-process --no-target --no-reference-default > $O/bench_stats_c2.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -- python3 bench.py --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c3.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c5 -- python3 bench.py --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c5.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-strong --no-single-process --no-target --no-reference-default > $O/bench_stats_c2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -- python3 bench.py --full --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c3.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c5 -- python3 bench.py --full --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_stats_c5.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c0 -- python3 tools/demo_time.py 100 > $O/bench_stats_c0.log 2>&1
 echo "stats done"
-python3 bench.py --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench.err
-python3 bench.py --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c3.json 2>> $O/bench.err
-python3 bench.py --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c5.json 2>> $O/bench.err
-python3 bench.py --steps 2 --warmup 1 --config 5 --passes 16 --no-strong --no-single-process > $O/bench_c5_progressive.json 2>> $O/bench.err
-python3 bench.py --steps 4 --warmup 1 --config 4 --no-cpu-baseline --no-single-process > $O/bench_c4_8k.json 2>> $O/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench.err
+python3 bench.py --full --steps 6 --warmup 2 --config 3 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c3.json 2>> $O/bench.err
+python3 bench.py --full --steps 6 --warmup 2 --config 5 --no-cpu-baseline --no-strong --no-single-process > $O/bench_c5.json 2>> $O/bench.err
+python3 bench.py --full --steps 2 --warmup 1 --config 5 --passes 16 --no-strong --no-single-process > $O/bench_c5_progressive.json 2>> $O/bench.err
+python3 bench.py --full --steps 4 --warmup 1 --config 4 --no-cpu-baseline --no-single-process > $O/bench_c4_8k.json 2>> $O/bench.err
 python3 tools/demo_time.py 100 > $O/demo_time.txt 2>&1
 # pass statistics of the product kernels (a -DTDT_STATS build of the same sources: build_ab/lib_stats.so) for the loss budget
 for C in 2 3 5 0; do for M in fresh replay; do
