@@ -234,6 +234,27 @@ class Octree {
     ctx.check(tdt_raycast(ctx.raw(), rays.data(), out.size(), out.data()));
     return out;
   }
+  // NEW: the bound tree read back as voxels {x, y, z, material + 1} (4 ints each), in Morton order (tdt_octree_extract)
+  std::vector<int32_t> voxels(const Context &ctx) const {
+    size_t n = 0;
+    ctx.check(tdt_octree_extract(ctx.raw(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract(ctx.raw(), v.data(), n, &n));
+    return v;
+  }
+  // NEW: {reachable cells, leaf nodes, voxels, highest cell reached, cells the buffer holds, counter} (tdt_octree_census)
+  std::array<int64_t, 6> census(const Context &ctx) const {
+    std::array<int64_t, 6> c{};
+    ctx.check(tdt_octree_census(ctx.raw(), c.data()));
+    return c;
+  }
+  // NEW: what the reference's TODOs (octree_update.comp:86-94) would reclaim: the bound cells buffer rewritten in place into the
+  // canonical tree of its voxels, the counter reset to its size (tdt_octree_compact); returns the number of cells
+  uint32_t compact(const Context &ctx) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_compact(ctx.raw(), &n));
+    return n;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

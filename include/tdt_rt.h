@@ -282,6 +282,33 @@ int tdt_raycast_device(tdt_ctx *ctx, const void *rays_dev, size_t n, void *hits_
  * A TDT_PROGRAM_OCTREE_UPDATE program: TDT_ERR_INVALID_OPERATION. */
 int tdt_pick_pixels(tdt_compute *c, const int32_t *xy, size_t n, int sample, float *rays_out, tdt_ray_hit *out);
 
+/* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
+ * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
+ * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.
+ * All three walk the LOGICAL tree of the buffers bound to slots 0 and 7, as treeLookup resolves it (raytracer.comp:372-393):
+ * node index = 8 * cell + (x*4 + y*2 + z) from cell 0 for max_depth (slot 7) levels; EMPTY -> nothing; LEAF -> the whole
+ * block under the node, material = value; any other type -> descend into cell `value`, except on level max_depth; nodes
+ * past the end of the buffer read as EMPTY.  A shared cell is walked once per path that reaches it.  max_depth must be
+ * 1..10 (TDT_ERR_INVALID_VALUE otherwise); slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Each call is ordered after the work
+ * already queued on the context's stream (an edit dispatched just before needs no tdt_finish).  A multi-device context
+ * answers census / extract from device_ids[0] and compacts every replica. */
+/* out = {reachable cells (once per path), leaf nodes, finest-level voxels, highest cell index descended into, cells the
+ * buffer holds (bytes / 64), first word of the atomic counter (slot 0) or -1 when none is bound}.  Synchronous. */
+int tdt_octree_census(tdt_ctx *ctx, int64_t out[6]);
+/* the tree's voxels {x, y, z, material + 1} (int32, the input format of tdt_octree_build_cells), sorted by ascending Morton
+ * key (spread3(x) << 2 | spread3(y) << 1 | spread3(z)), into host memory.  *n_voxels = their number; voxels_xyzm == NULL:
+ * only the count.  capacity (in voxels) < the count, or a LEAF value >= 2^31 - 1: TDT_ERR_INVALID_VALUE (*n_voxels still
+ * set, nothing written).  Synchronous. */
+int tdt_octree_extract(tdt_ctx *ctx, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+/* rewrite the bound cells buffer IN PLACE into canonical form: its first *n_cells * 64 bytes become exactly what
+ * tdt_octree_build_cells(extract, max_depth) builds (uniform subtrees merged, breadth-first numbering), every byte after
+ * them zero (the buffer keeps its size: the freed cells return to the edit program's free pool), and the first word of the
+ * atomic counter, when one is bound, becomes *n_cells.  Slots 1-7 are untouched; tables the trace derives from the cells
+ * buffer are rebuilt on the next dispatch.  An empty tree becomes one all-EMPTY root cell.  A LEAF value >= 254 (not a
+ * material the builder takes), or a canonical tree larger than the buffer (possible only with shared cells):
+ * TDT_ERR_INVALID_VALUE, every byte left as it was.  Synchronous. */
+int tdt_octree_compact(tdt_ctx *ctx, uint32_t *n_cells);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

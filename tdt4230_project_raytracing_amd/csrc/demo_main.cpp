@@ -3,7 +3,8 @@
 // `src/renderer`), then the frame is read back and written as a PFM instead of being blitted to a window.
 //
 //   tdt_demo [--size WxH] [--spp N] [--bounce N] [--settings camera.ron] [--move KEYS] [--edit x,y,z,type,value]
-//            [--device N] [--out frame.pfm] [--png frame.png]
+//            [--pick X,Y [--click left|right] [--material N]] [--compact] [--config N] [--device N] [--out frame.pfm]
+//            [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -12,6 +13,10 @@
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
+// --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
+//   rendered; prints the census (Octree::census) before and after.
+// --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
+//   parameters (slots 6 / 7) and cell count.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,7 +32,8 @@ int main(int argc, char **argv) {
   std::string out, png, settings_path, moves;
   std::vector<float> edit;
   int pick_x = -1, pick_y = -1, material = 1;
-  bool place = true;
+  bool place = true, compact = false;
+  int config = -1;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -43,6 +49,8 @@ int main(int argc, char **argv) {
     else if (a == "--pick") { if (std::sscanf(next(), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
     else if (a == "--click") { const std::string v = next(); if (v != "left" && v != "right") { std::fprintf(stderr, "--click left|right\n"); return 2; } place = v == "left"; }
     else if (a == "--material") material = std::atoi(next());
+    else if (a == "--compact") compact = true;
+    else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   try {
@@ -92,7 +100,20 @@ int main(int argc, char **argv) {
     ComputeShader octree_update_program = ComputeShader::new_(ctx, TDT_PROGRAM_OCTREE_UPDATE);
     // main.rs:238-450: the scene literal, one buffer per table, each bound to its shader-storage slot
     tdt_scene *scene = nullptr;
-    if (tdt_scene_demo(&scene)) { std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1; }
+    if (config < 0 ? tdt_scene_demo(&scene) : tdt_scene_config(config, &scene)) { std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1; }
+    // main.rs:455-468's octree parameters, or the synthetic scene's own (its slots 6 / 7 and cell count)
+    Vector3f min_point{-0.5f, -0.5f, -1.0f};
+    float scale = 1.0f;
+    int32_t ints[3] = {10, 100, 100000};
+    int64_t counts[6] = {19, 0, 0, 0, 0, 0};
+    if (config >= 0) {
+      size_t nf = 0, ni = 0;
+      const float *f = (const float *)tdt_scene_blob(scene, 6, &nf);
+      const int32_t *in = (const int32_t *)tdt_scene_blob(scene, 7, &ni);
+      if (nf < 28 || ni < 12 || tdt_scene_counts(scene, counts)) { std::fprintf(stderr, "config %d: no octree parameters\n", config); return 1; }
+      min_point = {f[0], f[1], f[2]}; scale = f[4];
+      std::memcpy(ints, in, sizeof ints);
+    }
     std::vector<VertexBufferObject> keep;
     for (unsigned slot = 0; slot <= 4; slot++) {
       size_t bytes = 0;
@@ -102,7 +123,7 @@ int main(int argc, char **argv) {
     }
     tdt_scene_destroy(scene);
     // main.rs:455-468
-    Octree octree = Octree::new_({-0.5f, -0.5f, -1.0f}, 1.0f, 10, 100000, 19, 100);
+    Octree octree = Octree::new_(min_point, scale, ints[0], ints[2], (int)counts[0], ints[1]);
     octree.init_global_buffers(ctx);
     if (!edit.empty()) {                                                                  // main.rs:555-569, one click
       std::vector<float> delta(500, 0.0f);
@@ -115,6 +136,15 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
                   h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
+    }
+    if (compact) {
+      auto print = [](const char *when, const std::array<int64_t, 6> &c) {
+        std::printf("census %s reachable %lld leaves %lld voxels %lld max_cell %lld buffer_cells %lld counter %lld\n", when, (long long)c[0],
+                    (long long)c[1], (long long)c[2], (long long)c[3], (long long)c[4], (long long)c[5]);
+      };
+      print("before", octree.census(ctx));
+      std::printf("compact cells %u\n", octree.compact(ctx));
+      print("after", octree.census(ctx));
     }
     // main.rs:578-580
     octree.vao.bind();

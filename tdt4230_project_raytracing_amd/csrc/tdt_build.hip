@@ -203,6 +203,24 @@ __global__ __launch_bounds__(256) void build_materials_kernel(const uint32_t *us
   for (int c = 0; c < 3; c++) albedos[3u * m + c] = (float)rgb[3u * i + c] / 255.0f;
 }
 
+size_t sort_hist_words(uint32_t n) { return (size_t)256 * ((n + kSortTile - 1) / kSortTile); }
+size_t sort_scratch_words(uint32_t n) { return scan_scratch_words(sort_hist_words(n)); }
+
+hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *k_alt, uint32_t *v_alt, uint32_t n, uint32_t *hist,
+                          uint32_t *scratch) {
+  if (n == 0) return hipSuccess;
+  const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
+  for (int pass = 0; pass < 4; pass++) {
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(256), 0, st, (const uint32_t *)k, n, pass * 8, tiles, hist);
+    const hipError_t e = exclusive_scan_u32(st, hist, hist, 256u * tiles, scratch);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(256), 0, st, (const uint32_t *)k, (const uint32_t *)v, n, pass * 8, tiles,
+                       (const uint32_t *)hist, k_alt, v_alt);
+    std::swap(k, k_alt); std::swap(v, v_alt);
+  }
+  return hipGetLastError();
+}
+
 namespace {
 
 struct DeviceArena {          // temporaries of one build, freed together
@@ -228,16 +246,9 @@ int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const Key
   KeyArgs A = key_args; A.vox = d_vox; A.n = n;
   hipLaunchKernelGGL(build_keys_kernel, dim3(blocks(n)), dim3(256), 0, st, A, k0, v0);
   // sort
-  const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
-  TDT_ALLOC(hist, uint32_t, (size_t)256 * tiles);
-  TDT_ALLOC(hscr, uint32_t, scan_scratch_words((size_t)256 * tiles));
-  for (int pass = 0; pass < 4; pass++) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(256), 0, st, (const uint32_t *)k0, n, pass * 8, tiles, hist);
-    TDT_HIP(ctx, exclusive_scan_u32(st, hist, hist, 256u * tiles, hscr));
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(256), 0, st, (const uint32_t *)k0, (const uint32_t *)v0, n, pass * 8, tiles,
-                       (const uint32_t *)hist, k1, v1);
-    std::swap(k0, k1); std::swap(v0, v1);
-  }
+  TDT_ALLOC(hist, uint32_t, sort_hist_words(n));
+  TDT_ALLOC(hscr, uint32_t, sort_scratch_words(n));
+  TDT_HIP(ctx, sort_pairs_u32(st, k0, v0, k1, v1, n, hist, hscr));
   // level arrays: capacity of level l = min(n, 8^l)
   std::vector<uint32_t> cap(D + 1);
   for (int l = 1; l <= D; l++) { const unsigned long long c = 1ull << (3 * l); cap[l] = c < n ? (uint32_t)c : n; }
@@ -310,6 +321,14 @@ int replicate_to_front(tdt_ctx *front, tdt_ctx *m0, tdt_buffer *built, tdt_buffe
 }
 
 }  // namespace
+
+int build_cells_from_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, int depth, tdt_buffer **out, uint32_t *n_cells) {
+  KeyArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.ax = 0; A.ay = 1; A.az = 2; A.depth = depth;
+  return build_cells_device(ctx, d_vox, n, A, out, n_cells);
+}
+
 }  // namespace tdt
 
 extern "C" {

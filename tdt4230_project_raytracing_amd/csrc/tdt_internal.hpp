@@ -1,5 +1,6 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
-// tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits).
+// tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
+// tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -149,10 +150,21 @@ int multi_dispatch_resolve(tdt_compute *c, int width, int height, int depth, int
 int multi_dispatch_counted(tdt_compute *c, int width, int height, int depth, uint64_t counts[8]);
 int multi_forget_costs(tdt_ctx *ctx);
 tdt_ctx *multi_first_member(tdt_ctx *front);
+const std::vector<tdt_ctx *> &multi_members(tdt_ctx *front);
 
 // ---- tdt_edit.hip ----
 int launch_update(tdt_compute *c, int width, int height, int depth);
 void edit_scratch_destroy(tdt_ctx *ctx);
+
+// ---- tdt_build.hip: pieces of the builder other units reuse ----
+// stable LSD radix sort of n (key, value) pairs by the whole 32-bit key, asynchronous on `st`; k / v end up pointing at the
+// sorted arrays (the other pair is scratch); hist / scratch: sort_hist_words(n) / sort_scratch_words(n) words
+size_t sort_hist_words(uint32_t n);
+size_t sort_scratch_words(uint32_t n);
+hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *k_alt, uint32_t *v_alt, uint32_t n, uint32_t *hist,
+                          uint32_t *scratch);
+// tdt_octree_build_cells over n > 0 voxels {x, y, z, material + 1} already in device memory of ctx (synchronises)
+int build_cells_from_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, int depth, tdt_buffer **out, uint32_t *n_cells);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -410,6 +410,7 @@ int multi_dispatch_counted(tdt_compute *c, int width, int height, int depth, uin
 }
 
 tdt_ctx *multi_first_member(tdt_ctx *front) { return front->multi->member[0]; }
+const std::vector<tdt_ctx *> &multi_members(tdt_ctx *front) { return front->multi->member; }
 
 int multi_forget_costs(tdt_ctx *front) {
   for (tdt_ctx *m : front->multi->member) (void)tdt_forget_costs(m);

@@ -98,6 +98,9 @@ SYMBOLS = [
     ("tdt_raycast", _I, [_P, _P, _S, _P]),
     ("tdt_raycast_device", _I, [_P, _P, _S, _P]),
     ("tdt_pick_pixels", _I, [_P, _P, _S, _I, _P, _P]),
+    ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -221,6 +224,30 @@ class Context:
         out = np.zeros(r.shape[0], RAY_HIT_DTYPE)
         self.check(lib().tdt_raycast(self.h, r.ctypes.data, r.shape[0], out.ctypes.data))
         return out
+
+    CENSUS_FIELDS = ("reachable_cells", "leaf_nodes", "voxels", "max_cell", "buffer_cells", "counter")
+
+    def octree_census(self):
+        """tdt_octree_census: what a walk of the bound tree (slots 0, 7) reaches, as a dict of CENSUS_FIELDS; counter = the first word
+        of the atomic counter, -1 when none is bound."""
+        out = (ctypes.c_int64 * 6)()
+        self.check(lib().tdt_octree_census(self.h, out))
+        return dict(zip(self.CENSUS_FIELDS, [int(v) for v in out]))
+
+    def octree_extract(self):
+        """tdt_octree_extract: the bound tree's voxels as an (n, 4) int32 array {x, y, z, material + 1}, sorted by Morton key."""
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract(self.h, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def octree_compact(self):
+        """tdt_octree_compact: rewrite the bound cells buffer in place into the canonical tree of its voxels; returns its cell count."""
+        n = ctypes.c_uint32(0)
+        self.check(lib().tdt_octree_compact(self.h, ctypes.byref(n)))
+        return int(n.value)
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
@@ -548,6 +575,10 @@ class Renderer:
     def pick(self, xy, sample=0, return_rays=False):
         """ComputeShader.pick with this renderer's camera: what is under each pixel."""
         return self.shader.pick(xy, sample, return_rays)
+
+    def compact(self):
+        """Context.octree_compact on this renderer's scene: the number of cells the canonical tree takes."""
+        return self.ctx.octree_compact()
 
     def close(self):
         self.ctx.close()
