@@ -175,6 +175,7 @@ class ComputeShader {
     ctx_->check(tdt_dispatch_compute(program.id(), width, height, depth));
   }
   const int *group_size() const { return group_size_; }
+  Context &context() const { return *ctx_; }
   // NEW (the reference has no ray query): what the primary ray of each pixel (x, y) and sample `sample` hits first, traced from
   // this program's camera uniforms with the bits the renderer traces (tdt_pick_pixels); `rays` (may be null) receives the rays
   std::vector<tdt_ray_hit> pick(const std::vector<std::array<int32_t, 2>> &xy, int sample = 0, std::vector<float> *rays = nullptr) const {
@@ -254,6 +255,40 @@ class Octree {
     uint32_t n = 0;
     ctx.check(tdt_octree_compact(ctx.raw(), &n));
     return n;
+  }
+  // NEW: op (TDT_REGION_*) over the union of `regions`, brush material 0..253; the bound tree rebuilt in place in canonical
+  // form, merged LEAFs included (tdt_octree_edit_region); returns the number of cells
+  uint32_t edit_region(const Context &ctx, int op, const std::vector<tdt_region> &regions, int32_t material) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_region(ctx.raw(), op, regions.empty() ? nullptr : regions.data(), regions.size(), material, &n));
+    return n;
+  }
+  // NEW: op over a voxel list {x, y, z, material + 1} (last duplicate wins, off-grid voxels dropped; tdt_octree_edit_voxels)
+  uint32_t edit_voxels(const Context &ctx, int op, const std::vector<int32_t> &voxels_xyzm) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_voxels(ctx.raw(), op, voxels_xyzm.empty() ? nullptr : voxels_xyzm.data(), voxels_xyzm.size() / 4, &n));
+    return n;
+  }
+  // NEW: a brush click: pick pixel (x, y) of the raytracer's camera (sample 0) and on a hit apply `op` over a TDT_SHAPE_SPHERE
+  // of radius `size` or a TDT_SHAPE_BOX of half-width `size` centred on the grid voxel in front of the face (SET / FILL) or
+  // behind it (PAINT / CLEAR) (tdt_pick_grid_voxel).  Returns whether an edit ran; *hit receives the pick, *n_cells the size.
+  bool brush(const ComputeShader &raytracer, int x, int y, int shape, int size, int op, int32_t material, tdt_ray_hit *hit = nullptr,
+             uint32_t *n_cells = nullptr) const {
+    const tdt_ray_hit h = raytracer.pick({{{x, y}}}, 0)[0];
+    if (hit) *hit = h;
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    const int place = op == TDT_REGION_SET || op == TDT_REGION_FILL ? 1 : 0;
+    int32_t c[3];
+    if (tdt_pick_grid_voxel(&h, floats, ints, place, c) != 0) return false;                  // miss / stale record / outside
+    tdt_region r{};
+    r.shape = shape;
+    for (int a = 0; a < 3; a++) r.a[a] = c[a];
+    if (shape == TDT_SHAPE_SPHERE) r.b[0] = size;
+    else for (int a = 0; a < 3; a++) { r.a[a] = c[a] - size; r.b[a] = c[a] + size; }
+    const uint32_t n = edit_region(raytracer.context(), op, {r}, material);
+    if (n_cells) *n_cells = n;
+    return true;
   }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one

@@ -163,6 +163,10 @@ int tdt_scene_from_ply(const tdt_ply *p, int max_iter, int z_up, tdt_scene **out
 typedef struct tdt_ray_hit tdt_ray_hit;
 int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, float value,
                         float delta_out[8]);
+/* The same finest-level cell as integer grid coordinates in [0, 2^max_depth)^3 (the k of snap's (k + 1/2) 2^-max_depth): just
+ * in front of the hit face (place = 1) or just behind it (place = 0).  How a click becomes a brush centre for
+ * tdt_octree_edit_region.  Same errors as tdt_pick_edit_delta. */
+int tdt_pick_grid_voxel(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, int32_t out[3]);
 
 #ifdef __cplusplus
 }

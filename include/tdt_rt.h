@@ -309,6 +309,50 @@ int tdt_octree_extract(tdt_ctx *ctx, int32_t *voxels_xyzm, size_t capacity, size
  * TDT_ERR_INVALID_VALUE, every byte left as it was.  Synchronous. */
 int tdt_octree_compact(tdt_ctx *ctx, uint32_t *n_cells);
 
+/* ---- region edits ----------------------------------------------------------------------------------------------------
+ * Change any set of voxels of any tree the library renders (merged LEAFs of built or compacted trees included) and leave it
+ * canonical.  V = the tree's voxel set (what tdt_octree_extract returns, over [0, 2^max_depth)^3), B = the brush's voxel set
+ * clipped to the grid; the bound cells buffer is rewritten IN PLACE into tdt_octree_build_cells(op(V, B), max_depth), by
+ * tdt_octree_compact's install rule (tail zeroed, counter = *n_cells, versions bumped), so an empty brush gives the
+ * compacted bytes.  For a voxel p:
+ *                      p in B, occupied    p in B, empty       p not in B
+ *   TDT_REGION_SET     brush material      brush material      unchanged
+ *   TDT_REGION_FILL    unchanged           brush material      unchanged
+ *   TDT_REGION_PAINT   brush material      stays empty         unchanged
+ *   TDT_REGION_CLEAR   removed             stays empty         unchanged
+ * Shapes, in exact integer arithmetic: box a = lo, b = hi, both inclusive, empty if lo > hi on an axis; sphere a = centre
+ * (anywhere), b[0] = radius >= 0, p inside when (x-cx)^2 + (y-cy)^2 + (z-cz)^2 <= r^2 (int64).  Several shapes: their union.
+ * Errors, with nothing written: a bad op or shape, a material outside 0..253, a LEAF value >= 254, SET / FILL shapes whose
+ * grid-clipped bounding boxes hold more than 2^26 candidate voxels together (TDT_REGION_BRUSH_CAP), or a result larger than
+ * the buffer (*n_cells then receives the cell count it needs): TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound:
+ * TDT_ERR_INCOMPLETE.  Each call is ordered after work already queued on the context's stream.  A multi-device context
+ * edits every replica (a failure leaves them all unchanged).  Synchronous. */
+enum { TDT_SHAPE_BOX = 0, TDT_SHAPE_SPHERE = 1 };
+enum { TDT_REGION_SET = 0, TDT_REGION_FILL = 1, TDT_REGION_PAINT = 2, TDT_REGION_CLEAR = 3 };
+#define TDT_REGION_BRUSH_CAP (1u << 26)
+typedef struct tdt_region {
+  int32_t shape;               /* TDT_SHAPE_* */
+  int32_t a[3];                /* box: lo; sphere: centre */
+  int32_t b[3];                /* box: hi; sphere: b[0] = radius */
+  int32_t pad;
+} tdt_region;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_region) == 32, "tdt_region is 32 bytes");
+#else
+_Static_assert(sizeof(tdt_region) == 32, "tdt_region is 32 bytes");
+#endif
+/* op over the union of n_regions shapes, brush material 0..253 (the LEAF value; voxel lists carry it + 1) */
+int tdt_octree_edit_region(tdt_ctx *ctx, int op, const tdt_region *regions, size_t n_regions, int32_t material, uint32_t *n_cells);
+/* op over n voxels {x, y, z, m} (per-voxel material + 1), by the builder's input rules: voxels outside the grid are
+ * dropped, of duplicates the last one wins; m must be 1..254 (TDT_ERR_INVALID_VALUE otherwise), except for
+ * TDT_REGION_CLEAR, which ignores it.  Stamps a model, or applies a batch of clicks. */
+int tdt_octree_edit_voxels(tdt_ctx *ctx, int op, const int32_t *voxels_xyzm, size_t n, uint32_t *n_cells);
+/* V and B intersected, as {x, y, z, material + 1}, Morton-sorted (tdt_octree_extract's order and rules: voxels_xyzm == NULL only counts;
+ * capacity < the count: TDT_ERR_INVALID_VALUE with *n_voxels set).  Copy / paste, and undo: clear a region, then
+ * tdt_octree_edit_voxels(SET, saved) puts it back.  A multi-device context answers from device_ids[0]. */
+int tdt_octree_extract_region(tdt_ctx *ctx, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm, size_t capacity,
+                              size_t *n_voxels);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -43,7 +43,8 @@ def build_host(force=False):
     return out
 
 
-DEVICE_UNITS = ("tdt_rt.hip", "tdt_multi.hip", "tdt_build.hip", "tdt_edit.hip", "tdt_query.hip", "tdt_compact.hip")
+DEVICE_UNITS = ("tdt_rt.hip", "tdt_multi.hip", "tdt_build.hip", "tdt_edit.hip", "tdt_query.hip", "tdt_compact.hip",
+                "tdt_region.hip")
 DEVICE_HEADERS = ("trace_device.hpp", "trace_params.h", "tdt_internal.hpp", "device_scan.hpp")
 
 

@@ -3,8 +3,8 @@
 // `src/renderer`), then the frame is read back and written as a PFM instead of being blitted to a window.
 //
 //   tdt_demo [--size WxH] [--spp N] [--bounce N] [--settings camera.ron] [--move KEYS] [--edit x,y,z,type,value]
-//            [--pick X,Y [--click left|right] [--material N]] [--compact] [--config N] [--device N] [--out frame.pfm]
-//            [--png frame.png]
+//            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
+//            [--op set|fill|paint|clear] [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -13,6 +13,10 @@
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
+// --brush sphere:R|box:R [--op set|fill|paint|clear] [--material N]: with --pick, a region edit instead of the click
+//   (Octree::brush): a sphere of radius R, or the cube of half-width R, centred on the grid voxel in front of the picked face
+//   (set, the default, / fill) or behind it (paint / clear), brush material N.  Prints the pick and the new cell count.
+// --box x0,y0,z0,x1,y1,z1 [--op ..] [--material N]: the same edit over a fixed box of grid voxels (both corners inclusive).
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -33,6 +37,8 @@ int main(int argc, char **argv) {
   std::vector<float> edit;
   int pick_x = -1, pick_y = -1, material = 1;
   bool place = true, compact = false;
+  int brush_shape = -1, brush_size = 0, op = TDT_REGION_SET;
+  std::vector<int32_t> box;
   int config = -1;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -50,6 +56,19 @@ int main(int argc, char **argv) {
     else if (a == "--click") { const std::string v = next(); if (v != "left" && v != "right") { std::fprintf(stderr, "--click left|right\n"); return 2; } place = v == "left"; }
     else if (a == "--material") material = std::atoi(next());
     else if (a == "--compact") compact = true;
+    else if (a == "--brush") {
+      char kind[16] = {0};
+      if (std::sscanf(next(), "%15[a-z]:%d", kind, &brush_size) != 2 || brush_size < 0 || (std::strcmp(kind, "sphere") && std::strcmp(kind, "box"))) {
+        std::fprintf(stderr, "--brush sphere:R|box:R\n"); return 2;
+      }
+      brush_shape = std::strcmp(kind, "sphere") ? TDT_SHAPE_BOX : TDT_SHAPE_SPHERE;
+    }
+    else if (a == "--box") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--box x0,y0,z0,x1,y1,z1\n"); return 2; } box.assign(v, v + 6); }
+    else if (a == "--op") {
+      const std::string v = next();
+      if (v == "set") op = TDT_REGION_SET; else if (v == "fill") op = TDT_REGION_FILL; else if (v == "paint") op = TDT_REGION_PAINT;
+      else if (v == "clear") op = TDT_REGION_CLEAR; else { std::fprintf(stderr, "--op set|fill|paint|clear\n"); return 2; }
+    }
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -130,7 +149,20 @@ int main(int argc, char **argv) {
       std::copy(edit.begin(), edit.end(), delta.begin());
       octree.update_vbo(delta, 5, octree_update_program);
     }
-    if (pick_x >= 0) {                                                                   // main.rs:551-568, aimed at the pixel
+    if (!box.empty()) {
+      tdt_region r{};
+      r.shape = TDT_SHAPE_BOX;
+      for (int a = 0; a < 3; a++) { r.a[a] = box[a]; r.b[a] = box[3 + a]; }
+      std::printf("box cells %u\n", octree.edit_region(ctx, op, {r}, material));
+    }
+    if (pick_x >= 0 && brush_shape >= 0) {                                               // a brush click at the pixel
+      tdt_ray_hit h;
+      uint32_t cells = 0;
+      const bool edited = octree.brush(raytrace_program, pick_x, pick_y, brush_shape, brush_size, op, material, &h, &cells);
+      std::printf("pick %d,%d status %d material %u t %.9g point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d brush %s cells %u\n", pick_x, pick_y,
+                  h.status, h.material, h.t, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1], h.normal[2], h.fresh_record,
+                  edited ? "applied" : "none", cells);
+    } else if (pick_x >= 0) {                                                            // main.rs:551-568, aimed at the pixel
       tdt_ray_hit h;
       const bool edited = octree.click(raytrace_program, pick_x, pick_y, place, (float)material, octree_update_program, &h);
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",

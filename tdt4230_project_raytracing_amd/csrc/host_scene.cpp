@@ -664,9 +664,12 @@ int tdt_scene_from_ply(const tdt_ply *p, int max_iter, int z_up, tdt_scene **out
 // query found instead of at a point a fixed distance in front of the camera.  Arithmetic in double: the face point is within a few
 // ulps of a cell boundary, the half-cell offset moves it well inside the neighbouring (place) or the hit (remove) finest cell, and
 // the snapped centre (k + 1/2) 2^-max_depth is exact in float for max_depth <= 23.
-int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, float value,
-                        float delta_out[8]) {
-  if (!hit || !octree_floats || !octree_ints || !delta_out) { g_err = "null argument"; return TDT_ERR_INVALID_VALUE; }
+}  // extern "C"
+
+namespace {
+// the finest-level cell just outside (place) or just inside (remove) the hit face: its integer grid coordinates k[3]
+int pick_cell(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, double k[3]) {
+  if (!hit || !octree_floats || !octree_ints) { g_err = "null argument"; return TDT_ERR_INVALID_VALUE; }
   if (place != 0 && place != 1) { g_err = "place must be 1 (place a voxel) or 0 (remove one)"; return TDT_ERR_INVALID_VALUE; }
   if (hit->status != TDT_RAY_HIT) { g_err = "the ray did not hit a voxel"; return TDT_ERR_INVALID_VALUE; }
   if (!hit->fresh_record) { g_err = "the hit's record is a stale temporary: no face to edit at"; return TDT_ERR_INVALID_VALUE; }
@@ -674,17 +677,37 @@ int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], co
   const double scale = octree_floats[4];
   if (depth < 1 || depth > 23 || !(scale > 0.0) || !std::isfinite(scale)) { g_err = "octree max_depth outside [1, 23] or scale not positive"; return TDT_ERR_INVALID_VALUE; }
   const double cells = std::ldexp(1.0, depth), half = 0.5 / cells, side = place ? 1.0 : -1.0;
-  float pos[3];
   for (int a = 0; a < 3; a++) {
     const double q = ((double)hit->point[a] - (double)octree_floats[a]) / scale + side * (double)hit->normal[a] * half;
-    const double k = std::floor(q * cells);
-    if (!(k >= 0.0 && k < cells)) { g_err = "the edit position lies outside the octree"; return TDT_ERR_INVALID_VALUE; }   // point_inside, octree.rs:165-168
-    pos[a] = (float)((k + 0.5) / cells);
+    k[a] = std::floor(q * cells);
+    if (!(k[a] >= 0.0 && k[a] < cells)) { g_err = "the edit position lies outside the octree"; return TDT_ERR_INVALID_VALUE; }   // point_inside, octree.rs:165-168
   }
-  delta_out[0] = pos[0]; delta_out[1] = pos[1]; delta_out[2] = pos[2];
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, float value,
+                        float delta_out[8]) {
+  if (!delta_out) { g_err = "null argument"; return TDT_ERR_INVALID_VALUE; }
+  double k[3];
+  if (const int rc = pick_cell(hit, octree_floats, octree_ints, place, k)) return rc;
+  const double cells = std::ldexp(1.0, octree_ints[0]);
+  for (int a = 0; a < 3; a++) delta_out[a] = (float)((k[a] + 0.5) / cells);
   delta_out[3] = place ? 2.0f : 0.0f;                // DeltaNode.type: LEAF (ClickEvent::Left) / EMPTY (ClickEvent::Right)
   delta_out[4] = value;
   delta_out[5] = delta_out[6] = delta_out[7] = 0.0f;  // std430 padding of the 32-byte stride (octree_update.comp:41-48)
+  g_err.clear();
+  return 0;
+}
+
+// the same cell as grid coordinates: a brush centre for tdt_octree_edit_region
+int tdt_pick_grid_voxel(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, int32_t out[3]) {
+  if (!out) { g_err = "null argument"; return TDT_ERR_INVALID_VALUE; }
+  double k[3];
+  if (const int rc = pick_cell(hit, octree_floats, octree_ints, place, k)) return rc;
+  for (int a = 0; a < 3; a++) out[a] = (int32_t)k[a];
   g_err.clear();
   return 0;
 }

@@ -141,19 +141,21 @@ __global__ __launch_bounds__(256) void compact_expand_kernel(const uint32_t *sta
   out[v] = make_int4((int)compact3(key >> 2), (int)compact3(key >> 1), (int)compact3(key), (int)(leaf_val[order[lo]] + 1u));
 }
 
+// the bound slots 0 / 7 of ctx (a single-device context); errors are reported on `front`
+int walk_inputs(tdt_ctx *front, tdt_ctx *ctx, int *depth) {
+  if (!ctx->ssbo[TDT_SLOT_CELLS]) return fail(front, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot 0");
+  if (!ctx->ssbo[TDT_SLOT_OCTREE_INTS]) return fail(front, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot 7");
+  if (ctx->ssbo[TDT_SLOT_OCTREE_INTS]->bytes < 4) return fail(front, TDT_ERR_INVALID_VALUE, "octree uniform buffer (slot 7) is too small");
+  int32_t d = 0;
+  std::memcpy(&d, ctx->ssbo[TDT_SLOT_OCTREE_INTS]->shadow, sizeof d);
+  if (d < 1 || d > kMaxWalkDepth) return fail(front, TDT_ERR_INVALID_VALUE, "max_depth must be 1..10 to walk the tree");
+  *depth = d;
+  return TDT_OK;
+}
+
 namespace {
 
-struct Scratch {               // device temporaries of one operation, freed together
-  std::vector<void *> ptrs;
-  ~Scratch() { release(); }
-  void release() { for (void *p : ptrs) (void)hipFree(p); ptrs.clear(); }
-  template <class T> T *get(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-};
+using Scratch = DeviceScratch;
 inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the octree walk";
 
@@ -167,18 +169,6 @@ struct Walk {
   uint32_t *leaf_start = nullptr, *leaf_val = nullptr; uint8_t *leaf_lvl = nullptr;
   uint32_t n_leaves = 0;
 };
-
-// the bound slots 0 / 7 of ctx (a single-device context); errors are reported on `front`
-int walk_inputs(tdt_ctx *front, tdt_ctx *ctx, int *depth) {
-  if (!ctx->ssbo[TDT_SLOT_CELLS]) return fail(front, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot 0");
-  if (!ctx->ssbo[TDT_SLOT_OCTREE_INTS]) return fail(front, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot 7");
-  if (ctx->ssbo[TDT_SLOT_OCTREE_INTS]->bytes < 4) return fail(front, TDT_ERR_INVALID_VALUE, "octree uniform buffer (slot 7) is too small");
-  int32_t d = 0;
-  std::memcpy(&d, ctx->ssbo[TDT_SLOT_OCTREE_INTS]->shadow, sizeof d);
-  if (d < 1 || d > kMaxWalkDepth) return fail(front, TDT_ERR_INVALID_VALUE, "max_depth must be 1..10 to walk the tree");
-  *depth = d;
-  return TDT_OK;
-}
 
 // the level-by-level walk of the bound tree; leaves = keep the leaf records for an expansion.  One host synchronisation,
 // unless shared cells overflow the frontier capacities (then once more per retry).
@@ -280,29 +270,30 @@ int expand_voxels(tdt_ctx *front, tdt_ctx *ctx, Walk &W, Scratch &S, int4 **out)
 
 tdt_ctx *walk_member(tdt_ctx *ctx) { return ctx->multi ? multi_first_member(ctx) : ctx; }
 
-// compaction of one single-device context
-int compact_one(tdt_ctx *front, tdt_ctx *ctx, uint32_t *n_cells) {
+}  // namespace
+
+int tree_voxels(tdt_ctx *front, tdt_ctx *ctx, uint32_t leaf_limit, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
+  *out = nullptr; *n = 0;
   Walk W;
   if (int rc = walk_tree(front, ctx, true, W)) return rc;
-  if (W.meta.leaves && W.meta.max_leaf >= 254u)
-    return fail(front, TDT_ERR_INVALID_VALUE, "a LEAF value >= 254 cannot be rebuilt (the builder's materials are 0..253)");
+  *depth = W.depth;
+  if (W.meta.leaves && W.meta.max_leaf >= leaf_limit)
+    return fail(front, TDT_ERR_INVALID_VALUE, leaf_limit == 254u ? "a LEAF value >= 254 cannot be rebuilt (the builder's materials are 0..253)"
+                                                                 : "a LEAF value >= 2^31 - 1 does not fit the voxel list");
+  if (W.meta.voxels == 0) return TDT_OK;
+  if (int rc = expand_voxels(front, ctx, W, S, out)) return rc;
+  *n = (uint32_t)W.meta.voxels;
+  return TDT_OK;                                          // the walk's leaf records are freed here: they are in *out now
+}
+
+int install_cells(tdt_ctx *front, tdt_ctx *ctx, tdt_buffer *built, uint32_t nc) {
   tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
   hipStream_t st = ctx->stream;
-  tdt_buffer *built = nullptr;
-  uint32_t nc = 1;
-  if (W.meta.voxels) {
-    Scratch S;
-    int4 *vox = nullptr;
-    if (int rc = expand_voxels(front, ctx, W, S, &vox)) return rc;
-    W.mem.release();                                      // the leaf records are in `vox` now
-    const int rc = build_cells_from_device(ctx, (const int32_t *)vox, (uint32_t)W.meta.voxels, W.depth, &built, &nc);
-    if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
-  }
   const size_t bytes = (size_t)nc * 64;
   if (bytes > cb->bytes) {
     if (built) tdt_buffer_destroy(built);
     return fail(front, TDT_ERR_INVALID_VALUE, "the canonical tree (" + std::to_string(nc) + " cells) does not fit in the cells buffer (" +
-                                                  std::to_string(W.buffer_cells) + " cells)");
+                                                  std::to_string(cb->bytes / 64) + " cells)");
   }
   hipError_t e = built ? hipMemcpyAsync(cb->dev, built->dev, bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync(cb->dev, 0, bytes, st);
   if (e == hipSuccess && cb->bytes > bytes) e = hipMemsetAsync((char *)cb->dev + bytes, 0, cb->bytes - bytes, st);
@@ -316,6 +307,27 @@ int compact_one(tdt_ctx *front, tdt_ctx *ctx, uint32_t *n_cells) {
   cb->version += 0x100000000ull;
   if (counter) { std::memcpy(counter->shadow, &nc, sizeof nc); counter->version += 0x100000000ull; }
   if (built) tdt_buffer_destroy(built);
+  return TDT_OK;
+}
+
+namespace {
+
+// compaction of one single-device context
+int compact_one(tdt_ctx *front, tdt_ctx *ctx, uint32_t *n_cells) {
+  tdt_buffer *built = nullptr;
+  uint32_t nc = 1;
+  {
+    Scratch S;
+    int4 *vox = nullptr;
+    uint32_t nv = 0;
+    int depth = 0;
+    if (int rc = tree_voxels(front, ctx, 254u, S, &vox, &nv, &depth)) return rc;
+    if (nv) {
+      const int rc = build_cells_from_device(ctx, (const int32_t *)vox, nv, depth, &built, &nc);
+      if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
+    }
+  }
+  if (int rc = install_cells(front, ctx, built, nc)) return rc;
   *n_cells = nc;
   return TDT_OK;
 }

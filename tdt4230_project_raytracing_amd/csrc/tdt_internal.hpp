@@ -1,6 +1,6 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
-// tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction).
+// tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -165,6 +165,27 @@ hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *
                           uint32_t *scratch);
 // tdt_octree_build_cells over n > 0 voxels {x, y, z, material + 1} already in device memory of ctx (synchronises)
 int build_cells_from_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, int depth, tdt_buffer **out, uint32_t *n_cells);
+
+// ---- tdt_compact.hip: pieces region edits reuse ----
+struct DeviceScratch {         // device temporaries of one operation, freed together
+  std::vector<void *> ptrs;
+  ~DeviceScratch() { release(); }
+  void release() { for (void *p : ptrs) (void)hipFree(p); ptrs.clear(); }
+  template <class T> T *get(size_t n) {
+    void *p = nullptr;
+    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
+    ptrs.push_back(p);
+    return (T *)p;
+  }
+};
+// slot 0 / 7 bound and max_depth 1..10 on ctx (a single-device context); errors are reported on `front`
+int walk_inputs(tdt_ctx *front, tdt_ctx *ctx, int *depth);
+// the bound tree's voxels {x, y, z, value + 1}, Morton-sorted, in device memory of ctx (*out allocated in S, null when
+// *n == 0).  A LEAF value >= leaf_limit: TDT_ERR_INVALID_VALUE.  Ordered after queued work; one host synchronisation.
+int tree_voxels(tdt_ctx *front, tdt_ctx *ctx, uint32_t leaf_limit, DeviceScratch &S, int4 **out, uint32_t *n, int *depth);
+// the fit check and in-place install of compaction: nc cells of `built` (null: one all-EMPTY root) over the bound cells
+// buffer, tail zeroed, counter = nc, versions bumped.  Too large: TDT_ERR_INVALID_VALUE, nothing written.  Takes `built`.
+int install_cells(tdt_ctx *front, tdt_ctx *ctx, tdt_buffer *built, uint32_t nc);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -286,6 +286,25 @@ def pick_edit_delta(hit, scene, place, value):
     return out
 
 
+def pick_grid_voxel(hit, scene, place):
+    """tdt_pick_grid_voxel: the (3,) int32 grid voxel just in front of the face `hit` found (place = 1) or just behind it
+    (place = 0) — the cell pick_edit_delta aims at, as a brush centre for rt.Context.octree_edit_region.  Raises ValueError
+    when the hit cannot be edited at."""
+    L = lib()
+    L.tdt_pick_grid_voxel.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
+    rec = np.ascontiguousarray(np.asarray(hit).reshape(-1)[:1])
+    if rec.dtype.itemsize != 64:
+        raise TypeError("hit must be a tdt_ray_hit record (rt.RAY_HIT_DTYPE)")
+    floats, ints = (scene.blobs[6], scene.blobs[7]) if isinstance(scene, Scene) else scene
+    of = np.ascontiguousarray(np.asarray(floats).view(np.float32).reshape(-1)[:7], np.float32)
+    oi = np.ascontiguousarray(np.asarray(ints).view(np.int32).reshape(-1)[:3], np.int32)
+    out = np.zeros(3, np.int32)
+    rc = L.tdt_pick_grid_voxel(rec.ctypes.data, of.ctypes.data, oi.ctypes.data, int(place), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return out
+
+
 def scene_with_cell_count(scene, cell_count, zero_tail_nodes=0):
     """The same tree as a host with other conventions uploads it: Octree::init_global_buffers writes floats[6] = 1.0 / cell_count as
     f32 and ints[2] = cell_count (octree.rs:49, 79) — the reference's main.rs passes 100000 — and a pre-allocated cells buffer ends in

@@ -38,6 +38,38 @@ def hits_from_bytes(b):
     return np.ascontiguousarray(b, np.uint8).reshape(-1, 64).view(RAY_HIT_DTYPE).reshape(-1)
 
 
+# region edits (include/tdt_rt.h): shapes, ops, and struct tdt_region
+SHAPE_BOX, SHAPE_SPHERE = 0, 1
+REGION_SET, REGION_FILL, REGION_PAINT, REGION_CLEAR = 0, 1, 2, 3
+REGION_BRUSH_CAP = 1 << 26
+
+
+class Region(ctypes.Structure):
+    """struct tdt_region: box a = lo, b = hi (inclusive); sphere a = centre, b[0] = radius."""
+    _fields_ = [("shape", ctypes.c_int32), ("a", ctypes.c_int32 * 3), ("b", ctypes.c_int32 * 3), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Region) == 32
+
+
+def box(lo, hi):
+    return Region(SHAPE_BOX, (ctypes.c_int32 * 3)(*[int(v) for v in lo]), (ctypes.c_int32 * 3)(*[int(v) for v in hi]), 0)
+
+
+def sphere(centre, radius):
+    return Region(SHAPE_SPHERE, (ctypes.c_int32 * 3)(*[int(v) for v in centre]), (ctypes.c_int32 * 3)(int(radius), 0, 0), 0)
+
+
+def _regions(regions):
+    """One Region, or a sequence of them -> (ctypes array or None, count)."""
+    if isinstance(regions, Region):
+        regions = [regions]
+    regions = list(regions)
+    if not regions:
+        return None, 0
+    return (Region * len(regions))(*regions), len(regions)
+
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -101,6 +133,9 @@ SYMBOLS = [
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_edit_region", _I, [_P, _I, _P, _S, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_edit_voxels", _I, [_P, _I, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_region", _I, [_P, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -248,6 +283,40 @@ class Context:
         n = ctypes.c_uint32(0)
         self.check(lib().tdt_octree_compact(self.h, ctypes.byref(n)))
         return int(n.value)
+
+    def _check_edit(self, rc, n):
+        """check() for the region edits: a TdtError carries n_cells, the cell count a too-small buffer would need (else 0)."""
+        try:
+            self.check(rc)
+        except TdtError as e:
+            e.n_cells = int(n.value)
+            raise
+
+    def octree_edit_region(self, op, regions, material=0):
+        """tdt_octree_edit_region: op (REGION_*) over the union of `regions` (one Region or a list; see box / sphere) with brush
+        material 0..253, rebuilding the bound tree in place; returns the canonical tree's cell count."""
+        arr, k = _regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_region(self.h, int(op), arr, k, int(material), ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_edit_voxels(self, op, voxels):
+        """tdt_octree_edit_voxels: op over an (n, 4) int32 voxel list {x, y, z, m} (m = material + 1; last duplicate wins,
+        voxels off the grid are dropped); returns the canonical tree's cell count."""
+        v = np.ascontiguousarray(np.asarray(voxels, np.int32).reshape(-1, 4))
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_voxels(self.h, int(op), v.ctypes.data if len(v) else None, len(v), ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_region(self, regions):
+        """tdt_octree_extract_region: the bound tree's voxels inside the union of `regions`, (n, 4) int32, Morton-sorted."""
+        arr, k = _regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_region(self.h, arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_region(self.h, arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
