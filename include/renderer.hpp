@@ -290,6 +290,56 @@ class Octree {
     if (n_cells) *n_cells = n;
     return true;
   }
+  // NEW: connected components of the bound tree (tdt_octree_components): the table, numbered in the Morton order of each
+  // component's first voxel; labels (may be null) receive the component of every voxel of extract's list.  A count query costs
+  // a whole labelling, so this labels once: labels sized by a walk (tdt_octree_extract's count), the table by `capacity`; only a
+  // tree of more components is labelled again, into a table of the size the first call reported.
+  std::vector<tdt_component> components(const Context &ctx, int connectivity, int match, std::vector<uint32_t> *labels = nullptr,
+                                        size_t capacity = 4096) const {
+    size_t nv = 0, nc = 0;
+    if (labels) {
+      ctx.check(tdt_octree_extract(ctx.raw(), nullptr, 0, &nv));
+      labels->assign(nv, 0u);
+    }
+    std::vector<tdt_component> table(capacity ? capacity : 1);
+    auto run = [&]() {
+      return tdt_octree_components(ctx.raw(), connectivity, match, labels ? labels->data() : nullptr, labels ? labels->size() : 0, &nv,
+                                   table.data(), table.size(), &nc);
+    };
+    int rc = run();
+    if (rc == TDT_ERR_INVALID_VALUE && (nc > table.size() || (labels && nv > labels->size()))) {
+      table.resize(nc);
+      if (labels) labels->assign(nv, 0u);
+      rc = run();
+    }
+    ctx.check(rc);
+    table.resize(nc);
+    return table;
+  }
+  // NEW: op (TDT_REGION_PAINT / TDT_REGION_CLEAR) over the components `sel` selects among those holding one of the seed voxels
+  // (x, y, z triples; none: any) and touching `regions` (none: any); the bound tree rebuilt in place (tdt_octree_edit_connected)
+  uint32_t edit_connected(const Context &ctx, int op, const tdt_select &sel, const std::vector<int32_t> &seeds_xyz,
+                          const std::vector<tdt_region> &regions, int32_t material) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_connected(ctx.raw(), op, &sel, seeds_xyz.empty() ? nullptr : seeds_xyz.data(), seeds_xyz.size() / 3,
+                                        regions.empty() ? nullptr : regions.data(), regions.size(), material, &n));
+    return n;
+  }
+  // NEW: a flood click, the paint bucket / delete-object tool: pick pixel (x, y) of the raytracer's camera (sample 0) and on a
+  // hit apply `op` to the components `sel` selects that hold the grid voxel behind the face (tdt_pick_grid_voxel, place 0).
+  // Returns whether an edit ran; *hit receives the pick, *n_cells the size.
+  bool flood(const ComputeShader &raytracer, int x, int y, int op, const tdt_select &sel, int32_t material, tdt_ray_hit *hit = nullptr,
+             uint32_t *n_cells = nullptr) const {
+    const tdt_ray_hit h = raytracer.pick({{{x, y}}}, 0)[0];
+    if (hit) *hit = h;
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    int32_t c[3];
+    if (tdt_pick_grid_voxel(&h, floats, ints, 0, c) != 0) return false;                      // miss / stale record / outside
+    const uint32_t n = edit_connected(raytracer.context(), op, sel, {c[0], c[1], c[2]}, {}, material);
+    if (n_cells) *n_cells = n;
+    return true;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

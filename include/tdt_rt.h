@@ -353,6 +353,71 @@ int tdt_octree_edit_voxels(tdt_ctx *ctx, int op, const int32_t *voxels_xyzm, siz
 int tdt_octree_extract_region(tdt_ctx *ctx, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm, size_t capacity,
                               size_t *n_voxels);
 
+/* ---- connected components ------------------------------------------------------------------------------------------------
+ * Act on objects rather than shapes.  V = the bound tree's voxel set, exactly what tdt_octree_extract returns, in its Morton
+ * order.  Two voxels of V are neighbours when they share a face (connectivity 6) or a face, an edge or a corner
+ * (connectivity 26); nothing wraps around the grid (a voxel at x = 2^max_depth - 1 has no +x neighbour).  With
+ * TDT_MATCH_ANY any two neighbours are connected, with TDT_MATCH_MATERIAL only neighbours of equal material + 1.  A component
+ * is a maximal connected set.  Numbering is canonical: components are numbered 0, 1, ... in the Morton order of their first
+ * (lowest-key) voxel, so a result does not depend on scheduling and compares bit for bit.
+ *
+ * Selection (tdt_select): a component C is selected when min_voxels <= |C| <= max_voxels, and n_seeds == 0 or C holds one of
+ * the seed voxels {x, y, z}, and n_regions == 0 or some voxel of C lies inside the union of the regions (tdt_region shapes,
+ * the same exact integer test as region edits); invert = 1 flips the selection.  Seeds off the grid or on empty voxels
+ * match nothing (a click on air does nothing).  The user stories:
+ *   paint bucket      {seed}, TDT_MATCH_MATERIAL, TDT_REGION_PAINT
+ *   delete object     {seed}, TDT_MATCH_ANY, TDT_REGION_CLEAR
+ *   remove debris     min_voxels = 1, max_voxels = N - 1, TDT_REGION_CLEAR
+ *   remove floating   regions = {ground box}, invert = 1, TDT_REGION_CLEAR
+ *
+ * Errors, with nothing written: connectivity other than 6 or 26, match outside 0..1, invert outside 0..1, min_voxels >
+ * max_voxels, an op other than PAINT / CLEAR, a material outside 0..253, NULL seeds or regions with a count above 0, a bad
+ * shape, a LEAF value >= 254 in the edit form, or a result larger than the buffer (*n_cells then receives the cell count it
+ * needs): TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Each call is ordered after the work already queued
+ * on the context's stream.  Synchronous.  A multi-device context answers labels and extraction from device_ids[0] and edits
+ * every replica. */
+enum { TDT_MATCH_ANY = 0, TDT_MATCH_MATERIAL = 1 };
+typedef struct tdt_component {
+  uint32_t first;              /* index in tdt_octree_extract's order of its first voxel */
+  uint32_t voxels;             /* its size */
+  int32_t lo[3];               /* bounding box, inclusive */
+  int32_t hi[3];
+  int32_t material;            /* material + 1 of its first voxel */
+  int32_t pad;
+} tdt_component;
+typedef struct tdt_select {
+  int32_t connectivity, match;
+  uint32_t min_voxels, max_voxels;   /* size window, inclusive */
+  int32_t invert;              /* 1: act on the components NOT selected */
+  int32_t pad;
+} tdt_select;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_component) == 40, "tdt_component is 40 bytes");
+static_assert(sizeof(tdt_select) == 24, "tdt_select is 24 bytes");
+#else
+_Static_assert(sizeof(tdt_component) == 40, "tdt_component is 40 bytes");
+_Static_assert(sizeof(tdt_select) == 24, "tdt_select is 24 bytes");
+#endif
+/* labels[i] = the component of voxel i of tdt_octree_extract; *n_voxels, *n_components = the counts (both pointers required).
+ * NULL arrays: counts only; a capacity below its count: TDT_ERR_INVALID_VALUE with the counts set and nothing written.  A
+ * LEAF value >= 2^31 - 1: TDT_ERR_INVALID_VALUE (extract's limit).  Every call labels the whole tree, a count query too, so
+ * count-then-fill costs two labellings: size the labels by tdt_octree_extract(NULL)'s count (a walk only) and pass a generous
+ * table, calling again only when *n_components exceeds it. */
+int tdt_octree_components(tdt_ctx *ctx, int connectivity, int match, uint32_t *labels, size_t labels_capacity, size_t *n_voxels,
+                          tdt_component *components, size_t capacity, size_t *n_components);
+/* op = TDT_REGION_PAINT (every voxel of a selected component gets `material`) or TDT_REGION_CLEAR (removed); the tree is
+ * rewritten in place into tdt_octree_build_cells(result) by tdt_octree_compact's install rule, like tdt_octree_edit_region.
+ * seeds_xyz: n_seeds triples. */
+int tdt_octree_edit_connected(tdt_ctx *ctx, int op, const tdt_select *sel, const int32_t *seeds_xyz, size_t n_seeds,
+                              const tdt_region *regions, size_t n_regions, int32_t material, uint32_t *n_cells);
+/* the selected components' voxels {x, y, z, material + 1}, Morton-sorted (tdt_octree_extract's order and rules: voxels_xyzm
+ * == NULL only counts; capacity < the count: TDT_ERR_INVALID_VALUE with *n_voxels set).  A count query labels the tree too:
+ * tdt_octree_extract(NULL)'s count (a walk only) bounds the result.  Copy, and undo: extract, edit, then
+ * tdt_octree_edit_voxels(TDT_REGION_SET, saved). */
+int tdt_octree_extract_connected(tdt_ctx *ctx, const tdt_select *sel, const int32_t *seeds_xyz, size_t n_seeds,
+                                 const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm, size_t capacity,
+                                 size_t *n_voxels);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

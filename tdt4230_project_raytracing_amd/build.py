@@ -44,8 +44,8 @@ def build_host(force=False):
 
 
 DEVICE_UNITS = ("tdt_rt.hip", "tdt_multi.hip", "tdt_build.hip", "tdt_edit.hip", "tdt_query.hip", "tdt_compact.hip",
-                "tdt_region.hip")
-DEVICE_HEADERS = ("trace_device.hpp", "trace_params.h", "tdt_internal.hpp", "device_scan.hpp")
+                "tdt_region.hip", "tdt_connect.hip")
+DEVICE_HEADERS = ("trace_device.hpp", "trace_params.h", "tdt_internal.hpp", "device_scan.hpp", "region_device.hpp")
 
 
 def build_device(force=False, extra_flags=(), out=None):

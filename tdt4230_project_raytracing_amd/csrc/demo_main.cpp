@@ -4,7 +4,8 @@
 //
 //   tdt_demo [--size WxH] [--spp N] [--bounce N] [--settings camera.ron] [--move KEYS] [--edit x,y,z,type,value]
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
-//            [--op set|fill|paint|clear] [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
+//            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
+//            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -17,6 +18,11 @@
 //   (Octree::brush): a sphere of radius R, or the cube of half-width R, centred on the grid voxel in front of the picked face
 //   (set, the default, / fill) or behind it (paint / clear), brush material N.  Prints the pick and the new cell count.
 // --box x0,y0,z0,x1,y1,z1 [--op ..] [--material N]: the same edit over a fixed box of grid voxels (both corners inclusive).
+// --flood paint|clear [--match any|material] [--connect 6|26] [--material N]: with --pick, the paint bucket / delete-object
+//   tool (Octree::flood): the connected component that holds the grid voxel behind the picked face is painted with material N
+//   or removed (neighbours by face, 6, the default, or also by edge and corner, 26; any voxel, the default, or only the same
+//   material).  Prints the pick and the new cell count.
+// --components [--connect 6|26] [--match any|material]: prints the component count and the largest component's size.
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -38,6 +44,8 @@ int main(int argc, char **argv) {
   int pick_x = -1, pick_y = -1, material = 1;
   bool place = true, compact = false;
   int brush_shape = -1, brush_size = 0, op = TDT_REGION_SET;
+  int flood_op = -1, connect = 6, match = TDT_MATCH_ANY;
+  bool components = false;
   std::vector<int32_t> box;
   int config = -1;
   for (int i = 1; i < argc; i++) {
@@ -69,6 +77,18 @@ int main(int argc, char **argv) {
       if (v == "set") op = TDT_REGION_SET; else if (v == "fill") op = TDT_REGION_FILL; else if (v == "paint") op = TDT_REGION_PAINT;
       else if (v == "clear") op = TDT_REGION_CLEAR; else { std::fprintf(stderr, "--op set|fill|paint|clear\n"); return 2; }
     }
+    else if (a == "--flood") {
+      const std::string v = next();
+      if (v == "paint") flood_op = TDT_REGION_PAINT; else if (v == "clear") flood_op = TDT_REGION_CLEAR;
+      else { std::fprintf(stderr, "--flood paint|clear\n"); return 2; }
+    }
+    else if (a == "--match") {
+      const std::string v = next();
+      if (v == "any") match = TDT_MATCH_ANY; else if (v == "material") match = TDT_MATCH_MATERIAL;
+      else { std::fprintf(stderr, "--match any|material\n"); return 2; }
+    }
+    else if (a == "--connect") { connect = std::atoi(next()); if (connect != 6 && connect != 26) { std::fprintf(stderr, "--connect 6|26\n"); return 2; } }
+    else if (a == "--components") components = true;
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -155,7 +175,16 @@ int main(int argc, char **argv) {
       for (int a = 0; a < 3; a++) { r.a[a] = box[a]; r.b[a] = box[3 + a]; }
       std::printf("box cells %u\n", octree.edit_region(ctx, op, {r}, material));
     }
-    if (pick_x >= 0 && brush_shape >= 0) {                                               // a brush click at the pixel
+    if (pick_x >= 0 && flood_op >= 0) {                                                  // a flood click at the pixel
+      tdt_ray_hit h;
+      uint32_t cells = 0;
+      tdt_select sel{};
+      sel.connectivity = connect; sel.match = match; sel.min_voxels = 0; sel.max_voxels = 0xFFFFFFFFu;
+      const bool edited = octree.flood(raytrace_program, pick_x, pick_y, flood_op, sel, material, &h, &cells);
+      std::printf("pick %d,%d status %d material %u t %.9g point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d flood %s cells %u\n", pick_x, pick_y,
+                  h.status, h.material, h.t, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1], h.normal[2], h.fresh_record,
+                  edited ? "applied" : "none", cells);
+    } else if (pick_x >= 0 && brush_shape >= 0) {                                        // a brush click at the pixel
       tdt_ray_hit h;
       uint32_t cells = 0;
       const bool edited = octree.brush(raytrace_program, pick_x, pick_y, brush_shape, brush_size, op, material, &h, &cells);
@@ -168,6 +197,12 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
                   h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
+    }
+    if (components) {
+      const std::vector<tdt_component> table = octree.components(ctx, connect, match);
+      uint32_t largest = 0;
+      for (const tdt_component &c : table) largest = c.voxels > largest ? c.voxels : largest;
+      std::printf("components %zu largest %u\n", table.size(), largest);
     }
     if (compact) {
       auto print = [](const char *when, const std::array<int64_t, 6> &c) {

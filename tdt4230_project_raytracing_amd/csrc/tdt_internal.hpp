@@ -1,6 +1,7 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
-// tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits).
+// tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
+// tdt_connect.hip: connected components).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,6 +187,21 @@ int tree_voxels(tdt_ctx *front, tdt_ctx *ctx, uint32_t leaf_limit, DeviceScratch
 // the fit check and in-place install of compaction: nc cells of `built` (null: one all-EMPTY root) over the bound cells
 // buffer, tail zeroed, counter = nc, versions bumped.  Too large: TDT_ERR_INVALID_VALUE, nothing written.  Takes `built`.
 int install_cells(tdt_ctx *front, tdt_ctx *ctx, tdt_buffer *built, uint32_t nc);
+
+// ---- tdt_region.hip: the V-only path of region edits (PAINT / CLEAR / intersect) driven by a per-voxel membership ----
+struct VoxelSelect {
+  // queued on ctx's stream once V exists (nv > 0 voxels {x, y, z, value + 1}, Morton-sorted, in S): voxel i is selected when
+  // (*selected)[(*label)[i]] != 0; both arrays live in S.  Errors are reported on `front`.
+  virtual int run(tdt_ctx *front, tdt_ctx *ctx, const int4 *v, uint32_t nv, int depth, DeviceScratch &S, const uint32_t **label,
+                  const uint32_t **selected) = 0;
+ protected:
+  ~VoxelSelect() = default;
+};
+// op TDT_REGION_PAINT (material 0..253) or TDT_REGION_CLEAR of the selected voxels, on every replica, by
+// tdt_octree_edit_region's rules (the caller has checked op and material)
+int region_edit_selected(tdt_ctx *ctx, int op, int32_t material, VoxelSelect &sel, uint32_t *n_cells);
+// the selected voxels of device_ids[0]'s tree into host memory, by tdt_octree_extract_region's rules
+int region_extract_selected(tdt_ctx *ctx, VoxelSelect &sel, int32_t *host_out, size_t capacity, size_t *n_out);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -7,7 +7,8 @@
 //            ballot + popcount compacts the hits into (Morton key, material) pairs behind one atomic per wave.  Voxel list:
 //            one lane per voxel -> key (off-grid: the all-ones "dropped" key).  Then the builder's stable radix sort and a
 //            last-of-each-run unique.  Queued before the walk, so the walk's one host synchronisation also reads |B raw|.
-//            PAINT / CLEAR with shapes build no B: the merge tests each voxel of V against the shapes instead (cost |V|).
+//            PAINT / CLEAR with shapes build no B: the merge tests each voxel of V against the shapes instead (cost |V|), or
+//            reads a per-voxel membership a VoxelSelect computed on V (connected components, tdt_connect.hip).
 //   merge    rank merge: a V lane binary-searches B (lower bound j, slot i + j), a B lane binary-searches V (upper bound i,
 //            slot i + j): V before B on equal keys, so the slots are a permutation of the merged order.  The op table sets
 //            each slot's keep flag and voxel; exclusive_scan_u32 over the flags and one compaction give the result, sorted.
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "device_scan.hpp"
+#include "region_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
@@ -25,43 +27,6 @@ namespace tdt {
 constexpr uint32_t kRegionDropped = 0xFFFFFFFFu;   // key of a voxel outside the grid: sorts behind everything
 constexpr int kOpIntersect = 4;                    // extract_region: keep V inside the shapes
 constexpr unsigned long long kBrushCap = 1ull << 26;
-
-struct RegionShape {           // a tdt_region with its grid-clipped bounding box (lo, ext) and first candidate lane
-  int32_t shape, a[3], b[3];
-  int32_t lo[3];
-  uint32_t ext[3], lane0;
-};
-
-__device__ __forceinline__ uint32_t region_spread3(uint32_t v) {   // 10 bits -> every third bit (the builder's spread3)
-  v = (v | (v << 16)) & 0x030000FFu;
-  v = (v | (v << 8)) & 0x0300F00Fu;
-  v = (v | (v << 4)) & 0x030C30C3u;
-  v = (v | (v << 2)) & 0x09249249u;
-  return v;
-}
-__device__ __forceinline__ uint32_t region_compact3(uint32_t v) {
-  v &= 0x09249249u;
-  v = (v | (v >> 2)) & 0x030C30C3u;
-  v = (v | (v >> 4)) & 0x0300F00Fu;
-  v = (v | (v >> 8)) & 0x030000FFu;
-  v = (v | (v >> 16)) & 0x000003FFu;
-  return v;
-}
-__device__ __forceinline__ uint32_t region_key(int x, int y, int z) {
-  return (region_spread3((uint32_t)x) << 2) | (region_spread3((uint32_t)y) << 1) | region_spread3((uint32_t)z);
-}
-
-// the shape predicate in exact integer arithmetic: box lo <= p <= hi; sphere |p - c|^2 <= r^2 (each |d| <= r first, so the
-// sum of three squares <= 3 * 2^62 fits in 64 unsigned bits)
-__device__ __forceinline__ bool region_inside(const RegionShape &s, int x, int y, int z) {
-  if (s.shape == TDT_SHAPE_BOX)
-    return x >= s.a[0] && x <= s.b[0] && y >= s.a[1] && y <= s.b[1] && z >= s.a[2] && z <= s.b[2];
-  const long long r = s.b[0];
-  const long long dx = (long long)x - s.a[0], dy = (long long)y - s.a[1], dz = (long long)z - s.a[2];
-  if (dx > r || dx < -r || dy > r || dy < -r || dz > r || dz < -r) return false;
-  const unsigned long long d2 = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy) + (unsigned long long)(dz * dz);
-  return d2 <= (unsigned long long)(r * r);
-}
 
 // one lane per candidate voxel of every shape's clipped box; hits -> (key, m) behind one atomic per wave
 __global__ __launch_bounds__(256) void region_brush_kernel(const RegionShape *shapes, uint32_t n_shapes, uint32_t n_lanes, uint32_t m,
@@ -123,6 +88,7 @@ struct MergeArgs {
   const int4 *v; const uint32_t *kv; uint32_t nv;
   const uint32_t *kb, *mb, *nb;                 // B (kb null: test V against the shapes)
   const RegionShape *shapes; uint32_t n_shapes; uint32_t m;
+  const uint32_t *label, *selected;             // a membership (VoxelSelect) in place of the shapes: selected[label[i]] != 0
   int op;
   int4 *slot; uint32_t *keep;                   // nv + |B| slots (keep zeroed beforehand)
 };
@@ -141,6 +107,8 @@ __global__ __launch_bounds__(256) void region_merge_v_kernel(const MergeArgs A) 
     in = lo < nb && A.kb[lo] == k;
     if (in) bm = A.mb[lo];
     pos = i + lo;
+  } else if (A.selected) {
+    in = A.selected[A.label[i]] != 0u;
   } else {
     for (uint32_t s = 0; s < A.n_shapes && !in; s++) in = region_inside(A.shapes[s], p.x, p.y, p.z);
   }
@@ -186,6 +154,7 @@ struct Request {
   const tdt_region *regions = nullptr; size_t n_regions = 0;
   int32_t material = 0;                         // shapes: 0..253
   const int32_t *vox = nullptr; size_t n_vox = 0; bool list = false;
+  VoxelSelect *select = nullptr;                // PAINT / CLEAR / intersect of the voxels it selects (no shapes)
 };
 
 int check_request(tdt_ctx *ctx, const Request &R) {
@@ -284,6 +253,9 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
   int4 *v = nullptr;
   uint32_t nv = 0;
   if (int rc = tree_voxels(front, ctx, R.op == kOpIntersect ? 0x7FFFFFFFu : 254u, S, &v, &nv, &depth)) return rc;
+  const uint32_t *label = nullptr, *selected = nullptr;
+  if (R.select && nv)
+    if (int rc = R.select->run(front, ctx, v, nv, depth, S, &label, &selected)) return rc;
   // ---- sort and unique B ----
   uint32_t *kb = nullptr, *mb = nullptr, *nb = nullptr;
   if (build_b && b_cap && b_raw) {
@@ -314,6 +286,7 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
     std::memset(&A, 0, sizeof A);
     A.v = v; A.kv = kv; A.nv = nv; A.kb = kb; A.mb = mb; A.nb = nb;
     A.shapes = d_shapes; A.n_shapes = (uint32_t)shapes.size(); A.m = (uint32_t)R.material + 1u; A.op = R.op;
+    A.label = label; A.selected = selected;
     A.slot = slot; A.keep = keep;
     if (nv) {
       if (kb) hipLaunchKernelGGL(region_vkeys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, kv);
@@ -374,6 +347,19 @@ int region_edit(tdt_ctx *ctx, const Request &R, uint32_t *n_cells) {
 }
 
 }  // namespace
+
+int region_edit_selected(tdt_ctx *ctx, int op, int32_t material, VoxelSelect &sel, uint32_t *n_cells) {
+  Request R;
+  R.op = op; R.material = material; R.select = &sel;
+  return region_edit(ctx, R, n_cells);
+}
+
+int region_extract_selected(tdt_ctx *ctx, VoxelSelect &sel, int32_t *host_out, size_t capacity, size_t *n_out) {
+  Request R;
+  R.op = kOpIntersect; R.select = &sel;
+  return region_one(ctx, first_member(ctx), R, nullptr, host_out, capacity, n_out);
+}
+
 }  // namespace tdt
 
 extern "C" {

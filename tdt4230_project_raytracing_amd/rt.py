@@ -70,6 +70,43 @@ def _regions(regions):
     return (Region * len(regions))(*regions), len(regions)
 
 
+# connected components (include/tdt_rt.h): match rules, struct tdt_select, struct tdt_component
+MATCH_ANY, MATCH_MATERIAL = 0, 1
+COMPONENT_DTYPE = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("material", "<i4"),
+                            ("pad", "<i4")])
+assert COMPONENT_DTYPE.itemsize == 40
+
+
+class Select(ctypes.Structure):
+    """struct tdt_select: connectivity 6 / 26, match MATCH_*, the inclusive size window, invert 0 / 1."""
+    _fields_ = [("connectivity", ctypes.c_int32), ("match", ctypes.c_int32), ("min_voxels", ctypes.c_uint32),
+                ("max_voxels", ctypes.c_uint32), ("invert", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Select) == 24
+
+
+def _seeds(seeds):
+    """None (no seed filter) or (n, 3) voxel coordinates -> (contiguous int32 array or None, count).  An empty sequence is a seed
+    filter that matches nothing, not the absence of one (the C ABI reads n_seeds = 0 as "any component"): it becomes one seed
+    off the grid, which matches nothing."""
+    if seeds is None:
+        return None, 0
+    s = np.asarray(seeds, np.int32).reshape(-1, 3)
+    if not len(s):
+        s = np.full((1, 3), -1, np.int32)
+    return np.ascontiguousarray(s), len(s)
+
+
+def _touch_regions(regions):
+    """None (no region filter), one Region or a sequence -> (ctypes array or None, count); an empty sequence is a region filter
+    that matches nothing (one empty box), as with seeds."""
+    if regions is None:
+        return None, 0
+    arr, k = _regions(regions)
+    return _regions(box((0, 0, 0), (-1, -1, -1))) if k == 0 else (arr, k)
+
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -136,6 +173,9 @@ SYMBOLS = [
     ("tdt_octree_edit_region", _I, [_P, _I, _P, _S, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_octree_edit_voxels", _I, [_P, _I, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_octree_extract_region", _I, [_P, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_components", _I, [_P, _I, _I, _P, _S, ctypes.POINTER(ctypes.c_size_t), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_connected", _I, [_P, _I, ctypes.POINTER(Select), _P, _S, _P, _S, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_connected", _I, [_P, ctypes.POINTER(Select), _P, _S, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -317,6 +357,70 @@ class Context:
         if n.value:
             self.check(lib().tdt_octree_extract_region(self.h, arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
         return out
+
+    def _voxel_count(self):
+        """The bound tree's voxel count from a walk alone (tdt_octree_extract with a null array), without labelling anything."""
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract(self.h, None, 0, ctypes.byref(n)))
+        return n.value
+
+    def octree_components(self, connectivity=6, match=MATCH_ANY, capacity=4096):
+        """tdt_octree_components: (labels, components) of the bound tree's voxels — labels (n,) uint32 in octree_extract's order,
+        components a COMPONENT_DTYPE array numbered in the Morton order of each component's first voxel.  A count query would cost a
+        whole labelling, so this labels once: the labels are sized by a walk, the table by `capacity`, and only a tree of more
+        components than that is labelled a second time, into a table of the size the first call reported."""
+        nv, nc = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        labels = np.zeros(self._voxel_count(), np.uint32)
+        comps = np.zeros(max(int(capacity), 1), COMPONENT_DTYPE)
+
+        def run():
+            return lib().tdt_octree_components(self.h, int(connectivity), int(match), labels.ctypes.data, len(labels), ctypes.byref(nv),
+                                               comps.ctypes.data, len(comps), ctypes.byref(nc))
+
+        rc = run()
+        if rc == ERR_INVALID_VALUE and (nv.value > len(labels) or nc.value > len(comps)):
+            labels = np.zeros(nv.value, np.uint32)
+            comps = np.zeros(nc.value, COMPONENT_DTYPE)
+            rc = run()
+        self.check(rc)
+        return labels, comps[: nc.value].copy()
+
+    @staticmethod
+    def _select(connectivity, match, min_voxels, max_voxels, invert):
+        """struct tdt_select; the size window must be 0 .. 2^32 - 1 (ctypes would wrap a negative value silently)."""
+        for name, v in (("min_voxels", min_voxels), ("max_voxels", max_voxels)):
+            if not 0 <= int(v) <= 2**32 - 1:
+                raise ValueError(f"{name} must be 0 .. 2^32 - 1, not {v}")
+        return Select(int(connectivity), int(match), int(min_voxels), int(max_voxels), int(invert), 0)
+
+    def octree_edit_connected(self, op, seeds=None, regions=None, connectivity=6, match=MATCH_ANY, min_voxels=0, max_voxels=2**32 - 1,
+                              invert=False, material=0):
+        """tdt_octree_edit_connected: op (REGION_PAINT / REGION_CLEAR, brush material 0..253) over the selected components — those
+        holding one of `seeds` ((n, 3) voxels), touching `regions` (one Region or a list) and of min_voxels..max_voxels voxels,
+        or (invert) all others; rebuilds the bound tree in place and returns the canonical tree's cell count.  seeds / regions
+        None: no such filter; an empty list: a filter that matches nothing (so a click on nothing edits nothing)."""
+        sel = self._select(connectivity, match, min_voxels, max_voxels, invert)
+        s, ns = _seeds(seeds)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_connected(self.h, int(op), ctypes.byref(sel), s.ctypes.data if ns else None, ns, arr, k,
+                                                         int(material), ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_connected(self, seeds=None, regions=None, connectivity=6, match=MATCH_ANY, min_voxels=0, max_voxels=2**32 - 1,
+                                 invert=False):
+        """tdt_octree_extract_connected: the selected components' voxels, (n, 4) int32 {x, y, z, material + 1}, Morton-sorted;
+        seeds / regions as octree_edit_connected.  One labelling: the output is sized by the tree's voxel count (a walk), an upper
+        bound of the selection."""
+        sel = self._select(connectivity, match, min_voxels, max_voxels, invert)
+        s, ns = _seeds(seeds)
+        arr, k = _touch_regions(regions)
+        sp = s.ctypes.data if ns else None
+        out = np.empty((self._voxel_count(), 4), np.int32)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_connected(self.h, ctypes.byref(sel), sp, ns, arr, k, out.ctypes.data if len(out) else None,
+                                                      len(out), ctypes.byref(n)))
+        return out[: n.value].copy()
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
