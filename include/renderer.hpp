@@ -340,6 +340,23 @@ class Octree {
     if (n_cells) *n_cells = n;
     return true;
   }
+  // NEW: voxel morphology (tdt_octree_morph): m.op (TDT_MORPH_*) of m.radius steps with the 6- / 26-neighbourhood, inside the
+  // union of `mask` (none: everywhere); the bound tree rebuilt in place; returns the number of cells
+  uint32_t morph(const Context &ctx, const tdt_morph &m, const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_morph(ctx.raw(), &m, mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: what morph would leave, as voxels {x, y, z, material + 1} in Morton order, the tree untouched
+  // (tdt_octree_extract_morph); TDT_MORPH_SHELL with radius 1: the surface voxels
+  std::vector<int32_t> extract_morph(const Context &ctx, const tdt_morph &m, const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_morph(ctx.raw(), &m, r, mask.size(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_morph(ctx.raw(), &m, r, mask.size(), v.data(), n, &n));
+    return v;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

@@ -418,6 +418,53 @@ int tdt_octree_extract_connected(tdt_ctx *ctx, const tdt_select *sel, const int3
                                  const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm, size_t capacity,
                                  size_t *n_voxels);
 
+/* ---- voxel morphology ----------------------------------------------------------------------------------------------------
+ * Edit by distance to the surface: grow, shrink, open, close, hollow.  V = what tdt_octree_extract returns, over the grid
+ * G = [0, 2^max_depth)^3.  Offsets d in {-1,0,1}^3 \ {0}, all 26 (connectivity 26) or the 6 with |dx|+|dy|+|dz| = 1
+ * (connectivity 6), ordered by t(d) = 9 (dx+1) + 3 (dy+1) + (dz+1).  Nothing wraps around the grid.
+ *   One dilate step  D(S) = S + { q in G \ S : q + d in S for some d }.  Voxels of S keep their material.  A new q gets
+ *     `material` when that is >= 0; otherwise the material of q + d for the first d in ascending t(d) with q + d in S (S = the
+ *     set BEFORE this step, so the result does not depend on scheduling).
+ *   One erode step   E_b(S) = { p in S : for every d, p + d in S, or p + d not in G and b = 1 }.  Materials unchanged.
+ *   TDT_MORPH_DILATE = D^r(V).  TDT_MORPH_ERODE = E_border^r(V).  TDT_MORPH_SHELL = V \ E_border^r(V): the voxels within r
+ *     steps of the surface, original materials (radius 1: the surface voxels).  TDT_MORPH_OPEN = D^r(E_1^r(V)) and
+ *     TDT_MORPH_CLOSE = E_1^r(D^r(V)): both ignore `border` and erode with the outside solid.  On the bounded grid that makes
+ *     (E_1, D) an adjunction, so OPEN(V) <= V <= CLOSE(V) holds up to the grid faces and both are idempotent.  OPEN's voxels
+ *     carry their original materials (it is a subset of V, so `material` has no effect on it); CLOSE's new voxels carry what
+ *     the dilate step that created them gave them.
+ *   Mask: with n_regions > 0 (tdt_region shapes, the exact integer test of region edits, union of shapes = M) the result is
+ *     (op(V) & M) + (V \ M): neighbourhoods are always evaluated on the whole tree, the mask only limits where voxels may
+ *     appear or disappear.  n_regions == 0: no mask.
+ * tdt_octree_morph rewrites the bound cells buffer IN PLACE into tdt_octree_build_cells(result, max_depth) by
+ * tdt_octree_compact's install rule (tail zeroed, counter = *n_cells, versions bumped; an empty result installs the all-EMPTY
+ * root), on every replica of a multi-device context.  tdt_octree_extract_morph returns the same result as a Morton-sorted
+ * {x, y, z, material + 1} list by tdt_octree_extract's rules (voxels_xyzm == NULL only counts; capacity < the count:
+ * TDT_ERR_INVALID_VALUE with *n_voxels set; a multi-device context answers from device_ids[0]) and leaves the tree, its
+ * counter and its versions untouched: the preview, the undo record's other half, and with TDT_MORPH_SHELL, radius 1, the
+ * surface-voxel query.
+ * Errors, nothing written: a bad op / connectivity / border, radius outside 1..64, material outside -1..253, a bad shape, NULL
+ * regions with a count above 0, a LEAF value >= 254, the tree's or any intermediate or final list above 2^26 voxels
+ * (TDT_REGION_BRUSH_CAP), a result larger than the buffer (*n_cells then receives the cell count it needs):
+ * TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream;
+ * synchronous. */
+enum { TDT_MORPH_DILATE = 0, TDT_MORPH_ERODE = 1, TDT_MORPH_OPEN = 2, TDT_MORPH_CLOSE = 3, TDT_MORPH_SHELL = 4 };
+typedef struct tdt_morph {
+  int32_t op;                  /* TDT_MORPH_* */
+  int32_t connectivity;        /* 6 or 26: the structuring element of ONE step */
+  int32_t radius;              /* number of steps, 1..64 */
+  int32_t material;            /* -1: a new voxel inherits (rule above); 0..253: every new voxel gets this LEAF value */
+  int32_t border;              /* DILATE / ERODE / SHELL only: 0 = outside the grid is empty, 1 = outside the grid is solid */
+  int32_t pad;
+} tdt_morph;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_morph) == 24, "tdt_morph is 24 bytes");
+#else
+_Static_assert(sizeof(tdt_morph) == 24, "tdt_morph is 24 bytes");
+#endif
+int tdt_octree_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+int tdt_octree_extract_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                             size_t capacity, size_t *n_voxels);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -5,6 +5,7 @@
 //   tdt_demo [--size WxH] [--spp N] [--bounce N] [--settings camera.ron] [--move KEYS] [--edit x,y,z,type,value]
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
+//            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
 //            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -23,6 +24,10 @@
 //   or removed (neighbours by face, 6, the default, or also by edge and corner, 26; any voxel, the default, or only the same
 //   material).  Prints the pick and the new cell count.
 // --components [--connect 6|26] [--match any|material]: prints the component count and the largest component's size.
+// --morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]: voxel morphology (Octree::morph) of R steps with
+//   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
+//   change to a box of grid voxels (both corners inclusive).  Applied after the other edits, before the frame; prints the new
+//   cell count.  --cells N: the cells buffer is uploaded padded with zeros to N cells (room for an edit that grows the tree).
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -46,6 +51,10 @@ int main(int argc, char **argv) {
   int brush_shape = -1, brush_size = 0, op = TDT_REGION_SET;
   int flood_op = -1, connect = 6, match = TDT_MATCH_ANY;
   bool components = false;
+  int morph_op = -1, morph_radius = 0, morph_conn = 6;
+  std::string morph_name;
+  std::vector<int32_t> mask;
+  long long pad_cells = 0;
   std::vector<int32_t> box;
   int config = -1;
   for (int i = 1; i < argc; i++) {
@@ -89,6 +98,17 @@ int main(int argc, char **argv) {
     }
     else if (a == "--connect") { connect = std::atoi(next()); if (connect != 6 && connect != 26) { std::fprintf(stderr, "--connect 6|26\n"); return 2; } }
     else if (a == "--components") components = true;
+    else if (a == "--morph") {
+      char kind[16] = {0};
+      static const char *names[5] = {"dilate", "erode", "open", "close", "shell"};
+      if (std::sscanf(next(), "%15[a-z]:%d", kind, &morph_radius) == 2)
+        for (int k = 0; k < 5; k++) if (!std::strcmp(kind, names[k])) morph_op = k;
+      if (morph_op < 0) { std::fprintf(stderr, "--morph dilate|erode|open|close|shell:R\n"); return 2; }
+      morph_name = kind;
+    }
+    else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
+    else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
+    else if (a == "--cells") { pad_cells = std::atoll(next()); if (pad_cells < 0) { std::fprintf(stderr, "--cells N\n"); return 2; } }
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -157,7 +177,9 @@ int main(int argc, char **argv) {
     for (unsigned slot = 0; slot <= 4; slot++) {
       size_t bytes = 0;
       const uint32_t *p = (const uint32_t *)tdt_scene_blob(scene, (int)slot, &bytes);
-      keep.push_back(VertexBufferObject::new_<uint32_t>(ctx, std::vector<uint32_t>(p, p + bytes / 4)));
+      std::vector<uint32_t> words(p, p + bytes / 4);
+      if (slot == 0 && (size_t)pad_cells * 16 > words.size()) words.resize((size_t)pad_cells * 16, 0u);
+      keep.push_back(VertexBufferObject::new_<uint32_t>(ctx, words));
       bind_buffer_base(ctx, TDT_SHADER_STORAGE_BUFFER, slot, keep.back());
     }
     tdt_scene_destroy(scene);
@@ -197,6 +219,18 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
                   h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
+    }
+    if (morph_op >= 0) {
+      tdt_morph m{};
+      m.op = morph_op; m.connectivity = morph_conn; m.radius = morph_radius; m.material = -1; m.border = 0;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      std::printf("morph %s:%d conn %d cells %u\n", morph_name.c_str(), morph_radius, morph_conn, octree.morph(ctx, m, regions));
     }
     if (components) {
       const std::vector<tdt_component> table = octree.components(ctx, connect, match);

@@ -1,8 +1,10 @@
-// Device helpers shared by region edits (tdt_region.hip) and connected components (tdt_connect.hip): Morton keys of grid
-// voxels and the exact integer shape test of a tdt_region.
+// Device helpers shared by region edits (tdt_region.hip), connected components (tdt_connect.hip) and voxel morphology
+// (tdt_morph.hip): Morton keys of grid voxels, the exact integer shape test of a tdt_region, and the neighbour lookup in a
+// sorted key list.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 
 #include "tdt_rt.h"
@@ -44,6 +46,30 @@ __device__ __forceinline__ bool region_inside(const RegionShape &s, int x, int y
   if (dx > r || dx < -r || dy > r || dy < -r || dz > r || dz < -r) return false;
   const unsigned long long d2 = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy) + (unsigned long long)(dz * dz);
   return d2 <= (unsigned long long)(r * r);
+}
+
+// index of key kn in keys[0, n), or -1: a gallop from i (keys[i] = k != kn) toward kn, then a binary search
+__device__ __forceinline__ int gallop_find(const uint32_t *keys, int n, int i, uint32_t k, uint32_t kn) {
+  if (kn > k) {
+    int lo = i, hi = n;                                    // keys[lo] < kn <= keys[hi] (hi = n: past the end)
+    for (int step = 1; step <= n - 1 - i; step <<= 1) {
+      const int j = i + step;
+      if (keys[j] >= kn) { hi = j; break; }
+      lo = j;
+      if (step > (INT_MAX >> 1)) break;
+    }
+    while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if (keys[mid] < kn) lo = mid; else hi = mid; }
+    return hi < n && keys[hi] == kn ? hi : -1;
+  }
+  int lo = -1, hi = i;                                     // keys[lo] <= kn < keys[hi] (lo = -1: before the start)
+  for (int step = 1; step <= i; step <<= 1) {
+    const int j = i - step;
+    if (keys[j] <= kn) { lo = j; break; }
+    hi = j;
+    if (step > (INT_MAX >> 1)) break;
+  }
+  while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if (keys[mid] <= kn) lo = mid; else hi = mid; }
+  return lo >= 0 && keys[lo] == kn ? lo : -1;
 }
 
 }  // namespace tdt

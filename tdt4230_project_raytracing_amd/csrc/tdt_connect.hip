@@ -56,30 +56,6 @@ __device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t a, uint32_t 
   }
 }
 
-// index of key kn in keys[0, n), or -1: a gallop from i (keys[i] = k != kn) toward kn, then a binary search
-__device__ __forceinline__ int gallop_find(const uint32_t *keys, int n, int i, uint32_t k, uint32_t kn) {
-  if (kn > k) {
-    int lo = i, hi = n;                                    // keys[lo] < kn <= keys[hi] (hi = n: past the end)
-    for (int step = 1; step <= n - 1 - i; step <<= 1) {
-      const int j = i + step;
-      if (keys[j] >= kn) { hi = j; break; }
-      lo = j;
-      if (step > (INT_MAX >> 1)) break;
-    }
-    while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if (keys[mid] < kn) lo = mid; else hi = mid; }
-    return hi < n && keys[hi] == kn ? hi : -1;
-  }
-  int lo = -1, hi = i;                                     // keys[lo] <= kn < keys[hi] (lo = -1: before the start)
-  for (int step = 1; step <= i; step <<= 1) {
-    const int j = i - step;
-    if (keys[j] <= kn) { lo = j; break; }
-    hi = j;
-    if (step > (INT_MAX >> 1)) break;
-  }
-  while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if (keys[mid] <= kn) lo = mid; else hi = mid; }
-  return lo >= 0 && keys[lo] == kn ? lo : -1;
-}
-
 __global__ __launch_bounds__(256) void connect_init_kernel(const int4 *v, uint32_t n, uint32_t *keys, uint32_t *parent) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;

@@ -1,7 +1,7 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
-// tdt_connect.hip: connected components).
+// tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -167,7 +167,7 @@ hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *
 // tdt_octree_build_cells over n > 0 voxels {x, y, z, material + 1} already in device memory of ctx (synchronises)
 int build_cells_from_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, int depth, tdt_buffer **out, uint32_t *n_cells);
 
-// ---- tdt_compact.hip: pieces region edits reuse ----
+// ---- tdt_compact.hip: pieces region edits and voxel morphology reuse ----
 struct DeviceScratch {         // device temporaries of one operation, freed together
   std::vector<void *> ptrs;
   ~DeviceScratch() { release(); }

@@ -107,6 +107,20 @@ def _touch_regions(regions):
     return _regions(box((0, 0, 0), (-1, -1, -1))) if k == 0 else (arr, k)
 
 
+# voxel morphology (include/tdt_rt.h): ops and struct tdt_morph
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_SHELL = 0, 1, 2, 3, 4
+
+
+class Morph(ctypes.Structure):
+    """struct tdt_morph: op MORPH_*, connectivity 6 / 26 (one step's structuring element), radius 1..64 steps, material -1
+    (inherit) or 0..253, border 0 / 1 (outside the grid empty / solid)."""
+    _fields_ = [("op", ctypes.c_int32), ("connectivity", ctypes.c_int32), ("radius", ctypes.c_int32), ("material", ctypes.c_int32),
+                ("border", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Morph) == 24
+
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -176,6 +190,8 @@ SYMBOLS = [
     ("tdt_octree_components", _I, [_P, _I, _I, _P, _S, ctypes.POINTER(ctypes.c_size_t), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_edit_connected", _I, [_P, _I, ctypes.POINTER(Select), _P, _S, _P, _S, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_octree_extract_connected", _I, [_P, ctypes.POINTER(Select), _P, _S, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -421,6 +437,42 @@ class Context:
         self.check(lib().tdt_octree_extract_connected(self.h, ctypes.byref(sel), sp, ns, arr, k, out.ctypes.data if len(out) else None,
                                                       len(out), ctypes.byref(n)))
         return out[: n.value].copy()
+
+    @staticmethod
+    def _morph(op, radius, connectivity, material, border):
+        """struct tdt_morph (material None: inherit); every field must fit an int32 (ctypes would wrap it silently) and a bool is
+        not a number here.  The ranges themselves are the library's to check."""
+        material = -1 if material is None else material
+        for name, v in (("op", op), ("radius", radius), ("connectivity", connectivity), ("material", material), ("border", border)):
+            if isinstance(v, bool) and name != "border":
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+            if int(v) != v or not -2**31 <= int(v) <= 2**31 - 1:
+                raise ValueError(f"{name} must be an int32, not {v!r}")
+        return Morph(int(op), int(connectivity), int(radius), int(material), int(border), 0)
+
+    def octree_morph(self, op, radius=1, connectivity=6, material=None, border=0, regions=None):
+        """tdt_octree_morph: op (MORPH_*) of `radius` steps with the 6- or 26-neighbourhood on the bound tree, rebuilt in place;
+        new voxels inherit their material (None) or get `material` 0..253; border 1 treats the outside of the grid as solid;
+        regions (one Region or a list): a mask outside of which nothing changes (None: no mask; an empty list: an empty mask, so
+        nothing changes).  Returns the canonical tree's cell count."""
+        m = self._morph(op, radius, connectivity, material, border)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_morph(self.h, ctypes.byref(m), arr, k, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_morph(self, op, radius=1, connectivity=6, material=None, border=0, regions=None):
+        """tdt_octree_extract_morph: what octree_morph would leave, as an (n, 4) int32 list {x, y, z, material + 1}, Morton-sorted;
+        the tree is untouched.  MORPH_SHELL with radius 1: the surface voxels.  The result's size is known only once it exists
+        (a DILATE grows the list), so this counts first and fills second: two runs of the steps."""
+        m = self._morph(op, radius, connectivity, material, border)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_morph(self.h, ctypes.byref(m), arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_morph(self.h, ctypes.byref(m), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
