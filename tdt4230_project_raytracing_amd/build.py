@@ -1,4 +1,4 @@
-"""Build recipes for the two in-tree shared libraries (explicit compiler invocations, outputs
+"""Build recipes for the in-tree shared libraries (explicit compiler invocations, outputs
 stay in-tree so they travel to the GPU box with the snapshot)."""
 import os
 import shutil
@@ -86,5 +86,18 @@ def build_demo(force=False):
     return out
 
 
+def build_selftest(force=False):
+    """libtdtprims_selftest.so: the test-only harness over the device scan and the radix sort (csrc/prims_selftest.hip).
+    The scan is compiled into it from device_scan.hpp with the product's flags; the sort is libtdtrt.so's own, found next
+    to it at load time.  Not part of libtdtrt.so or its ABI."""
+    out = os.path.join(_HERE, "libtdtprims_selftest.so")
+    src = os.path.join(CSRC, "prims_selftest.hip")
+    deps = [src, os.path.join(CSRC, "device_scan.hpp"), os.path.join(CSRC, "tdt_internal.hpp"),
+            os.path.join(INCLUDE, "tdt_rt.h"), os.path.abspath(__file__)]
+    if force or _newer(out, deps):
+        _run([HIPCC] + HIP_FLAGS + ["-I", INCLUDE, "-I", CSRC, src, "-o", out, "-L", _HERE, "-ltdtrt", "-Wl,-rpath,$ORIGIN"])
+    return out
+
+
 def build_all(force=False):
-    return build_host(force), build_device(force), build_demo(force)
+    return build_host(force), build_device(force), build_demo(force), build_selftest(force)

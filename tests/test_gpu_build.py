@@ -66,6 +66,40 @@ def test_random_ragged_models(ctx, seed):
     assert_same_payloads(ctx, host.Ply(ply_bytes(xyz, rgb)), max_iter=50, z_up=bool(seed & 2))
 
 
+def tile_edge_model(u, dups):
+    """A PLY of exactly u distinct voxels spanning 64^3 (depth 6).  dups: every voxel stands in the file twice, the earlier
+    time under another colour, both at random file positions, so the two copies of a key reach the sort lanes, waves,
+    rounds and tiles apart and only a stable sort lets the later one win."""
+    rng = np.random.default_rng(u * 2 + int(dups))
+    g = 64
+    idx = rng.permutation(g ** 3 - 2)[:u - 2] + 1
+    idx = np.concatenate([[0, g ** 3 - 1], idx])                        # both corners: the extent is the whole grid
+    xyz = np.stack([idx // (g * g), (idx // g) % g, idx % g], 1) - 20
+    pal = np.stack([np.arange(40) * 6, 255 - np.arange(40) * 5, (np.arange(40) * 37) % 256], 1)
+    col = rng.integers(0, len(pal), size=u)
+    if not dups:
+        return xyz, pal[col]
+    pos = np.sort(rng.permutation(2 * u).reshape(u, 2), axis=1)         # file positions of the two copies, earlier first
+    f_xyz, f_col = np.zeros((2 * u, 3), np.int64), np.zeros(2 * u, np.int64)
+    f_xyz[pos[:, 0]] = xyz; f_col[pos[:, 0]] = (col + 1 + rng.integers(0, len(pal) - 1, size=u)) % len(pal)
+    f_xyz[pos[:, 1]] = xyz; f_col[pos[:, 1]] = col
+    assert (f_col[pos[:, 0]] != f_col[pos[:, 1]]).all()
+    return f_xyz, pal[f_col]
+
+
+@pytest.mark.parametrize("dups", [False, True], ids=["distinct", "each_twice"])
+@pytest.mark.parametrize("u", [2047, 2048, 2049, 4096, 16385])
+def test_models_at_scan_and_sort_tile_edges(ctx, u, dups):
+    """u distinct voxels at the tile size of the scan and the sort (the leaf scan runs over u + 1 or 2u + 1 flags) and at
+    the first size whose digit histogram needs a two-level scan; with duplicates the last one in the file must win."""
+    xyz, rgb = tile_edge_model(u, dups)
+    assert len(np.unique(xyz, axis=0)) == u and len(xyz) == (2 * u if dups else u)
+    ply = host.Ply(ply_bytes(xyz, rgb))
+    scene, _ = assert_same_payloads(ctx, ply, max_iter=50, z_up=bool(u & 1))
+    assert scene.max_depth == 6
+    assert len(expand_cells(scene.blobs[0], scene.max_depth)) == u     # the copies collapsed: one voxel per position
+
+
 @pytest.mark.parametrize("cfg", [1, 2, 3])
 def test_synthetic_scene_cells(ctx, cfg):
     scene = host.Scene.config(cfg)

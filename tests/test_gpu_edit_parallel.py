@@ -20,6 +20,10 @@ def test_non_colliding_batch_runs_in_parallel_and_equals_the_ordered_walk(oracle
     rng = np.random.default_rng(7 + cfg)
     delta = distinct_deltas(rng, n, depth, scene.blobs[0])
     assert len(delta) >= min(n, 12)
+    check_parallel_batch(oracle, scene, used, delta)
+
+
+def check_parallel_batch(oracle, scene, used, delta):
     n = len(delta)
     want_cells, want_counter = oracle_py.oracle_octree_update(oracle, scene, delta, used, (n, 1, 1))
     r, upd, counter = setup(scene, used, delta)
@@ -40,6 +44,19 @@ def test_non_colliding_batch_runs_in_parallel_and_equals_the_ordered_walk(oracle
         assert (r.render().view(np.uint32) == oracle.render(scene, r.camera, threads=4).view(np.uint32)).all()
     finally:
         r.close()
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049])
+def test_batch_sizes_at_the_plan_scan_tile_edge(oracle, n):
+    """The planner scans n + 1 items in tiles of 2048: at n = 2047 one full tile, at 2048 a second tile that holds nothing
+    but the terminator (the cell total then comes from the tile sums alone), at 2049 one edit beyond it."""
+    scene = host.Scene.config(3)
+    used = scene.counts["cells"]
+    depth = scene.max_depth
+    scene.blobs[0] = np.concatenate([scene.blobs[0], np.zeros(16 * (2049 * depth + 8), np.uint32)])
+    delta = distinct_deltas(np.random.default_rng(10), 2049, depth, scene.blobs[0])
+    assert len(delta) == 2049, "config 3 must have room for 2049 edits that do not collide"      # before the GPU is touched
+    check_parallel_batch(oracle, scene, used, delta[:n].copy())
 
 
 @pytest.mark.parametrize("case", ["same_cell", "same_delta_twice", "dirty_pool", "out_of_room", "piled_up"])
