@@ -470,6 +470,9 @@ int tdt_octree_extract_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region 
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this
  * lets a test tell a scene that fell back to the general kernel from one that runs its specialised build. */
 int tdt_debug_last_variant(const tdt_ctx *ctx, int out[6]);
+/* every scene-specialised build of the trace kernel the library holds, six ints per build in the order above; needs no context or
+ * device.  *count receives the number of builds; the first min(capacity, *count) are written to rows (capacity 0: count only). */
+int tdt_debug_trace_variants(int *rows, int capacity, int *count);
 /* pass / lane statistics of the PRODUCT trace kernels (how many traversal and event passes the waves ran, how many lanes were live in
  * each code region: the STAT_* rows of csrc/tdt_rt.hip) since the last reset — collected only by a -DTDT_STATS build of the library
  * (tools/loss_budget.py builds one beside the product library; the product library answers TDT_ERR_INVALID_OPERATION).  The first

@@ -2259,6 +2259,22 @@ int tdt_debug_last_variant(const tdt_ctx *ctx, int out[6]) {
   return TDT_OK;
 }
 
+/* the scene-specialised builds the library holds (kTraceVariants), six ints per build in tdt_debug_last_variant's order; *count is
+ * the number of builds, of which the first min(capacity, *count) are written — so that a test's list of builds cannot fall behind */
+int tdt_debug_trace_variants(int *rows, int capacity, int *count) {
+  if (!count || capacity < 0 || (capacity > 0 && !rows)) return TDT_ERR_INVALID_VALUE;
+  int n = 0;
+  for (const TraceVariant &v : kTraceVariants) {
+    if (n < capacity) {
+      const int r[6] = {v.form, v.depth, v.resident ? 1 : 0, v.full ? 1 : 0, v.brick ? 1 : 0, v.unit ? 1 : 0};
+      std::memcpy(rows + 6 * n, r, sizeof r);
+    }
+    n++;
+  }
+  *count = n;
+  return TDT_OK;
+}
+
 /* -DTDT_STATS builds of the library only (tools/loss_budget.py): pass / lane statistics of the product trace kernels launched on this
  * context since the last reset (the STAT_* rows of tdt_rt.hip); the first call switches the collection on.  The product library
  * answers TDT_ERR_INVALID_OPERATION. */

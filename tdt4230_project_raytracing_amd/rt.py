@@ -174,6 +174,7 @@ SYMBOLS = [
     ("tdt_debug_edit_mode", _I, [_P, _I]),
     ("tdt_debug_last_edit_path", _I, [_P]),
     ("tdt_debug_last_variant", _I, [_P, ctypes.POINTER(ctypes.c_int)]),
+    ("tdt_debug_trace_variants", _I, [ctypes.POINTER(ctypes.c_int), _I, ctypes.POINTER(ctypes.c_int)]),
     ("tdt_debug_counters", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_debug_stats", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _I, _I]),
     ("tdt_debug_wave_ends", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _I]),
@@ -702,6 +703,20 @@ class ComputeShader:
         self.ctx.check(lib().tdt_dispatch_counted_range(self.h, width, height, depth, spp_begin, spp_count,
                                                         ctypes.c_void_p(carry_ptr) if carry_ptr else None, c))
         return dict(zip(self.COUNT_FIELDS, [int(v) for v in c]))
+
+
+def trace_variants():
+    """Every scene-specialised build of the trace kernel the library holds (tdt_debug_trace_variants): a list of
+    (form, depth, resident, full, brick, unit) tuples in Context.last_variant's field order.  Needs no device."""
+    n = ctypes.c_int(0)
+    rc = lib().tdt_debug_trace_variants(None, 0, ctypes.byref(n))
+    if rc != 0:
+        raise TdtError(rc, "tdt_debug_trace_variants")
+    rows = (ctypes.c_int * (6 * n.value))()
+    rc = lib().tdt_debug_trace_variants(rows, n.value, ctypes.byref(n))
+    if rc != 0:
+        raise TdtError(rc, "tdt_debug_trace_variants")
+    return [tuple(int(x) for x in rows[6 * i:6 * i + 6]) for i in range(n.value)]
 
 
 def octree_build_cells(ctx, voxels_xyzm, depth):

@@ -65,6 +65,34 @@ def test_probe_launch_and_scaled_octrees_run_the_multiplying_build():
     assert (v["form"], v["full"], v["unit"]) == (POW2, 1, 0)
 
 
+def test_a_zero_corner_component_runs_the_multiplying_build():
+    """The unit builds leave out the `+ 0.0f` that turns -0 into +0 in the in-octree test (kNoNegZero in csrc/tdt_rt.hip): only a
+    corner with no zero component, of either sign, may select them."""
+    def placed(corner):
+        scene = host.Scene.config(2)
+        of = scene.blobs[6].copy()
+        of[:3] = corner
+        scene.blobs[6] = of
+        assert of[:3].view(np.uint32).tolist() == np.asarray(corner, np.float32).view(np.uint32).tolist() and of[4] == 1.0 and of[5] == 1.0
+        return scene
+
+    def moved(cam, by):
+        cam = cam.copy()
+        for i in range(3):
+            cam.origin[i] = float(np.float32(cam.origin[i]) + np.float32(by[i]))
+            cam.lower_left_corner[i] = float(np.float32(cam.lower_left_corner[i]) + np.float32(by[i]))
+        return cam
+
+    cam = host.camera_reference_pose(128, 96, 2, 4)
+    usual = np.array([-0.5, -0.5, -1.0], np.float32)
+    neg_zero = np.array([0x80000000], np.uint32).view(np.float32)[0]
+    for corner, unit in ((np.array([0.0, -0.5, -1.0], np.float32), 0),
+                         (np.array([-0.5, -0.5, neg_zero], np.float32), 0),
+                         (np.array([0.75, -1.5, 0.25], np.float32), 1)):
+        v = _variant(placed(corner), moved(cam, corner - usual))
+        assert (v["form"], v["depth"], v["resident"], v["full"], v["brick"], v["unit"]) == (POW2, 6, 1, 1, 0, unit), corner
+
+
 def test_switches_select_the_general_builds(monkeypatch):
     cam = host.camera_reference_pose(128, 96, 2, 4)
     monkeypatch.setenv("TDT_NO_SPECIALISE", "1")
