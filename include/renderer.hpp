@@ -357,6 +357,24 @@ class Octree {
     if (n) ctx.check(tdt_octree_extract_morph(ctx.raw(), &m, r, mask.size(), v.data(), n, &n));
     return v;
   }
+  // NEW: stamp a triangle mesh (tdt_octree_edit_triangles): op (TDT_REGION_*) over the voxels the closed triangles touch —
+  // vertices {x, y, z} fixed point, 64 units per voxel (tdt_mesh_quantize), triangles 3 vertex indices each, material 0..253 for
+  // every triangle or, with `materials`, material + 1 per triangle (the highest covering triangle wins).  A surface
+  // voxelisation: interiors stay as they are.  Returns the number of cells; *n_voxels receives the size of the mesh's voxel
+  // list at this tree's depth (a second rasterisation, tdt_voxelize_triangles counting only).
+  uint32_t stamp_mesh(const Context &ctx, int op, const std::vector<int32_t> &vertices_xyz, const std::vector<uint32_t> &triangles,
+                      int32_t material, const std::vector<int32_t> &materials = {}, size_t *n_voxels = nullptr) const {
+    tdt_mesh m{};
+    m.vertices = vertices_xyz.empty() ? nullptr : vertices_xyz.data();
+    m.triangles = triangles.empty() ? nullptr : triangles.data();
+    m.materials = materials.empty() ? nullptr : materials.data();
+    m.n_vertices = (uint32_t)(vertices_xyz.size() / 3); m.n_triangles = (uint32_t)(triangles.size() / 3);
+    m.material = material;
+    if (n_voxels) ctx.check(tdt_voxelize_triangles(ctx.raw(), &m, max_depth_, nullptr, 0, n_voxels));
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_triangles(ctx.raw(), op, &m, &n));
+    return n;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

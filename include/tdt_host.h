@@ -151,6 +151,33 @@ int64_t tdt_ply_albedos(const tdt_ply *p, uint32_t *keys, uint8_t *rgb, int64_t 
  * the far (z = 0) side of the octree so that the reference camera (main.rs:165-168) looks at it. */
 int tdt_scene_from_ply(const tdt_ply *p, int max_iter, int z_up, tdt_scene **out);
 
+/* ---------------------------------------------------------------- triangle meshes ------------ */
+/* Float vertices -> the fixed-point vertices of tdt_voxelize_triangles / tdt_octree_edit_triangles (include/tdt_rt.h: 64 units
+ * per voxel, |coordinate| <= 2^18 units).  out[3 i + a] = llrint(((double)xyz[3 i + a] * scale + offset[a]) * 64.0), in double,
+ * unfused, ties to even — numpy float64 with np.rint reproduces it exactly.  A result that is not finite or beyond +-2^18:
+ * TDT_ERR_INVALID_VALUE (0x0501), message in tdt_host_last_error, nothing written. */
+int tdt_mesh_quantize(const float *xyz, size_t n, double scale, const double offset[3], int32_t *out);
+/* The uniform scale and the offset (voxels) that centre the bounding box of n > 0 vertices in the voxel box lo..hi inclusive,
+ * i.e. the continuous box [lo, hi + 1]: scale = the smallest of (hi + 1 - lo)[a] / extent[a] over the axes of non-zero extent,
+ * so the mesh fits and its limiting edge spans the box; a mesh of zero extent gets scale 1.  offset[a] = the box's centre -
+ * the bounding box's centre * scale.  Coverage is closed: a vertex exactly on an outer face of the box also touches the voxel
+ * layer beyond it.  Errors (0x0501): NULL, n == 0, an empty box, a vertex that is not finite. */
+int tdt_mesh_fit(const float *xyz, size_t n, const int32_t lo[3], const int32_t hi[3], double *scale, double offset[3]);
+/* A minimal ASCII PLY mesh reader, separate from tdt_ply_parse (which restates the reference's point loader).  Grammar: "ply",
+ * "format ascii 1.0", LF or CRLF lines; comment / obj_info lines; "element vertex N" whose first three properties are float or
+ * double x, y, z (further scalar vertex properties are read and skipped: colours are IGNORED, materials come from the
+ * caller); then "element face M" with exactly one "property list uchar|uint8 int|uint|int32|uint32 vertex_indices|vertex_index";
+ * "end_header"; N vertices, M faces.  A polygon of k >= 3 vertices becomes the fan (0, i, i + 1).  Anything else — another
+ * format, other elements, a list of fewer than 3 indices, an index >= N, truncated or trailing data — is 0x0501 with a
+ * message in tdt_host_last_error. */
+typedef struct tdt_ply_mesh tdt_ply_mesh;
+int tdt_ply_mesh_parse(const void *data, size_t bytes, tdt_ply_mesh **out);
+void tdt_ply_mesh_destroy(tdt_ply_mesh *m);
+int tdt_ply_mesh_info(const tdt_ply_mesh *m, int64_t *n_vertices, int64_t *n_faces, int64_t *n_triangles);
+/* n_vertices x {x, y, z} / n_triangles x 3 indices, owned by m (NULL when empty) */
+const float *tdt_ply_mesh_vertices(const tdt_ply_mesh *m);
+const uint32_t *tdt_ply_mesh_triangles(const tdt_ply_mesh *m);
+
 /* ---------------------------------------------------------------- pick-to-edit --------------- */
 /* The DeltaNode (8 floats: the 32-byte std430 stride of octree_update.comp:41-48) for a click on the voxel face a ray query found
  * (tdt_ray_hit, include/tdt_rt.h) — what the reference's click handler (main.rs:551-568) hands Octree::update_vbo, aimed at the

@@ -465,6 +465,45 @@ int tdt_octree_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions
 int tdt_octree_extract_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
                              size_t capacity, size_t *n_voxels);
 
+/* ---- triangle meshes ------------------------------------------------------------------------------------------------------
+ * Turn a surface into voxels.  Vertices are fixed point: TDT_MESH_FRAC fractional bits, so one voxel is 64 units and voxel
+ * (x, y, z) is the closed cube [64x, 64x + 64] x [64y, 64y + 64] x [64z, 64z + 64]; every coordinate must satisfy |c| <=
+ * TDT_MESH_COORD_MAX (tdt_mesh_quantize / tdt_mesh_fit of include/tdt_host.h produce such vertices from floats).  A triangle
+ * covers a voxel of the grid [0, 2^depth)^3 iff the closed triangle and the closed cube share a point, decided exactly in
+ * integers; it may be degenerate (a segment or a point), a triangle lying in the plane between two voxel layers covers both,
+ * and whatever lies outside the grid contributes nothing.  Triangle t carries materials[t] = material + 1 in 1..254 (materials
+ * == NULL: `material` + 1 for all, material 0..253); a voxel covered by several triangles takes the material of the one with
+ * the highest index — the builder's last-duplicate-wins rule over (triangle, voxel) pairs in triangle order.  This is a
+ * surface voxelisation: interiors are not filled.
+ * tdt_voxelize_triangles needs no bound tree (depth 1..10) and returns the covered voxels {x, y, z, material + 1}, Morton-sorted
+ * and unique, by tdt_octree_extract's rules (voxels_xyzm == NULL only counts; capacity < the count: TDT_ERR_INVALID_VALUE with
+ * *n_voxels set and nothing written; a multi-device context answers from device_ids[0]).
+ * tdt_octree_edit_triangles is tdt_octree_edit_voxels(op, that list at the max_depth of slot 7) — same op table, install rule,
+ * *n_cells on a misfit, every replica of a multi-device context edited and a failure leaving all of them unchanged — without
+ * the list ever leaving the device.
+ * Limits: the 8^3-voxel tiles inside the triangles' grid-clipped bounding boxes, summed over the mesh, and the covered
+ * (triangle, voxel) pairs must each be <= 2^26 (TDT_REGION_BRUSH_CAP).
+ * Errors, nothing written: NULL mesh, NULL arrays with a count above 0, a vertex index >= n_vertices, a coordinate or a
+ * material out of range, a bad depth or op, a limit exceeded: TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound (edit form):
+ * TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream; synchronous. */
+#define TDT_MESH_FRAC 6
+#define TDT_MESH_COORD_MAX (1 << 18)
+typedef struct tdt_mesh {
+  const int32_t *vertices;     /* n_vertices x {x, y, z}, fixed point */
+  const uint32_t *triangles;   /* n_triangles x 3 vertex indices */
+  const int32_t *materials;    /* n_triangles x (material + 1), or NULL */
+  uint32_t n_vertices, n_triangles;
+  int32_t material;            /* used when materials == NULL: 0..253 */
+  int32_t pad;
+} tdt_mesh;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_mesh) == 40, "tdt_mesh is 40 bytes");
+#else
+_Static_assert(sizeof(tdt_mesh) == 40, "tdt_mesh is 40 bytes");
+#endif
+int tdt_voxelize_triangles(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+int tdt_octree_edit_triangles(tdt_ctx *ctx, int op, const tdt_mesh *mesh, uint32_t *n_cells);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

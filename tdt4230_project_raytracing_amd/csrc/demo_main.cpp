@@ -6,6 +6,7 @@
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
+//            [--mesh FILE.ply [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -28,6 +29,10 @@
 //   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
 //   change to a box of grid voxels (both corners inclusive).  Applied after the other edits, before the frame; prints the new
 //   cell count.  --cells N: the cells buffer is uploaded padded with zeros to N cells (room for an edit that grows the tree).
+// --mesh FILE.ply [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]: stamp a triangle mesh (Octree::stamp_mesh):
+//   the ASCII PLY's polygons (tdt_ply_mesh_parse; colours ignored) are fitted into the box of grid voxels (tdt_mesh_fit; default
+//   the whole grid minus a one-voxel margin; with --mesh, --box is this box, not an edit of its own), quantised and applied with
+//   `op` and material K before the frame.  Prints the triangle count, the mesh's voxel count and the new cell count.
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -44,7 +49,7 @@ using namespace renderer;
 
 int main(int argc, char **argv) {
   int W = 1280, H = 720, spp = 4, bounce = 6, device = 0;
-  std::string out, png, settings_path, moves;
+  std::string out, png, settings_path, moves, mesh_path;
   std::vector<float> edit;
   int pick_x = -1, pick_y = -1, material = 1;
   bool place = true, compact = false;
@@ -109,6 +114,7 @@ int main(int argc, char **argv) {
     else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
     else if (a == "--cells") { pad_cells = std::atoll(next()); if (pad_cells < 0) { std::fprintf(stderr, "--cells N\n"); return 2; } }
+    else if (a == "--mesh") mesh_path = next();
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -191,7 +197,34 @@ int main(int argc, char **argv) {
       std::copy(edit.begin(), edit.end(), delta.begin());
       octree.update_vbo(delta, 5, octree_update_program);
     }
-    if (!box.empty()) {
+    if (!mesh_path.empty()) {
+      FILE *f = std::fopen(mesh_path.c_str(), "rb");
+      if (!f) { std::perror(mesh_path.c_str()); return 1; }
+      std::string text; char buf[4096]; size_t got;
+      while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+      std::fclose(f);
+      tdt_ply_mesh *pm = nullptr;
+      if (tdt_ply_mesh_parse(text.data(), text.size(), &pm)) { std::fprintf(stderr, "%s: %s\n", mesh_path.c_str(), tdt_host_last_error()); return 1; }
+      int64_t nv = 0, nf = 0, nt = 0;
+      tdt_ply_mesh_info(pm, &nv, &nf, &nt);
+      const int32_t N = 1 << ints[0];
+      int32_t lo[3] = {1, 1, 1}, hi[3] = {N - 2, N - 2, N - 2};
+      if (N < 4) { lo[0] = lo[1] = lo[2] = 0; hi[0] = hi[1] = hi[2] = N - 1; }
+      if (!box.empty()) for (int a = 0; a < 3; a++) { lo[a] = box[a]; hi[a] = box[3 + a]; }
+      double fit_scale = 1.0, fit_offset[3] = {0, 0, 0};
+      std::vector<int32_t> q(3 * (size_t)nv);
+      if (tdt_mesh_fit(tdt_ply_mesh_vertices(pm), (size_t)nv, lo, hi, &fit_scale, fit_offset) ||
+          tdt_mesh_quantize(tdt_ply_mesh_vertices(pm), (size_t)nv, fit_scale, fit_offset, q.data())) {
+        std::fprintf(stderr, "%s: %s\n", mesh_path.c_str(), tdt_host_last_error()); tdt_ply_mesh_destroy(pm); return 1;
+      }
+      const uint32_t *tp = tdt_ply_mesh_triangles(pm);
+      const std::vector<uint32_t> tris(tp, tp + 3 * (size_t)nt);
+      tdt_ply_mesh_destroy(pm);
+      static const char *op_names[4] = {"set", "fill", "paint", "clear"};
+      size_t voxels = 0;
+      const uint32_t cells = octree.stamp_mesh(ctx, op, q, tris, material, {}, &voxels);
+      std::printf("mesh triangles %lld voxels %zu op %s cells %u\n", (long long)nt, voxels, op_names[op], cells);
+    } else if (!box.empty()) {
       tdt_region r{};
       r.shape = TDT_SHAPE_BOX;
       for (int a = 0; a < 3; a++) { r.a[a] = box[a]; r.b[a] = box[3 + a]; }

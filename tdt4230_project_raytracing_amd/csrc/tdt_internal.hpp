@@ -1,7 +1,7 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
-// tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology).
+// tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -202,6 +202,18 @@ struct VoxelSelect {
 int region_edit_selected(tdt_ctx *ctx, int op, int32_t material, VoxelSelect &sel, uint32_t *n_cells);
 // the selected voxels of device_ids[0]'s tree into host memory, by tdt_octree_extract_region's rules
 int region_extract_selected(tdt_ctx *ctx, VoxelSelect &sel, int32_t *host_out, size_t capacity, size_t *n_out);
+
+// ---- tdt_region.hip: the voxel-list form driven by a list that is produced in device memory and never leaves it ----
+struct VoxelSource {
+  // once slots 0 / 7 are known good on ctx (depth = its max_depth): *vox = *n voxels {x, y, z, material + 1} inside the grid,
+  // m 1..254, in device memory of ctx (allocated in S; may be null when *n == 0).  Runs on ctx's stream and may synchronise it.
+  // Errors are reported on `front`.
+  virtual int run(tdt_ctx *front, tdt_ctx *ctx, int depth, DeviceScratch &S, const int4 **vox, uint32_t *n) = 0;
+ protected:
+  ~VoxelSource() = default;
+};
+// tdt_octree_edit_voxels(op, the source's list) on every replica (the caller has checked op)
+int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -5,7 +5,8 @@
 //   V        the walk of the bound tree, expanded to its Morton-sorted voxel list (tree_voxels); keys  one lane per voxel
 //   B        shapes (SET / FILL): one lane per candidate of each shape's grid-clipped bounding box runs the shape test, a wave64
 //            ballot + popcount compacts the hits into (Morton key, material) pairs behind one atomic per wave.  Voxel list:
-//            one lane per voxel -> key (off-grid: the all-ones "dropped" key).  Then the builder's stable radix sort and a
+//            one lane per voxel -> key (off-grid: the all-ones "dropped" key); the list comes from the host, or from a
+//            VoxelSource that produced it in device memory (tdt_mesh.hip: a rasterised mesh).  Then the builder's stable radix sort and a
 //            last-of-each-run unique.  Queued before the walk, so the walk's one host synchronisation also reads |B raw|.
 //            PAINT / CLEAR with shapes build no B: the merge tests each voxel of V against the shapes instead (cost |V|), or
 //            reads a per-voxel membership a VoxelSelect computed on V (connected components, tdt_connect.hip).
@@ -155,10 +156,12 @@ struct Request {
   int32_t material = 0;                         // shapes: 0..253
   const int32_t *vox = nullptr; size_t n_vox = 0; bool list = false;
   VoxelSelect *select = nullptr;                // PAINT / CLEAR / intersect of the voxels it selects (no shapes)
+  VoxelSource *source = nullptr;                // list form: the list is produced in device memory (vox / n_vox unused)
 };
 
 int check_request(tdt_ctx *ctx, const Request &R) {
   if (R.op < TDT_REGION_SET || R.op > kOpIntersect) return fail(ctx, TDT_ERR_INVALID_VALUE, "op must be a TDT_REGION_* value");
+  if (R.list && R.source) return TDT_OK;           // a device-resident list: its producer has checked its input
   if (R.list) {
     if (R.n_vox && !R.vox) return fail(ctx, TDT_ERR_INVALID_VALUE, "null voxel list");
     if (R.n_vox >= (1ull << 31)) return fail(ctx, TDT_ERR_INVALID_VALUE, "more than 2^31 voxels");
@@ -220,9 +223,13 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
   uint32_t b_raw = 0, n_res = 0;                          // host words the stream writes: the guard below outlives them
   struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
   DeviceScratch S;
+  const int4 *src_vox = nullptr;                          // the device-resident list
+  uint32_t src_n = 0;
+  if (R.source)
+    if (int rc = R.source->run(front, ctx, depth, S, &src_vox, &src_n)) return rc;
   // ---- B, queued before the walk ----
   const bool build_b = R.list || ((R.op == TDT_REGION_SET || R.op == TDT_REGION_FILL) && lanes > 0);
-  const uint32_t b_cap = R.list ? (uint32_t)R.n_vox : (uint32_t)lanes;
+  const uint32_t b_cap = R.source ? src_n : R.list ? (uint32_t)R.n_vox : (uint32_t)lanes;
   uint32_t *bk = nullptr, *bv = nullptr, *bk_alt = nullptr, *bv_alt = nullptr, *b_count = nullptr;
   RegionShape *d_shapes = nullptr;
   b_raw = b_cap;
@@ -236,7 +243,9 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
     b_count = S.get<uint32_t>(2);
     if (!bk || !bv || !bk_alt || !bv_alt || !b_count) return fail(front, TDT_ERR_HIP, kNoMemory);
     TDT_HIP(front, hipMemsetAsync(b_count, 0, 2 * sizeof(uint32_t), st));
-    if (R.list) {
+    if (R.source) {
+      hipLaunchKernelGGL(region_list_keys_kernel, dim3(blocks_of(b_cap)), dim3(256), 0, st, src_vox, b_cap, depth, R.op == TDT_REGION_CLEAR, bk, bv);
+    } else if (R.list) {
       int4 *d_vox = S.get<int4>(b_cap);
       if (!d_vox) return fail(front, TDT_ERR_HIP, kNoMemory);
       TDT_HIP(front, hipMemcpyAsync(d_vox, R.vox, (size_t)b_cap * sizeof(int4), hipMemcpyHostToDevice, st));
@@ -351,6 +360,12 @@ int region_edit(tdt_ctx *ctx, const Request &R, uint32_t *n_cells) {
 int region_edit_selected(tdt_ctx *ctx, int op, int32_t material, VoxelSelect &sel, uint32_t *n_cells) {
   Request R;
   R.op = op; R.material = material; R.select = &sel;
+  return region_edit(ctx, R, n_cells);
+}
+
+int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells) {
+  Request R;
+  R.op = op; R.list = true; R.source = &src;
   return region_edit(ctx, R, n_cells);
 }
 

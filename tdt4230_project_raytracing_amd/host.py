@@ -402,3 +402,64 @@ class Ply:
                 lib().tdt_ply_destroy(self._h)
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- triangle meshes ---
+def mesh_quantize(xyz, scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """tdt_mesh_quantize: (n, 3) float32 vertices -> (n, 3) int32 fixed point, rint((x * scale + offset) * 64) in float64.
+    Raises ValueError when a result is not finite or beyond +-2^18 units."""
+    L = lib()
+    L.tdt_mesh_quantize.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    p = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+    out = np.zeros(p.shape, np.int32)
+    off = (ctypes.c_double * 3)(*[float(v) for v in offset])
+    rc = L.tdt_mesh_quantize(p.ctypes.data if len(p) else None, len(p), float(scale), off, out.ctypes.data if len(p) else None)
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return out
+
+
+def mesh_fit(xyz, lo, hi):
+    """tdt_mesh_fit: (scale, offset (3,) float64) that centre the vertices' bounding box in the voxel box lo..hi inclusive,
+    the limiting edge spanning it."""
+    L = lib()
+    L.tdt_mesh_fit.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    p = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+    scale, off = ctypes.c_double(0), (ctypes.c_double * 3)()
+    rc = L.tdt_mesh_fit(p.ctypes.data if len(p) else None, len(p), (ctypes.c_int32 * 3)(*[int(v) for v in lo]),
+                        (ctypes.c_int32 * 3)(*[int(v) for v in hi]), ctypes.byref(scale), off)
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return float(scale.value), np.array(list(off), np.float64)
+
+
+class PlyMesh:
+    """tdt_ply_mesh_parse of a byte buffer: vertices (n, 3) float32, triangles (m, 3) uint32 (polygons fan-triangulated),
+    faces = the file's polygon count.  Colours are ignored.  Raises ValueError with the reader's message."""
+
+    def __init__(self, data):
+        L = lib()
+        L.tdt_ply_mesh_parse.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        L.tdt_ply_mesh_destroy.argtypes = [ctypes.c_void_p]
+        L.tdt_ply_mesh_destroy.restype = None
+        L.tdt_ply_mesh_info.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int64)] * 3
+        L.tdt_ply_mesh_vertices.argtypes = [ctypes.c_void_p]
+        L.tdt_ply_mesh_vertices.restype = ctypes.POINTER(ctypes.c_float)
+        L.tdt_ply_mesh_triangles.argtypes = [ctypes.c_void_p]
+        L.tdt_ply_mesh_triangles.restype = ctypes.POINTER(ctypes.c_uint32)
+        h = ctypes.c_void_p()
+        data = bytes(data)
+        rc = L.tdt_ply_mesh_parse(data, len(data), ctypes.byref(h))
+        if rc != 0:
+            raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+        try:
+            nv, nf, nt = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+            _check(L.tdt_ply_mesh_info(h, ctypes.byref(nv), ctypes.byref(nf), ctypes.byref(nt)))
+            self.faces = nf.value
+            self.vertices = (np.ctypeslib.as_array(L.tdt_ply_mesh_vertices(h), shape=(nv.value, 3)).copy() if nv.value
+                             else np.zeros((0, 3), np.float32))
+            self.triangles = (np.ctypeslib.as_array(L.tdt_ply_mesh_triangles(h), shape=(nt.value, 3)).copy() if nt.value
+                              else np.zeros((0, 3), np.uint32))
+        finally:
+            L.tdt_ply_mesh_destroy(h)

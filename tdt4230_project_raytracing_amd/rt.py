@@ -121,6 +121,50 @@ class Morph(ctypes.Structure):
 assert ctypes.sizeof(Morph) == 24
 
 
+# triangle meshes (include/tdt_rt.h): fixed-point vertices (MESH_FRAC fractional bits) and struct tdt_mesh
+MESH_FRAC, MESH_COORD_MAX = 6, 1 << 18
+
+
+class Mesh(ctypes.Structure):
+    """struct tdt_mesh: vertices n_vertices x {x, y, z} int32 fixed point, triangles n_triangles x 3 uint32 indices, materials
+    n_triangles x (material + 1) int32 or NULL (then `material` 0..253 for every triangle)."""
+    _fields_ = [("vertices", ctypes.c_void_p), ("triangles", ctypes.c_void_p), ("materials", ctypes.c_void_p),
+                ("n_vertices", ctypes.c_uint32), ("n_triangles", ctypes.c_uint32), ("material", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Mesh) == 40
+
+
+def _exact_ints(a, dtype, name):
+    """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
+    src = np.asarray(a)
+    if src.size and src.dtype.kind not in "iu":
+        raise ValueError(f"{name} must be integers, not {src.dtype}")
+    out = np.ascontiguousarray(src.astype(dtype))
+    if src.size and not np.array_equal(out.astype(object), src.astype(object)):
+        raise ValueError(f"{name} holds values outside {np.dtype(dtype).name}")
+    return out
+
+
+def _mesh(vertices, triangles, materials, material):
+    """(struct tdt_mesh, the arrays it points into) from (n, 3) fixed-point vertices, (m, 3) vertex indices, None or (m,)
+    per-triangle material + 1, and the material used without them.  The ranges are the library's to check."""
+    v = _exact_ints(vertices, np.int32, "vertices")
+    t = _exact_ints(triangles, np.uint32, "triangles")
+    if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("vertices and triangles must be (n, 3) arrays")
+    m = None
+    if materials is not None:
+        m = _exact_ints(materials, np.int32, "materials").reshape(-1)
+        if len(m) != len(t):
+            raise ValueError(f"{len(m)} materials for {len(t)} triangles")
+    if isinstance(material, bool) or int(material) != material or not -2**31 <= int(material) <= 2**31 - 1:
+        raise ValueError(f"material must be an int32, not {material!r}")
+    mesh = Mesh(v.ctypes.data if len(v) else None, t.ctypes.data if len(t) else None, m.ctypes.data if m is not None and len(m) else None,
+                len(v), len(t), int(material), 0)
+    return mesh, (v, t, m)
+
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -193,6 +237,8 @@ SYMBOLS = [
     ("tdt_octree_extract_connected", _I, [_P, ctypes.POINTER(Select), _P, _S, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_octree_extract_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_voxelize_triangles", _I, [_P, ctypes.POINTER(Mesh), _I, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_triangles", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -474,6 +520,29 @@ class Context:
         if n.value:
             self.check(lib().tdt_octree_extract_morph(self.h, ctypes.byref(m), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
         return out
+
+    def voxelize_triangles(self, vertices, triangles, depth, materials=None, material=0):
+        """tdt_voxelize_triangles: the voxels of the grid [0, 2^depth)^3 the closed triangles touch, as an (n, 4) int32 list
+        {x, y, z, material + 1}, Morton-sorted; vertices (n, 3) int32 fixed point (64 units per voxel; host.mesh_quantize),
+        triangles (m, 3) indices, materials None or (m,) material + 1 per triangle (the highest covering triangle wins).
+        Needs no bound tree.  Counts first, fills second: two rasterisations."""
+        mesh, keep = _mesh(vertices, triangles, materials, material)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_voxelize_triangles(self.h, ctypes.byref(mesh), int(depth), None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_voxelize_triangles(self.h, ctypes.byref(mesh), int(depth), out.ctypes.data, n.value, ctypes.byref(n)))
+        del keep
+        return out
+
+    def octree_edit_triangles(self, op, vertices, triangles, materials=None, material=0):
+        """tdt_octree_edit_triangles: octree_edit_voxels(op, voxelize_triangles(..., max_depth of slot 7)) without the list
+        leaving the device; returns the canonical tree's cell count."""
+        mesh, keep = _mesh(vertices, triangles, materials, material)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_triangles(self.h, int(op), ctypes.byref(mesh), ctypes.byref(n)), n)
+        del keep
+        return int(n.value)
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
