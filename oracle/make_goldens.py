@@ -5,6 +5,7 @@ $REF_DIR at run time) on Mesa llvmpipe through oracle/_ref/libglref.so.
 Run in the build container only (needs /root/reference and the swrast DRI driver):
     make -C oracle && python oracle/make_goldens.py
     python oracle/make_goldens.py --live     (only the fixtures of the formerly live comparisons)
+    python oracle/make_goldens.py --degenerate [name ...]   (only tests/golden/degenerate/: axis-parallel and on-face ray bundles)
 Fixtures are data: scene parameters, camera uniforms and the RGBA32F image the reference wrote.
 Scenes are regenerated from their parameters by libtdthost.so (byte-identical everywhere; a
 sha256 of every payload is stored and re-checked by the tests).
@@ -328,7 +329,40 @@ def live():
     print("monu1_point:", rows.shape)
 
 
+def degenerate():
+    """tests/golden/degenerate/<name>.npz for every case of tests/degenerate_cams.py FIXTURES: cameras whose rays have a direction
+    component of exactly +-0 (or 2^-120, or a denormal) and lie in a cell-face plane, where the slab operands are +-inf and
+    0 * inf = NaN.  Stored: the scene's parameters and digests, the twelve camera floats as raw uint32 bits, and llvmpipe's image.
+    llvmpipe drops samples on heavy frames (oracle/README.md), so a frame the oracle does not reproduce is not written."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import degenerate_cams as dc
+    gl = oracle_py.GLRef.get()
+    oracle = oracle_py.Oracle()
+    out = os.path.join(OUT, "degenerate")
+    os.makedirs(out, exist_ok=True)
+    only = [a for a in sys.argv[1:] if not a.startswith("--")]               # names after the flag: only these cases
+    assert all(n in dc.FIXTURES for n in only), only
+    for name, (spec, corner, axis, kind, _) in dc.FIXTURES.items():
+        if only and name not in only:
+            continue
+        scene, cam, _, _ = dc.fixture_case(name)
+        img = gl.render(scene, cam)
+        mine = oracle.render(scene, cam, threads=8)
+        bad = int((img.view(np.uint32) != mine.view(np.uint32)).any(axis=2).sum())
+        if bad:
+            raise SystemExit(f"{name}: the oracle differs from llvmpipe in {bad} pixels; not written")
+        meta = {"renderer": gl.renderer(), "scene": list(spec), "axis": axis, "kind": kind,
+                "W": cam.image_width, "H": cam.image_height, "spp": cam.samples_per_pixel, "max_bounce": cam.max_bounce,
+                "scene_sha256": scene_digest(scene)}
+        np.savez_compressed(os.path.join(out, name + ".npz"), image=img, camera_bits=dc.camera_bits(cam),
+                            corner_bits=scene.blobs[6][:3].view(np.uint32).copy(), meta=json.dumps(meta))
+        print(f"{name}: {img.shape} oracle == llvmpipe, nan pixels {int(np.isnan(img).any(axis=2).sum())}")
+
+
 if __name__ == "__main__":
+    if "--degenerate" in sys.argv[1:]:
+        degenerate()
+        sys.exit(0)
     if "--live" in sys.argv[1:]:
         live()
         sys.exit(0)

@@ -16,7 +16,7 @@ REF_DIR = os.environ.get("REF_DIR", "/root/reference")
 REF_SHADER = os.path.join(REF_DIR, "assets", "shaders", "raytracer.comp")
 
 STAT_FIELDS = ["pixels", "samples", "octree_hit_calls", "iterations", "node_loads", "lambertian", "metal",
-               "dielectric", "unknown_material"]
+               "dielectric", "unknown_material", "nan_slab_tests", "inf_slab_tests"]
 _SLOT_NAMES = {0: "cells", 1: "materials", 2: "albedos", 3: "metal", 4: "dielectric", 6: "octree_floats", 7: "octree_ints"}
 
 

@@ -157,9 +157,15 @@ static inline void cube_hit_record(const ray *r, float t, float cx, float cy, fl
 
 /* slab test (rc:317-334): returns entry/exit parameters */
 static inline void cube_slabs(const ray *r, float ix, float iy, float iz, float cx, float cy, float cz, float size,
-                              float t_min, float t_max, float *t_enter, float *t_exit) {
+                              float t_min, float t_max, float *t_enter, float *t_exit, oracle_stats *st) {
   float lx = (cx + -r->ox) * ix, ly = (cy + -r->oy) * iy, lz = (cz + -r->oz) * iz;
   float ux = ((cx + size) + -r->ox) * ix, uy = ((cy + size) + -r->oy) * iy, uz = ((cz + size) + -r->oz) * iz;
+  if (st) {   /* degenerate operands: 0 * inf from a ray lying in a face plane, +-inf from a zero direction component */
+    const float v[6] = { lx, ly, lz, ux, uy, uz };
+    int has_nan = 0, has_inf = 0;
+    for (int k = 0; k < 6; k++) { has_nan |= v[k] != v[k]; has_inf |= fabsf(v[k]) == INFINITY; }
+    st->nan_slab_tests += (uint64_t)has_nan; st->inf_slab_tests += (uint64_t)has_inf;
+  }
   float mnx = f_min(lx, ux), mny = f_min(ly, uy), mnz = f_min(lz, uz);
   float mxx = f_max(lx, ux), mxy = f_max(ly, uy), mxz = f_max(lz, uz);
   /* t_min / t_max sit in the FIRST operand slot of the compiled min/max chain; for the root
@@ -245,7 +251,7 @@ static int octree_hit(const tracer *T, const ray *r, pixel_carry *pc, hit_record
       if (i > 0) {                                                             /* rc:426-433 */
         float cx = gx * T->scale + T->min_x, cy = gy * T->scale + T->min_y, cz = gz * T->scale + T->min_z;
         float cs = T->scale * inv_pow_depth;
-        cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, &t_enter, &t_exit);
+        cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, &t_enter, &t_exit, st);
         if (!(t_exit < t_enter))
           cube_hit_record(r, t_enter, cx, cy, cz, cs, &pc->leaf);
         src = &pc->leaf;             /* on a miss: whatever this call site produced last time */
@@ -259,7 +265,7 @@ static int octree_hit(const tracer *T, const ray *r, pixel_carry *pc, hit_record
     float cx = (gx * T->scale + T->min_x) + -0.00001f, cy = (gy * T->scale + T->min_y) + -0.00001f,
           cz = (gz * T->scale + T->min_z) + -0.00001f;
     float cs = T->scale * inv_pow_depth + 0.00002f;
-    cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, &t_enter, &t_exit);
+    cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, &t_enter, &t_exit, st);
     t_stride = (!(t_exit < t_enter)) ? t_exit : t_octree_max;
   }
   return 0;

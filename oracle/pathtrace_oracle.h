@@ -47,6 +47,8 @@ typedef struct {
   uint64_t iterations;      /* OctreeHit loop iterations that reached treeLookup         */
   uint64_t node_loads;      /* tree levels visited = 8-byte Node loads (raytracer.comp:381) */
   uint64_t lambertian, metal, dielectric, unknown_material; /* scatter calls by type     */
+  uint64_t nan_slab_tests;  /* cell slab tests (cube_slabs) with a NaN among their six slab operands */
+  uint64_t inf_slab_tests;  /* ... with a +-inf among them                                */
 } oracle_stats;
 
 /* Renders what ComputeShader::dispatch_compute(dispatch_w, dispatch_h, 1) would write

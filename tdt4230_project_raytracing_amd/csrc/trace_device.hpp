@@ -99,8 +99,9 @@ TDT_DEV float schlick_q(float x) {
 TDT_DEV float f_min(float a, float b) { return (b != b) ? a : (a < b ? a : b); }
 TDT_DEV float f_max(float a, float b) { return (b != b) ? a : (a > b ? a : b); }
 // v_min_f32 / v_max_f32 (IEEE minNum / maxNum): identical to f_min / f_max except for which
-// zero a (+0,-0) tie returns — which no consumer below can observe (the slab chains only
-// compare these values, or use them when they are strictly positive)
+// zero a (+0,-0) tie returns.  The slab chains only compare these values, or use them when they
+// are strictly positive; that this never shows is checked by tests/test_gpu_degenerate_rays.py,
+// whose rays lie in cell-face planes (slab operands 0 * inf = NaN, +-inf and +-0) in every build
 TDT_DEV float hw_min(float a, float b) { return __builtin_fminf(a, b); }
 TDT_DEV float hw_max(float a, float b) { return __builtin_fmaxf(a, b); }
 TDT_DEV float b2f(bool b) { return b ? 1.0f : 0.0f; }

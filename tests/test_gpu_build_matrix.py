@@ -175,6 +175,17 @@ def _row_id(row):
     return f"{'pow2' if form == POW2 else 'table'}-d{depth}-{'lds' if resident else 'mem'}" + ("-full" if full else "") + ("-brick" if brick else "")
 
 
+def row_switches(row):
+    """The environment switches that select the row where its tree alone would select a more specialised build."""
+    form, depth, resident, full, brick = row
+    names = []
+    if form == POW2 and not resident and not brick:
+        names.append("TDT_NO_BRICKS")
+    if form == POW2 and resident and not full and depth in (5, 6):
+        names.append("TDT_NO_FULL_GRID")
+    return names
+
+
 def test_the_rows_are_the_librarys_builds():
     """A build added to kTraceVariants without a scene here fails this test; it is not skipped."""
     mine = [row + (unit,) for row in ROWS for unit in (0, 1)]
@@ -187,12 +198,8 @@ def test_the_rows_are_the_librarys_builds():
 @pytest.mark.parametrize("unit", [1, 0], ids=["unit", "mul"])
 @pytest.mark.parametrize("row", ROWS, ids=_row_id)
 def test_build_runs_and_equals_the_oracle(oracle, row, unit, monkeypatch):
-    form, depth, resident, full, brick = row
-    # the switches that select the row where the tree alone would select a more specialised one
-    if form == POW2 and not resident and not brick:
-        monkeypatch.setenv("TDT_NO_BRICKS", "1")
-    if form == POW2 and resident and not full and depth in (5, 6):
-        monkeypatch.setenv("TDT_NO_FULL_GRID", "1")
+    for name in row_switches(row):
+        monkeypatch.setenv(name, "1")
     scene, cams, refs = _case(oracle, row, unit, ROWS.index(row))
     for name, cam, ref in zip(("inside", "outside"), cams, refs):
         r = rt.Renderer(scene, cam)

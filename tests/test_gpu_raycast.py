@@ -60,6 +60,32 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _assert_first_hit(oracle, scene, alb, cam, hits, rays, sample, w=W, h=H):
+    """`hits` and `rays` (pick's, for every pixel of the camera's w x h image, row-major) against what the oracle's first bounce
+    of that sample leaves behind on the Lambertian `scene`: the albedo or the sky as the colour, and normal, point, front_face
+    and the root t in the carry.  Returns (hits, hits on a leaf)."""
+    accum = np.zeros((h, w, 4), np.float32)
+    carry = np.zeros((h, w, 16), np.float32)
+    oracle.accumulate(scene, cam, accum, carry, sample, 1, dispatch=(max(w, 32), max(2 * h, 32)))   # (covers the whole image: 64 x 96 for 64 x 48)
+    hits = hits.reshape(h, w)
+    col = accum[..., :3]
+    hit = hits["status"] == rt.RAY_HIT
+    assert not (hits["status"] > rt.RAY_ITER_LIMIT).any()
+    mat = np.where(hit, hits["material"], 0)
+    assert (_bits(col[hit]) == _bits(alb[mat[hit]])).all()
+    sky = _sky(rays[:, 4].reshape(h, w))
+    assert (_bits(col[~hit]) == _bits(sky[~hit])).all()
+    root = hit & (hits["iterations"] == 1)
+    leaf = hit & (hits["iterations"] > 1)
+    cv = carry.view(np.uint32)
+    for sel, n_off, ff_off, p_off in ((root, 0, 3, 4), (leaf, 8, 11, 12)):
+        assert (_bits(hits["normal"][sel]) == cv[sel][:, n_off:n_off + 3]).all()
+        assert (_bits(hits["point"][sel]) == cv[sel][:, p_off:p_off + 3]).all()
+        assert (hits["front_face"][sel].astype(np.uint32) == cv[sel][:, ff_off]).all()
+    assert (_bits(hits["t"][root]) == cv[root][:, 7]).all()
+    return int(hit.sum()), int(leaf.sum())
+
+
 @pytest.mark.parametrize("si", range(6))
 def test_pick_is_the_reference_first_hit(oracle, si):
     scene, alb = _lambertian(_scenes()[si])
@@ -73,26 +99,7 @@ def test_pick_is_the_reference_first_hit(oracle, si):
                 hits, rays = r.pick(xy, sample=s, return_rays=True)
                 again = r.ctx.raycast(rays)                          # the same rays through tdt_raycast: the same bytes
                 assert again.tobytes() == hits.tobytes()
-                accum = np.zeros((H, W, 4), np.float32)
-                carry = np.zeros((H, W, 16), np.float32)
-                oracle.accumulate(scene, cam, accum, carry, s, 1, dispatch=(W, 2 * H))    # (covers the whole 64 x 48)
-                hits = hits.reshape(H, W)
-                col = accum[..., :3]
-                hit = hits["status"] == rt.RAY_HIT
-                hits_seen += int(hit.sum())
-                assert not (hits["status"] > rt.RAY_ITER_LIMIT).any()
-                mat = np.where(hit, hits["material"], 0)
-                assert (_bits(col[hit]) == _bits(alb[mat[hit]])).all()
-                sky = _sky(rays[:, 4].reshape(H, W))
-                assert (_bits(col[~hit]) == _bits(sky[~hit])).all()
-                root = hit & (hits["iterations"] == 1)
-                leaf = hit & (hits["iterations"] > 1)
-                cv = carry.view(np.uint32)
-                for sel, n_off, ff_off, p_off in ((root, 0, 3, 4), (leaf, 8, 11, 12)):
-                    assert (_bits(hits["normal"][sel]) == cv[sel][:, n_off:n_off + 3]).all()
-                    assert (_bits(hits["point"][sel]) == cv[sel][:, p_off:p_off + 3]).all()
-                    assert (hits["front_face"][sel].astype(np.uint32) == cv[sel][:, ff_off]).all()
-                assert (_bits(hits["t"][root]) == cv[root][:, 7]).all()
+                hits_seen += _assert_first_hit(oracle, scene, alb, cam, hits, rays, s)[0]
         finally:
             r.close()
     assert hits_seen > 0
