@@ -375,6 +375,45 @@ class Octree {
     ctx.check(tdt_octree_edit_triangles(ctx.raw(), op, &m, &n));
     return n;
   }
+  // NEW: stamp_mesh's solid form (tdt_octree_edit_triangles_solid): the mesh's surface voxels AND the empty voxels that surface
+  // seals off from the grid's faces (fill.connectivity 6 / 26 between empty voxels; fill.material -1: each takes the material of
+  // the surface voxel at its -x side, 0..253: that material), decided by the mesh alone, whatever the tree holds.  *n_voxels
+  // receives the solid's size, at the price of a second rasterisation and flood (tdt_voxelize_triangles_solid counting only).
+  // (A name of its own: as an overload, a `{}` argument would fit the tdt_fill and the materials list alike.)
+  uint32_t stamp_mesh_solid(const Context &ctx, int op, const std::vector<int32_t> &vertices_xyz, const std::vector<uint32_t> &triangles,
+                            int32_t material, const tdt_fill &fill, const std::vector<int32_t> &materials = {}, size_t *n_voxels = nullptr) const {
+    tdt_mesh m{};
+    m.vertices = vertices_xyz.empty() ? nullptr : vertices_xyz.data();
+    m.triangles = triangles.empty() ? nullptr : triangles.data();
+    m.materials = materials.empty() ? nullptr : materials.data();
+    m.n_vertices = (uint32_t)(vertices_xyz.size() / 3); m.n_triangles = (uint32_t)(triangles.size() / 3);
+    m.material = material;
+    if (n_voxels) ctx.check(tdt_voxelize_triangles_solid(ctx.raw(), &m, max_depth_, &fill, nullptr, 0, n_voxels));
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_triangles_solid(ctx.raw(), op, &m, &fill, &n));
+    return n;
+  }
+  // NEW: fill the tree's cavities (tdt_octree_fill_enclosed): every empty voxel that no path of empty neighbours
+  // (fill.connectivity 6 / 26) connects to a face of the grid becomes solid (fill.material, or -1: the material of the wall at its
+  // -x side), inside the union of `mask` (none: everywhere); the bound tree rebuilt in place; returns the number of cells.
+  // *n_voxels receives the number of voxels filled (a second flood, tdt_octree_extract_enclosed counting only).
+  uint32_t fill_enclosed(const Context &ctx, const tdt_fill &fill, const std::vector<tdt_region> &mask = {}, size_t *n_voxels = nullptr) const {
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    if (n_voxels) ctx.check(tdt_octree_extract_enclosed(ctx.raw(), &fill, r, mask.size(), nullptr, 0, n_voxels));
+    uint32_t n = 0;
+    ctx.check(tdt_octree_fill_enclosed(ctx.raw(), &fill, r, mask.size(), &n));
+    return n;
+  }
+  // NEW: what fill_enclosed would add, as voxels {x, y, z, material + 1} in Morton order, the tree untouched
+  // (tdt_octree_extract_enclosed): the preview, and the undo record (edit_voxels(TDT_REGION_CLEAR, it) undoes the fill)
+  std::vector<int32_t> extract_enclosed(const Context &ctx, const tdt_fill &fill, const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_enclosed(ctx.raw(), &fill, r, mask.size(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_enclosed(ctx.raw(), &fill, r, mask.size(), v.data(), n, &n));
+    return v;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

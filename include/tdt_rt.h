@@ -504,6 +504,59 @@ _Static_assert(sizeof(tdt_mesh) == 40, "tdt_mesh is 40 bytes");
 int tdt_voxelize_triangles(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
 int tdt_octree_edit_triangles(tdt_ctx *ctx, int op, const tdt_mesh *mesh, uint32_t *n_cells);
 
+/* ---- enclosed space ---------------------------------------------------------------------------------------------------------
+ * Fill what is sealed off: the cavities of a tree, the inside of a watertight mesh.  Let G = [0, 2^depth)^3 and W, a subset of
+ * G, a wall set.  Two EMPTY voxels (G \ W) are neighbours under connectivity 6 when they share a face, under connectivity 26
+ * when they share a face, an edge or a corner; nothing wraps around the grid.  An empty voxel is OUTSIDE when it lies on a face
+ * of G (a coordinate 0 or 2^depth - 1) or is connected to such a voxel through empty neighbours.  E(W, c) = the empty voxels
+ * that are not outside.  The space beyond the grid is open: a cavity that reaches a grid face through empties is not enclosed.
+ * The definition is a fixed point of the grid alone, so a result does not depend on scheduling and compares bit for bit.
+ * Connectivity 6 for the empties is the permissive choice (a diagonal gap in a wall does not leak), 26 the strict one.  The
+ * closed-triangle-against-closed-cube coverage of tdt_voxelize_triangles separates even under 26: where the surface passes
+ * through a point, every closed cube holding that point is covered, so no empty voxel inside touches one outside, not even by
+ * a corner.
+ * Material of a voxel q of E: `material` 0..253 is that LEAF value; `material` -1 inherits the material of the first voxel of W
+ * met walking from q in decreasing x (it exists, or q would reach the face x = 0).
+ * tdt_octree_extract_enclosed: W = V, what tdt_octree_extract returns over max_depth (slot 7).  Returns E(V, c) & M as
+ * {x, y, z, material + 1}, Morton-sorted, by tdt_octree_extract's rules (voxels_xyzm == NULL only counts; capacity < the count:
+ * TDT_ERR_INVALID_VALUE with *n_voxels set and nothing written; a multi-device context answers from device_ids[0]).  M = the
+ * union of the regions (tdt_region shapes, the exact integer test of region edits); n_regions == 0: no mask.  The flood always
+ * runs on the whole tree, the mask only limits what is reported.  The tree, its counter and its versions are untouched: it is
+ * the preview and the undo record — tdt_octree_edit_voxels(TDT_REGION_CLEAR, that list) undoes a fill.
+ * tdt_octree_fill_enclosed rewrites the bound cells buffer IN PLACE into tdt_octree_build_cells(V + that list, max_depth) by
+ * tdt_octree_compact's install rule (tail zeroed, counter = *n_cells, versions bumped; an empty E installs the compacted
+ * bytes), on every replica of a multi-device context, a failure leaving all of them unchanged.
+ * tdt_voxelize_triangles_solid: S = tdt_voxelize_triangles(mesh, depth); the result is S + E(S, c), E's materials by tdt_fill
+ * (inherit carries per-triangle materials inward along -x), by the same list rules.  Needs no bound tree.
+ * tdt_octree_edit_triangles_solid is tdt_octree_edit_voxels(op, that list at the max_depth of slot 7), all four ops, without the
+ * list ever leaving the device, exactly like tdt_octree_edit_triangles.  Enclosure is decided by the mesh's own surface alone,
+ * never by what the tree already holds.
+ * Errors, nothing written: a NULL tdt_fill, connectivity other than 6 / 26, material outside -1..253, a bad shape, NULL regions
+ * with a count above 0, a LEAF value >= 254, a bad op or depth, the mesh errors of tdt_voxelize_triangles, |V|, |S| or |E| above
+ * 2^26 (TDT_REGION_BRUSH_CAP), a result larger than the buffer (*n_cells then receives the cell count it needs):
+ * TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound (tree forms, mesh edit form): TDT_ERR_INCOMPLETE.  The DOMAIN has no cap: the flood
+ * runs on bit volumes over the bounding box of W, at most 2^30 bits = 128 MiB each at depth 10: occupancy, reach, and 128 MiB of
+ * per-word counts, 384 MiB in all besides the lists (|S| is bounded by tdt_voxelize_triangles' own limit of 2^26 covered pairs).  Ordered after work queued
+ * on the context's stream; synchronous. */
+typedef struct tdt_fill {
+  int32_t connectivity;        /* 6 or 26: how EMPTY voxels connect */
+  int32_t material;            /* -1: inherit (rule above); 0..253: every filled voxel gets this LEAF value */
+} tdt_fill;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_fill) == 8, "tdt_fill is 8 bytes");
+#else
+_Static_assert(sizeof(tdt_fill) == 8, "tdt_fill is 8 bytes");
+#endif
+int tdt_octree_extract_enclosed(tdt_ctx *ctx, const tdt_fill *fill, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                                size_t capacity, size_t *n_voxels);
+int tdt_octree_fill_enclosed(tdt_ctx *ctx, const tdt_fill *fill, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+int tdt_voxelize_triangles_solid(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, const tdt_fill *fill, int32_t *voxels_xyzm, size_t capacity,
+                                 size_t *n_voxels);
+int tdt_octree_edit_triangles_solid(tdt_ctx *ctx, int op, const tdt_mesh *mesh, const tdt_fill *fill, uint32_t *n_cells);
+/* the flood passes of the context's last enclosed-space call that changed the volume (0: the seeds were the fixed point, or the
+ * box needed no flood); the host queues passes in batches of 8, so up to 8 more ran idle.  Measurement only. */
+int tdt_debug_fill_passes(const tdt_ctx *ctx);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

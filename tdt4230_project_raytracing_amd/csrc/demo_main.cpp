@@ -6,7 +6,8 @@
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
-//            [--mesh FILE.ply [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
+//            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
+//            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -33,6 +34,13 @@
 //   the ASCII PLY's polygons (tdt_ply_mesh_parse; colours ignored) are fitted into the box of grid voxels (tdt_mesh_fit; default
 //   the whole grid minus a one-voxel margin; with --mesh, --box is this box, not an edit of its own), quantised and applied with
 //   `op` and material K before the frame.  Prints the triangle count, the mesh's voxel count and the new cell count.
+//   --solid: the mesh's inside is stamped too (Octree::stamp_mesh_solid): the empty voxels its surface seals off from the
+//   grid's faces (by face, --conn 6, the default, or also by edge and corner, --conn 26), in material K; the voxel count printed
+//   is the solid's.
+// --fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]: fill the tree's cavities (Octree::fill_enclosed): every
+//   empty voxel that no path of empty 6- (default) or 26-neighbours connects to a face of the grid becomes solid, in material K
+//   or, without --material, the material of the wall at its -x side; --mask limits the fill to a box of grid voxels.  Applied
+//   after --morph, before the frame; prints the number of voxels filled and the new cell count.
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -52,7 +60,7 @@ int main(int argc, char **argv) {
   std::string out, png, settings_path, moves, mesh_path;
   std::vector<float> edit;
   int pick_x = -1, pick_y = -1, material = 1;
-  bool place = true, compact = false;
+  bool place = true, compact = false, material_given = false, solid = false, fill_enclosed = false;
   int brush_shape = -1, brush_size = 0, op = TDT_REGION_SET;
   int flood_op = -1, connect = 6, match = TDT_MATCH_ANY;
   bool components = false;
@@ -76,7 +84,7 @@ int main(int argc, char **argv) {
     else if (a == "--edit") { float v[5]; if (std::sscanf(next(), "%f,%f,%f,%f,%f", v, v + 1, v + 2, v + 3, v + 4) != 5) { std::fprintf(stderr, "--edit x,y,z,type,value\n"); return 2; } edit.assign(v, v + 5); }
     else if (a == "--pick") { if (std::sscanf(next(), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
     else if (a == "--click") { const std::string v = next(); if (v != "left" && v != "right") { std::fprintf(stderr, "--click left|right\n"); return 2; } place = v == "left"; }
-    else if (a == "--material") material = std::atoi(next());
+    else if (a == "--material") { material = std::atoi(next()); material_given = true; }
     else if (a == "--compact") compact = true;
     else if (a == "--brush") {
       char kind[16] = {0};
@@ -115,9 +123,12 @@ int main(int argc, char **argv) {
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
     else if (a == "--cells") { pad_cells = std::atoll(next()); if (pad_cells < 0) { std::fprintf(stderr, "--cells N\n"); return 2; } }
     else if (a == "--mesh") mesh_path = next();
+    else if (a == "--solid") solid = true;
+    else if (a == "--fill-enclosed") fill_enclosed = true;
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
+  if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
   try {
     Context ctx(device);
     // main.rs:156-160
@@ -222,8 +233,10 @@ int main(int argc, char **argv) {
       tdt_ply_mesh_destroy(pm);
       static const char *op_names[4] = {"set", "fill", "paint", "clear"};
       size_t voxels = 0;
-      const uint32_t cells = octree.stamp_mesh(ctx, op, q, tris, material, {}, &voxels);
-      std::printf("mesh triangles %lld voxels %zu op %s cells %u\n", (long long)nt, voxels, op_names[op], cells);
+      tdt_fill fill{};
+      fill.connectivity = morph_conn; fill.material = -1;
+      const uint32_t cells = solid ? octree.stamp_mesh_solid(ctx, op, q, tris, material, fill, {}, &voxels) : octree.stamp_mesh(ctx, op, q, tris, material, {}, &voxels);
+      std::printf("mesh triangles %lld voxels %zu%s op %s cells %u\n", (long long)nt, voxels, solid ? " solid" : "", op_names[op], cells);
     } else if (!box.empty()) {
       tdt_region r{};
       r.shape = TDT_SHAPE_BOX;
@@ -264,6 +277,20 @@ int main(int argc, char **argv) {
         regions.push_back(r);
       }
       std::printf("morph %s:%d conn %d cells %u\n", morph_name.c_str(), morph_radius, morph_conn, octree.morph(ctx, m, regions));
+    }
+    if (fill_enclosed) {
+      tdt_fill fill{};
+      fill.connectivity = morph_conn; fill.material = material_given ? material : -1;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      size_t voxels = 0;
+      const uint32_t cells = octree.fill_enclosed(ctx, fill, regions, &voxels);
+      std::printf("fill-enclosed conn %d voxels %zu cells %u\n", morph_conn, voxels, cells);
     }
     if (components) {
       const std::vector<tdt_component> table = octree.components(ctx, connect, match);

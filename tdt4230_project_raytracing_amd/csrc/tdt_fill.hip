@@ -1,0 +1,478 @@
+// Enclosed space (include/tdt_rt.h tdt_octree_extract_enclosed / tdt_octree_fill_enclosed / tdt_voxelize_triangles_solid /
+// tdt_octree_edit_triangles_solid): E(W, c), the EMPTY voxels of the grid [0, 2^depth)^3 that no path through empty
+// c-neighbours connects to a face of the grid, W being the bound tree's voxels or a mesh's surface voxels.
+//
+// Every other editing unit works on the Morton-sorted list of OCCUPIED voxels; enclosure is a property of the empty ones, which
+// are in no list, so this unit keeps a dense bit volume instead.  It only has to span bbox(W): a voxel outside the bounding box
+// of W is beyond it on some axis, walking away from the box along that axis stays empty up to the grid face, so every voxel
+// outside bbox(W) is outside and E lies inside bbox(W).  An empty voxel on one of the six faces of bbox(W) is either on a grid
+// face or next to a voxel outside the box: those are the seeds, and the flood never has to leave the box.
+//
+//   bbox       one reduction over W: wave shuffles, then one vector atomicMin / atomicMax per wave and axis.     fill_bbox_kernel
+//   rasterise  one lane per voxel of W sets its bit in the occupancy volume with a vector atomicOr and writes its (Morton key,
+//              material + 1).  x runs along the 32-bit word: a row (y, z) of the box is nw <= 32 consecutive words, word w of a
+//              row holding x = 32 (wx0 + w) .. + 31, so rows are word-aligned in ABSOLUTE x and the box itself need not be: the
+//              bits of the first and last word that lie outside [x0, x1] are masked (fill_valid).           fill_rasterise_kernel
+//   seed       reach = the empty bits of the rows on the four y / z faces, and the bits x0 and x1 of every other row.  fill_seed_kernel
+//   flood      one block owns a tile of 8 x 8 whole rows, held in LDS with a halo of one row all round (10 x 10 rows); a tile
+//              holds its rows whole, so there is no halo along x.  A round computes, per word,
+//                reach |= fill(empty, empty & (carry bits of the row's neighbouring words | the 4 face rows (connectivity 6)
+//                                               or the 8 rows around it, each spread by +-1 bit across words (connectivity 26)))
+//              where fill() floods every run of empties that holds a seed bit in O(1) word operations: e & ~(e + s) | s carries
+//              a seed upwards to the end of its run, the same on the bit-reversed words carries it downwards.  Rounds repeat
+//              inside the tile until __syncthreads_or reports no change; then the tile's words are written back and, if any
+//              changed, the pass's flag word is raised.                                                       fill_flood_kernel
+//              Bits are only ever set, and a word of the volume is written by the one block that owns its row, with a plain
+//              store of a superset of what it loaded; a block that reads a neighbour's row for its halo while that neighbour
+//              writes it sees, word by word, the old or the new value, both subsets of the fixed point, so a half-updated
+//              volume is harmless.  A pass whose flag stays clear changed nothing anywhere, so every block saw the final volume
+//              and found its tile stable: that is the fixed point.
+//              Passes: information crosses one tile boundary per pass at least, so the number of passes is bounded by 1 + the
+//              length, in tiles entered, of the longest shortest path from a seed through empties (the longest corridor).  The
+//              host queues kFillBatch passes, each with a flag word of its own, and reads the flags with ONE synchronisation per
+//              batch; it stops when the last pass of a batch changed nothing, so at most kFillBatch - 1 passes run idle.
+//   count      per word popc(empty & ~reach & in-mask), the mask being the exact integer test of region edits per set bit;
+//              exclusive_scan_u32 over the words; the total is read (one synchronisation) and held to 2^26.  fill_count_kernel
+//   emit       (Morton key, material + 1) per enclosed voxel at its word's offset.  Inherit: the first voxel of W in decreasing
+//              x is the highest set occupancy bit below the voxel, in its word (a count of leading zeros) or the words before
+//              it — it exists, or the voxel would reach the box's x0 face and be a seed — and its material is looked up in W's
+//              sorted keys.  The builder's radix sort then orders the pairs (W's own pairs in front of them for the solid mesh
+//              forms), and one lane per pair writes {x, y, z, m}.                                  fill_emit_kernel, fill_list_kernel
+//   memory     at the largest box (depth 10, the whole grid: 2^25 words): occupancy 128 MiB + reach 128 MiB + the per-word counts
+//              and their scan 128 MiB (+ 64 KiB of scan scratch), besides W's list (16 B per voxel) and its (key, material)
+//              pairs (8 B), and 32 B per resulting voxel for the pairs, the sort's second pair and the list.
+#include <climits>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "device_scan.hpp"
+#include "region_device.hpp"
+#include "tdt_internal.hpp"
+
+namespace tdt {
+
+constexpr int kFillTile = 8;                           // rows per tile side, in y and in z
+constexpr int kFillHalo = kFillTile + 2;
+constexpr int kFillMaxWords = 32;                      // words per row: 2^10 voxels / 32
+constexpr int kFillBatch = 8;                          // flood passes per flag read
+constexpr unsigned long long kFillCap = 1ull << 26;
+
+struct FillBox {               // bbox(W) and the layout of the bit volumes over it
+  int32_t lo[3], hi[3];        // inclusive
+  int32_t ey, ez;              // rows per axis
+  int32_t nw, wx0;             // words per row; the absolute word index of word 0
+  uint32_t n_words;            // ey * ez * nw <= 2^25
+};
+
+// the bits of word w of a row that lie inside [x0, x1]
+__device__ __forceinline__ uint32_t fill_valid(const FillBox &B, int w) {
+  uint32_t m = 0xFFFFFFFFu;
+  if (w == 0) m &= 0xFFFFFFFFu << (B.lo[0] & 31);
+  if (w == B.nw - 1) m &= 0xFFFFFFFFu >> (31 - (B.hi[0] & 31));
+  return m;
+}
+
+// every run of set bits of e that holds a bit of s (s a subset of e), whole.  e + s: the lowest seed of a run carries through
+// the run's bits above it and stops in the clear bit behind the run (or leaves the word); a higher seed of the same run stays
+// set in the sum, hence the final | s.
+__device__ __forceinline__ uint32_t fill_runs(uint32_t e, uint32_t s) {
+  const uint32_t up = (e & ~(e + s)) | s;
+  const uint32_t eb = __brev(e), sb = __brev(s);
+  return up | __brev((eb & ~(eb + sb)) | sb);
+}
+
+__device__ __forceinline__ int fill_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+  return v;
+}
+
+// box[0..2] = min, box[3..5] = max over the list (initialised to INT_MAX / -1)
+__global__ __launch_bounds__(256) void fill_bbox_kernel(const int4 *v, uint32_t n, int *box) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+  if (i < n) { const int4 p = v[i]; lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z; }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int l = fill_wave_min(lo[a]), h = -fill_wave_min(-hi[a]);
+    if ((threadIdx.x & 63u) == 0 && h >= 0) { atomicMin(box + a, l); atomicMax(box + 3 + a, h); }
+  }
+}
+
+__global__ __launch_bounds__(256) void fill_rasterise_kernel(const int4 *v, uint32_t n, const FillBox B, uint32_t *occ, uint32_t *keys,
+                                                            uint32_t *vals) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const int4 p = v[i];
+  const uint32_t row = (uint32_t)(p.z - B.lo[2]) * (uint32_t)B.ey + (uint32_t)(p.y - B.lo[1]);
+  atomicOr(occ + row * (uint32_t)B.nw + (uint32_t)((p.x >> 5) - B.wx0), 1u << (p.x & 31));
+  keys[i] = region_key(p.x, p.y, p.z);
+  vals[i] = (uint32_t)p.w;
+}
+
+__global__ __launch_bounds__(256) void fill_seed_kernel(const FillBox B, const uint32_t *occ, uint32_t *reach) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= B.n_words) return;
+  const int w = (int)(g % (uint32_t)B.nw);
+  const uint32_t row = g / (uint32_t)B.nw;
+  const int y = (int)(row % (uint32_t)B.ey), z = (int)(row / (uint32_t)B.ey);
+  const uint32_t empty = ~occ[g] & fill_valid(B, w);
+  uint32_t seed = 0xFFFFFFFFu;
+  if (y != 0 && y != B.ey - 1 && z != 0 && z != B.ez - 1) {
+    seed = 0;
+    if (w == 0) seed |= 1u << (B.lo[0] & 31);
+    if (w == B.nw - 1) seed |= 1u << (B.hi[0] & 31);
+  }
+  reach[g] = empty & seed;
+}
+
+// r: the halo'd tile's reach words, row-major; the word w of row h spread by one bit either way, across its neighbouring words
+__device__ __forceinline__ uint32_t fill_spread(const uint32_t *r, int h, int w, int nw) {
+  const uint32_t c = r[h * nw + w];
+  uint32_t s = c | (c << 1) | (c >> 1);
+  if (w > 0) s |= r[h * nw + w - 1] >> 31;
+  if (w < nw - 1) s |= r[h * nw + w + 1] << 31;
+  return s;
+}
+
+template <int CONN>
+__global__ __launch_bounds__(256) void fill_flood_kernel(const FillBox B, const uint32_t *occ, uint32_t *reach, uint32_t *flag) {
+  __shared__ uint32_t r[kFillHalo * kFillHalo * kFillMaxWords];
+  __shared__ uint32_t e[kFillTile * kFillTile * kFillMaxWords];
+  const int nw = B.nw;
+  const int ty0 = (int)blockIdx.x * kFillTile, tz0 = (int)blockIdx.y * kFillTile;
+  for (int i = (int)threadIdx.x; i < kFillHalo * kFillHalo * nw; i += 256) {
+    const int h = i / nw, w = i - h * nw;
+    const int y = ty0 + h % kFillHalo - 1, z = tz0 + h / kFillHalo - 1;
+    r[i] = (y >= 0 && y < B.ey && z >= 0 && z < B.ez) ? reach[((uint32_t)z * (uint32_t)B.ey + (uint32_t)y) * (uint32_t)nw + (uint32_t)w] : 0u;
+  }
+  for (int i = (int)threadIdx.x; i < kFillTile * kFillTile * nw; i += 256) {
+    const int t = i / nw, w = i - t * nw;
+    const int y = ty0 + t % kFillTile, z = tz0 + t / kFillTile;
+    e[i] = (y < B.ey && z < B.ez) ? ~occ[((uint32_t)z * (uint32_t)B.ey + (uint32_t)y) * (uint32_t)nw + (uint32_t)w] & fill_valid(B, w) : 0u;
+  }
+  __syncthreads();
+  int any = 0, changed;
+  // Inside a round lanes read words of r[] that other lanes store in the same round, with no barrier between: deliberate.  A word
+  // has one writer, a store only adds bits, and a 32-bit LDS access is whole, so a reader sees the word before or after the store,
+  // both subsets of the fixed point; and whenever any lane stored, __syncthreads_or forces another round that sees it.
+  do {
+    changed = 0;
+    for (int i = (int)threadIdx.x; i < kFillTile * kFillTile * nw; i += 256) {
+      const uint32_t ee = e[i];
+      if (!ee) continue;
+      const int t = i / nw, w = i - t * nw;
+      const int h = (t / kFillTile + 1) * kFillHalo + t % kFillTile + 1;
+      const uint32_t old = r[h * nw + w];
+      if (old == ee) continue;                               // all of it reached already
+      uint32_t in = old;
+      if (CONN == 6) {
+        if (w > 0) in |= r[h * nw + w - 1] >> 31;
+        if (w < nw - 1) in |= r[h * nw + w + 1] << 31;
+        in |= r[(h - 1) * nw + w] | r[(h + 1) * nw + w] | r[(h - kFillHalo) * nw + w] | r[(h + kFillHalo) * nw + w];
+      } else {
+#pragma unroll
+        for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+          for (int dy = -1; dy <= 1; dy++) in |= fill_spread(r, h + dz * kFillHalo + dy, w, nw);
+      }
+      const uint32_t now = fill_runs(ee, in & ee);
+      if (now != old) { r[h * nw + w] = now; changed = 1; }
+    }
+    any |= changed;
+  } while (__syncthreads_or(changed));
+  if (any) {                                                 // a lane's words are the same in every round
+    for (int i = (int)threadIdx.x; i < kFillTile * kFillTile * nw; i += 256) {
+      const int t = i / nw, w = i - t * nw;
+      const int y = ty0 + t % kFillTile, z = tz0 + t / kFillTile;
+      if (y < B.ey && z < B.ez)
+        reach[((uint32_t)z * (uint32_t)B.ey + (uint32_t)y) * (uint32_t)nw + (uint32_t)w] = r[((t / kFillTile + 1) * kFillHalo + t % kFillTile + 1) * nw + w];
+    }
+    *flag = 1u;
+  }
+}
+
+// the enclosed bits of word g that the mask keeps
+__device__ __forceinline__ uint32_t fill_enclosed_bits(const FillBox &B, const uint32_t *occ, const uint32_t *reach, uint32_t g,
+                                                       const RegionShape *shapes, uint32_t n_shapes, int *x0, int *y, int *z) {
+  const int w = (int)(g % (uint32_t)B.nw);
+  const uint32_t row = g / (uint32_t)B.nw;
+  *x0 = (B.wx0 + w) << 5; *y = B.lo[1] + (int)(row % (uint32_t)B.ey); *z = B.lo[2] + (int)(row / (uint32_t)B.ey);
+  uint32_t bits = ~occ[g] & ~reach[g] & fill_valid(B, w);
+  if (n_shapes) {
+    uint32_t kept = 0;
+    for (uint32_t b = bits; b; b &= b - 1u) {
+      const int bit = __ffs((int)b) - 1;
+      bool in = false;
+      for (uint32_t s = 0; s < n_shapes && !in; s++) in = region_inside(shapes[s], *x0 + bit, *y, *z);
+      if (in) kept |= 1u << bit;
+    }
+    bits = kept;
+  }
+  return bits;
+}
+
+__global__ __launch_bounds__(256) void fill_count_kernel(const FillBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
+                                                        uint32_t n_shapes, uint32_t *count) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g > B.n_words) return;
+  if (g == B.n_words) { count[g] = 0; return; }               // the scan's extra item: its slot receives the total
+  int x0, y, z;
+  count[g] = (uint32_t)__popc(fill_enclosed_bits(B, occ, reach, g, shapes, n_shapes, &x0, &y, &z));
+}
+
+// index of key k in the sorted keys[0, n) (k is there)
+__device__ __forceinline__ uint32_t fill_find(const uint32_t *keys, uint32_t n, uint32_t k) {
+  uint32_t lo = 0, hi = n;                                   // keys[lo] <= k < keys[hi]
+  while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (keys[mid] <= k) lo = mid; else hi = mid; }
+  return lo;
+}
+
+// fixed: material + 1 of every enclosed voxel, or 0: inherit along -x from W (wkeys / wvals, n_w sorted pairs)
+__global__ __launch_bounds__(256) void fill_emit_kernel(const FillBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
+                                                       uint32_t n_shapes, const uint32_t *excl, uint32_t fixed, const uint32_t *wkeys,
+                                                       const uint32_t *wvals, uint32_t n_w, uint32_t *keys, uint32_t *vals) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= B.n_words || excl[g + 1u] == excl[g]) return;
+  int x0, y, z;
+  uint32_t pos = excl[g];
+  for (uint32_t b = fill_enclosed_bits(B, occ, reach, g, shapes, n_shapes, &x0, &y, &z); b; b &= b - 1u) {
+    const int bit = __ffs((int)b) - 1;
+    uint32_t m = fixed;
+    if (!m) {
+      uint32_t below = occ[g] & ((1u << bit) - 1u);
+      int xw = x0;
+      for (uint32_t q = g; !below && xw > (B.wx0 << 5);) { q--; xw -= 32; below = occ[q]; }   // stays in the row: see the header
+      m = below ? wvals[fill_find(wkeys, n_w, region_key(xw + 31 - __clz((int)below), y, z))] : 1u;
+    }
+    keys[pos] = region_key(x0 + bit, y, z); vals[pos] = m;
+    pos++;
+  }
+}
+
+__global__ __launch_bounds__(256) void fill_list_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, int4 *out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t k = keys[i];
+  out[i] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)vals[i]);
+}
+
+namespace {
+
+inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
+const char *kNoMemory = "out of device memory in the enclosed-space fill";
+
+// what one call asks for, validated on the host before anything is queued
+struct Request {
+  tdt_fill f;
+  std::vector<RegionShape> shapes;
+};
+
+int make_request(tdt_ctx *ctx, const tdt_fill *f, const tdt_region *regions, size_t n_regions, Request &R) {
+  if (!f) return fail(ctx, TDT_ERR_INVALID_VALUE, "null tdt_fill pointer");
+  if (f->connectivity != 6 && f->connectivity != 26) return fail(ctx, TDT_ERR_INVALID_VALUE, "connectivity must be 6 or 26");
+  if (f->material < -1 || f->material > 253) return fail(ctx, TDT_ERR_INVALID_VALUE, "material must be -1 (inherit) or 0..253");
+  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
+  R.f = *f;
+  R.shapes.assign(n_regions, RegionShape{});
+  for (size_t s = 0; s < n_regions; s++) {
+    const tdt_region &g = regions[s];
+    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
+    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
+    R.shapes[s].shape = g.shape;
+    for (int a = 0; a < 3; a++) { R.shapes[s].a[a] = g.a[a]; R.shapes[s].b[a] = g.b[a]; }
+  }
+  return TDT_OK;
+}
+
+// E(W, c) within the mask, or (with_walls) W + E(W, c), as {x, y, z, material + 1}, Morton-sorted, in device memory of ctx
+// (allocated in S; null when *n == 0).  W: n_w voxels inside the grid of side 2^depth, Morton-sorted and unique, in device
+// memory of ctx, n_w <= 2^26 (fill_list has checked the tree's list; a mesh's cannot be larger).  Queued on ctx's stream; synchronises.
+int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, int depth, const Request &R, bool with_walls, DeviceScratch &S,
+                    const int4 **out, uint32_t *n) {
+  *out = nullptr; *n = 0;
+  front->fill_passes = 0;
+  if (n_w == 0) return TDT_OK;                             // nothing encloses anything
+  hipStream_t st = ctx->stream;
+  // ---- bbox(W) ----
+  int box[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
+  int *d_box = S.get<int>(6);
+  uint32_t *wk = S.get<uint32_t>(n_w), *wv = S.get<uint32_t>(n_w);
+  if (!d_box || !wk || !wv) return fail(front, TDT_ERR_HIP, kNoMemory);
+  TDT_HIP(front, hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fill_bbox_kernel, dim3(blocks_of(n_w)), dim3(256), 0, st, w, n_w, d_box);
+  TDT_HIP(front, hipGetLastError());
+  TDT_HIP(front, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, st));
+  TDT_HIP(front, hipStreamSynchronize(st));                // the box sizes the volumes
+  const int N = 1 << depth;
+  for (int a = 0; a < 3; a++)
+    if (box[a] < 0 || box[3 + a] >= N || box[a] > box[3 + a]) return fail(front, TDT_ERR_INVALID_VALUE, "a wall voxel lies outside the grid");
+  FillBox B;
+  std::memset(&B, 0, sizeof B);
+  for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }
+  B.ey = B.hi[1] - B.lo[1] + 1; B.ez = B.hi[2] - B.lo[2] + 1;
+  B.wx0 = B.lo[0] >> 5; B.nw = (B.hi[0] >> 5) - B.wx0 + 1;
+  B.n_words = (uint32_t)B.ey * (uint32_t)B.ez * (uint32_t)B.nw;
+  // ---- occupancy, seeds ----
+  uint32_t *occ = S.get<uint32_t>(B.n_words), *reach = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kFillBatch);
+  if (!occ || !reach || !flags) return fail(front, TDT_ERR_HIP, kNoMemory);
+  TDT_HIP(front, hipMemsetAsync(occ, 0, (size_t)B.n_words * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(fill_rasterise_kernel, dim3(blocks_of(n_w)), dim3(256), 0, st, w, n_w, B, occ, wk, wv);
+  hipLaunchKernelGGL(fill_seed_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, reach);
+  TDT_HIP(front, hipGetLastError());
+  // ---- flood: a box thinner than 3 rows on an axis is all faces, and seeded whole ----
+  if (B.ey > 2 && B.ez > 2 && B.hi[0] - B.lo[0] > 1) {
+    const dim3 tiles((unsigned)((B.ey + kFillTile - 1) / kFillTile), (unsigned)((B.ez + kFillTile - 1) / kFillTile));
+    uint32_t h_flags[kFillBatch], queued = 0;
+    do {
+      TDT_HIP(front, hipMemsetAsync(flags, 0, sizeof h_flags, st));
+      for (int p = 0; p < kFillBatch; p++) {
+        if (R.f.connectivity == 6) hipLaunchKernelGGL(fill_flood_kernel<6>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flags + p);
+        else hipLaunchKernelGGL(fill_flood_kernel<26>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flags + p);
+      }
+      TDT_HIP(front, hipGetLastError());
+      TDT_HIP(front, hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
+      TDT_HIP(front, hipStreamSynchronize(st));            // one per batch of passes
+      for (int p = kFillBatch - 1; p >= 0; p--)
+        if (h_flags[p]) { front->fill_passes = queued + (uint32_t)p + 1u; break; }   // the last pass that changed the volume
+      queued += kFillBatch;
+    } while (h_flags[kFillBatch - 1]);
+  }
+  // ---- count ----
+  RegionShape *d_shapes = nullptr;
+  const uint32_t n_shapes = with_walls ? 0u : (uint32_t)R.shapes.size();
+  if (n_shapes) {
+    d_shapes = S.get<RegionShape>(n_shapes);
+    if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
+    TDT_HIP(front, hipMemcpyAsync(d_shapes, R.shapes.data(), n_shapes * sizeof(RegionShape), hipMemcpyHostToDevice, st));
+  }
+  uint32_t *count = S.get<uint32_t>((size_t)B.n_words + 1), *scr = S.get<uint32_t>(scan_scratch_words((size_t)B.n_words + 1));
+  if (!count || !scr) return fail(front, TDT_ERR_HIP, kNoMemory);
+  hipLaunchKernelGGL(fill_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
+                     (const RegionShape *)d_shapes, n_shapes, count);
+  TDT_HIP(front, exclusive_scan_u32(st, count, count, B.n_words + 1u, scr));
+  TDT_HIP(front, hipGetLastError());
+  uint32_t n_e = 0;                                        // <= 2^30: 32 per word
+  TDT_HIP(front, hipMemcpyAsync(&n_e, count + B.n_words, sizeof n_e, hipMemcpyDeviceToHost, st));
+  TDT_HIP(front, hipStreamSynchronize(st));                // the enclosed count
+  if (n_e > kFillCap) return fail(front, TDT_ERR_INVALID_VALUE, "the enclosed space holds " + std::to_string(n_e) + " voxels (more than 2^26)");
+  const uint32_t n_out = n_e + (with_walls ? n_w : 0u);
+  if (n_out == 0) return TDT_OK;
+  // ---- emit, sort ----
+  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out), *k1 = S.get<uint32_t>(n_out), *v1 = S.get<uint32_t>(n_out);
+  uint32_t *hist = S.get<uint32_t>(sort_hist_words(n_out)), *hscr = S.get<uint32_t>(sort_scratch_words(n_out));
+  int4 *vox = S.get<int4>(n_out);
+  if (!k0 || !v0 || !k1 || !v1 || !hist || !hscr || !vox) return fail(front, TDT_ERR_HIP, kNoMemory);
+  const uint32_t at = with_walls ? n_w : 0u;
+  if (with_walls) {
+    TDT_HIP(front, hipMemcpyAsync(k0, wk, (size_t)n_w * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    TDT_HIP(front, hipMemcpyAsync(v0, wv, (size_t)n_w * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  }
+  if (n_e)
+    hipLaunchKernelGGL(fill_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
+                       (const RegionShape *)d_shapes, n_shapes, (const uint32_t *)count, R.f.material >= 0 ? (uint32_t)R.f.material + 1u : 0u,
+                       (const uint32_t *)wk, (const uint32_t *)wv, n_w, k0 + at, v0 + at);
+  uint32_t *k = k0, *v = v0;
+  TDT_HIP(front, sort_pairs_u32(st, k, v, k1, v1, n_out, hist, hscr));
+  hipLaunchKernelGGL(fill_list_kernel, dim3(blocks_of(n_out)), dim3(256), 0, st, (const uint32_t *)k, (const uint32_t *)v, n_out, vox);
+  TDT_HIP(front, hipGetLastError());
+  TDT_HIP(front, hipStreamSynchronize(st));
+  *out = vox; *n = n_out;
+  return TDT_OK;
+}
+
+// the list a call produces on one single-device context: the tree form (mesh == null: E(V, c) within the mask) or the solid mesh
+int fill_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, const tdt_mesh *mesh, int depth, DeviceScratch &S, const int4 **out, uint32_t *n) {
+  if (mesh) {
+    const int4 *s = nullptr;
+    uint32_t ns = 0;
+    if (int rc = mesh_voxels(front, ctx, mesh, depth, S, &s, &ns)) return rc;   // |S| <= its covered pairs <= 2^26, or it has failed
+    return enclosed_voxels(front, ctx, s, ns, depth, R, true, S, out, n);
+  }
+  int4 *v = nullptr;
+  uint32_t nv = 0;
+  // (as in the sibling units the cap is checked on the expanded list: 16 B per voxel of the tree before it can fail)
+  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
+  if (nv > kFillCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  return enclosed_voxels(front, ctx, v, nv, depth, R, false, S, out, n);
+}
+
+struct FillSource final : VoxelSource {
+  const Request &R;
+  const tdt_mesh *mesh;
+  FillSource(const Request &r, const tdt_mesh *m) : R(r), mesh(m) {}
+  int run(tdt_ctx *front, tdt_ctx *ctx, int depth, DeviceScratch &S, const int4 **vox, uint32_t *n) override {
+    return fill_list(front, ctx, R, mesh, depth, S, vox, n);
+  }
+};
+
+// the list into host memory by tdt_octree_extract's rules, from device_ids[0] of a multi-device context
+int fill_extract(tdt_ctx *ctx, const Request &R, const tdt_mesh *mesh, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {
+  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  TDT_HIP(ctx, hipSetDevice(m->device));
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};
+  DeviceScratch S;
+  const int4 *vox = nullptr;
+  uint32_t n = 0;
+  if (int rc = fill_list(ctx, m, R, mesh, depth, S, &vox, &n)) return rc;
+  *n_out = n;
+  if (!host_out || n == 0) return TDT_OK;
+  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " voxels");
+  TDT_HIP(ctx, hipMemcpyAsync(host_out, vox, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost, m->stream));
+  TDT_HIP(ctx, hipStreamSynchronize(m->stream));
+  return TDT_OK;
+}
+
+}  // namespace
+}  // namespace tdt
+
+extern "C" {
+
+int tdt_octree_extract_enclosed(tdt_ctx *ctx, const tdt_fill *f, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                                size_t capacity, size_t *n_voxels) {
+  using namespace tdt;
+  if (!ctx) return TDT_ERR_INVALID_VALUE;
+  if (!n_voxels) return fail(ctx, TDT_ERR_INVALID_VALUE, "null n_voxels pointer");
+  *n_voxels = 0;
+  Request R;
+  if (int rc = make_request(ctx, f, regions, n_regions, R)) return rc;
+  return fill_extract(ctx, R, nullptr, 0, voxels_xyzm, capacity, n_voxels);
+}
+
+int tdt_octree_fill_enclosed(tdt_ctx *ctx, const tdt_fill *f, const tdt_region *regions, size_t n_regions, uint32_t *n_cells) {
+  using namespace tdt;
+  if (!ctx) return TDT_ERR_INVALID_VALUE;
+  Request R;
+  if (int rc = make_request(ctx, f, regions, n_regions, R)) return rc;
+  FillSource src(R, nullptr);
+  return region_edit_source(ctx, TDT_REGION_FILL, src, n_cells);
+}
+
+int tdt_voxelize_triangles_solid(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, const tdt_fill *f, int32_t *voxels_xyzm, size_t capacity,
+                                 size_t *n_voxels) {
+  using namespace tdt;
+  if (!ctx) return TDT_ERR_INVALID_VALUE;
+  if (!n_voxels) return fail(ctx, TDT_ERR_INVALID_VALUE, "null n_voxels pointer");
+  *n_voxels = 0;
+  if (depth < 1 || depth > 10) return fail(ctx, TDT_ERR_INVALID_VALUE, "depth must be 1..10");
+  if (int rc = check_mesh(ctx, mesh)) return rc;
+  Request R;
+  if (int rc = make_request(ctx, f, nullptr, 0, R)) return rc;
+  return fill_extract(ctx, R, mesh, depth, voxels_xyzm, capacity, n_voxels);
+}
+
+int tdt_octree_edit_triangles_solid(tdt_ctx *ctx, int op, const tdt_mesh *mesh, const tdt_fill *f, uint32_t *n_cells) {
+  using namespace tdt;
+  if (!ctx) return TDT_ERR_INVALID_VALUE;
+  if (op < TDT_REGION_SET || op > TDT_REGION_CLEAR) return fail(ctx, TDT_ERR_INVALID_VALUE, "op must be a TDT_REGION_* value");
+  if (int rc = check_mesh(ctx, mesh)) return rc;
+  Request R;
+  if (int rc = make_request(ctx, f, nullptr, 0, R)) return rc;
+  FillSource src(R, mesh);
+  return region_edit_source(ctx, op, src, n_cells);
+}
+
+int tdt_debug_fill_passes(const tdt_ctx *ctx) { return ctx ? (int)ctx->fill_passes : 0; }
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 // Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
-// tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation).
+// tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
+// tdt_fill.hip: enclosed space).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +94,7 @@ struct tdt_ctx {
   tdt::Multi *multi;            // non-null: this is a multi-device context (tdt_ctx_create_multi); see tdt_multi.hip
   tdt::EditScratch *edit;       // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
   void *query; size_t query_bytes;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
+  uint32_t fill_passes;         // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   std::vector<tdt_buffer *> buffers;
   std::vector<tdt_image *> images;
   std::vector<tdt_compute *> computes;
@@ -214,6 +216,13 @@ struct VoxelSource {
 };
 // tdt_octree_edit_voxels(op, the source's list) on every replica (the caller has checked op)
 int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells);
+
+// ---- tdt_mesh.hip: what the solid forms (tdt_fill.hip) start from ----
+// everything about a mesh that does not depend on the grid, checked on the host before anything is queued
+int check_mesh(tdt_ctx *ctx, const tdt_mesh *m);
+// the voxels of a mesh that passed check_mesh, {x, y, z, material + 1}, Morton-sorted and unique, in device memory of ctx
+// (allocated in S; null when *n == 0).  Queued on ctx's stream; synchronises.  Errors are reported on `front`.
+int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, DeviceScratch &S, const int4 **out, uint32_t *n);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -260,7 +260,26 @@ namespace {
 inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the mesh voxelisation";
 
-// everything about a mesh that does not depend on the grid, checked on the host before anything is queued
+// level-1 candidates of the whole mesh on a grid of side 2^depth (what mesh_setup_kernel's counts sum to)
+unsigned long long tile_candidates(const tdt_mesh *m, int depth) {
+  unsigned long long total = 0;
+  for (size_t t = 0; t < m->n_triangles; t++) {
+    int lo[3], hi[3], vlo[3], vhi[3];
+    for (int k = 0; k < 3; k++) {
+      lo[k] = hi[k] = m->vertices[3 * (size_t)m->triangles[3 * t] + k];
+      for (int i = 1; i < 3; i++) {
+        const int c = m->vertices[3 * (size_t)m->triangles[3 * t + i] + k];
+        lo[k] = c < lo[k] ? c : lo[k]; hi[k] = c > hi[k] ? c : hi[k];
+      }
+    }
+    total += mesh_tile_count(lo, hi, 1 << depth, vlo, vhi);
+  }
+  return total;
+}
+
+}  // namespace
+
+// everything about a mesh that does not depend on the grid, checked on the host before anything is queued (tdt_internal.hpp)
 int check_mesh(tdt_ctx *ctx, const tdt_mesh *m) {
   if (!m) return fail(ctx, TDT_ERR_INVALID_VALUE, "null mesh");
   if (m->n_triangles && !m->triangles) return fail(ctx, TDT_ERR_INVALID_VALUE, "null triangle array");
@@ -280,25 +299,9 @@ int check_mesh(tdt_ctx *ctx, const tdt_mesh *m) {
   return TDT_OK;
 }
 
-// level-1 candidates of the whole mesh on a grid of side 2^depth (what mesh_setup_kernel's counts sum to)
-unsigned long long tile_candidates(const tdt_mesh *m, int depth) {
-  unsigned long long total = 0;
-  for (size_t t = 0; t < m->n_triangles; t++) {
-    int lo[3], hi[3], vlo[3], vhi[3];
-    for (int k = 0; k < 3; k++) {
-      lo[k] = hi[k] = m->vertices[3 * (size_t)m->triangles[3 * t] + k];
-      for (int i = 1; i < 3; i++) {
-        const int c = m->vertices[3 * (size_t)m->triangles[3 * t + i] + k];
-        lo[k] = c < lo[k] ? c : lo[k]; hi[k] = c > hi[k] ? c : hi[k];
-      }
-    }
-    total += mesh_tile_count(lo, hi, 1 << depth, vlo, vhi);
-  }
-  return total;
-}
-
 // the mesh's voxels {x, y, z, material + 1}, Morton-sorted and unique, in device memory of ctx (allocated in S; null when
 // *n == 0).  The mesh has passed check_mesh.  Queued on ctx's stream, so ordered after the work already there; synchronises.
+// (tdt_internal.hpp: the solid forms of tdt_fill.hip start from this list)
 int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, DeviceScratch &S, const int4 **out, uint32_t *n) {
   *out = nullptr; *n = 0;
   const uint32_t nt = m->n_triangles;
@@ -372,6 +375,8 @@ int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, Devi
   *out = vox; *n = nu;
   return TDT_OK;
 }
+
+namespace {
 
 struct MeshSource final : VoxelSource {
   const tdt_mesh *mesh;

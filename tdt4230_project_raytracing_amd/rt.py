@@ -135,6 +135,16 @@ class Mesh(ctypes.Structure):
 assert ctypes.sizeof(Mesh) == 40
 
 
+# enclosed space (include/tdt_rt.h): struct tdt_fill
+class Fill(ctypes.Structure):
+    """struct tdt_fill: connectivity 6 / 26 of the EMPTY voxels, material -1 (inherit along -x) or 0..253."""
+    _fields_ = [("connectivity", ctypes.c_int32), ("material", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Fill) == 8
+assert Fill.connectivity.offset == 0 and Fill.material.offset == 4
+
+
 def _exact_ints(a, dtype, name):
     """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
     src = np.asarray(a)
@@ -239,6 +249,11 @@ SYMBOLS = [
     ("tdt_octree_extract_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_voxelize_triangles", _I, [_P, ctypes.POINTER(Mesh), _I, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_edit_triangles", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_enclosed", _I, [_P, ctypes.POINTER(Fill), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_fill_enclosed", _I, [_P, ctypes.POINTER(Fill), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_voxelize_triangles_solid", _I, [_P, ctypes.POINTER(Mesh), _I, ctypes.POINTER(Fill), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_triangles_solid", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(Fill), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_debug_fill_passes", _I, [_P]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -543,6 +558,70 @@ class Context:
         self._check_edit(lib().tdt_octree_edit_triangles(self.h, int(op), ctypes.byref(mesh), ctypes.byref(n)), n)
         del keep
         return int(n.value)
+
+    @staticmethod
+    def _fill(connectivity, material):
+        """struct tdt_fill (material None: inherit); both fields must fit an int32 (ctypes would wrap them silently) and a bool is
+        not a number here.  The ranges themselves are the library's to check."""
+        material = -1 if material is None else material
+        for name, v in (("connectivity", connectivity), ("material", material)):
+            if isinstance(v, bool):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+            if int(v) != v or not -2**31 <= int(v) <= 2**31 - 1:
+                raise ValueError(f"{name} must be an int32, not {v!r}")
+        return Fill(int(connectivity), int(material))
+
+    def octree_extract_enclosed(self, connectivity=6, material=None, regions=None):
+        """tdt_octree_extract_enclosed: the empty voxels of the bound tree that no path of empty 6- / 26-neighbours connects to a
+        face of the grid, as an (n, 4) int32 list {x, y, z, material + 1}, Morton-sorted; they inherit the material of the wall
+        at their -x side (None) or get `material` 0..253; regions (one Region or a list) limit what is reported (None: no mask;
+        an empty list: an empty mask).  The tree is untouched.  Counts first, fills second: two floods."""
+        f = self._fill(connectivity, material)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_enclosed(self.h, ctypes.byref(f), arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_enclosed(self.h, ctypes.byref(f), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def octree_fill_enclosed(self, connectivity=6, material=None, regions=None):
+        """tdt_octree_fill_enclosed: octree_edit_voxels(REGION_FILL, octree_extract_enclosed(...)) without the list leaving the
+        device; rebuilds the bound tree in place and returns the canonical tree's cell count."""
+        f = self._fill(connectivity, material)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_fill_enclosed(self.h, ctypes.byref(f), arr, k, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def voxelize_triangles_solid(self, vertices, triangles, depth, materials=None, material=0, connectivity=6, fill_material=None):
+        """tdt_voxelize_triangles_solid: voxelize_triangles(...) plus the space its surface encloses (connectivity of the empty
+        voxels 6 / 26; fill_material None: inherit the surface's material along -x, or 0..253), (n, 4) int32, Morton-sorted.
+        Needs no bound tree.  Counts first, fills second."""
+        mesh, keep = _mesh(vertices, triangles, materials, material)
+        f = self._fill(connectivity, fill_material)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_voxelize_triangles_solid(self.h, ctypes.byref(mesh), int(depth), ctypes.byref(f), None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_voxelize_triangles_solid(self.h, ctypes.byref(mesh), int(depth), ctypes.byref(f), out.ctypes.data, n.value,
+                                                          ctypes.byref(n)))
+        del keep
+        return out
+
+    def octree_edit_triangles_solid(self, op, vertices, triangles, materials=None, material=0, connectivity=6, fill_material=None):
+        """tdt_octree_edit_triangles_solid: octree_edit_voxels(op, voxelize_triangles_solid(..., max_depth of slot 7)) without the
+        list leaving the device; returns the canonical tree's cell count."""
+        mesh, keep = _mesh(vertices, triangles, materials, material)
+        f = self._fill(connectivity, fill_material)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_triangles_solid(self.h, int(op), ctypes.byref(mesh), ctypes.byref(f), ctypes.byref(n)), n)
+        del keep
+        return int(n.value)
+
+    def fill_passes(self):
+        """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
+        return int(lib().tdt_debug_fill_passes(self.h))
 
     def bind_buffer_base(self, target, slot, vbo):
         """gl::BindBufferBase(target, slot, vbo.id()) — main.rs:352,383,408,430,448; octree.rs:67,98,115,144."""
