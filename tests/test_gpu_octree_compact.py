@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_py
+import tree_model
 from octree_util import distinct_deltas, edit_setup, expand_cells, written_node
 from tdt4230_project_raytracing_amd import build, host, rt
 
@@ -87,11 +88,21 @@ def monument_scene():
     return host.Scene({s: z[f"blob_{s}"] for s in (0, 1, 2, 3, 4, 6, 7)})
 
 
-def canonical(ctx, cells, depth, nbytes):
-    """What compaction must leave in a buffer of nbytes: the builder's tree of the voxels, then zeros."""
-    vbo, n = rt.octree_build_cells(ctx, sorted_expand(cells, depth), depth)
+MODEL_LIMIT = 1 << 20                         # voxels up to which an expected tree is also checked against the numpy builder
+
+
+def canonical(ctx, cells, depth, nbytes, model=True):
+    """What compaction must leave in a buffer of nbytes: the builder's tree of the voxels, then zeros.  Up to MODEL_LIMIT voxels
+    the GPU builder's bytes must also be those of the numpy builder (tests/tree_model.py), which shares no code with it;
+    model=False: for a list the model does not take."""
+    vox = sorted_expand(cells, depth)
+    vbo, n = rt.octree_build_cells(ctx, vox, depth)
+    built = vbo.read(np.uint32)
+    if model and len(vox) <= MODEL_LIMIT:
+        want = tree_model.build_cells(vox, depth)
+        assert n == len(want) // 16 and built.size == want.size and np.array_equal(built, want), "the GPU builder differs from tree_model"
     out = np.zeros(nbytes // 4, np.uint32)
-    out[: 16 * n] = vbo.read(np.uint32)
+    out[: 16 * n] = built
     return out, n
 
 

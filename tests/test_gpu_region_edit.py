@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_py
+import tree_model
 from octree_util import distinct_deltas, edit_setup, written_node
 from tdt4230_project_raytracing_amd import build, host, rt
 
@@ -100,12 +101,22 @@ def expected_region(V, op, regions, material, depth):
     return apply_op(V, op, B, material + 1)
 
 
-def built_cells(ctx, vox, depth):
-    """The builder's tree of vox (one all-EMPTY root for no voxels) as uint32 words."""
+MODEL_LIMIT = 1 << 20                         # voxels up to which an expected tree is also checked against the numpy builder
+
+
+def built_cells(ctx, vox, depth, model=True):
+    """The builder's tree of vox (one all-EMPTY root for no voxels) as uint32 words.  Lists of at most MODEL_LIMIT voxels must
+    also come out as the bytes of the numpy builder (tests/tree_model.py), so that what the edit suites expect does not rest
+    on the GPU builder alone (tests/test_gpu_tree_roots.py pins the two to each other on aimed cases; this does it on every
+    list the suites really use).  model=False: for a list the model does not take (a position listed twice)."""
     if len(vox) == 0:
         return np.zeros(16, np.uint32)
-    vbo, _ = rt.octree_build_cells(ctx, np.ascontiguousarray(vox, np.int32), depth)
-    return vbo.read(np.uint32)
+    vbo, n = rt.octree_build_cells(ctx, np.ascontiguousarray(vox, np.int32), depth)
+    built = vbo.read(np.uint32)
+    if model and len(vox) <= MODEL_LIMIT:
+        want = tree_model.build_cells(vox, depth)
+        assert n == len(want) // 16 and built.size == want.size and np.array_equal(built, want), "the GPU builder differs from tree_model"
+    return built
 
 
 def padded(built, nbytes):
