@@ -52,8 +52,10 @@ TDT_DEV float rcp_core(float y) {          // RN(1/y) for y in the window
   const float e = __builtin_fmaf(-y, r, 1.0f);
   return __builtin_fmaf(e, r, r);
 }
+// one seed: v_rsq_f32 gives y ~ 1/sqrt(x), x * y the root to refine and y / 2 the step's factor (v_sqrt_f32 for the root was a second
+// quarter-rate instruction for the same information).  tdt_selftest mode 1: all 2^32 inputs.
 TDT_DEV float sqrt_core(float x) {         // RN(sqrt(x)) for positive x in the window
-  const float s = __builtin_amdgcn_sqrtf(x), h = 0.5f * __builtin_amdgcn_rsqf(x);
+  const float y = __builtin_amdgcn_rsqf(x), s = x * y, h = 0.5f * y;
   return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);     // seed + one step on the exact residual
 }
 TDT_DEV float q_rcp(float y) {
@@ -71,6 +73,8 @@ TDT_DEV float q_sqrt(float x) {
 }
 TDT_DEV float q_rsq(float x) {             // RN(1 / RN(sqrt(x))): sqrt of a window value stays in the window
   if (__builtin_expect(__ballot(!pos_in_window(x)) != 0ull, 0)) return 1.0f / __builtin_sqrtf(x);
+  // (the reciprocal keeps its own seed: refining y = rsq(x), which is within ~1.5 ulp of 1 / s, by one step misses RN(1 / s) on 202 of
+  // the 2^32 inputs — tdt_selftest mode 2 — and a second step costs what the seed does)
   return rcp_core(sqrt_core(x));
 }
 // a / b through the correctly rounded reciprocal and one residual step.  NOT claimed for all operand pairs: used at two call sites
