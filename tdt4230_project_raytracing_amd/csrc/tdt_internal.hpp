@@ -1,4 +1,5 @@
-// Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, trace, helpers;
+// Internal definitions shared by the translation units of libtdtrt.so (tdt_rt.hip: context, the trace path and its state
+// (tdt::TraceState: only forward-declared here), helpers;
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
 // tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
@@ -16,7 +17,7 @@
 constexpr int kNumSlots = 8;
 
 // What a trace dispatch depends on besides the sample range — compared with what the recorded pixel costs were measured on
-// (see launch()).  A plain struct, zero-filled before it is written, so that a field added later is part of the comparison
+// (see plan_order() in tdt_rt.hip).  A plain struct, zero-filled before it is written, so that a field added later is part of the comparison
 // by construction (it used to be a byte string that silently dropped what did not fit).
 struct CostSig {
   int32_t cam_i[4]; float cam_f[12]; int32_t part[2];
@@ -25,7 +26,7 @@ struct CostSig {
   struct { const void *buffer; unsigned long long version; } slot[kNumSlots];
 };
 
-namespace tdt { struct Multi; struct EditScratch; }
+namespace tdt { struct Multi; struct EditScratch; struct TraceState; }
 struct TraceParams;
 
 struct tdt_buffer {
@@ -45,56 +46,22 @@ struct tdt_image {
   tdt_image *full;              // multi-device context: the assembled frame on the first device (dev aliases its memory)
 };
 
+// What more than one translation unit uses.  Everything the trace path keeps between launches is tdt::TraceState (tdt_rt.hip).
 struct tdt_ctx {
-  int device;
-  hipStream_t stream;
-  bool own_stream;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
   std::string err;
-  tdt_buffer *ssbo[kNumSlots];
-  tdt_buffer *atomic0;
-  tdt_image *image0;
-  unsigned long long *counters;
-  unsigned int *queue; unsigned queue_parity, order_parity;   // two pixel-queue heads / two sets of sort counters, used alternately (each launch zeroes the other)
-  uint16_t *packed;             // LDS-table image of the bound cells buffer
-  const tdt_buffer *packed_of;  // which buffer/version `packed` was built from
-  unsigned long long packed_version;
-  uint32_t *slot_cost, *slot_acc, *slot_order, *order_hist;   // per queue slot: cost feedback of the last trace dispatch, the hand-out order derived from it; 2 x 256 sort counters
-  uint32_t cost_dispatches;            // dispatches summed into slot_cost so far
-  uint32_t acc_samples, last_launch_samples;   // samples per pixel behind slot_acc / traced by the last launch
-  int two_phase_min_spp;               // TDT_TWO_PHASE_MIN_SPP: frames with fewer samples per pixel take one pass (16)
-  int probe_div;                       // TDT_PROBE_DIV: probe samples of a two-phase frame = spp / probe_div (16)
-  float order_blend;                   // TDT_ORDER_BLEND: weight of the 8x8-tile mean in a thin (probe) cost estimate
-  uint32_t tile_capacity, cost_tiles;  // allocation size (work-groups); number of work-groups slot_cost holds the last dispatch's costs for (0: none)
-  int cost_range[2]; bool order_exact, no_order_reuse;   // sample range of the launch that recorded slot_cost; slot_order was sorted from the costs of that very launch repeated (TDT_NO_ORDER_REUSE=1: sort every frame)
-  CostSig cost_sig;                    // what those costs were measured on (camera, octree parameters, buffer versions, partition)
-  // miss pre-pass (cameras outside the octree: miss_prepass_kernel): done flag per queue slot, the filtered hand-out order, scratch
-  uint8_t *slot_done; uint32_t *slot_live, *filter_counts; uint32_t done_capacity; bool use_done, no_prepass;   // use_done: set for the launches of a frame whose pre-pass ran (TDT_NO_PREPASS=1: never)
-  bool no_cost_order;           // TDT_NO_COST_ORDER=1: always hand work-groups out in image order
-  uint32_t *scan;               // device scratch of scan_cells_kernel
-  uint32_t max_parent_value, max_any_value, live_nodes;   // its result for `packed_of` (live_nodes: one past the last node that is not all zeros)
-  float *thr; int32_t thr_cc; uint32_t thr_ic_bits, thr_n; float thr_f0max; bool thr_ok, no_table_form;   // FORM_TABLE builds: per-cell x-index thresholds for (cell_count, inv_cell_count) over thr_n cells (TDT_NO_TABLE_FORM=1: off)
-  int num_cus;
-  bool force_generic;   // TDT_FORCE_GENERIC=1: always run the literal-arithmetic kernel (A/B testing)
-  int event_threshold;  // TDT_EVENT_THRESHOLD=n fixes the event threshold (experiments); 0 = adaptive
-  int force_smooth; bool no_cost_accum; float max_share;   // TDT_ORDER_SMOOTH / TDT_NO_COST_ACCUM / TDT_MAX_SHARE (diagnostics)
-  int event_clamp;      // TDT_EVENT_CLAMP: upper clamp of the adaptive event threshold
-  float event_k;        // TDT_EVENT_K overrides the adaptive threshold's r (0: chosen from the tree size)
-  void *frame_carry; size_t frame_carry_bytes;   // hit-record carry between the two phases of a frame (tdt_dispatch_compute)
-  bool no_two_phase;                             // TDT_NO_TWO_PHASE=1
-  uint16_t *full_grid; const tdt_buffer *full_of; unsigned long long full_version; int full_depth; bool full_ok, no_full;   // whole-depth lookup table of small resident trees (TDT_NO_FULL_GRID=1: off)
-  uint32_t *brick_grid; void *bricks; size_t bricks_bytes; const tdt_buffer *brick_of; unsigned long long brick_version; int brick_depth; bool brick_ok, no_bricks;   // BRICK builds (depth-8 / 9 trees that are not LDS-resident; TDT_NO_BRICKS=1: off)
-  bool carry_final;                              // set around the last launch of a two-phase frame: its records need not be stored
-  bool probe_launch;                             // set around the probe launch of a two-phase frame (kernel name only)
-  bool phase_timing; hipEvent_t phase_ev[4]; int phase_n;   // tdt_debug_phase_timing: events around the launches of the last frame
-  uint32_t *present; size_t present_bytes;   // staging of tdt_image_read_rgba8
-  uint32_t *pixel_log; size_t pixel_log_u32;   // TDT_PIXEL_LOG diagnostics (instrumented dispatches only)
-  unsigned long long *stats;    // tdt_debug_stats: pass statistics of -DTDT_STATS builds (null otherwise)
-  int last_variant[6];  // tdt_debug_last_variant: the build the last trace launch ran
-  bool no_specialise;   // TDT_NO_SPECIALISE=1: never pick a scene-specialised kernel (A/B testing)
-  tdt::Multi *multi;            // non-null: this is a multi-device context (tdt_ctx_create_multi); see tdt_multi.hip
-  tdt::EditScratch *edit;       // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
-  void *query; size_t query_bytes;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
-  uint32_t fill_passes;         // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
+  tdt_buffer *ssbo[kNumSlots] = {};
+  tdt_buffer *atomic0 = nullptr;
+  tdt_image *image0 = nullptr;
+  unsigned long long *counters = nullptr;   // instrumented dispatches and tdt_selftest (on a multi-device front too: tdt_multi.hip frees it)
+  int num_cus = 0;
+  tdt::TraceState *trace = nullptr;        // state of the trace path (tdt_rt.hip); null on a multi-device front, whose members have their own
+  tdt::Multi *multi = nullptr;             // non-null: this is a multi-device context (tdt_ctx_create_multi); see tdt_multi.hip
+  tdt::EditScratch *edit = nullptr;        // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
+  void *query = nullptr; size_t query_bytes = 0;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
+  uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   std::vector<tdt_buffer *> buffers;
   std::vector<tdt_image *> images;
   std::vector<tdt_compute *> computes;
@@ -170,10 +137,13 @@ hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *
 int build_cells_from_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, int depth, tdt_buffer **out, uint32_t *n_cells);
 
 // ---- tdt_compact.hip: pieces region edits and voxel morphology reuse ----
-struct DeviceScratch {         // device temporaries of one operation, freed together
+struct DeviceScratch {         // device temporaries of one operation (or the arrays of a longer-lived owner), freed together
   std::vector<void *> ptrs;
   ~DeviceScratch() { release(); }
   void release() { for (void *p : ptrs) (void)hipFree(p); ptrs.clear(); }
+  void drop(void *p) {           // one of them ahead of the others (null: nothing)
+    for (size_t i = 0; i < ptrs.size(); i++) if (ptrs[i] == p) { (void)hipFree(p); ptrs.erase(ptrs.begin() + i); return; }
+  }
   template <class T> T *get(size_t n) {
     void *p = nullptr;
     if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;

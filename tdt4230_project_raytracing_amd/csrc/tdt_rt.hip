@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -1304,7 +1305,7 @@ void make_sig(const tdt_ctx *ctx, const tdt_compute *c, const Cover &k, const td
 }
 
 // The scene-specialised builds of the trace kernel (all SAFEV, COUNT = false), looked up by what the dispatch found out about the
-// scene.  One row per instantiation; a build that is not listed does not exist, and launch() falls back to the general kernel.
+// scene.  One row per instantiation; a build that is not listed does not exist, and launch_trace() falls back to the general kernel.
 using TraceFn = void (*)(const TraceParams);
 struct TraceVariant { int form, depth; bool resident, full, brick, unit; TraceFn fn; };
 #define TDT_V1(FORM, D, R, F, B, U) {tdt::FORM, D, R, F, B, U, tdt::trace_kernel<false, tdt::FORM, D, R, true, F, U, B>}
@@ -1354,18 +1355,123 @@ int tdt::octree_uniforms(tdt_ctx *ctx, TraceParams &P) {
 }
 
 namespace {
-int launch(tdt_compute *c, int width, int height, int depth, int mode, int spp_begin, int spp_count, void *carry,
-           int total_spp, unsigned long long *counts_out) {
+bool env_set(const char *name) { return getenv(name) != nullptr; }
+bool env_one(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
+float env_float(const char *name, float otherwise) { const char *v = getenv(name); return v ? (float)atof(v) : otherwise; }
+int env_int(const char *name, int lo, int hi, int otherwise) {      // a value outside [lo, hi] counts as not set
+  const char *v = getenv(name);
+  return v && atoi(v) >= lo && atoi(v) <= hi ? atoi(v) : otherwise;
+}
+constexpr int kAnyLo = -2147483647 - 1, kAnyHi = 2147483647;
+}  // namespace
+
+// Everything the trace path keeps between launches of one single-device context.  A multi-device front has none: its members do.
+struct tdt::TraceState {
+  tdt::DeviceScratch mem;       // owns every device array below: teardown is this struct's destructor, a new array joins no list
+  struct Switches {             // read from the environment once, when the context is created
+    bool no_cost_order = env_one("TDT_NO_COST_ORDER");        // always hand work-groups out in image order
+    int force_smooth = env_int("TDT_ORDER_SMOOTH", kAnyLo, kAnyHi, -1);      // TDT_ORDER_SMOOTH / TDT_NO_COST_ACCUM / TDT_MAX_SHARE (diagnostics)
+    bool no_cost_accum = env_set("TDT_NO_COST_ACCUM");
+    bool no_two_phase = env_set("TDT_NO_TWO_PHASE");
+    bool no_prepass = env_set("TDT_NO_PREPASS");              // never run the miss pre-pass
+    bool no_order_reuse = env_set("TDT_NO_ORDER_REUSE");      // sort every frame
+    bool no_full = env_set("TDT_NO_FULL_GRID");               // whole-depth lookup table off
+    bool no_table_form = env_set("TDT_NO_TABLE_FORM");        // FORM_TABLE builds off
+    bool no_bricks = env_set("TDT_NO_BRICKS");                // BRICK builds off (also set when the bricks cannot be allocated)
+    float max_share = env_float("TDT_MAX_SHARE", 1.0f);
+    float order_blend = env_float("TDT_ORDER_BLEND", 0.5f);   // weight of the 8x8-tile mean in a thin (probe) cost estimate
+    int two_phase_min_spp = env_int("TDT_TWO_PHASE_MIN_SPP", 2, kAnyHi, 16);   // frames with fewer samples per pixel take one pass (16)
+    int probe_div = env_int("TDT_PROBE_DIV", 2, 64, 16);      // probe samples of a two-phase frame = spp / probe_div (16)
+    bool force_generic = env_one("TDT_FORCE_GENERIC");        // always run the literal-arithmetic kernel (A/B testing)
+    bool no_specialise = env_one("TDT_NO_SPECIALISE");        // never pick a scene-specialised kernel (A/B testing)
+    int event_threshold = env_int("TDT_EVENT_THRESHOLD", kAnyLo, kAnyHi, 0);   // fixes the event threshold (experiments); 0 = adaptive
+    float event_k = env_float("TDT_EVENT_K", 0.0f);           // overrides the adaptive threshold's r (0: chosen from the tree size)
+    int event_clamp = env_int("TDT_EVENT_CLAMP", 2, 64, 40);  // upper clamp of the adaptive event threshold
+  } env;
+  struct Queue {                // two pixel-queue heads, used alternately (each launch zeroes the other)
+    unsigned int *heads = nullptr; unsigned parity = 0;
+  } queue;
+  struct CostOrder {            // per queue slot: cost feedback of the last trace dispatch, the hand-out order derived from it
+    uint32_t *slot_cost = nullptr, *slot_acc = nullptr, *slot_order = nullptr;
+    uint32_t *hist = nullptr; unsigned parity = 0;            // 2 x 256 sort counters, used alternately
+    uint32_t tile_capacity = 0, cost_tiles = 0;               // allocation size (work-groups); number of work-groups slot_cost holds the last dispatch's costs for (0: none)
+    uint32_t cost_dispatches = 0;                             // dispatches summed into slot_cost so far
+    uint32_t acc_samples = 0, last_launch_samples = 0;        // samples per pixel behind slot_acc / traced by the last launch
+    int cost_range[2] = {0, 0}; bool order_exact = false;     // sample range of the launch that recorded slot_cost; slot_order was sorted from the costs of that very launch repeated
+    CostSig cost_sig = {};                                    // what those costs were measured on (camera, octree parameters, buffer versions, partition)
+  } order;
+  struct MissPrepass {          // cameras outside the octree (miss_prepass_kernel): done flag per queue slot, the filtered hand-out order, scratch
+    uint8_t *slot_done = nullptr; uint32_t *slot_live = nullptr, *filter_counts = nullptr; uint32_t capacity = 0;
+  } miss;
+  // one (buffer, version, depth): what a table derived from the bound cells buffer was built from
+  struct TableKey {
+    const tdt_buffer *buffer = nullptr; unsigned long long version = 0; int depth = 0;
+    bool operator==(const TableKey &o) const { return buffer == o.buffer && version == o.version && depth == o.depth; }
+  };
+  struct ThresholdKey {         // the thresholds depend on the octree uniforms and the number of cells alone
+    int32_t cell_count = 0; uint32_t ic_bits = 0, n = 0;
+    bool operator==(const ThresholdKey &o) const { return cell_count == o.cell_count && ic_bits == o.ic_bits && n == o.n; }
+  };
+  struct Tables {               // derived from the bound cells buffer, each rebuilt when its key changes
+    uint16_t *packed = nullptr; TableKey packed_key;          // LDS-table image
+    uint32_t *scan = nullptr;                                 // device scratch of scan_cells_kernel, and its result for packed_key:
+    uint32_t max_parent_value = 0xFFFFFFFFu, max_any_value = 0xFFFFFFFFu, live_nodes = 0xFFFFFFFFu;   // (live_nodes: one past the last node that is not all zeros)
+    float *thr = nullptr; ThresholdKey thr_key; float thr_f0max = 0.0f; bool thr_ok = false;   // FORM_TABLE builds: per-cell x-index thresholds for (cell_count, inv_cell_count) over thr_key.n cells
+    uint16_t *full_grid = nullptr; TableKey full_key; bool full_ok = false;   // whole-depth lookup table of small resident trees
+    uint32_t *brick_grid = nullptr; uint16_t *bricks = nullptr; size_t bricks_bytes = 0; TableKey brick_key; bool brick_ok = false;   // BRICK builds (depth-8 / 9 trees that are not LDS-resident)
+  } tables;
+  float *frame_carry = nullptr; size_t frame_carry_bytes = 0;   // hit-record carry between the two phases of a frame (tdt_dispatch_compute)
+  bool phase_timing = false; hipEvent_t phase_ev[4] = {}; int phase_n = 0;   // tdt_debug_phase_timing: events around the launches of the last frame
+  uint32_t *present = nullptr; size_t present_bytes = 0;   // staging of tdt_image_read_rgba8
+  uint32_t *pixel_log = nullptr; size_t pixel_log_u32 = 0;   // TDT_PIXEL_LOG diagnostics (instrumented dispatches only)
+  unsigned long long *stats = nullptr;   // tdt_debug_stats: pass statistics of -DTDT_STATS builds (null otherwise)
+  int last_variant[6] = {};     // tdt_debug_last_variant: the build the last trace launch ran
+
+  ~TraceState() { if (phase_timing) for (auto &e : phase_ev) (void)hipEventDestroy(e); }
+  template <class T> hipError_t alloc(T *&p, size_t n) { p = mem.get<T>(n); return p ? hipSuccess : hipErrorOutOfMemory; }
+  // The one grow-only sequence: arrays that share a capacity are dropped and allocated anew when more is needed (contents are not kept).
+  // After a failed allocation every pointer of the group is null and the capacity 0, so that the next call tries again.
+  struct Array {
+    void **p; size_t bytes;
+    template <class T> Array(T *&ptr, size_t count) : p(reinterpret_cast<void **>(&ptr)), bytes(count * sizeof(T)) {}
+  };
+  template <class C> hipError_t grow(C &capacity, C need, std::initializer_list<Array> arrays) {
+    if (capacity >= need) return hipSuccess;
+    capacity = 0;
+    for (const Array &a : arrays) { mem.drop(*a.p); *a.p = nullptr; }
+    for (const Array &a : arrays)
+      if (!(*a.p = mem.get<unsigned char>(a.bytes))) {
+        for (const Array &b : arrays) { mem.drop(*b.p); *b.p = nullptr; }
+        return hipErrorOutOfMemory;
+      }
+    capacity = need;
+    return hipSuccess;
+  }
+};
+
+namespace {
+using tdt::TraceState;
+
+// What a launch is asked to do.  The values of Kind are TraceParams::mode.
+struct LaunchRequest {
+  enum Kind { kRender = 0, kAccumulate = 1, kResolve = 2, kMissPrepass = 3 } kind = kRender;
+  int spp_begin = 0, spp_count = 0, total_spp = 0;
+  void *carry = nullptr; bool carry_final = false;    // carry_final: the last launch of a two-phase frame, whose records need not be stored
+  bool probe = false;                                  // the probe launch of a two-phase frame (kernel name only)
+  bool prepass_ran = false;                            // the frame's miss pre-pass ran: its done slots are left out (tdt_dispatch_resolve on its own: false, every pixel is resolved)
+  unsigned long long *counts_out = nullptr;            // instrumented dispatch: where its eight totals go
+};
+
+int bind_params(const tdt_compute *c, int width, int height, const LaunchRequest &rq, TraceParams &P, Cover &k, Tiles &t) {
   tdt_ctx *ctx = c->ctx;
-  (void)depth;   // raytracer.comp is a 2-D dispatch: groups_z = max(depth / 1, 1) layers all write the same pixels
+  const TraceState::Switches &env = ctx->trace->env;
   static const int required[] = {TDT_SLOT_CELLS, TDT_SLOT_MATERIALS, TDT_SLOT_ALBEDOS, TDT_SLOT_METAL,
                                  TDT_SLOT_DIELECTRIC, TDT_SLOT_OCTREE_FLOATS, TDT_SLOT_OCTREE_INTS};
   for (int s : required)
     if (!ctx->ssbo[s]) return fail(ctx, TDT_ERR_INCOMPLETE, "no buffer bound to shader-storage slot " + std::to_string(s));
   if (!ctx->image0) return fail(ctx, TDT_ERR_INCOMPLETE, "no image bound to unit 0");
-  tdt_image *img = ctx->image0;
+  const tdt_image *img = ctx->image0;
 
-  TraceParams P;
   std::memset(&P, 0, sizeof P);
   if (int rc = tdt::octree_uniforms(ctx, P)) return rc;
   P.image_width = c->image_width; P.image_height = c->image_height;
@@ -1379,10 +1485,11 @@ int launch(tdt_compute *c, int width, int height, int depth, int mode, int spp_b
   P.albedos = (const uint32_t *)ctx->ssbo[TDT_SLOT_ALBEDOS]->dev; P.albedos_dwords = dwords(ctx->ssbo[TDT_SLOT_ALBEDOS]);
   P.metal = (const uint32_t *)ctx->ssbo[TDT_SLOT_METAL]->dev; P.metal_dwords = dwords(ctx->ssbo[TDT_SLOT_METAL]);
   P.dielectric = (const uint32_t *)ctx->ssbo[TDT_SLOT_DIELECTRIC]->dev; P.dielectric_dwords = dwords(ctx->ssbo[TDT_SLOT_DIELECTRIC]);
-  P.image = img->dev; P.carry = (float *)carry; P.carry_final = ctx->carry_final ? 1 : 0;
-  if (mode == 2) P.carry_final = ctx->use_done ? 1 : 0;      // resolve: skip the pixels the frame's miss pre-pass finished (only then: tdt_dispatch_resolve on its own resolves every pixel)
-  Cover k = cover_of(c, width, height);
-  Tiles t = tiles_of(c, k);
+  P.image = img->dev; P.carry = (float *)rq.carry;
+  // resolve: skip the pixels the frame's miss pre-pass finished (only then: tdt_dispatch_resolve on its own resolves every pixel)
+  P.carry_final = (rq.kind == LaunchRequest::kResolve ? rq.prepass_ran : rq.carry_final) ? 1 : 0;
+  k = cover_of(c, width, height);
+  t = tiles_of(c, k);
   P.cover_w = k.cover_w; P.cover_h = k.cover_h;
   P.tiles_x = t.tiles_x > 0 ? t.tiles_x : 1; P.owned_tiles = t.owned;
   // t / tiles_x by multiplication: with m = floor(2^32 / d) + 1, mulhi(t, m) = floor(t / d) whenever t * d < 2^32
@@ -1393,322 +1500,378 @@ int launch(tdt_compute *c, int width, int height, int depth, int mode, int spp_b
   else if (img->w == 32 && img->h >= 32 * t.owned && (img->h % 32) == 0) P.compact = 1;   // tile buffer [k][32][32]
   else return fail(ctx, TDT_ERR_INVALID_OPERATION,
                    "bound image is neither camera.image_width x image_height nor a 32 x 32*tiles tile buffer");
-  P.spp_begin = spp_begin; P.spp_count = spp_count; P.mode = mode; P.total_spp = total_spp;
-  P.event_threshold = ctx->event_threshold;   // 0: adaptive (see trace_kernel)
-  P.event_clamp = (float)ctx->event_clamp;
+  P.spp_begin = rq.spp_begin; P.spp_count = rq.spp_count; P.mode = rq.kind; P.total_spp = rq.total_spp;
+  P.accumulate = rq.kind == LaunchRequest::kAccumulate ? 1 : 0;
+  P.event_threshold = env.event_threshold;   // 0: adaptive (see trace_kernel)
+  P.event_clamp = (float)env.event_clamp;
   {  // r of the adaptive event threshold (see trace_kernel): 0.10 up to 1.4 MiB of cells, 0.35 from 5 MiB on (refitted twice in round 2:
      // the traversal step lost a fifth of its instructions, which moves the optimum towards fewer, fuller event passes)
     const float mib = (float)ctx->ssbo[TDT_SLOT_CELLS]->bytes / 1048576.0f;
     const float r = 0.07f * mib;
-    P.event_k = ctx->event_k > 0.0f ? ctx->event_k : (r < 0.10f ? 0.10f : (r > 0.35f ? 0.35f : r));
+    P.event_k = env.event_k > 0.0f ? env.event_k : (r < 0.10f ? 0.10f : (r > 0.35f ? 0.35f : r));
     { static const char *ks = getenv("TDT_EVENT_K_SCALE"); if (ks && atof(ks) > 0.0) P.event_k *= (float)atof(ks); }      // (diagnostics: refitting r)
   }
-
-#ifdef TDT_STATS
-  P.stats = (mode == 0 || mode == 1) && !counts_out && !(ctx->probe_launch && getenv("TDT_STATS_SKIP_PROBE")) ? ctx->stats : nullptr;   // (SKIP_PROBE: the main launch of a two-phase frame alone)
-#endif
   TDT_HIP(ctx, hipSetDevice(ctx->device));
   if (ctx->ssbo[TDT_SLOT_CELLS]->bytes > 0xFFFFFFF8ull)
     return fail(ctx, TDT_ERR_INVALID_VALUE, "cells buffer larger than 4 GiB is not addressable by the shader's 32-bit offsets");
-  if (counts_out) {
+  return TDT_OK;
+}
+
+// the miss pre-pass of a frame (see miss_prepass_kernel): done flags for every queue slot
+int launch_miss_prepass(tdt_ctx *ctx, TraceState &S, int owned, const TraceParams &P) {
+  if (owned <= 0) return TDT_OK;
+  const size_t n = (size_t)owned * 1024;
+  TDT_HIP(ctx, S.grow(S.miss.capacity, (uint32_t)owned, {{S.miss.slot_done, n}, {S.miss.slot_live, n},
+                                                         {S.miss.filter_counts, (n + tdt::kFilterChunk - 1) / tdt::kFilterChunk + 1}}));
+  hipLaunchKernelGGL(tdt::miss_prepass_kernel, dim3((unsigned)owned * 4u), dim3(256), 0, ctx->stream, P, S.miss.slot_done);
+  TDT_HIP(ctx, hipGetLastError());
+  return TDT_OK;
+}
+
+// a thread per pixel
+int launch_resolve(tdt_ctx *ctx, int owned, const TraceParams &P) {
+  if (owned <= 0) return TDT_OK;
+  hipLaunchKernelGGL(tdt::resolve_kernel, dim3((unsigned)owned * 4u, 1, 1), dim3(256, 1, 1), 0, ctx->stream, P);
+  TDT_HIP(ctx, hipGetLastError());
+  return TDT_OK;
+}
+
+// counters of an instrumented dispatch, pass statistics of a -DTDT_STATS build, and the pixel log either of them may ask for
+int begin_instrumented(tdt_ctx *ctx, TraceState &S, const LaunchRequest &rq, int owned, TraceParams &P) {
+  bool logged = rq.counts_out != nullptr;
+#ifdef TDT_STATS
+  P.stats = !rq.counts_out && !(rq.probe && getenv("TDT_STATS_SKIP_PROBE")) ? S.stats : nullptr;   // (SKIP_PROBE: the main launch of a two-phase frame alone)
+  logged = logged || P.stats;
+#endif
+  if (rq.counts_out) {
     if (!ctx->counters) TDT_HIP(ctx, hipMalloc((void **)&ctx->counters, (32 + 16384 + 256) * sizeof(unsigned long long)));
     TDT_HIP(ctx, hipMemsetAsync(ctx->counters, 0, 32 * sizeof(unsigned long long), ctx->stream));
     TDT_HIP(ctx, hipMemsetAsync(ctx->counters + 18, 0xFF, sizeof(unsigned long long), ctx->stream));   // running minima
     TDT_HIP(ctx, hipMemsetAsync(ctx->counters + 22, 0xFF, sizeof(unsigned long long), ctx->stream));
     TDT_HIP(ctx, hipMemsetAsync(ctx->counters + 32 + 16384, 0, 256 * sizeof(unsigned long long), ctx->stream));
     P.counters = ctx->counters;
-    if (getenv("TDT_PIXEL_LOG")) {
-      const size_t need = (size_t)t.owned * 1024 * 8;
-      if (ctx->pixel_log_u32 < need) { if (ctx->pixel_log) (void)hipFree(ctx->pixel_log); TDT_HIP(ctx, hipMalloc((void **)&ctx->pixel_log, need * 4)); ctx->pixel_log_u32 = need; }
-      TDT_HIP(ctx, hipMemsetAsync(ctx->pixel_log, 0, need * 4, ctx->stream));
-      P.pixel_log = ctx->pixel_log;
-    }
   }
-#ifdef TDT_STATS
-  if (P.stats && !counts_out && getenv("TDT_PIXEL_LOG")) {
-    const size_t need = (size_t)t.owned * 1024 * 8;
-    if (ctx->pixel_log_u32 < need) { if (ctx->pixel_log) (void)hipFree(ctx->pixel_log); TDT_HIP(ctx, hipMalloc((void **)&ctx->pixel_log, need * 4)); ctx->pixel_log_u32 = need; }
-    TDT_HIP(ctx, hipMemsetAsync(ctx->pixel_log, 0, need * 4, ctx->stream));
-    P.pixel_log = ctx->pixel_log;
+  if (logged && getenv("TDT_PIXEL_LOG")) {
+    const size_t need = (size_t)owned * 1024 * 8;
+    TDT_HIP(ctx, S.grow(S.pixel_log_u32, need, {{S.pixel_log, need}}));
+    TDT_HIP(ctx, hipMemsetAsync(S.pixel_log, 0, need * 4, ctx->stream));
+    P.pixel_log = S.pixel_log;
   }
-#endif
+  return TDT_OK;
+}
+
+int bind_queue(tdt_ctx *ctx, TraceState::Queue &Q, tdt::DeviceScratch &mem, TraceParams &P) {
+  if (!Q.heads) {
+    unsigned int *heads = mem.get<unsigned int>(2);
+    if (!heads) return hip_fail(ctx, hipErrorOutOfMemory, "pixel-queue heads");
+    const hipError_t e = hipMemsetAsync(heads, 0, 2 * sizeof(unsigned int), ctx->stream);
+    if (e != hipSuccess) { mem.drop(heads); return hip_fail(ctx, e, "pixel-queue heads"); }      // (never a queue with undefined heads)
+    Q.heads = heads; Q.parity = 0;
+  }
+  P.queue = Q.heads + Q.parity; P.queue_next = Q.heads + (Q.parity ^ 1u);      // (the parity flips once the launch is in the stream)
+  return TDT_OK;
+}
+
+// LDS-table image of the bound cells buffer and the scan of its values (rebuilt only when the buffer or its contents changed)
+int refresh_packed(tdt_ctx *ctx, TraceState &S, TraceParams &P) {
+  TraceState::Tables &T = S.tables;
+  const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
   const uint32_t buf_nodes = P.cells_dwords >> 1;
-  if (mode == 3) {                                    // the miss pre-pass of a frame (see miss_prepass_kernel): done flags for every queue slot
-    if (t.owned <= 0) return TDT_OK;
-    if (ctx->done_capacity < (uint32_t)t.owned) {
-      if (ctx->slot_done) (void)hipFree(ctx->slot_done);
-      if (ctx->slot_live) (void)hipFree(ctx->slot_live);
-      if (ctx->filter_counts) (void)hipFree(ctx->filter_counts);
-      ctx->slot_done = nullptr; ctx->slot_live = nullptr; ctx->filter_counts = nullptr; ctx->done_capacity = 0;
-      const size_t n = (size_t)t.owned * 1024;
-      TDT_HIP(ctx, hipMalloc((void **)&ctx->slot_done, n));
-      TDT_HIP(ctx, hipMalloc((void **)&ctx->slot_live, n * sizeof(uint32_t)));
-      TDT_HIP(ctx, hipMalloc((void **)&ctx->filter_counts, ((n + tdt::kFilterChunk - 1) / tdt::kFilterChunk + 1) * sizeof(uint32_t)));
-      ctx->done_capacity = (uint32_t)t.owned;
+  if (!T.packed) TDT_HIP(ctx, S.alloc(T.packed, (size_t)tdt::kLdsCells * 8));
+  P.lds_nodes = buf_nodes < tdt::kLdsCells * 8u ? (buf_nodes & ~7u) : tdt::kLdsCells * 8u;
+  const TraceState::TableKey key{cb, cb->version, 0};
+  if (!(T.packed_key == key)) {
+    if (!T.scan) TDT_HIP(ctx, S.alloc(T.scan, 4));
+    TDT_HIP(ctx, hipMemsetAsync(T.scan, 0, 4 * sizeof(uint32_t), ctx->stream));
+    if (P.lds_nodes)
+      hipLaunchKernelGGL(tdt::pack_cells_kernel, dim3((P.lds_nodes + 255) / 256), dim3(256), 0, ctx->stream,
+                         P.cells, P.cells_dwords, T.packed, P.lds_nodes);
+    if (buf_nodes) {
+      unsigned nb = (buf_nodes + 255) / 256; if (nb > 4096) nb = 4096;
+      hipLaunchKernelGGL(tdt::scan_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, P.cells, buf_nodes, T.scan);
     }
-    hipLaunchKernelGGL(tdt::miss_prepass_kernel, dim3((unsigned)t.owned * 4u), dim3(256), 0, ctx->stream, P, ctx->slot_done);
     TDT_HIP(ctx, hipGetLastError());
-    return TDT_OK;
+    uint32_t res[3] = {0, 0, 0};
+    TDT_HIP(ctx, hipMemcpyAsync(res, T.scan, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+    TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
+    T.max_parent_value = res[0]; T.max_any_value = res[1]; T.live_nodes = res[2];
+    T.packed_key = key;
   }
-  if (t.owned > 0 && mode != 2) {
-    // LDS-table image of the bound cells buffer (rebuilt only when the buffer or its contents changed)
-    const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
-    if (!ctx->packed) TDT_HIP(ctx, hipMalloc((void **)&ctx->packed, (size_t)tdt::kLdsCells * 8 * sizeof(uint16_t)));
-    if (!ctx->queue) {
-      TDT_HIP(ctx, hipMalloc((void **)&ctx->queue, 2 * sizeof(unsigned int)));
-      const hipError_t e = hipMemsetAsync(ctx->queue, 0, 2 * sizeof(unsigned int), ctx->stream);
-      if (e != hipSuccess) { (void)hipFree(ctx->queue); ctx->queue = nullptr; return hip_fail(ctx, e, "pixel-queue heads"); }      // (never a queue with undefined heads)
-      ctx->queue_parity = 0;
-    }
-    P.lds_nodes = buf_nodes < tdt::kLdsCells * 8u ? (buf_nodes & ~7u) : tdt::kLdsCells * 8u;
-    if (ctx->packed_of != cb || ctx->packed_version != cb->version) {
-      if (!ctx->scan) TDT_HIP(ctx, hipMalloc((void **)&ctx->scan, 4 * sizeof(uint32_t)));
-      TDT_HIP(ctx, hipMemsetAsync(ctx->scan, 0, 4 * sizeof(uint32_t), ctx->stream));
-      if (P.lds_nodes)
-        hipLaunchKernelGGL(tdt::pack_cells_kernel, dim3((P.lds_nodes + 255) / 256), dim3(256), 0, ctx->stream,
-                           P.cells, P.cells_dwords, ctx->packed, P.lds_nodes);
-      if (buf_nodes) {
-        unsigned nb = (buf_nodes + 255) / 256; if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(tdt::scan_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, P.cells, buf_nodes, ctx->scan);
-      }
-      TDT_HIP(ctx, hipGetLastError());
-      uint32_t res[3] = {0, 0, 0};
-      TDT_HIP(ctx, hipMemcpyAsync(res, ctx->scan, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
-      TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
-      ctx->max_parent_value = res[0]; ctx->max_any_value = res[1]; ctx->live_nodes = res[2];
-      ctx->packed_of = cb; ctx->packed_version = cb->version;
-    }
-    P.packed = ctx->packed; P.queue = ctx->queue + ctx->queue_parity; P.queue_next = ctx->queue + (ctx->queue_parity ^ 1u);      // (the parity flips once the launch is in the stream)
-    // cost-feedback hand-out order (see order_scatter_kernel); TDT_NO_COST_ORDER=1: image order
-    if (!ctx->no_cost_order) {
-      if (ctx->tile_capacity < (uint32_t)t.owned) {
-        if (ctx->slot_cost) (void)hipFree(ctx->slot_cost);
-        if (ctx->slot_order) (void)hipFree(ctx->slot_order);
-        if (ctx->slot_acc) (void)hipFree(ctx->slot_acc);
-        ctx->slot_cost = ctx->slot_order = ctx->slot_acc = nullptr; ctx->tile_capacity = 0; ctx->cost_tiles = 0; ctx->order_exact = false;
-        TDT_HIP(ctx, hipMalloc((void **)&ctx->slot_cost, (size_t)t.owned * 1024 * sizeof(uint32_t)));
-        TDT_HIP(ctx, hipMalloc((void **)&ctx->slot_order, (size_t)t.owned * 1024 * sizeof(uint32_t)));
-        TDT_HIP(ctx, hipMalloc((void **)&ctx->slot_acc, (size_t)t.owned * 1024 * sizeof(uint32_t)));
-        if (!ctx->order_hist) { TDT_HIP(ctx, hipMalloc((void **)&ctx->order_hist, (2048 + 4 + 512) * sizeof(uint32_t))); TDT_HIP(ctx, hipMemsetAsync(ctx->order_hist, 0, (2048 + 4 + 512) * sizeof(uint32_t), ctx->stream)); ctx->order_parity = 0; }
-        ctx->tile_capacity = (uint32_t)t.owned;
-      }
-      // what this dispatch traces: if it equals what the recorded costs were measured on (a still camera: progressive
-      // passes, repeated frames) every pixel will cost exactly what it did, and pixels are sorted one by one; otherwise
-      // (the camera moved, the scene was edited) only the low-frequency part of the cost image is still true, and 8x8
-      // tiles are sorted by their summed cost — measured on a 60 fps walk, exact-order-of-a-stale-frame is no better
-      // than image order (256^3: 3 % worse), the tile form keeps about half of the gain
-      CostSig sig;
-      make_sig(ctx, c, k, img, &sig);
-      P.slot_cost = ctx->slot_cost;
-      // The same launch again (same inputs, same sample range) as the one whose costs the current order was built from, those costs
-      // themselves recorded by such a launch: every pixel costs what it did, the sort would reproduce the order it produced last time
-      // (the sums only double) — so a still camera's frames, from the third on, skip the three sort kernels and the cost stores
-      // (1280x720 / 4 spp: 0.46 -> 0.41 ms; the order, a schedule, changes no pixel)
-      const bool same_launch = ctx->cost_tiles == (uint32_t)t.owned && std::memcmp(&sig, &ctx->cost_sig, sizeof sig) == 0 &&
-                               ctx->cost_range[0] == spp_begin && ctx->cost_range[1] == spp_count && ctx->force_smooth < 0;
-      if (same_launch && ctx->order_exact && !ctx->no_order_reuse) {
-        P.slot_order = ctx->slot_order; P.plan = ctx->order_hist + 2048; P.slot_cost = nullptr;
-      } else
-      if (ctx->cost_tiles == (uint32_t)t.owned) {
-        if (ctx->order_exact) {
-          // leaving the reuse state (the camera moved after standing still, another sample range): the launches that reused the order
-          // recorded no costs and the last sort zeroed cost[], but acc[] still holds the sums that order was sorted from — they are the
-          // prior for this launch (the tile sums of a moved camera's frame; a sort from all-zero costs would be image order)
-          TDT_HIP(ctx, hipMemcpyAsync(ctx->slot_cost, ctx->slot_acc, (size_t)t.owned * 1024 * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-          ctx->order_exact = false;
-        }
-        const int smooth = ctx->force_smooth >= 0 ? ctx->force_smooth : (std::memcmp(&sig, &ctx->cost_sig, sizeof sig) != 0 ? 1 : 0);
-        // same inputs again (progressive passes, repeated frames): keep adding to the costs — every pass sharpens the
-        // estimate of what a pixel costs; otherwise start over
-        const bool keep_costs = !smooth && !ctx->no_cost_accum && ctx->cost_dispatches < 256;   // (restart before the sums can saturate)
-        ctx->cost_dispatches = keep_costs ? ctx->cost_dispatches + 1 : 0;
-        // samples per pixel behind the estimate this order is built from; a thin one (the probe of a two-phase frame) is
-        // shrunk towards the 8x8-tile mean (blended_cost)
-        ctx->acc_samples = (keep_costs ? ctx->acc_samples : 0u) + ctx->last_launch_samples;
-        const float blend = (!smooth && ctx->acc_samples < 16u) ? ctx->order_blend : 0.0f;
-        if (smooth) ctx->acc_samples = 0;               // (tile-sum mode drops the sums after use: order_scatter_kernel)
-        const uint32_t n_slots = (uint32_t)t.owned * 1024u, n_chunks = (n_slots + tdt::kOrderChunk - 1) / tdt::kOrderChunk;
-        const uint32_t og = tdt::kOrderBits;
-        // two sets of sort counters alternate: the plan kernel of this pass zeroes the set of the next one
-        uint32_t *hist = ctx->order_hist + 1024u * ctx->order_parity, *hist_next = ctx->order_hist + 1024u * (ctx->order_parity ^ 1u), *plan = ctx->order_hist + 2048;
-        hipLaunchKernelGGL(tdt::order_hist_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, ctx->slot_cost, ctx->slot_acc, n_slots, hist, og, smooth, keep_costs ? 1 : 0, blend);
-        {
-          const float max_share = ctx->max_share;
-          const uint32_t lanes = (uint32_t)ctx->num_cus * TDT_BLOCKS_PER_CU * TDT_BLOCK;
-          hipLaunchKernelGGL(tdt::order_plan_kernel, dim3(1), dim3(512), 0, ctx->stream, hist, og, lanes, max_share, plan, smooth, hist_next, plan + 4);
-          P.plan = plan;
-        }
-        hipLaunchKernelGGL(tdt::order_scatter_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, ctx->slot_cost, ctx->slot_acc, n_slots,
-                           plan + 4, hist + 512, ctx->slot_order, og, smooth, blend);
-        {
-          const hipError_t e = hipGetLastError();
-          if (e != hipSuccess) {
-            // a launch of the sequence failed: the histogram may be half filled and the other counter set half zeroed — clear both and
-            // drop the history, so that the next frame starts from image order instead of scattering through a dirty prefix
-            (void)hipMemsetAsync(ctx->order_hist, 0, (2048 + 4 + 512) * sizeof(uint32_t), ctx->stream);
-            ctx->cost_tiles = 0; ctx->order_exact = false; ctx->order_parity = 0;
-            return hip_fail(ctx, e, "cost-order sort");
-          }
-        }
-        ctx->order_parity ^= 1u;                        // (only now: the plan kernel of this pass zeroed the other set)
-        P.slot_order = ctx->slot_order;
-        ctx->order_exact = same_launch && !smooth && blend == 0.0f;      // built from what this very launch cost last time
-      } else {                                        // no usable history: image order, fresh cost array
-        TDT_HIP(ctx, hipMemsetAsync(ctx->slot_cost, 0, (size_t)t.owned * 1024 * sizeof(uint32_t), ctx->stream));
-        TDT_HIP(ctx, hipMemsetAsync(ctx->slot_acc, 0, (size_t)t.owned * 1024 * sizeof(uint32_t), ctx->stream));
-        ctx->cost_dispatches = 0; ctx->acc_samples = 0; ctx->order_exact = false;
-      }
-      if (P.slot_cost) {                              // the kernel launched below records this dispatch's costs
-        ctx->last_launch_samples = (uint32_t)(spp_count > 0 ? spp_count : 0);
-        ctx->cost_sig = sig; ctx->cost_range[0] = spp_begin; ctx->cost_range[1] = spp_count;
-        ctx->cost_tiles = (uint32_t)t.owned;
-      }
-    }
+  P.packed = T.packed;
+  return TDT_OK;
+}
+
+// cost-feedback hand-out order (see order_scatter_kernel): what the launch hands out and where it records its costs
+struct HandOut { const uint32_t *slot_order = nullptr, *plan = nullptr; uint32_t *slot_cost = nullptr; };
+
+int plan_order(tdt_ctx *ctx, TraceState &S, const CostSig &sig, const LaunchRequest &rq, int owned, HandOut &out) {
+  TraceState::CostOrder &O = S.order;
+  const TraceState::Switches &env = S.env;
+  const size_t n = (size_t)owned * 1024;
+  if (O.tile_capacity < (uint32_t)owned) { O.cost_tiles = 0; O.order_exact = false; }
+  TDT_HIP(ctx, S.grow(O.tile_capacity, (uint32_t)owned, {{O.slot_cost, n}, {O.slot_order, n}, {O.slot_acc, n}}));
+  if (!O.hist) {
+    TDT_HIP(ctx, S.alloc(O.hist, 2048 + 4 + 512));
+    TDT_HIP(ctx, hipMemsetAsync(O.hist, 0, (2048 + 4 + 512) * sizeof(uint32_t), ctx->stream));
+    O.parity = 0;
   }
-  if (t.owned > 0 && mode != 2 && ctx->use_done && !counts_out) {
-    // the frame's pre-pass finished some pixels: hand out the others only (the order just built, or image order, minus the done slots)
-    const uint32_t n_slots = (uint32_t)t.owned * 1024u, n_chunks = (n_slots + tdt::kFilterChunk - 1) / tdt::kFilterChunk;
-    hipLaunchKernelGGL(tdt::filter_count_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, P.slot_order, ctx->slot_done, n_slots, ctx->filter_counts);
-    hipLaunchKernelGGL(tdt::filter_write_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, P.slot_order, ctx->slot_done, n_slots, ctx->filter_counts, ctx->slot_live);
+  // what this dispatch traces: if it equals what the recorded costs were measured on (a still camera: progressive
+  // passes, repeated frames) every pixel will cost exactly what it did, and pixels are sorted one by one; otherwise
+  // (the camera moved, the scene was edited) only the low-frequency part of the cost image is still true, and 8x8
+  // tiles are sorted by their summed cost — measured on a 60 fps walk, exact-order-of-a-stale-frame is no better
+  // than image order (256^3: 3 % worse), the tile form keeps about half of the gain
+  out.slot_cost = O.slot_cost;
+  // The same launch again (same inputs, same sample range) as the one whose costs the current order was built from, those costs
+  // themselves recorded by such a launch: every pixel costs what it did, the sort would reproduce the order it produced last time
+  // (the sums only double) — so a still camera's frames, from the third on, skip the three sort kernels and the cost stores
+  // (1280x720 / 4 spp: 0.46 -> 0.41 ms; the order, a schedule, changes no pixel)
+  const bool same_sig = std::memcmp(&sig, &O.cost_sig, sizeof sig) == 0;
+  const bool same_launch = O.cost_tiles == (uint32_t)owned && same_sig &&
+                           O.cost_range[0] == rq.spp_begin && O.cost_range[1] == rq.spp_count && env.force_smooth < 0;
+  if (same_launch && O.order_exact && !env.no_order_reuse) {
+    out.slot_order = O.slot_order; out.plan = O.hist + 2048; out.slot_cost = nullptr;
+  } else if (O.cost_tiles == (uint32_t)owned) {
+    if (O.order_exact) {
+      // leaving the reuse state (the camera moved after standing still, another sample range): the launches that reused the order
+      // recorded no costs and the last sort zeroed cost[], but acc[] still holds the sums that order was sorted from — they are the
+      // prior for this launch (the tile sums of a moved camera's frame; a sort from all-zero costs would be image order)
+      TDT_HIP(ctx, hipMemcpyAsync(O.slot_cost, O.slot_acc, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+      O.order_exact = false;
+    }
+    const int smooth = env.force_smooth >= 0 ? env.force_smooth : (same_sig ? 0 : 1);
+    // same inputs again (progressive passes, repeated frames): keep adding to the costs — every pass sharpens the
+    // estimate of what a pixel costs; otherwise start over
+    const bool keep_costs = !smooth && !env.no_cost_accum && O.cost_dispatches < 256;   // (restart before the sums can saturate)
+    O.cost_dispatches = keep_costs ? O.cost_dispatches + 1 : 0;
+    // samples per pixel behind the estimate this order is built from; a thin one (the probe of a two-phase frame) is
+    // shrunk towards the 8x8-tile mean (blended_cost)
+    O.acc_samples = (keep_costs ? O.acc_samples : 0u) + O.last_launch_samples;
+    const float blend = (!smooth && O.acc_samples < 16u) ? env.order_blend : 0.0f;
+    if (smooth) O.acc_samples = 0;               // (tile-sum mode drops the sums after use: order_scatter_kernel)
+    const uint32_t n_slots = (uint32_t)owned * 1024u, n_chunks = (n_slots + tdt::kOrderChunk - 1) / tdt::kOrderChunk;
+    const uint32_t og = tdt::kOrderBits;
+    // two sets of sort counters alternate: the plan kernel of this pass zeroes the set of the next one
+    uint32_t *hist = O.hist + 1024u * O.parity, *hist_next = O.hist + 1024u * (O.parity ^ 1u), *plan = O.hist + 2048;
+    const uint32_t lanes = (uint32_t)ctx->num_cus * TDT_BLOCKS_PER_CU * TDT_BLOCK;
+    hipLaunchKernelGGL(tdt::order_hist_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, O.slot_cost, O.slot_acc, n_slots, hist, og, smooth, keep_costs ? 1 : 0, blend);
+    hipLaunchKernelGGL(tdt::order_plan_kernel, dim3(1), dim3(512), 0, ctx->stream, hist, og, lanes, env.max_share, plan, smooth, hist_next, plan + 4);
+    hipLaunchKernelGGL(tdt::order_scatter_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, O.slot_cost, O.slot_acc, n_slots,
+                       plan + 4, hist + 512, O.slot_order, og, smooth, blend);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      // a launch of the sequence failed: the histogram may be half filled and the other counter set half zeroed — clear both and
+      // drop the history, so that the next frame starts from image order instead of scattering through a dirty prefix
+      (void)hipMemsetAsync(O.hist, 0, (2048 + 4 + 512) * sizeof(uint32_t), ctx->stream);
+      O.cost_tiles = 0; O.order_exact = false; O.parity = 0;
+      return hip_fail(ctx, e, "cost-order sort");
+    }
+    O.parity ^= 1u;                        // (only now: the plan kernel of this pass zeroed the other set)
+    out.slot_order = O.slot_order; out.plan = plan;
+    O.order_exact = same_launch && !smooth && blend == 0.0f;      // built from what this very launch cost last time
+  } else {                                        // no usable history: image order, fresh cost array
+    TDT_HIP(ctx, hipMemsetAsync(O.slot_cost, 0, n * sizeof(uint32_t), ctx->stream));
+    TDT_HIP(ctx, hipMemsetAsync(O.slot_acc, 0, n * sizeof(uint32_t), ctx->stream));
+    O.cost_dispatches = 0; O.acc_samples = 0; O.order_exact = false;
+  }
+  if (out.slot_cost) {                              // the kernel launched next records this dispatch's costs
+    O.last_launch_samples = (uint32_t)(rq.spp_count > 0 ? rq.spp_count : 0);
+    O.cost_sig = sig; O.cost_range[0] = rq.spp_begin; O.cost_range[1] = rq.spp_count;
+    O.cost_tiles = (uint32_t)owned;
+  }
+  return TDT_OK;
+}
+
+// the frame's pre-pass finished some pixels: hand out the others only (the order just built, or image order, minus the done slots)
+int filter_done(tdt_ctx *ctx, const TraceState::MissPrepass &M, int owned, const uint32_t *&slot_order) {
+  const uint32_t n_slots = (uint32_t)owned * 1024u, n_chunks = (n_slots + tdt::kFilterChunk - 1) / tdt::kFilterChunk;
+  hipLaunchKernelGGL(tdt::filter_count_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, slot_order, M.slot_done, n_slots, M.filter_counts);
+  hipLaunchKernelGGL(tdt::filter_write_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, slot_order, M.slot_done, n_slots, M.filter_counts, M.slot_live);
+  TDT_HIP(ctx, hipGetLastError());
+  slot_order = M.slot_live;
+  return TDT_OK;
+}
+
+// what the uniforms and the scan say about the bound tree, and which of its derived tables this launch may use
+struct TreeForm { bool depth_ok, pow2, safev, resident, table_form = false, full = false, brick = false; };
+
+TreeForm classify_tree(const TraceState &S, TraceParams &P) {
+  const TraceState::Tables &T = S.tables;
+  TreeForm f;
+  // the exact-comparison form of treeLookup needs cell_count = 2^k <= 2^22 and inv_cell_count = 2^-k
+  // bit-for-bit (true for every scene Octree::init_global_buffers builds from such a count,
+  // octree.rs:49); any other count (the reference's own 100000, main.rs:459) takes the per-cell threshold form when the tree
+  // sits in the LDS table (FORM_TABLE, below), else the literal float form
+  const uint32_t cc = (uint32_t)P.cell_count;
+  f.depth_ok = P.max_depth >= 0 && P.max_depth <= 30;
+  f.pow2 = !S.env.force_generic && P.cell_count > 0 && (cc & (cc - 1)) == 0 && cc <= (1u << 22) &&
+           P.inv_cell_count == 1.0f / (float)cc && f.depth_ok;
+  // scene-property specialisations of the hot kernel (see tree_lookup_pow2); every variant is bit-identical
+  f.safev = T.max_parent_value < (1u << 22);
+  // resident: every node that is not all zeros sits in the LDS table (a pre-allocated buffer's tail of zero nodes reads as the
+  // table's all-EMPTY sentinel cell does, and as nodes past the end of the buffer do) and fits its 16-bit entries
+  f.resident = (P.cells_dwords >> 1) > 0 && T.live_nodes <= P.lds_nodes && T.max_any_value <= tdt::kPackedMaxValue;
+  // ... and then only the live cells are staged: the reference's demo scene is 19 cells in a buffer of 6259 (every block would copy
+  // 82 KB of zeros at launch), and whatever lies past them reads as the sentinel cell
+  if (f.resident && !S.env.no_specialise) P.lds_nodes = (T.live_nodes + 7u) & ~7u;
+  return f;
+}
+
+// FORM_TABLE: thresholds for every cell of the LDS table (trees outside it: for the top cells, whose decisions the jump table's
+// band is computed from — their walk evaluates the formula), built once per (cell_count, inv_cell_count, cells)
+int prepare_thresholds(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) {
+  TraceState::Tables &T = S.tables;
+  if (f.pow2 || S.env.force_generic || S.env.no_specialise || S.env.no_table_form || !f.depth_ok || P.cell_count <= 0 || P.lds_nodes == 0) return TDT_OK;
+  const uint32_t lds_cells = (P.lds_nodes + 7u) >> 3;
+  const uint32_t n_thr = f.resident ? lds_cells : (lds_cells < tdt::kThrTopCells ? lds_cells : tdt::kThrTopCells);
+  TraceState::ThresholdKey key{P.cell_count, 0, n_thr};
+  std::memcpy(&key.ic_bits, &P.inv_cell_count, 4);
+  if (!(T.thr_key == key)) {
+    if (!T.thr) TDT_HIP(ctx, S.alloc(T.thr, ((size_t)tdt::kLdsCells + 1) * 2));
+    uint32_t *aux = reinterpret_cast<uint32_t *>(T.thr + (size_t)tdt::kLdsCells * 2);      // {shape flag, bits of F0max}
+    TDT_HIP(ctx, hipMemsetAsync(aux, 0, 2 * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(tdt::build_thresholds_kernel, dim3((n_thr + 255u) / 256u), dim3(256), 0, ctx->stream, P.inv_cell_count, P.cell_count, n_thr,
+                       reinterpret_cast<float2 *>(T.thr), aux, (float4 *)nullptr);
     TDT_HIP(ctx, hipGetLastError());
-    P.slot_order = ctx->slot_live;
+    uint32_t res[2] = {1, 0};
+    TDT_HIP(ctx, hipMemcpyAsync(res, aux, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+    TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per octree-uniform change, not per frame
+    T.thr_key = key; T.thr_ok = res[0] == 0;
+    std::memcpy(&T.thr_f0max, &res[1], 4);
   }
-  if (t.owned > 0) {
-    // trace: one persistent block per CU (fewer when there is less work than lanes); resolve: a thread per pixel
-    unsigned nblk = (unsigned)(((long)t.owned * 1024 + 1023) / 1024);
-    if (nblk > (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU) nblk = (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU;
-    dim3 grid(nblk, 1, 1), block(TDT_BLOCK, 1, 1), grid4((unsigned)t.owned * 4u, 1, 1), block4(256, 1, 1);
-    // the exact-comparison form of treeLookup needs cell_count = 2^k <= 2^22 and inv_cell_count = 2^-k
-    // bit-for-bit (true for every scene Octree::init_global_buffers builds from such a count,
-    // octree.rs:49); any other count (the reference's own 100000, main.rs:459) takes the per-cell threshold form when the tree
-    // sits in the LDS table (FORM_TABLE, below), else the literal float form
-    const uint32_t cc = (uint32_t)P.cell_count;
-    const bool depth_ok = P.max_depth >= 0 && P.max_depth <= 30;
-    const bool pow2 = !ctx->force_generic && P.cell_count > 0 && (cc & (cc - 1)) == 0 && cc <= (1u << 22) &&
-                      P.inv_cell_count == 1.0f / (float)cc && depth_ok;
-    // scene-property specialisations of the hot kernel (see tree_lookup_pow2); every variant is bit-identical
-    const bool safev = ctx->max_parent_value < (1u << 22);
-    // resident: every node that is not all zeros sits in the LDS table (a pre-allocated buffer's tail of zero nodes reads as the
-    // table's all-EMPTY sentinel cell does, and as nodes past the end of the buffer do) and fits its 16-bit entries
-    const bool resident = buf_nodes > 0 && ctx->live_nodes <= P.lds_nodes && ctx->max_any_value <= tdt::kPackedMaxValue;
-    // ... and then only the live cells are staged: the reference's demo scene is 19 cells in a buffer of 6259 (every block would copy
-    // 82 KB of zeros at launch), and whatever lies past them reads as the sentinel cell
-    if (resident && !ctx->no_specialise) P.lds_nodes = (ctx->live_nodes + 7u) & ~7u;
-    // FORM_TABLE: thresholds for every cell of the LDS table (trees outside it: for the top cells, whose decisions the jump table's
-    // band is computed from — their walk evaluates the formula), built once per (cell_count, inv_cell_count, cells)
-    bool table_form = false;
-    if (mode != 2 && !counts_out && !pow2 && !ctx->force_generic && !ctx->no_specialise && !ctx->no_table_form && depth_ok && P.cell_count > 0 && P.lds_nodes > 0) {
-      const uint32_t lds_cells = (P.lds_nodes + 7u) >> 3;
-      const uint32_t n_thr = resident ? lds_cells : (lds_cells < tdt::kThrTopCells ? lds_cells : tdt::kThrTopCells);
-      uint32_t ic_bits; std::memcpy(&ic_bits, &P.inv_cell_count, 4);
-      if (ctx->thr_cc != P.cell_count || ctx->thr_ic_bits != ic_bits || ctx->thr_n != n_thr || !ctx->thr) {
-        if (!ctx->thr) TDT_HIP(ctx, hipMalloc((void **)&ctx->thr, ((size_t)tdt::kLdsCells + 1) * 2 * sizeof(float)));
-        uint32_t *aux = reinterpret_cast<uint32_t *>(ctx->thr + (size_t)tdt::kLdsCells * 2);      // {shape flag, bits of F0max}
-        TDT_HIP(ctx, hipMemsetAsync(aux, 0, 2 * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(tdt::build_thresholds_kernel, dim3((n_thr + 255u) / 256u), dim3(256), 0, ctx->stream, P.inv_cell_count, P.cell_count, n_thr,
-                           reinterpret_cast<float2 *>(ctx->thr), aux, (float4 *)nullptr);
-        TDT_HIP(ctx, hipGetLastError());
-        uint32_t res[2] = {1, 0};
-        TDT_HIP(ctx, hipMemcpyAsync(res, aux, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
-        TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per octree-uniform change, not per frame
-        ctx->thr_cc = P.cell_count; ctx->thr_ic_bits = ic_bits; ctx->thr_n = n_thr; ctx->thr_ok = res[0] == 0;
-        std::memcpy(&ctx->thr_f0max, &res[1], 4);
-      }
-      table_form = ctx->thr_ok && (!resident || ctx->max_parent_value < n_thr);      // resident: every cell index an x decision can meet has its thresholds
-      P.thr = ctx->thr; P.thr_cells = n_thr; P.thr_f0max = ctx->thr_f0max;
+  f.table_form = T.thr_ok && (!f.resident || T.max_parent_value < n_thr);      // resident: every cell index an x decision can meet has its thresholds
+  P.thr = T.thr; P.thr_cells = n_thr; P.thr_f0max = T.thr_f0max;
+  return TDT_OK;
+}
+
+// small resident trees: the whole-depth lookup table (tree_lookup_pow2 FULL), built once per cells buffer
+int prepare_full_grid(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) {
+  TraceState::Tables &T = S.tables;
+  if (!f.pow2 || !f.safev || !f.resident || S.env.no_specialise || S.env.no_full || (P.max_depth != 5 && P.max_depth != 6)) return TDT_OK;
+  const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
+  const TraceState::TableKey key{cb, cb->version, P.max_depth};
+  if (!(T.full_key == key)) {
+    const size_t entries = (size_t)1 << (3 * P.max_depth);
+    if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + sizeof(uint32_t) / sizeof(uint16_t)));
+    uint32_t *bad = reinterpret_cast<uint32_t *>(T.full_grid + ((size_t)1 << 18));
+    TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(tdt::build_full_grid_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
+    TDT_HIP(ctx, hipGetLastError());
+    uint32_t flag = 1;
+    TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
+    T.full_key = key; T.full_ok = flag == 0;
+  }
+  f.full = T.full_ok;
+  P.full_grid = T.full_grid;
+  return TDT_OK;
+}
+
+// trees of depth 6-10 that are not LDS-resident: the 32-bit level-5 table with per-position bands, and for depth 8 / 9 the bricks
+// (tree_lookup_pow2 BRICK), built once per cells buffer
+int prepare_bricks(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) {
+  TraceState::Tables &T = S.tables;
+  if (!f.pow2 || !f.safev || f.resident || S.env.no_specialise || S.env.no_bricks || P.max_depth < 6 || P.max_depth > 10) return TDT_OK;
+  const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
+  const TraceState::TableKey key{cb, cb->version, P.max_depth};
+  if (!(T.brick_key == key)) {
+    const bool has_bricks = tdt::brick_levels(P.max_depth) != 0u;     // (depth 10: the table alone, levels 6.. walked)
+    const size_t need = has_bricks ? ((size_t)1 << 15) * tdt::brick_entries(P.max_depth) * sizeof(uint16_t) : 0;
+    if (!T.brick_grid) TDT_HIP(ctx, S.alloc(T.brick_grid, ((size_t)1 << 15) + 1));
+    if (S.grow(T.bricks_bytes, need, {{T.bricks, need / sizeof(uint16_t)}}) != hipSuccess) {      // (a device that cannot spare the address space: the levels are walked)
+      (void)hipGetLastError();
+      S.env.no_bricks = true;
+      return TDT_OK;
     }
-    bool launched = false;
-    P.accumulate = mode == 1 ? 1 : 0;
-    // small resident trees: the whole-depth lookup table (tree_lookup_pow2 FULL), built once per cells buffer
-    bool full = false;
-    if (mode != 2 && !counts_out && pow2 && safev && resident && !ctx->no_specialise && !ctx->no_full && (P.max_depth == 5 || P.max_depth == 6)) {
-      const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
-      if (ctx->full_of != cb || ctx->full_version != cb->version || ctx->full_depth != P.max_depth) {
-        const size_t entries = (size_t)1 << (3 * P.max_depth);
-        if (!ctx->full_grid) TDT_HIP(ctx, hipMalloc((void **)&ctx->full_grid, ((size_t)1 << 18) * sizeof(uint16_t) + sizeof(uint32_t)));
-        uint32_t *bad = reinterpret_cast<uint32_t *>(ctx->full_grid + ((size_t)1 << 18));
-        TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(tdt::build_full_grid_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, ctx->full_grid, bad);
-        TDT_HIP(ctx, hipGetLastError());
-        uint32_t flag = 1;
-        TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
-        TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
-        ctx->full_of = cb; ctx->full_version = cb->version; ctx->full_depth = P.max_depth; ctx->full_ok = flag == 0;
-      }
-      full = ctx->full_ok;
-      P.full_grid = ctx->full_grid;
-    }
-    // trees of depth 6-10 that are not LDS-resident: the 32-bit level-5 table with per-position bands, and for depth 8 / 9 the bricks
-    // (tree_lookup_pow2 BRICK), built once per cells buffer
-    bool brick = false;
-    if (mode != 2 && !counts_out && pow2 && safev && !resident && !ctx->no_specialise && !ctx->no_bricks && P.max_depth >= 6 && P.max_depth <= 10) {
-      const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
-      if (ctx->brick_of != cb || ctx->brick_version != cb->version || ctx->brick_depth != P.max_depth) {
-        const bool has_bricks = tdt::brick_levels(P.max_depth) != 0u;     // (depth 10: the table alone, levels 6.. walked)
-        const size_t need = has_bricks ? ((size_t)1 << 15) * tdt::brick_entries(P.max_depth) * sizeof(uint16_t) : 0;
-        if (!ctx->brick_grid) TDT_HIP(ctx, hipMalloc((void **)&ctx->brick_grid, ((size_t)1 << 15) * sizeof(uint32_t) + sizeof(uint32_t)));
-        if (ctx->bricks_bytes < need) {
-          if (ctx->bricks) (void)hipFree(ctx->bricks);
-          ctx->bricks = nullptr; ctx->bricks_bytes = 0; ctx->brick_of = nullptr;
-          if (hipMalloc(&ctx->bricks, need) != hipSuccess) {      // (a device that cannot spare the address space: the levels are walked)
-            (void)hipGetLastError();
-            ctx->bricks = nullptr; ctx->no_bricks = true;
-          } else ctx->bricks_bytes = need;
-        }
-      }
-      if (!ctx->no_bricks && (ctx->brick_of != cb || ctx->brick_version != cb->version || ctx->brick_depth != P.max_depth)) {
-        uint32_t *bad = ctx->brick_grid + ((size_t)1 << 15);
-        TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
-        switch (tdt::brick_levels(P.max_depth)) {
-#define TDT_BUILD_BRICKS(B) case B: hipLaunchKernelGGL(tdt::build_bricks_kernel<B>, dim3(1u << 15), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, ctx->brick_grid, static_cast<uint16_t *>(ctx->bricks), bad); break
-          TDT_BUILD_BRICKS(1); TDT_BUILD_BRICKS(2); TDT_BUILD_BRICKS(3); TDT_BUILD_BRICKS(4);
-          default: TDT_BUILD_BRICKS(0);
+    uint32_t *bad = T.brick_grid + ((size_t)1 << 15);
+    TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
+    switch (tdt::brick_levels(P.max_depth)) {
+#define TDT_BUILD_BRICKS(B) case B: hipLaunchKernelGGL(tdt::build_bricks_kernel<B>, dim3(1u << 15), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, T.brick_grid, T.bricks, bad); break
+      TDT_BUILD_BRICKS(1); TDT_BUILD_BRICKS(2); TDT_BUILD_BRICKS(3); TDT_BUILD_BRICKS(4);
+      default: TDT_BUILD_BRICKS(0);
 #undef TDT_BUILD_BRICKS
-        }
-        TDT_HIP(ctx, hipGetLastError());
-        uint32_t flag = 1;
-        TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
-        TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
-        ctx->brick_of = cb; ctx->brick_version = cb->version; ctx->brick_depth = P.max_depth; ctx->brick_ok = flag == 0;
-      }
-      brick = !ctx->no_bricks && ctx->brick_ok;
-      if (brick) {
-        P.brick_grid = ctx->brick_grid; P.bricks = ctx->bricks;
-        if (P.lds_nodes > tdt::kBrickLdsCells * 8u) P.lds_nodes = tdt::kBrickLdsCells * 8u;      // (the BRICK builds' LDS node table)
-      }
     }
-    if (mode != 2 && !counts_out && (pow2 || table_form) && safev && !ctx->no_specialise) {
-      // UNIT builds do not multiply by a scale of exactly 1.0f (x * 1.0f is x).  The probe launch of a two-phase frame runs the build
-      // that multiplies — the same bits, and the short launch then has a row of its own in profiler statistics instead of halving the
-      // average of the launches that do the work
-      const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f && !ctx->probe_launch;      // (a zero corner component: see the in-octree test)
-      const int form = pow2 ? tdt::FORM_POW2 : tdt::FORM_TABLE;
-      TraceFn fn = nullptr;
-      if (brick) fn = find_variant(form, P.max_depth, false, false, true, unit);
-      if (!fn && full) fn = find_variant(form, P.max_depth, true, true, false, unit);
-      if (!fn) fn = find_variant(form, P.max_depth, resident, false, false, unit);
-      if (fn) {
-        hipLaunchKernelGGL(fn, grid, block, 0, ctx->stream, P); launched = true;
-        const int v[6] = {form, P.max_depth, (brick || !resident) ? 0 : 1, (!brick && full) ? 1 : 0, brick ? 1 : 0, unit ? 1 : 0};
-        std::memcpy(ctx->last_variant, v, sizeof v);
-      }
-    }
-    if (!launched && mode != 2) { const int v[6] = {pow2 ? tdt::FORM_POW2 : tdt::FORM_LITERAL, 0, 0, 0, 0, 0}; std::memcpy(ctx->last_variant, v, sizeof v); }
-#define TDT_LAUNCH(C) do { if (pow2) hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_POW2>), grid, block, 0, ctx->stream, P); \
-                           else hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_LITERAL>), grid, block, 0, ctx->stream, P); } while (0)
-    if (!launched && counts_out && getenv("TDT_COUNT_SPECIALISED") && pow2 && safev && resident && P.max_depth == 6) {
-      hipLaunchKernelGGL((tdt::trace_kernel<true, tdt::FORM_POW2, 6, true, true>), grid, block, 0, ctx->stream, P); launched = true;   // diagnostics: region timers of the specialised form
-    }
-    if (launched) {}
-    else if (mode != 2 && !counts_out) TDT_LAUNCH(false);
-    else if (mode != 2) TDT_LAUNCH(true);
-    else hipLaunchKernelGGL(tdt::resolve_kernel, grid4, block4, 0, ctx->stream, P);
-#undef TDT_LAUNCH
     TDT_HIP(ctx, hipGetLastError());
-    if (mode != 2) ctx->queue_parity ^= 1u;           // this launch zeroes the other head; a launch that failed leaves this one at zero
+    uint32_t flag = 1;
+    TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));    // once per cells buffer (version), not per frame
+    T.brick_key = key; T.brick_ok = flag == 0;
   }
-  if (counts_out) {
-    TDT_HIP(ctx, hipMemcpyAsync(counts_out, ctx->counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  f.brick = T.brick_ok;
+  if (f.brick) {
+    P.brick_grid = T.brick_grid; P.bricks = T.bricks;
+    if (P.lds_nodes > tdt::kBrickLdsCells * 8u) P.lds_nodes = tdt::kBrickLdsCells * 8u;      // (the BRICK builds' LDS node table)
+  }
+  return TDT_OK;
+}
+
+// choose the build and launch it: one persistent block per CU (fewer when there is less work than lanes)
+int launch_trace(tdt_ctx *ctx, TraceState &S, const LaunchRequest &rq, const TreeForm &f, int owned, const TraceParams &P) {
+  unsigned nblk = (unsigned)(((long)owned * 1024 + 1023) / 1024);
+  if (nblk > (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU) nblk = (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU;
+  const dim3 grid(nblk, 1, 1), block(TDT_BLOCK, 1, 1);
+  bool launched = false;
+  if (!rq.counts_out && (f.pow2 || f.table_form) && f.safev && !S.env.no_specialise) {
+    // UNIT builds do not multiply by a scale of exactly 1.0f (x * 1.0f is x).  The probe launch of a two-phase frame runs the build
+    // that multiplies — the same bits, and the short launch then has a row of its own in profiler statistics instead of halving the
+    // average of the launches that do the work
+    const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f && !rq.probe;      // (a zero corner component: see the in-octree test)
+    const int form = f.pow2 ? tdt::FORM_POW2 : tdt::FORM_TABLE;
+    TraceFn fn = nullptr;
+    if (f.brick) fn = find_variant(form, P.max_depth, false, false, true, unit);
+    if (!fn && f.full) fn = find_variant(form, P.max_depth, true, true, false, unit);
+    if (!fn) fn = find_variant(form, P.max_depth, f.resident, false, false, unit);
+    if (fn) {
+      hipLaunchKernelGGL(fn, grid, block, 0, ctx->stream, P); launched = true;
+      const int v[6] = {form, P.max_depth, (f.brick || !f.resident) ? 0 : 1, (!f.brick && f.full) ? 1 : 0, f.brick ? 1 : 0, unit ? 1 : 0};
+      std::memcpy(S.last_variant, v, sizeof v);
+    }
+  }
+  if (!launched) { const int v[6] = {f.pow2 ? tdt::FORM_POW2 : tdt::FORM_LITERAL, 0, 0, 0, 0, 0}; std::memcpy(S.last_variant, v, sizeof v); }
+#define TDT_LAUNCH(C) do { if (f.pow2) hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_POW2>), grid, block, 0, ctx->stream, P); \
+                           else hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_LITERAL>), grid, block, 0, ctx->stream, P); } while (0)
+  if (!launched && rq.counts_out && getenv("TDT_COUNT_SPECIALISED") && f.pow2 && f.safev && f.resident && P.max_depth == 6) {
+    hipLaunchKernelGGL((tdt::trace_kernel<true, tdt::FORM_POW2, 6, true, true>), grid, block, 0, ctx->stream, P); launched = true;   // diagnostics: region timers of the specialised form
+  }
+  if (launched) {}
+  else if (!rq.counts_out) TDT_LAUNCH(false);
+  else TDT_LAUNCH(true);
+#undef TDT_LAUNCH
+  TDT_HIP(ctx, hipGetLastError());
+  S.queue.parity ^= 1u;           // this launch zeroes the other head; a launch that failed leaves this one at zero
+  return TDT_OK;
+}
+
+// Every launch of the trace path: the miss pre-pass of a frame, a render or accumulate pass over a sample range, a resolve.
+int launch(tdt_compute *c, int width, int height, int depth, const LaunchRequest &rq) {
+  (void)depth;   // raytracer.comp is a 2-D dispatch: groups_z = max(depth / 1, 1) layers all write the same pixels
+  tdt_ctx *ctx = c->ctx;
+  TraceState &S = *ctx->trace;
+  TraceParams P; Cover k; Tiles t;
+  if (int rc = bind_params(c, width, height, rq, P, k, t)) return rc;
+  if (rq.kind == LaunchRequest::kMissPrepass) return launch_miss_prepass(ctx, S, t.owned, P);
+  if (rq.kind == LaunchRequest::kResolve) return launch_resolve(ctx, t.owned, P);
+  if (int rc = begin_instrumented(ctx, S, rq, t.owned, P)) return rc;
+  if (t.owned > 0) {
+    if (int rc = bind_queue(ctx, S.queue, S.mem, P)) return rc;
+    if (int rc = refresh_packed(ctx, S, P)) return rc;
+    if (!S.env.no_cost_order) {      // TDT_NO_COST_ORDER=1: image order
+      CostSig sig; HandOut h;
+      make_sig(ctx, c, k, ctx->image0, &sig);
+      if (int rc = plan_order(ctx, S, sig, rq, t.owned, h)) return rc;
+      P.slot_order = h.slot_order; P.plan = h.plan; P.slot_cost = h.slot_cost;
+    }
+    if (rq.prepass_ran && !rq.counts_out)
+      if (int rc = filter_done(ctx, S.miss, t.owned, P.slot_order)) return rc;
+    TreeForm f = classify_tree(S, P);
+    if (!rq.counts_out) {
+      if (int rc = prepare_thresholds(ctx, S, f, P)) return rc;
+      if (int rc = prepare_full_grid(ctx, S, f, P)) return rc;
+      if (int rc = prepare_bricks(ctx, S, f, P)) return rc;
+    }
+    if (int rc = launch_trace(ctx, S, rq, f, t.owned, P)) return rc;
+  }
+  if (rq.counts_out) {
+    TDT_HIP(ctx, hipMemcpyAsync(rq.counts_out, ctx->counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return TDT_OK;
@@ -1750,33 +1913,13 @@ int tdt_ctx_create(int device_id, void *stream, tdt_ctx **out) {
   tdt_ctx *ctx = new (std::nothrow) tdt_ctx();
   if (!ctx) return fail(nullptr, TDT_ERR_HIP, "out of host memory");
   ctx->device = device_id;
-  for (auto &s : ctx->ssbo) s = nullptr;
-  ctx->atomic0 = nullptr; ctx->image0 = nullptr; ctx->counters = nullptr; ctx->queue = nullptr; ctx->packed = nullptr; ctx->packed_of = nullptr; ctx->packed_version = 0; ctx->present = nullptr; ctx->present_bytes = 0; ctx->frame_carry = nullptr; ctx->frame_carry_bytes = 0; ctx->probe_launch = false; ctx->phase_timing = false; ctx->phase_n = 0; ctx->pixel_log = nullptr; ctx->pixel_log_u32 = 0; ctx->stats = nullptr; ctx->slot_cost = ctx->slot_acc = ctx->slot_order = ctx->order_hist = nullptr; ctx->tile_capacity = ctx->cost_tiles = 0; ctx->cost_dispatches = 0;
-  { const char *nc = getenv("TDT_NO_COST_ORDER"); ctx->no_cost_order = nc && nc[0] == '1';
-    const char *fs = getenv("TDT_ORDER_SMOOTH"); ctx->force_smooth = fs ? atoi(fs) : -1;
-    ctx->no_cost_accum = getenv("TDT_NO_COST_ACCUM") != nullptr;
-    ctx->no_two_phase = getenv("TDT_NO_TWO_PHASE") != nullptr;
-    ctx->no_prepass = getenv("TDT_NO_PREPASS") != nullptr;
-    ctx->no_order_reuse = getenv("TDT_NO_ORDER_REUSE") != nullptr;
-    ctx->no_full = getenv("TDT_NO_FULL_GRID") != nullptr;
-    ctx->no_table_form = getenv("TDT_NO_TABLE_FORM") != nullptr;
-    ctx->no_bricks = getenv("TDT_NO_BRICKS") != nullptr;
-    const char *ms = getenv("TDT_MAX_SHARE"); ctx->max_share = ms ? (float)atof(ms) : 1.0f;
-    const char *ob = getenv("TDT_ORDER_BLEND"); ctx->order_blend = ob ? (float)atof(ob) : 0.5f;
-    const char *tp = getenv("TDT_TWO_PHASE_MIN_SPP"); ctx->two_phase_min_spp = tp && atoi(tp) >= 2 ? atoi(tp) : 16;
-    const char *pd = getenv("TDT_PROBE_DIV"); ctx->probe_div = pd && atoi(pd) >= 2 && atoi(pd) <= 64 ? atoi(pd) : 16; }
-  ctx->scan = nullptr; ctx->max_parent_value = ctx->max_any_value = ctx->live_nodes = 0xFFFFFFFFu;
-  ctx->thr = nullptr; ctx->thr_cc = 0; ctx->thr_ic_bits = 0; ctx->thr_n = 0; ctx->thr_ok = false;
+  ctx->trace = new (std::nothrow) tdt::TraceState();      // (reads the switches)
+  if (!ctx->trace) { delete ctx; return fail(nullptr, TDT_ERR_HIP, "out of host memory"); }
   { hipDeviceProp_t prop; ctx->num_cus = (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256; }
-  { const char *fg = getenv("TDT_FORCE_GENERIC"); ctx->force_generic = fg && fg[0] == '1';
-    const char *ns_ = getenv("TDT_NO_SPECIALISE"); ctx->no_specialise = ns_ && ns_[0] == '1';
-    const char *et = getenv("TDT_EVENT_THRESHOLD"); ctx->event_threshold = et ? atoi(et) : 0;
-    const char *ek = getenv("TDT_EVENT_K"); ctx->event_k = ek ? (float)atof(ek) : 0.0f;
-    const char *ec = getenv("TDT_EVENT_CLAMP"); ctx->event_clamp = ec && atoi(ec) >= 2 && atoi(ec) <= 64 ? atoi(ec) : 40; }
   if (stream) { ctx->stream = (hipStream_t)stream; ctx->own_stream = false; }
   else {
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete ctx; return fail(nullptr, TDT_ERR_NO_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete ctx->trace; delete ctx; return fail(nullptr, TDT_ERR_NO_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
     ctx->own_stream = true;
   }
   *out = ctx;
@@ -1792,25 +1935,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   for (tdt_buffer *b : ctx->buffers) { (void)hipFree(b->dev); delete b; }
   for (tdt_image *i : ctx->images) { if (i->owned) (void)hipFree(i->dev); delete i; }
   if (ctx->counters) (void)hipFree(ctx->counters);
-  if (ctx->queue) (void)hipFree(ctx->queue);
-  if (ctx->packed) (void)hipFree(ctx->packed);
-  if (ctx->scan) (void)hipFree(ctx->scan);
-  if (ctx->slot_cost) (void)hipFree(ctx->slot_cost);
-  if (ctx->slot_order) (void)hipFree(ctx->slot_order);
-  if (ctx->slot_acc) (void)hipFree(ctx->slot_acc);
-  if (ctx->order_hist) (void)hipFree(ctx->order_hist);
-  if (ctx->pixel_log) (void)hipFree(ctx->pixel_log);
-  if (ctx->stats) (void)hipFree(ctx->stats);
-  if (ctx->present) (void)hipFree(ctx->present);
-  if (ctx->frame_carry) (void)hipFree(ctx->frame_carry);
-  if (ctx->slot_done) (void)hipFree(ctx->slot_done);
-  if (ctx->slot_live) (void)hipFree(ctx->slot_live);
-  if (ctx->filter_counts) (void)hipFree(ctx->filter_counts);
-  if (ctx->full_grid) (void)hipFree(ctx->full_grid);
-  if (ctx->thr) (void)hipFree(ctx->thr);
-  if (ctx->brick_grid) (void)hipFree(ctx->brick_grid);
-  if (ctx->bricks) (void)hipFree(ctx->bricks);
-  if (ctx->phase_timing) for (auto &e : ctx->phase_ev) (void)hipEventDestroy(e);
+  delete ctx->trace;
   tdt::edit_scratch_destroy(ctx);
   tdt::query_scratch_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
@@ -2067,28 +2192,25 @@ int tdt_image_read_rgba8(tdt_image *img, int top_down, uint8_t *dst) {
   if (img->ctx->multi) return tdt_image_read_rgba8(img->full, top_down, dst);
   tdt_ctx *ctx = img->ctx;
   TDT_HIP(ctx, hipSetDevice(ctx->device));
+  tdt::TraceState &S = *ctx->trace;
   const size_t bytes = (size_t)img->w * img->h * 4;
-  if (ctx->present_bytes < bytes) {
-    if (ctx->present) (void)hipFree(ctx->present);
-    ctx->present = nullptr; ctx->present_bytes = 0;
-    TDT_HIP(ctx, hipMalloc((void **)&ctx->present, bytes));
-    ctx->present_bytes = bytes;
-  }
+  TDT_HIP(ctx, S.grow(S.present_bytes, bytes, {{S.present, (size_t)img->w * img->h}}));
   hipLaunchKernelGGL(tdt::present_kernel, dim3((unsigned)(img->w + 63) / 64, (unsigned)(img->h + 3) / 4), dim3(256), 0, ctx->stream,
-                     (const float4 *)img->dev, ctx->present, img->w, img->h, top_down ? 1 : 0);
+                     (const float4 *)img->dev, S.present, img->w, img->h, top_down ? 1 : 0);
   TDT_HIP(ctx, hipGetLastError());
-  TDT_HIP(ctx, hipMemcpyAsync(dst, ctx->present, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  TDT_HIP(ctx, hipMemcpyAsync(dst, S.present, bytes, hipMemcpyDeviceToHost, ctx->stream));
   TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TDT_OK;
 }
 
 // events around the launches of a frame (only when tdt_debug_phase_timing switched them on)
 static void phase_mark(tdt_ctx *ctx, int i) {
-  if (!ctx->phase_timing) return;
-  if (hipEventRecord(ctx->phase_ev[i], ctx->stream) == hipSuccess) ctx->phase_n = i + 1;
+  tdt::TraceState &S = *ctx->trace;
+  if (!S.phase_timing) return;
+  if (hipEventRecord(S.phase_ev[i], ctx->stream) == hipSuccess) S.phase_n = i + 1;
 }
 
-static int dispatch_frame(tdt_compute *c, int width, int height, int depth);
+static int dispatch_frame(tdt_compute *c, int width, int height, int depth, bool prepass_ran);
 
 int tdt_dispatch_compute(tdt_compute *c, int width, int height, int depth) {
   if (!c) return TDT_ERR_INVALID_VALUE;
@@ -2097,33 +2219,36 @@ int tdt_dispatch_compute(tdt_compute *c, int width, int height, int depth) {
   tdt_ctx *ctx = c->ctx;
   // a camera outside the octree: the pixels whose rays all miss it are finished by the miss pre-pass (miss_prepass_kernel) and
   // taken out of the hand-out order of this frame's launches.  (Inside the octree every ray starts in the root cube: nothing to find.)
-  ctx->use_done = false;
+  bool prepass_ran = false;
   const tdt_buffer *of = ctx->ssbo[TDT_SLOT_OCTREE_FLOATS];
-  if (!ctx->no_prepass && of && of->bytes >= 28 && c->samples_per_pixel >= 1 && c->max_bounce >= 1) {
+  if (!ctx->trace->env.no_prepass && of && of->bytes >= 28 && c->samples_per_pixel >= 1 && c->max_bounce >= 1) {
     float f[7];
     std::memcpy(f, of->shadow, sizeof f);
     bool outside = false;
     for (int a = 0; a < 3; a++) outside = outside || c->origin[a] < f[a] || c->origin[a] > f[a] + f[4];
     if (outside) {
-      const int rc = launch(c, width, height, depth, 3, 0, 0, nullptr, 0, nullptr);
+      LaunchRequest rq;
+      rq.kind = LaunchRequest::kMissPrepass;
+      const int rc = launch(c, width, height, depth, rq);
       if (rc != TDT_OK) return rc;
-      ctx->use_done = true;
+      prepass_ran = true;
     }
   }
-  const int rc = dispatch_frame(c, width, height, depth);
-  ctx->use_done = false;
-  return rc;
+  return dispatch_frame(c, width, height, depth, prepass_ran);
 }
 
-static int dispatch_frame(tdt_compute *c, int width, int height, int depth) {
+static int dispatch_frame(tdt_compute *c, int width, int height, int depth, bool prepass_ran) {
   // A frame whose inputs differ from what the recorded pixel costs were measured on (first frame, moved camera, edited
   // scene) is traced in two phases: spp/16 probe samples per pixel in image (or tile-sum) order, then — the launch below
   // sees identical inputs and fresh costs — the rest in the per-pixel cost order of THIS frame's probe, and a resolve.  Running
   // sums and the hit-record carry go through HBM between the phases exactly as in progressive rendering, so the frame is the
   // same bits as one pass (tests/test_gpu_fullsize.py).  Frames that repeat their inputs take one pass in the exact order.
   tdt_ctx *ctx = c->ctx;
+  tdt::TraceState &S = *ctx->trace;
   const int spp = c->samples_per_pixel;
-  bool ready = ctx->image0 != nullptr && !ctx->no_cost_order && !ctx->no_two_phase && spp >= ctx->two_phase_min_spp && spp >= 2;
+  LaunchRequest rq;
+  rq.prepass_ran = prepass_ran;
+  bool ready = ctx->image0 != nullptr && !S.env.no_cost_order && !S.env.no_two_phase && spp >= S.env.two_phase_min_spp && spp >= 2;
   for (int sl : {TDT_SLOT_CELLS, TDT_SLOT_MATERIALS, TDT_SLOT_ALBEDOS, TDT_SLOT_METAL, TDT_SLOT_DIELECTRIC, TDT_SLOT_OCTREE_FLOATS, TDT_SLOT_OCTREE_INTS})
     ready = ready && ctx->ssbo[sl] != nullptr;
   if (ready && ctx->ssbo[TDT_SLOT_OCTREE_FLOATS]->bytes >= 28 && ctx->ssbo[TDT_SLOT_OCTREE_INTS]->bytes >= 12) {
@@ -2131,34 +2256,32 @@ static int dispatch_frame(tdt_compute *c, int width, int height, int depth) {
     const Tiles t = tiles_of(c, k);
     CostSig sig;
     make_sig(ctx, c, k, ctx->image0, &sig);
-    const bool replay = ctx->cost_tiles == (uint32_t)t.owned && std::memcmp(&sig, &ctx->cost_sig, sizeof sig) == 0;
+    const bool replay = S.order.cost_tiles == (uint32_t)t.owned && std::memcmp(&sig, &S.order.cost_sig, sizeof sig) == 0;
     if (!replay && t.owned > 0) {
       TDT_HIP(ctx, hipSetDevice(ctx->device));
       const size_t px = (size_t)ctx->image0->w * (size_t)ctx->image0->h, slots = (size_t)t.owned * 1024;
       const size_t need = (px > slots ? px : slots) * 16 * sizeof(float);
-      if (ctx->frame_carry_bytes < need) {
-        if (ctx->frame_carry) (void)hipFree(ctx->frame_carry);
-        ctx->frame_carry = nullptr; ctx->frame_carry_bytes = 0; ctx->probe_launch = false;
-        TDT_HIP(ctx, hipMalloc(&ctx->frame_carry, need));
-        ctx->frame_carry_bytes = need;
-      }
-      const int probe = spp / ctx->probe_div >= 1 ? spp / ctx->probe_div : 1;        // spp/16; measured: 1/8 and 1/32 are 0-3 % slower, 1/64 5 % (TDT_PROBE_DIV)
-      ctx->probe_launch = true;
+      TDT_HIP(ctx, S.grow(S.frame_carry_bytes, need, {{S.frame_carry, need / sizeof(float)}}));
+      const int probe = spp / S.env.probe_div >= 1 ? spp / S.env.probe_div : 1;        // spp/16; measured: 1/8 and 1/32 are 0-3 % slower, 1/64 5 % (TDT_PROBE_DIV)
+      rq.kind = LaunchRequest::kAccumulate; rq.carry = S.frame_carry;
+      rq.spp_begin = 0; rq.spp_count = probe; rq.probe = true;
       phase_mark(ctx, 0);
-      int rc = launch(c, width, height, depth, 1, 0, probe, ctx->frame_carry, 0, nullptr);
-      ctx->probe_launch = false;
+      int rc = launch(c, width, height, depth, rq);
       phase_mark(ctx, 1);
-      ctx->carry_final = true;                       // 64 B per pixel that the resolve does not read: not written
-      if (rc == TDT_OK) rc = launch(c, width, height, depth, 1, probe, spp - probe, ctx->frame_carry, 0, nullptr);
-      ctx->carry_final = false;
+      rq.spp_begin = probe; rq.spp_count = spp - probe; rq.probe = false;
+      rq.carry_final = true;                         // 64 B per pixel that the resolve does not read: not written
+      if (rc == TDT_OK) rc = launch(c, width, height, depth, rq);
       phase_mark(ctx, 2);
-      if (rc == TDT_OK) rc = launch(c, width, height, depth, 2, 0, 0, nullptr, spp, nullptr);
+      LaunchRequest resolve;
+      resolve.kind = LaunchRequest::kResolve; resolve.total_spp = spp; resolve.prepass_ran = prepass_ran;
+      if (rc == TDT_OK) rc = launch(c, width, height, depth, resolve);
       phase_mark(ctx, 3);
       return rc;
     }
   }
+  rq.spp_count = rq.total_spp = spp;
   phase_mark(ctx, 0);
-  const int rc = launch(c, width, height, depth, 0, 0, spp, nullptr, spp, nullptr);
+  const int rc = launch(c, width, height, depth, rq);
   phase_mark(ctx, 1);
   return rc;
 }
@@ -2177,14 +2300,18 @@ int tdt_dispatch_accumulate(tdt_compute *c, int width, int height, int depth, in
   if (spp_begin < 0 || spp_count < 0) return fail(c->ctx, TDT_ERR_INVALID_VALUE, "negative sample range");
   if (c->ctx->multi) return tdt::multi_dispatch_accumulate(c, width, height, depth, spp_begin, spp_count, carry);
   if (carry && ((uintptr_t)carry & 15) != 0) return fail(c->ctx, TDT_ERR_INVALID_VALUE, "carry memory must be 16-byte aligned");
-  return launch(c, width, height, depth, 1, spp_begin, spp_count, carry, 0, nullptr);
+  LaunchRequest rq;
+  rq.kind = LaunchRequest::kAccumulate; rq.spp_begin = spp_begin; rq.spp_count = spp_count; rq.carry = carry;
+  return launch(c, width, height, depth, rq);
 }
 
 int tdt_dispatch_resolve(tdt_compute *c, int width, int height, int depth, int total_spp) {
   if (!c) return TDT_ERR_INVALID_VALUE;
   if (c->kind != TDT_PROGRAM_RAYTRACER) return fail(c->ctx, TDT_ERR_INVALID_OPERATION, "not the raytracer program");
   if (c->ctx->multi) return tdt::multi_dispatch_resolve(c, width, height, depth, total_spp);
-  return launch(c, width, height, depth, 2, 0, 0, nullptr, total_spp, nullptr);
+  LaunchRequest rq;                                   // (no pre-pass ran: every pixel is resolved)
+  rq.kind = LaunchRequest::kResolve; rq.total_spp = total_spp;
+  return launch(c, width, height, depth, rq);
 }
 
 int64_t tdt_covered_pixels(const tdt_compute *c, int width, int height, int depth) {
@@ -2208,8 +2335,9 @@ int tdt_dispatch_counted(tdt_compute *c, int width, int height, int depth, uint6
   if (c->ctx->multi) return tdt::multi_dispatch_counted(c, width, height, depth, counts);
   if (c->kind != TDT_PROGRAM_RAYTRACER) return fail(c->ctx, TDT_ERR_INVALID_OPERATION, "not the raytracer program");
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
-  return launch(c, width, height, depth, 0, 0, c->samples_per_pixel, nullptr, c->samples_per_pixel,
-                reinterpret_cast<unsigned long long *>(counts));
+  LaunchRequest rq;
+  rq.spp_count = rq.total_spp = c->samples_per_pixel; rq.counts_out = reinterpret_cast<unsigned long long *>(counts);
+  return launch(c, width, height, depth, rq);
 }
 
 int tdt_dispatch_counted_range(tdt_compute *c, int width, int height, int depth, int spp_begin, int spp_count, void *carry,
@@ -2219,32 +2347,36 @@ int tdt_dispatch_counted_range(tdt_compute *c, int width, int height, int depth,
   if (c->kind != TDT_PROGRAM_RAYTRACER) return fail(c->ctx, TDT_ERR_INVALID_OPERATION, "not the raytracer program");
   if (spp_begin < 0 || spp_count < 0) return fail(c->ctx, TDT_ERR_INVALID_VALUE, "negative sample range");
   if (carry && ((uintptr_t)carry & 15) != 0) return fail(c->ctx, TDT_ERR_INVALID_VALUE, "carry memory must be 16-byte aligned");
-  return launch(c, width, height, depth, 1, spp_begin, spp_count, carry, 0, reinterpret_cast<unsigned long long *>(counts));
+  LaunchRequest rq;
+  rq.kind = LaunchRequest::kAccumulate; rq.spp_begin = spp_begin; rq.spp_count = spp_count; rq.carry = carry;
+  rq.counts_out = reinterpret_cast<unsigned long long *>(counts);
+  return launch(c, width, height, depth, rq);
 }
 
 int tdt_forget_costs(tdt_ctx *ctx) {
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   if (ctx->multi) return tdt::multi_forget_costs(ctx);
-  ctx->cost_tiles = 0; ctx->cost_dispatches = 0; ctx->order_exact = false;      // launch(): "no usable history" -> image order, fresh cost arrays
+  tdt::TraceState::CostOrder &O = ctx->trace->order;
+  O.cost_tiles = 0; O.cost_dispatches = 0; O.order_exact = false;      // plan_order(): "no usable history" -> image order, fresh cost arrays
   return TDT_OK;
 }
 
 int tdt_debug_phase_timing(tdt_ctx *ctx, int enable, float ms[3]) {
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   TDT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ms) {
-    ms[0] = ms[1] = ms[2] = 0.f;
-    if (ctx->phase_timing && ctx->phase_n >= 2) {
-      TDT_HIP(ctx, hipEventSynchronize(ctx->phase_ev[ctx->phase_n - 1]));
-      for (int i = 0; i + 1 < ctx->phase_n; i++) TDT_HIP(ctx, hipEventElapsedTime(&ms[ctx->phase_n == 2 ? 1 : i], ctx->phase_ev[i], ctx->phase_ev[i + 1]));
-    }
+  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  if (!ctx->trace) return TDT_OK;                     // (a multi-device front: its members are not timed through it)
+  tdt::TraceState &S = *ctx->trace;
+  if (ms && S.phase_timing && S.phase_n >= 2) {
+    TDT_HIP(ctx, hipEventSynchronize(S.phase_ev[S.phase_n - 1]));
+    for (int i = 0; i + 1 < S.phase_n; i++) TDT_HIP(ctx, hipEventElapsedTime(&ms[S.phase_n == 2 ? 1 : i], S.phase_ev[i], S.phase_ev[i + 1]));
   }
-  if (enable && !ctx->phase_timing) {
-    for (auto &e : ctx->phase_ev) TDT_HIP(ctx, hipEventCreate(&e));
-    ctx->phase_timing = true; ctx->phase_n = 0;
-  } else if (!enable && ctx->phase_timing) {
-    for (auto &e : ctx->phase_ev) (void)hipEventDestroy(e);
-    ctx->phase_timing = false; ctx->phase_n = 0;
+  if (enable && !S.phase_timing) {
+    for (auto &e : S.phase_ev) TDT_HIP(ctx, hipEventCreate(&e));
+    S.phase_timing = true; S.phase_n = 0;
+  } else if (!enable && S.phase_timing) {
+    for (auto &e : S.phase_ev) (void)hipEventDestroy(e);
+    S.phase_timing = false; S.phase_n = 0;
   }
   return TDT_OK;
 }
@@ -2255,7 +2387,7 @@ int tdt_debug_phase_timing(tdt_ctx *ctx, int enable, float ms[3]) {
 int tdt_debug_last_variant(const tdt_ctx *ctx, int out[6]) {
   if (!ctx || !out) return TDT_ERR_INVALID_VALUE;
   if (ctx->multi) ctx = tdt::multi_first_member(const_cast<tdt_ctx *>(ctx));
-  std::memcpy(out, ctx->last_variant, 6 * sizeof(int));
+  std::memcpy(out, ctx->trace->last_variant, 6 * sizeof(int));
   return TDT_OK;
 }
 
@@ -2283,17 +2415,18 @@ int tdt_debug_stats(tdt_ctx *ctx, uint64_t *out, int n_words, int reset) {
   if (ctx->multi) ctx = tdt::multi_first_member(ctx);
 #ifdef TDT_STATS
   TDT_HIP(ctx, hipSetDevice(ctx->device));
-  const bool fresh = ctx->stats == nullptr;
+  unsigned long long *&stats = ctx->trace->stats;
+  const bool fresh = stats == nullptr;
   constexpr size_t kStatWords = tdt::STAT_COUNT + 1 + 8192;      // totals, the time the queue ran dry, per-wave end times
-  if (fresh) TDT_HIP(ctx, hipMalloc((void **)&ctx->stats, kStatWords * sizeof(unsigned long long)));
+  if (fresh) TDT_HIP(ctx, ctx->trace->alloc(stats, kStatWords));
   TDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const size_t n_out = n_words > 0 ? ((size_t)n_words < kStatWords ? (size_t)n_words : kStatWords) : (size_t)tdt::STAT_COUNT;
-  if (out && !fresh) TDT_HIP(ctx, hipMemcpy(out, ctx->stats, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (out && !fresh) TDT_HIP(ctx, hipMemcpy(out, stats, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost));
   else if (out) std::memset(out, 0, n_out * sizeof(uint64_t));
   if (reset || fresh) {
     std::vector<unsigned long long> init(kStatWords, 0ull);
     init[tdt::STAT_T_FIRST] = ~0ull; init[tdt::STAT_COUNT] = ~0ull;
-    TDT_HIP(ctx, hipMemcpy(ctx->stats, init.data(), kStatWords * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    TDT_HIP(ctx, hipMemcpy(stats, init.data(), kStatWords * sizeof(unsigned long long), hipMemcpyHostToDevice));
   }
   return TDT_OK;
 #else
@@ -2310,9 +2443,9 @@ int tdt_debug_counters(tdt_ctx *ctx, uint64_t out[32]) {
   return TDT_OK;
 }
 int tdt_debug_pixel_log(tdt_ctx *ctx, uint32_t *out, size_t n_u32) {
-  if (!ctx || !out || !ctx->pixel_log || n_u32 > ctx->pixel_log_u32) return TDT_ERR_INVALID_VALUE;
+  if (!ctx || !out || !ctx->trace || !ctx->trace->pixel_log || n_u32 > ctx->trace->pixel_log_u32) return TDT_ERR_INVALID_VALUE;
   TDT_HIP(ctx, hipSetDevice(ctx->device));
-  TDT_HIP(ctx, hipMemcpy(out, ctx->pixel_log, n_u32 * 4, hipMemcpyDeviceToHost));
+  TDT_HIP(ctx, hipMemcpy(out, ctx->trace->pixel_log, n_u32 * 4, hipMemcpyDeviceToHost));
   return TDT_OK;
 }
 /* per-wave end times (100 MHz ticks) of the last instrumented dispatch: n <= 16384 entries */

@@ -125,6 +125,36 @@ def test_resolve_on_its_own_resolves_every_pixel():
     assert np.allclose(got[..., 0], 0.5) and np.allclose(got[..., 1], 0.25) and (got[..., 2] == 1.0).all() and (got[..., 3] == 1.0).all()
 
 
+@pytest.mark.parametrize("origin", [None, (0.9, 0.6, 0.8)], ids=["inside", "outside"])
+def test_a_larger_frame_on_the_same_context(oracle, origin):
+    """A 64 x 64 frame, then a 168 x 100 one at 16 spp on the same context: the per-slot arrays of the cost order and of the miss
+    pre-pass (camera outside the octree) and the frame carry are too small for the second frame and grow.  Both frames equal the
+    oracle bit for bit, the larger one as a replay too."""
+    scene = host.Scene.config(2)
+
+    def cam(W, H):
+        if origin is None:
+            return host.camera_reference_pose(W, H, 16, 6)
+        c = host.Camera(70.0, W, aspect_ratio=np.float32(W) / np.float32(H), origin=origin, viewport_height=2.0, samples_per_pixel=16, max_bounce=6)
+        c.turn_yaw(-130.0)
+        c.turn_pitch(-20.0)
+        return c.uniforms()
+
+    small, large = cam(64, 64), cam(168, 100)
+    r = rt.Renderer(scene, small)
+    try:
+        first = r.render()
+        r.camera = large
+        rt.initial_uniforms(large, r.shader.program)
+        r.texture = rt.Texture.new_2d(r.ctx, 168, 100)
+        second, again = r.render(), r.render()
+    finally:
+        r.close()
+    assert _eq(first, oracle.render(scene, small, threads=8))
+    ref = oracle.render(scene, large, threads=8)
+    assert _eq(second, ref) and _eq(again, ref)
+
+
 def test_first_moved_frame_after_a_still_camera_keeps_a_prior(oracle):
     """Frames of a still camera reuse their hand-out order (no sort, no cost stores) from the third on; the first frame after that with
     other inputs must still be the right pixels — and is ordered from the still frames' sums (bench: reference_default.still_then_move_ms)."""
