@@ -593,7 +593,11 @@ int tdt_debug_pixel_log(tdt_ctx *ctx, uint32_t *out, size_t n_u32);
  * fl(v + f) - v depends on an integer v < 2^22 only through floor(log2 v), for every f in [0, 1); 15: the bands of their
  * level-5 table, one per cell index instead of one for all).  *mismatches must be 0.  Modes 3, 6, 8, 10, 12, 14 and 16 check the
  * harness: the raw reciprocal seed, the claims without the bands, the short normal without its guard, the divisions without
- * the residual step, the wrong binade, and half the band, must fail. */
+ * the residual step, the wrong binade, and half the band, must fail.
+ * Mode 17 reads the cells buffer and octree uniforms bound to ctx (max_depth 5 or 6, a tree the whole-depth table serves;
+ * TDT_ERR_INVALID_OPERATION otherwise): for every one of the 8^max_depth table positions, what a traversal step decodes from
+ * the table's entry (cell corner, cell size, value, LEAF or not) must equal, bit for bit, what the 16-bit entry's decode computes
+ * from the position and what the level walk over the packed node table ends on. */
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches);
 /* A cell_count that is not a power of two (the reference's own: 100000, main.rs:459) takes treeLookup's x index
  * (raytracer.comp:376-378) through two per-cell thresholds on the level's coordinate instead of the float formula (csrc/

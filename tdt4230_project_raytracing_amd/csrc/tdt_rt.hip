@@ -819,12 +819,16 @@ __global__ __launch_bounds__(256) void selftest_index_kernel(float inv_cell_coun
 }
 
 // The whole-depth table of FULL builds (see tree_lookup_pow2): entry (x, y, z digits of a finest-level voxel position) = what
-// treeLookup's descent with those child digits ends on.  16 bits: (depth - levels) << 2 | code, and for a LEAF its value << 5 (the only
-// value a traversal step uses; a PARENT can only be what the last level holds).  *bad is raised when the tree does not fit the
-// claim the table rests on (a PARENT of a level that feeds a later x decision at or above grid_v_bound) or a material index
-// does not fit 11 bits.
+// treeLookup's descent with those child digits ends on.  meta16: (depth - levels) << 2 | code, and for a LEAF its value << 5 (the only
+// value a traversal step uses; a PARENT can only be what the last level holds).  Entries of 32 / 64 bits carry, above meta16, the upper
+// fp32 halves of the corner (digit >> (depth - levels)) * 2^-levels of the cell the descent ends in: x alone, or x in w0 and y, z in w1
+// (full_entry_encode).  8^depth entries: 256 KB (depth 5) / 2 MB (depth 6) at 64 bits, 128 KB / 1 MB at 32, 64 KB / 512 KB at 16.
+// *bad is raised when the tree does not fit the claim the table rests on (a PARENT of a level that feeds a later x decision at or
+// above grid_v_bound), a material index does not fit 11 bits, or a corner component has a bit set in the lower half of its fp32
+// (none can for depth <= 6: six significand bits; checked, not argued).
+template <int BITS>
 __global__ __launch_bounds__(256) void build_full_grid_kernel(const uint32_t *__restrict__ cells, uint32_t cells_dwords, int depth,
-                                                             uint16_t *__restrict__ grid, uint32_t *__restrict__ bad) {
+                                                             typename FullEntry<BITS>::Type *__restrict__ grid, uint32_t *__restrict__ bad) {
   const uint32_t e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (1u << (3 * depth))) return;
   const uint32_t xg = e >> (2 * depth), yg = (e >> depth) & ((1u << depth) - 1u), zg = e & ((1u << depth) - 1u);
@@ -841,8 +845,44 @@ __global__ __launch_bounds__(256) void build_full_grid_kernel(const uint32_t *__
   }
   uint32_t enc = (((uint32_t)depth - m) << 2) | code;  // depth - levels: what the lookup shifts the digits by, and the exponent of the cell size above 2^-depth (a PARENT: 0)
   if (code == 2u) { enc |= v << 5; ok = ok && v < 2048u; }
-  grid[e] = (uint16_t)enc;
+  if (!full_entry_encode<BITS>(enc & 0xFFFFu, depth, xg, yg, zg, grid[e])) ok = false;
   if (!ok) atomicOr(bad, 1u);
+}
+
+// tdt_selftest 17: every position of the whole-depth table.  What a traversal step decodes from the product's entry must be, bit for
+// bit, what the 16-bit decode computes from the same position (corner, cell size, value, LEAF or not), and what the level walk
+// over the packed node table (the image every block stages in LDS) ends on: levels, corner from the digits, LEAF or not and
+// a LEAF's value.
+template <int DEPTH>
+__device__ __forceinline__ uint32_t full_grid_check(uint32_t e, const FullGridEntry *grid, const uint16_t *grid16, const uint16_t *packed, uint32_t lds_nodes) {
+  const uint32_t xg = e >> (2 * DEPTH), yg = (e >> DEPTH) & ((1u << DEPTH) - 1u), zg = e & ((1u << DEPTH) - 1u);
+  float ax, ay, az, ai, bx, by, bz, bi; uint32_t av, bv;
+  const bool al = full_entry_decode<kFullEntryBits, DEPTH>(grid[e], xg, yg, zg, ax, ay, az, ai, av);
+  const bool bl = full_entry_decode<16, DEPTH>(grid16[e], xg, yg, zg, bx, by, bz, bi, bv);
+  uint32_t bad = (__float_as_uint(ax) != __float_as_uint(bx) || __float_as_uint(ay) != __float_as_uint(by) || __float_as_uint(az) != __float_as_uint(bz) ||
+                  __float_as_uint(ai) != __float_as_uint(bi) || av != bv || al != bl) ? 1u : 0u;
+  uint32_t v = 0, code = 1u, m = 0;
+  for (int l = 1; l <= DEPTH && code == 1u; l++) {
+    const int sh = DEPTH - l;
+    const uint32_t idx = ((2u * v + ((xg >> sh) & 1u)) << 2) + (((yg >> sh) & 1u) << 1) + ((zg >> sh) & 1u);
+    const uint32_t n = idx < lds_nodes ? packed[idx] : 0u;                 // past the staged nodes: the all-EMPTY sentinel cell
+    v = n >> 2; code = n & 3u; m = (uint32_t)l;
+  }
+  const float wi = __uint_as_float((127u - m) << 23);                      // 2^-levels
+  const uint32_t sh = (uint32_t)DEPTH - m;
+  const float wx = (float)(xg >> sh) * wi, wy = (float)(yg >> sh) * wi, wz = (float)(zg >> sh) * wi;
+  const bool wl = code == 2u;
+  bad += (__float_as_uint(ax) != __float_as_uint(wx) || __float_as_uint(ay) != __float_as_uint(wy) || __float_as_uint(az) != __float_as_uint(wz) ||
+          __float_as_uint(ai) != __float_as_uint(wi) || al != wl || (wl && av != v)) ? 1u : 0u;
+  return bad;
+}
+__global__ __launch_bounds__(256) void selftest_full_grid_kernel(int depth, const FullGridEntry *__restrict__ grid, const uint16_t *__restrict__ grid16,
+                                                                const uint16_t *__restrict__ packed, uint32_t lds_nodes, unsigned long long *mismatches) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long bad = 0;
+  if (e < (1u << (3 * depth))) bad = depth == 5 ? full_grid_check<5>(e, grid, grid16, packed, lds_nodes) : full_grid_check<6>(e, grid, grid16, packed, lds_nodes);
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor((long long)bad, o, 64);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
 }
 
 // The bricks of BRICK builds (see tree_lookup_pow2): one block per level-5 position e = x5 << 10 | y5 << 5 | z5.  Every thread walks
@@ -1417,7 +1457,7 @@ struct tdt::TraceState {
     uint32_t *scan = nullptr;                                 // device scratch of scan_cells_kernel, and its result for packed_key:
     uint32_t max_parent_value = 0xFFFFFFFFu, max_any_value = 0xFFFFFFFFu, live_nodes = 0xFFFFFFFFu;   // (live_nodes: one past the last node that is not all zeros)
     float *thr = nullptr; ThresholdKey thr_key; float thr_f0max = 0.0f; bool thr_ok = false;   // FORM_TABLE builds: per-cell x-index thresholds for (cell_count, inv_cell_count) over thr_key.n cells
-    uint16_t *full_grid = nullptr; TableKey full_key; bool full_ok = false;   // whole-depth lookup table of small resident trees
+    FullGridEntry *full_grid = nullptr; TableKey full_key; bool full_ok = false;   // whole-depth lookup table of small resident trees
     uint32_t *brick_grid = nullptr; uint16_t *bricks = nullptr; size_t bricks_bytes = 0; TableKey brick_key; bool brick_ok = false;   // BRICK builds (depth-8 / 9 trees that are not LDS-resident)
   } tables;
   float *frame_carry = nullptr; size_t frame_carry_bytes = 0;   // hit-record carry between the two phases of a frame (tdt_dispatch_compute)
@@ -1751,10 +1791,10 @@ int prepare_full_grid(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) 
   const TraceState::TableKey key{cb, cb->version, P.max_depth};
   if (!(T.full_key == key)) {
     const size_t entries = (size_t)1 << (3 * P.max_depth);
-    if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + sizeof(uint32_t) / sizeof(uint16_t)));
+    if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + 2));      // 8^6 entries and the `bad` word behind them
     uint32_t *bad = reinterpret_cast<uint32_t *>(T.full_grid + ((size_t)1 << 18));
     TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(tdt::build_full_grid_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
+    hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryBits>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
     TDT_HIP(ctx, hipGetLastError());
     uint32_t flag = 1;
     TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
@@ -2458,8 +2498,55 @@ int tdt_debug_wave_ends(tdt_ctx *ctx, uint64_t *out, int n) {
 
 /* Exhaustive self-test of the kernels' short correctly-rounded rcp / sqrt / rsq forms against the
  * IEEE expressions on all 2^32 inputs; *mismatches must come back 0 (which: 0 rcp, 1 sqrt, 2 rsq). */
+// tdt_selftest 17 (selftest_full_grid_kernel) on the cells buffer bound to ctx: the tree must be one the whole-depth table serves
+static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
+  tdt_ctx *ctx = front->multi ? tdt::multi_first_member(front) : front;
+  TDT_HIP(front, hipSetDevice(ctx->device));
+  TraceParams P;
+  std::memset(&P, 0, sizeof P);
+  const tdt_buffer *cb = ctx->ssbo[TDT_SLOT_CELLS];
+  if (!cb) return tdt::fail(front, TDT_ERR_INCOMPLETE, "tdt_selftest 17: no cells buffer bound");
+  if (int rc = tdt::octree_uniforms(ctx, P)) return rc;
+  if (P.max_depth != 5 && P.max_depth != 6) return tdt::fail(front, TDT_ERR_INVALID_OPERATION, "tdt_selftest 17: max_depth must be 5 or 6");
+  if (cb->bytes > 0xFFFFFFF8ull) return tdt::fail(front, TDT_ERR_INVALID_OPERATION, "tdt_selftest 17: cells buffer too large");
+  const uint32_t *cells = (const uint32_t *)cb->dev;
+  const uint32_t cells_dwords = (uint32_t)(cb->bytes >> 2), buf_nodes = cells_dwords >> 1;
+  const uint32_t staged = buf_nodes < tdt::kLdsCells * 8u ? (buf_nodes & ~7u) : tdt::kLdsCells * 8u;
+  const size_t entries = (size_t)1 << (3 * P.max_depth);
+  tdt::DeviceScratch mem;
+  FullGridEntry *grid = mem.get<FullGridEntry>(entries);
+  uint16_t *grid16 = mem.get<uint16_t>(entries), *packed = mem.get<uint16_t>((size_t)tdt::kLdsCells * 8);
+  unsigned long long *words = mem.get<unsigned long long>(4);                // mismatches; bad (two builds); scan results
+  if (!grid || !grid16 || !packed || !words) return tdt::hip_fail(front, hipErrorOutOfMemory, "tdt_selftest 17");
+  uint32_t *bad = reinterpret_cast<uint32_t *>(words + 1), *scan = reinterpret_cast<uint32_t *>(words + 2);
+  TDT_HIP(front, hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  if (staged) hipLaunchKernelGGL(tdt::pack_cells_kernel, dim3((staged + 255) / 256), dim3(256), 0, ctx->stream, cells, cells_dwords, packed, staged);
+  if (buf_nodes) {
+    unsigned nb = (buf_nodes + 255) / 256; if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(tdt::scan_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, cells, buf_nodes, scan);
+  }
+  const dim3 blocks((unsigned)((entries + 255) / 256));
+  hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryBits>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid, bad);
+  hipLaunchKernelGGL(tdt::build_full_grid_kernel<16>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid16, bad + 1);
+  TDT_HIP(front, hipGetLastError());
+  uint32_t res[4] = {0, 0, 0, 0}, flags[2] = {1, 1};
+  TDT_HIP(front, hipMemcpyAsync(res, scan, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+  TDT_HIP(front, hipMemcpyAsync(flags, bad, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
+  TDT_HIP(front, hipStreamSynchronize(ctx->stream));
+  // the launch's own conditions for the whole-depth build (classify_tree, prepare_full_grid): resident, small PARENT values, table built
+  const bool served = buf_nodes > 0 && res[2] <= staged && res[1] <= tdt::kPackedMaxValue && res[0] < (1u << 22) && flags[0] == 0 && flags[1] == 0;
+  if (!served) return tdt::fail(front, TDT_ERR_INVALID_OPERATION, "tdt_selftest 17: the bound tree is not one the whole-depth table serves");
+  const uint32_t lds_nodes = (res[2] + 7u) & ~7u;                            // the live cells alone are staged (classify_tree)
+  hipLaunchKernelGGL(tdt::selftest_full_grid_kernel, blocks, dim3(256), 0, ctx->stream, P.max_depth, grid, grid16, packed, lds_nodes, words);
+  TDT_HIP(front, hipGetLastError());
+  TDT_HIP(front, hipMemcpyAsync(mismatches, words, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  TDT_HIP(front, hipStreamSynchronize(ctx->stream));
+  return TDT_OK;
+}
+
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches) {
-  if (!ctx || !mismatches || which < 0 || which > 16) return TDT_ERR_INVALID_VALUE;
+  if (!ctx || !mismatches || which < 0 || which > 17) return TDT_ERR_INVALID_VALUE;
+  if (which == 17) return selftest_full_grid(ctx, mismatches);
   TDT_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->counters) TDT_HIP(ctx, hipMalloc((void **)&ctx->counters, (32 + 16384 + 256) * sizeof(unsigned long long)));
   TDT_HIP(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));

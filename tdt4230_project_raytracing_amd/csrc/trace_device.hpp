@@ -195,7 +195,7 @@ struct NodeSource {
   uint32_t lds_cells;                                 // cells they make up (the last may be partial): index of the sentinel cell
   const void *grid;                                   // top-level jump table (Grid<GL>::Entry[], see build_top_grid), or unusable when !grid_ok
   bool grid_ok; float grid_band;                      // grid_band = kGridBand, or 2 when the table is unusable
-  const uint16_t *full;                               // FULL builds: the whole-depth table in global memory (see tree_lookup_pow2)
+  const FullGridEntry *full;                          // FULL builds: the whole-depth table in global memory (see tree_lookup_pow2)
   const uint32_t *grid32; const void *bricks;         // BRICK builds: the 5-level table with brick headers (LDS) and the bricks (global memory, 16-bit entries)
   const float2 *thr; float thr_f0max;                 // FORM_TABLE builds: (F1, F2) per cell (LDS) and the scene-wide bound on F0, see x_thresholds
   __amdgpu_buffer_rsrc_t cells;                       // raw buffer over the cells payload (8-byte granules)
@@ -517,11 +517,15 @@ constexpr int kMemoFirst = 3;       // levels 1..3 = cells 0..72 at most: always
 //   RESIDENT    : the whole cells buffer sits in the LDS table and no node needed the escape code
 //   SAFEV       : every PARENT value in the buffer is < 2^22 (scanned once per buffer), so the
 //                 literal-formula branch for huge cell indices cannot be taken
-// FULL (round 2; small trees: max_depth 5 or 6, wholly LDS-resident): the jump table idea taken to the last level — one 16-bit
-// entry per finest-level voxel position (8^depth of them: 64 KB / 512 KB, built once per cells buffer by build_full_grid_kernel,
+// FULL (round 2; small trees: max_depth 5 or 6, wholly LDS-resident): the jump table idea taken to the last level — one
+// entry per finest-level voxel position (8^depth of them, built once per cells buffer by build_full_grid_kernel,
 // read through L2) holds what the whole descent ends on, so a traversal step does ONE load instead of a table read plus two
 // more levels; the bands are those of the 5-level table (cell indices of a resident tree stay below 8192: 2^-11 around the
-// integers of 2^depth c), and a wave with a lane inside one walks all levels from the LDS node table.
+// integers of 2^depth c), and a wave with a lane inside one walks all levels from the LDS node table.  An entry is
+// kFullEntryBits wide (FullEntry<BITS>): 16 bits hold what the descent ends on (meta16); the wider forms also carry the corner of
+// the cell it ends in, which is a function of the table position alone — each component is k 2^-levels with k < 64, six
+// significand bits, so the upper half of its fp32 IS the value and the step gets it back with one bit operation per component
+// instead of shift, convert and multiply.  8^depth entries: 64 KB / 512 KB at 16 bits, 128 KB / 1 MB at 32, 256 KB / 2 MB at 64.
 // BRICK (round 2; depth-8 and depth-9 trees that are NOT LDS-resident, every PARENT value < 2^22): the levels below 5 in ONE load
 // as well.  Below level 5 cell indices are large and the x decision  a = fl(v + f) - v > 0.5, b = ... == 1  is far from the
 // coordinate's binary digit (v ~ 2^20: ulp(v + f) = 2^-3), so a table indexed by position would be wrong for a tenth of all
@@ -549,6 +553,46 @@ constexpr uint32_t kBrickLdsCells = 1024u;            // BRICK builds keep a sma
 TDT_DEV int brick_band_exp(int l, uint32_t v) { return (v == 0u ? -40 : (31 - (int)__builtin_clz(v)) + 5 - l - 23); }
 // fl(v + f) - v for any integer v in [2^e, 2^(e+1)), e <= 21
 TDT_DEV float brick_q(uint32_t e, float f) { const float V = __uint_as_float((127u + e) << 23); return (V + f) - V; }
+constexpr int kFullEntryBits = TDT_FULL_ENTRY_BITS;
+template <int BITS> struct FullEntry;
+template <> struct FullEntry<16> { typedef uint16_t Type; };
+template <> struct FullEntry<32> { typedef uint32_t Type; };
+template <> struct FullEntry<64> { typedef FullGridEntry64 Type; };
+static_assert(sizeof(FullEntry<kFullEntryBits>::Type) == sizeof(FullGridEntry) && sizeof(FullGridEntry) * 8 == kFullEntryBits, "the table's entry type");
+// meta16 = (depth - levels) << 2 | code | value << 5 and the corner (digit >> (depth - levels)) * 2^-levels of the cell the descent
+// from position (xg, yg, zg) ends in, as an entry; false when a corner component does not fit the upper half of its fp32
+template <int BITS>
+TDT_DEV bool full_entry_encode(uint32_t meta16, int depth, uint32_t xg, uint32_t yg, uint32_t zg, typename FullEntry<BITS>::Type &e) {
+  if constexpr (BITS == 16) { e = (uint16_t)meta16; return true; }
+  else {
+    const uint32_t sh = (meta16 >> 2) & 7u;
+    const float ipd = __uint_as_float(((127u - (uint32_t)depth) << 23) + (sh << 23));        // 2^-levels, as the step computes it
+    const uint32_t cx = __float_as_uint((float)(xg >> sh) * ipd), cy = __float_as_uint((float)(yg >> sh) * ipd), cz = __float_as_uint((float)(zg >> sh) * ipd);
+    if constexpr (BITS == 32) { e = (cx & 0xFFFF0000u) | meta16; return (cx & 0xFFFFu) == 0u; }
+    else { e.w0 = (cx & 0xFFFF0000u) | meta16; e.w1 = (cy & 0xFFFF0000u) | (cz >> 16); return ((cx | cy | cz) & 0xFFFFu) == 0u; }
+  }
+}
+// what a traversal step takes from the entry of position (xg, Yi, Zi): the cell's corner and size, a LEAF's value; true for a LEAF
+template <int BITS, int DEPTH>
+TDT_DEV bool full_entry_decode(const typename FullEntry<BITS>::Type &g, uint32_t xg, uint32_t Yi, uint32_t Zi, float &gx, float &gy, float &gz, float &ipd, uint32_t &value) {
+  uint32_t meta;
+  if constexpr (BITS == 64) meta = g.w0; else meta = g;
+  const uint32_t sh = (meta >> 2) & 7u;                                   // DEPTH - levels (build_full_grid_kernel stores it that way: one subtraction less per step)
+  ipd = __uint_as_float(((127u - (uint32_t)DEPTH) << 23) + (sh << 23));   // 2^-levels
+  if constexpr (BITS == 16) {
+    gx = (float)(xg >> sh) * ipd; gy = (float)(Yi >> sh) * ipd; gz = (float)(Zi >> sh) * ipd;
+    value = meta >> 5;
+  } else if constexpr (BITS == 32) {
+    gx = __uint_as_float(meta & 0xFFFF0000u); gy = (float)(Yi >> sh) * ipd; gz = (float)(Zi >> sh) * ipd;
+    value = (meta >> 5) & 0x7FFu;
+  } else {
+    // (the low half by a shift: of the three ways to move it up, all half-rate, v_lshlrev_b32 is the cheapest — 4.14 cycles against 4.25
+    // for an SDWA move and 4.40 for v_perm_b32, and beside a full-rate instruction 6.6 / 6.1 for those two: tools/micro/pipe_model.hip)
+    gx = __uint_as_float(meta & 0xFFFF0000u); gy = __uint_as_float(g.w1 & 0xFFFF0000u); gz = __uint_as_float(g.w1 << 16);
+    value = (meta >> 5) & 0x7FFu;
+  }
+  return (meta & 3u) == 2u;
+}
 template <bool COUNT, int CL, int DEPTH, bool RESIDENT, bool SAFEV, bool FULL = false, bool BRICK = false, bool TABLE = false>
 TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float fx, float fy, float fz, float &inv_pow_depth,
                               float &gx, float &gy, float &gz, uint32_t &value, NodeMemo<CL> &memo, Counters &cnt) {
@@ -573,13 +617,8 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
     if (__builtin_expect(__ballot(!safe) == 0ull, 1)) {
       // the whole lookup: levels visited, the cell's digits and what it holds (see build_full_grid_kernel)
       const uint32_t xg = (uint32_t)tg;
-      const uint32_t g = ns.full[(xg << (2 * DEPTH)) | (Yi << DEPTH) | Zi];
-      const uint32_t sh = (g >> 2) & 7u;                                      // DEPTH - levels (build_full_grid_kernel stores it that way: one subtraction less per step)
-      const float ipd = __uint_as_float(((127u - (uint32_t)DEPTH) << 23) + (sh << 23));      // 2^-levels
-      gx = (float)(xg >> sh) * ipd; gy = (float)(Yi >> sh) * ipd; gz = (float)(Zi >> sh) * ipd;
-      inv_pow_depth = ipd;
-      value = g >> 5;
-      return (g & 3u) == 2u;
+      const FullGridEntry g = ns.full[(xg << (2 * DEPTH)) | (Yi << DEPTH) | Zi];      // (64 bits: one 8-byte load)
+      return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
     }
   } else if constexpr (BRICK && !COUNT) {
     static_assert(!BRICK || (DEPTH >= 6 && DEPTH <= 10 && !RESIDENT && SAFEV), "the 32-bit table: trees of depth 6-10 outside the LDS table");

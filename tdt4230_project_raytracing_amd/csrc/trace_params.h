@@ -2,6 +2,23 @@
 #pragma once
 #include <stdint.h>
 
+// FULL builds: bits of a whole-depth table entry (build_full_grid_kernel).  16: what the descent ends on; 32: that and the x
+// component of the cell's corner; 64: that and all three components.  One constant, so that the three widths can be built
+// side by side and compared (-DTDT_FULL_ENTRY_BITS=...); the product's width is the default.
+#ifndef TDT_FULL_ENTRY_BITS
+#define TDT_FULL_ENTRY_BITS 64
+#endif
+struct alignas(8) FullGridEntry64 { uint32_t w0, w1; };       // corner_x_hi16 << 16 | meta16;  corner_y_hi16 << 16 | corner_z_hi16
+#if TDT_FULL_ENTRY_BITS == 64
+typedef FullGridEntry64 FullGridEntry;
+#elif TDT_FULL_ENTRY_BITS == 32
+typedef uint32_t FullGridEntry;                               // corner_x_hi16 << 16 | meta16
+#elif TDT_FULL_ENTRY_BITS == 16
+typedef uint16_t FullGridEntry;                               // meta16
+#else
+#error "TDT_FULL_ENTRY_BITS: 16, 32 or 64"
+#endif
+
 struct TraceParams {
   // `uniform Camera camera` raytracer.comp:133-146
   int32_t image_width, image_height;
@@ -28,7 +45,7 @@ struct TraceParams {
   uint32_t *slot_cost;          // per queue slot: pixel time of THIS dispatch (feeds the next one), or null
   const uint16_t *packed;       // cells [0, lds_cells) re-encoded as 16 bits per node: value << 2 | code
   uint32_t lds_nodes;           // number of nodes (8 per cell) staged in LDS by every block
-  const uint16_t *full_grid;    // FULL builds: one entry per finest-level voxel position (8^max_depth), see build_full_grid_kernel
+  const FullGridEntry *full_grid;   // FULL builds: one entry per finest-level voxel position (8^max_depth), see build_full_grid_kernel
   const uint32_t *brick_grid;   // BRICK builds: the 5-level jump table with brick headers (32^3 x 32 bit), see build_bricks_kernel
   const float *thr; uint32_t thr_cells; float thr_f0max;   // FORM_TABLE builds: (F1, F2) per cell index below thr_cells and the largest F0, see x_thresholds (trace_device.hpp)
   const void *bricks;           // BRICK builds: per level-5 position 27 x 64 (depth 8) or 81 x 256 (depth 9) 16-bit entries: what the levels below 5 end on, by decision sequence

@@ -628,7 +628,8 @@ class Context:
         self.check(lib().tdt_bind_buffer_base(self.h, target, slot, vbo.h if vbo is not None else None))
 
     def selftest(self, which):
-        """Mismatches of the short rcp (0) / sqrt (1) / rsq (2) forms vs IEEE over all 2^32 inputs."""
+        """Mismatches of the short rcp (0) / sqrt (1) / rsq (2) forms vs IEEE over all 2^32 inputs; the other modes: include/tdt_rt.h
+        (17: the whole-depth table of the bound cells buffer, every position)."""
         n = ctypes.c_uint64(0)
         self.check(lib().tdt_selftest(self.h, which, ctypes.byref(n)))
         return n.value

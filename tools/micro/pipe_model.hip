@@ -98,6 +98,13 @@ __global__ __launch_bounds__(1024) void k(float *out, int iters, float fs) {
         if (OP == 57) asm volatile("v_bfi_b32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(u[(i + 1) & 7]), "v"(u[(i + 2) & 7]));
         if (OP == 58) asm volatile("v_cmp_class_f32 vcc, %0, %1" :: "v"(f[i]), "v"(u[i]) : "vcc");
         if (OP == 59) asm volatile("v_sub_co_u32 %0, vcc, %0, %1" : "+v"(u[i]) : "v"(u[(i + 1) & 7]) : "vcc");
+        // ---- a 16-bit half of a register into the upper half of another (the corner components of the whole-depth table's entries) ----
+        if (OP == 81) asm volatile("v_lshlrev_b32 %0, 16, %0" : "+v"(u[i]));
+        if (OP == 82) asm volatile("v_and_b32 %0, 0xffff0000, %0" : "+v"(u[i]));
+        if (OP == 83) asm volatile("v_mov_b32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(u[i]) : "v"(u[(i + 1) & 7]));
+        if (OP == 84) asm volatile("v_bfe_u32 %0, %0, 5, 11" : "+v"(u[i]));
+        if (OP == 85) { F(i); asm volatile("v_mov_b32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(h[i]) : "v"(u[i])); }
+        if (OP == 86) { F(i); asm volatile("v_perm_b32 %0, %1, %1, %2" : "=v"(h[i]) : "v"(u[i]), "v"(u[(i + 1) & 7])); }
       }
     }
   }
@@ -136,6 +143,7 @@ int main() {
   run<30>("v_cmp_lt_f32 -> sgpr pair", d); run<31>("v_cmp_lt_u32 vcc", d); run<58>("v_cmp_class_f32", d); run<43>("v_cndmask_b32 vcc (vcc const)", d); run<44>("1 cmp + 2 cndmask", d);
   run<32>("v_add3_u32", d); run<33>("v_and_or_b32", d); run<37>("v_lshrrev_b32", d); run<38>("v_ashrrev_i32", d); run<40>("v_max_u32", d); run<41>("v_ldexp_f32", d);
   run<45>("v_max3_f32", d); run<46>("2 x v_max_f32 (dependent)", d); run<52>("v_med3_f32", d); run<50>("v_lshl_add_u64", d); run<51>("sub + mul dependent (2 instr)", d);
+  run<81>("v_lshlrev_b32", d); run<82>("v_and_b32 literal", d); run<83>("v_mov_b32_sdwa word0 -> word1", d); run<84>("v_bfe_u32", d); run<85>("1F + 1 sdwa move", d); run<86>("1F + 1 perm", d);
   run<53>("v_exp_f32", d); run<55>("v_perm_b32", d); run<56>("v_alignbit_b32", d); run<57>("v_bfi_b32", d); run<59>("v_sub_co_u32", d);
   return 0;
 }
