@@ -414,6 +414,18 @@ class Octree {
     if (n) ctx.check(tdt_octree_extract_enclosed(ctx.raw(), &fill, r, mask.size(), v.data(), n, &n));
     return v;
   }
+  // NEW: the tree's exposed voxel faces as quads (tdt_octree_extract_surface), ordered by face, w, u0, v0, the tree untouched:
+  // opt.merge 1 joins them into runs and stacks of identical runs (0: one quad per face), opt.by_material 1 keeps materials apart
+  // (0: the collision-mesh form), only the faces of voxels inside the union of `mask` (none: everywhere).  tdt_quads_to_mesh
+  // (tdt_host.h) turns them into an indexed triangle mesh, tdt_ply_mesh_write into a PLY file.
+  std::vector<tdt_quad> extract_surface(const Context &ctx, const tdt_surface &opt, const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_surface(ctx.raw(), &opt, r, mask.size(), nullptr, 0, &n));
+    std::vector<tdt_quad> q(n);
+    if (n) ctx.check(tdt_octree_extract_surface(ctx.raw(), &opt, r, mask.size(), q.data(), n, &n));
+    return q;
+  }
   // The click handler (main.rs:551-568) aimed at what is under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0),
   // and on a hit place (ClickEvent::Left) a voxel of `material` in front of the face, or remove (ClickEvent::Right) the one
   // behind it, through the same update_vbo(delta, 5, ..) call.  Returns whether an edit was dispatched; *hit receives the pick.

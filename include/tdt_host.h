@@ -177,6 +177,24 @@ int tdt_ply_mesh_info(const tdt_ply_mesh *m, int64_t *n_vertices, int64_t *n_fac
 /* n_vertices x {x, y, z} / n_triangles x 3 indices, owned by m (NULL when empty) */
 const float *tdt_ply_mesh_vertices(const tdt_ply_mesh *m);
 const uint32_t *tdt_ply_mesh_triangles(const tdt_ply_mesh *m);
+/* Quads -> the fixed-point indexed mesh of tdt_mesh: the way back from tdt_octree_extract_surface (include/tdt_rt.h) to polygons.
+ * quads: n_quads x tdt_quad as eight int32 {face, material, origin[3], size[2], pad}.  With a = face >> 1, s = face & 1, u = (a + 1) % 3,
+ * v = (a + 2) % 3 the corners are c0 = origin, c1 = c0 + size[0] e_u, c2 = c1 + size[1] e_v, c3 = c0 + size[1] e_v, in voxels; they
+ * are emitted as c0, c1, c2, c3 for s = 1 and as c0, c3, c2, c1 for s = 0, so every normal points out of the solid, and the quad's
+ * triangles are (0, 1, 2) and (0, 2, 3) of the emitted corners, in quad order.  Vertices are in units (64 per voxel), welded: each
+ * distinct corner once, in ascending (x, y, z) order.  materials[t] = the quad's material for both of its triangles (0 with
+ * by_material = 0: hand tdt_mesh a NULL materials array then).  Count-then-fill: *n_vertices and *n_triangles are always set; with
+ * vertices, triangles and materials all NULL nothing else happens; otherwise vertices and triangles are required (materials may
+ * be NULL) and a capacity below its count is 0x0501 with nothing written.  Also 0x0501: a face outside 0..5, a size below 1, a
+ * corner outside 0..4096 voxels (TDT_MESH_COORD_MAX), more than 2^30 quads. */
+int tdt_quads_to_mesh(const int32_t *quads, size_t n_quads, int32_t *vertices, size_t vertex_capacity, size_t *n_vertices,
+                      uint32_t *triangles, int32_t *materials, size_t triangle_capacity, size_t *n_triangles);
+/* A fixed-point mesh as ASCII PLY in the grammar tdt_ply_mesh_parse accepts: float x, y, z in VOXELS (units / 64: at most six
+ * decimals, exact, and exact again as the float the reader stores), faces as triangles "3 i j k".  *bytes = the length of the text
+ * (no terminating NUL is written); buffer == NULL only counts; capacity < *bytes: 0x0501 with *bytes set and nothing written.
+ * Also 0x0501: NULL arrays with a count above 0, an index >= n_vertices, a coordinate beyond +-2^18 units. */
+int tdt_ply_mesh_write(const int32_t *vertices, size_t n_vertices, const uint32_t *triangles, size_t n_triangles, char *buffer,
+                       size_t capacity, size_t *bytes);
 
 /* ---------------------------------------------------------------- pick-to-edit --------------- */
 /* The DeltaNode (8 floats: the 32-byte std430 stride of octree_update.comp:41-48) for a click on the voxel face a ray query found

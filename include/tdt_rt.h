@@ -557,6 +557,51 @@ int tdt_octree_edit_triangles_solid(tdt_ctx *ctx, int op, const tdt_mesh *mesh, 
  * box needed no flood); the host queues passes in batches of 8, so up to 8 more ran idle.  Measurement only. */
 int tdt_debug_fill_passes(const tdt_ctx *ctx);
 
+/* ---- surface extraction -----------------------------------------------------------------------------------------------------
+ * Turn the tree back into a surface: the inverse of tdt_voxelize_triangles.  V = what tdt_octree_extract returns, over the grid
+ * G = [0, 2^max_depth)^3.  Faces are numbered f = 0..5 as -x, +x, -y, +y, -z, +z: axis a = f >> 1, sign s = f & 1, in-plane axes
+ * u = (a + 1) % 3 and v = (a + 2) % 3.  Voxel p of V has an EXPOSED face f when p -+ e_a is not in V; a neighbour outside G counts
+ * as empty and nothing wraps around the grid.  Cavity walls are exposed faces like any other: call tdt_octree_fill_enclosed first
+ * for the outer skin only.
+ *   Mask: with n_regions > 0 (tdt_region shapes, the exact integer test of region edits) only the faces of voxels inside the union
+ *     of the shapes are reported; neighbourhoods are always evaluated on the whole tree (morphology's convention).
+ *   by_material = 1: a face carries its voxel's material + 1; by_material = 0: every face carries 0 (the collision-mesh form,
+ *     which merges across materials).
+ *   Merging is canonical, so a result does not depend on scheduling and compares bit for bit.  Write w for p[a], the voxel's OWN
+ *     coordinate along the axis (not the plane's position).  merge = 0: every exposed face is a 1 x 1 quad.  merge = 1, per face
+ *     direction f: within one (w, v) a RUN is a maximal set of exposed faces with consecutive u and equal carried material; runs
+ *     with the same (w, u0, u1) and carried material on consecutive v form a maximal STACK, and each stack is one quad.  "Runs,
+ *     then stacks of identical runs" is deliberately not an optimal greedy cover: it is unique.
+ *   Output: tdt_quad, eight int32.  origin is the minimum corner in lattice coordinates 0..2^max_depth: origin[a] = w + s,
+ *     origin[u] = u0, origin[v] = v0; size = {u1 - u0 + 1, v1 - v0 + 1}; pad = 0.  Quads are ordered by face, then w, then u0,
+ *     then v0.
+ * tdt_octree_extract_surface follows tdt_octree_extract's rules: quads == NULL only counts; capacity < the count:
+ * TDT_ERR_INVALID_VALUE with *n_quads set and nothing written; a multi-device context answers from device_ids[0].  The tree, its
+ * counter and its versions are untouched.  tdt_quads_to_mesh (include/tdt_host.h) turns the quads into the indexed mesh of tdt_mesh.
+ * Errors, nothing written: a NULL tdt_surface, merge or by_material outside 0..1, a bad shape, NULL regions with a count above 0,
+ * a LEAF value >= 254, |V| or the exposed faces of any one direction above 2^26 (TDT_REGION_BRUSH_CAP): TDT_ERR_INVALID_VALUE;
+ * slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream; synchronous. */
+typedef struct tdt_surface {
+  int32_t merge;               /* 0: one quad per exposed face; 1: runs, then stacks of identical runs */
+  int32_t by_material;         /* 1: faces carry material + 1 and merge within a material only; 0: they carry 0 */
+} tdt_surface;
+typedef struct tdt_quad {
+  int32_t face;                /* 0..5: -x, +x, -y, +y, -z, +z */
+  int32_t material;            /* material + 1, or 0 with by_material = 0 */
+  int32_t origin[3];           /* minimum corner, lattice coordinates */
+  int32_t size[2];             /* extent along u = (a + 1) % 3 and v = (a + 2) % 3 */
+  int32_t pad;
+} tdt_quad;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_surface) == 8, "tdt_surface is 8 bytes");
+static_assert(sizeof(tdt_quad) == 32, "tdt_quad is 32 bytes");
+#else
+_Static_assert(sizeof(tdt_surface) == 8, "tdt_surface is 8 bytes");
+_Static_assert(sizeof(tdt_quad) == 32, "tdt_quad is 32 bytes");
+#endif
+int tdt_octree_extract_surface(tdt_ctx *ctx, const tdt_surface *opt, const tdt_region *regions, size_t n_regions, tdt_quad *quads,
+                               size_t capacity, size_t *n_quads);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -8,6 +8,7 @@
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
+//            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -41,6 +42,11 @@
 //   empty voxel that no path of empty 6- (default) or 26-neighbours connects to a face of the grid becomes solid, in material K
 //   or, without --material, the material of the wall at its -x side; --mask limits the fill to a box of grid voxels.  Applied
 //   after --morph, before the frame; prints the number of voxels filled and the new cell count.
+// --export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]: the tree's surface as a triangle mesh
+//   (Octree::extract_surface, tdt_quads_to_mesh, tdt_ply_mesh_write): the exposed voxel faces merged into quads (--no-merge: one
+//   quad per face; --any-material: quads also merge across materials), of the voxels inside the --mask box only, written as an
+//   ASCII PLY in voxel coordinates.  Runs after every edit above, before --compact and the frame; prints the quad, vertex and
+//   triangle counts.
 // --compact: after the edits, rewrite the tree in place into its canonical form (Octree::compact) before the frame is
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
@@ -57,7 +63,8 @@ using namespace renderer;
 
 int main(int argc, char **argv) {
   int W = 1280, H = 720, spp = 4, bounce = 6, device = 0;
-  std::string out, png, settings_path, moves, mesh_path;
+  std::string out, png, settings_path, moves, mesh_path, export_path;
+  bool export_merge = true, export_by_material = true;
   std::vector<float> edit;
   int pick_x = -1, pick_y = -1, material = 1;
   bool place = true, compact = false, material_given = false, solid = false, fill_enclosed = false;
@@ -125,6 +132,9 @@ int main(int argc, char **argv) {
     else if (a == "--mesh") mesh_path = next();
     else if (a == "--solid") solid = true;
     else if (a == "--fill-enclosed") fill_enclosed = true;
+    else if (a == "--export-mesh") export_path = next();
+    else if (a == "--no-merge") export_merge = false;
+    else if (a == "--any-material") export_by_material = false;
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -291,6 +301,35 @@ int main(int argc, char **argv) {
       size_t voxels = 0;
       const uint32_t cells = octree.fill_enclosed(ctx, fill, regions, &voxels);
       std::printf("fill-enclosed conn %d voxels %zu cells %u\n", morph_conn, voxels, cells);
+    }
+    if (!export_path.empty()) {
+      tdt_surface opt{};
+      opt.merge = export_merge ? 1 : 0; opt.by_material = export_by_material ? 1 : 0;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      const std::vector<tdt_quad> quads = octree.extract_surface(ctx, opt, regions);
+      const int32_t *q = quads.empty() ? nullptr : &quads[0].face;
+      size_t nv = 0, nt = 0, bytes = 0;
+      if (tdt_quads_to_mesh(q, quads.size(), nullptr, 0, &nv, nullptr, nullptr, 0, &nt)) { std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1; }
+      std::vector<int32_t> vertices(3 * nv + 1);
+      std::vector<uint32_t> triangles(3 * nt + 1);
+      if (!quads.empty() && tdt_quads_to_mesh(q, quads.size(), vertices.data(), nv, &nv, triangles.data(), nullptr, nt, &nt)) {
+        std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1;
+      }
+      if (tdt_ply_mesh_write(vertices.data(), nv, triangles.data(), nt, nullptr, 0, &bytes)) { std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1; }
+      std::vector<char> text(bytes + 1);
+      if (tdt_ply_mesh_write(vertices.data(), nv, triangles.data(), nt, text.data(), bytes, &bytes)) { std::fprintf(stderr, "%s\n", tdt_host_last_error()); return 1; }
+      FILE *f = std::fopen(export_path.c_str(), "wb");
+      if (!f) { std::perror(export_path.c_str()); return 1; }
+      const bool written = std::fwrite(text.data(), 1, bytes, f) == bytes;
+      if (std::fclose(f) != 0 || !written) { std::fprintf(stderr, "%s: short write\n", export_path.c_str()); return 1; }
+      std::printf("export-mesh %s%s quads %zu vertices %zu triangles %zu\n", export_merge ? "merged" : "unmerged",
+                  export_by_material ? "" : " any-material", quads.size(), nv, nt);
     }
     if (components) {
       const std::vector<tdt_component> table = octree.components(ctx, connect, match);

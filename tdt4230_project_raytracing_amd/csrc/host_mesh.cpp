@@ -1,7 +1,10 @@
 // Host side of triangle-mesh voxelisation (include/tdt_host.h "triangle meshes"): float vertices -> the fixed-point vertices
 // tdt_voxelize_triangles takes (tdt_mesh_quantize, tdt_mesh_fit), and a minimal ASCII PLY mesh reader.  The reader is its
-// own grammar, not tdt_ply_parse's: that one restates the reference's point loader with its quirks.
+// own grammar, not tdt_ply_parse's: that one restates the reference's point loader with its quirks.  And the way back: the
+// quads of tdt_octree_extract_surface -> a welded indexed mesh (tdt_quads_to_mesh), and that mesh as ASCII PLY (tdt_ply_mesh_write).
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -226,5 +229,97 @@ int tdt_ply_mesh_info(const tdt_ply_mesh *m, int64_t *n_vertices, int64_t *n_fac
 
 const float *tdt_ply_mesh_vertices(const tdt_ply_mesh *m) { return m && !m->xyz.empty() ? m->xyz.data() : nullptr; }
 const uint32_t *tdt_ply_mesh_triangles(const tdt_ply_mesh *m) { return m && !m->tri.empty() ? m->tri.data() : nullptr; }
+
+int tdt_quads_to_mesh(const int32_t *quads, size_t n_quads, int32_t *vertices, size_t vertex_capacity, size_t *n_vertices,
+                      uint32_t *triangles, int32_t *materials, size_t triangle_capacity, size_t *n_triangles) {
+  if (!n_vertices || !n_triangles || (n_quads && !quads)) return fail("null argument");
+  *n_vertices = *n_triangles = 0;
+  if (n_quads > (size_t{1} << 30)) return fail("more than 2^30 quads");
+  constexpr int64_t kMaxVoxel = static_cast<int64_t>(kCoordMax / kUnit);
+  try {
+    // the four emitted corners of every quad as x << 42 | y << 21 | z (units <= 2^18): ascending keys = ascending (x, y, z)
+    std::vector<uint64_t> corner(4 * n_quads);
+    for (size_t q = 0; q < n_quads; q++) {
+      const int32_t *Q = quads + 8 * q;
+      const int f = Q[0];
+      if (f < 0 || f > 5) return fail("quad " + std::to_string(q) + ": face " + std::to_string(f) + " is not 0..5");
+      if (Q[5] < 1 || Q[6] < 1) return fail("quad " + std::to_string(q) + ": a size below 1");
+      const int a = f >> 1, u = (a + 1) % 3, v = (a + 2) % 3;
+      int64_t c[4][3];
+      for (int k = 0; k < 4; k++) for (int d = 0; d < 3; d++) c[k][d] = Q[2 + d];
+      c[1][u] += Q[5]; c[2][u] += Q[5]; c[2][v] += Q[6]; c[3][v] += Q[6];
+      for (int d = 0; d < 3; d++)
+        if (c[0][d] < 0 || c[2][d] > kMaxVoxel) return fail("quad " + std::to_string(q) + ": a corner outside 0..4096 voxels");
+      static const int order[2][4] = {{0, 3, 2, 1}, {0, 1, 2, 3}};
+      for (int k = 0; k < 4; k++) {
+        const int64_t *p = c[order[f & 1][k]];
+        corner[4 * q + k] = static_cast<uint64_t>(p[0] * 64) << 42 | static_cast<uint64_t>(p[1] * 64) << 21 | static_cast<uint64_t>(p[2] * 64);
+      }
+    }
+    std::vector<uint64_t> uniq(corner);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    *n_vertices = uniq.size();
+    *n_triangles = 2 * n_quads;
+    if (!vertices && !triangles && !materials) return 0;
+    if ((!vertices && *n_vertices) || (!triangles && *n_triangles)) return fail("vertices and triangles are both required to fill");
+    if (vertex_capacity < *n_vertices) return fail("capacity " + std::to_string(vertex_capacity) + " < " + std::to_string(*n_vertices) + " vertices");
+    if (triangle_capacity < *n_triangles)
+      return fail("capacity " + std::to_string(triangle_capacity) + " < " + std::to_string(*n_triangles) + " triangles");
+    for (size_t i = 0; i < uniq.size(); i++) {
+      vertices[3 * i] = static_cast<int32_t>(uniq[i] >> 42);
+      vertices[3 * i + 1] = static_cast<int32_t>((uniq[i] >> 21) & 0x1FFFFFu);
+      vertices[3 * i + 2] = static_cast<int32_t>(uniq[i] & 0x1FFFFFu);
+    }
+    for (size_t q = 0; q < n_quads; q++) {
+      uint32_t id[4];
+      for (int k = 0; k < 4; k++)
+        id[k] = static_cast<uint32_t>(std::lower_bound(uniq.begin(), uniq.end(), corner[4 * q + k]) - uniq.begin());
+      uint32_t *t = triangles + 6 * q;
+      t[0] = id[0]; t[1] = id[1]; t[2] = id[2]; t[3] = id[0]; t[4] = id[2]; t[5] = id[3];
+      if (materials) materials[2 * q] = materials[2 * q + 1] = quads[8 * q + 1];
+    }
+  } catch (const std::bad_alloc &) { return fail("out of memory"); }
+  return 0;
+}
+
+int tdt_ply_mesh_write(const int32_t *vertices, size_t n_vertices, const uint32_t *triangles, size_t n_triangles, char *buffer,
+                       size_t capacity, size_t *bytes) {
+  if (!bytes || (n_vertices && !vertices) || (n_triangles && !triangles)) return fail("null argument");
+  *bytes = 0;
+  for (size_t i = 0; i < 3 * n_vertices; i++)
+    if (vertices[i] > static_cast<int32_t>(kCoordMax) || vertices[i] < -static_cast<int32_t>(kCoordMax))
+      return fail("vertex " + std::to_string(i / 3) + ": a coordinate beyond +-2^18 units");
+  for (size_t i = 0; i < 3 * n_triangles; i++)
+    if (triangles[i] >= n_vertices)
+      return fail("triangle " + std::to_string(i / 3) + ": vertex index " + std::to_string(triangles[i]) + " >= " + std::to_string(n_vertices) + " vertices");
+  try {
+    std::string text = "ply\nformat ascii 1.0\nelement vertex " + std::to_string(n_vertices) +
+                       "\nproperty float x\nproperty float y\nproperty float z\nelement face " + std::to_string(n_triangles) +
+                       "\nproperty list uchar int vertex_indices\nend_header\n";
+    char line[96];
+    auto coord = [](char *at, int32_t units) {                // units / 64 in decimal, exact: the fraction k / 64 has six digits at most
+      const int64_t mag = units < 0 ? -static_cast<int64_t>(units) : units;
+      int n = std::sprintf(at, "%s%lld", units < 0 ? "-" : "", static_cast<long long>(mag >> 6));
+      const int frac = static_cast<int>(mag & 63) * 15625;   // (k / 64) * 10^6
+      if (frac) { n += std::sprintf(at + n, ".%06d", frac); while (at[n - 1] == '0') n--; }
+      return n;
+    };
+    for (size_t i = 0; i < n_vertices; i++) {
+      int n = 0;
+      for (int d = 0; d < 3; d++) { n += coord(line + n, vertices[3 * i + d]); line[n++] = d < 2 ? ' ' : '\n'; }
+      text.append(line, static_cast<size_t>(n));
+    }
+    for (size_t t = 0; t < n_triangles; t++) {
+      const int n = std::sprintf(line, "3 %u %u %u\n", triangles[3 * t], triangles[3 * t + 1], triangles[3 * t + 2]);
+      text.append(line, static_cast<size_t>(n));
+    }
+    *bytes = text.size();
+    if (!buffer) return 0;
+    if (capacity < text.size()) return fail("capacity " + std::to_string(capacity) + " < " + std::to_string(text.size()) + " bytes");
+    std::memcpy(buffer, text.data(), text.size());
+  } catch (const std::bad_alloc &) { return fail("out of memory"); }
+  return 0;
+}
 
 }  // extern "C"

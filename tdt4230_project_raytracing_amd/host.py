@@ -434,6 +434,43 @@ def mesh_fit(xyz, lo, hi):
     return float(scale.value), np.array(list(off), np.float64)
 
 
+def quads_to_mesh(quads):
+    """tdt_quads_to_mesh: (n, 8) int32 tdt_quad rows (rt.Context.octree_extract_surface) -> (vertices (k, 3) int32 fixed point, 64
+    units per voxel, welded and in ascending (x, y, z) order; triangles (2 n, 3) uint32, outward normals; materials (2 n,) int32,
+    the quad's material for both of its triangles)."""
+    L = lib()
+    sz = ctypes.POINTER(ctypes.c_size_t)
+    L.tdt_quads_to_mesh.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, sz, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_size_t, sz]
+    q = np.asarray(quads)
+    if q.size and q.dtype.kind not in "iu":
+        raise ValueError(f"quads must be integers, not {q.dtype}")
+    q = np.ascontiguousarray(q, np.int32).reshape(-1, 8)
+    nv, nt = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(L.tdt_quads_to_mesh(q.ctypes.data if len(q) else None, len(q), None, 0, ctypes.byref(nv), None, None, 0, ctypes.byref(nt)))
+    v, t, m = np.zeros((nv.value, 3), np.int32), np.zeros((nt.value, 3), np.uint32), np.zeros(nt.value, np.int32)
+    if len(q):
+        _check(L.tdt_quads_to_mesh(q.ctypes.data, len(q), v.ctypes.data, len(v), ctypes.byref(nv), t.ctypes.data, m.ctypes.data, len(t),
+                                   ctypes.byref(nt)))
+    return v, t, m
+
+
+def ply_mesh_write(vertices, triangles):
+    """tdt_ply_mesh_write: a fixed-point mesh ((n, 3) int32 units, (m, 3) vertex indices) as the bytes of an ASCII PLY with
+    coordinates in voxels (units / 64, exact), in the grammar PlyMesh reads."""
+    L = lib()
+    L.tdt_ply_mesh_write.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_size_t)]
+    v = np.ascontiguousarray(vertices, np.int32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    pv, pt = (v.ctypes.data if len(v) else None), (t.ctypes.data if len(t) else None)
+    n = ctypes.c_size_t(0)
+    _check(L.tdt_ply_mesh_write(pv, len(v), pt, len(t), None, 0, ctypes.byref(n)))
+    buf = ctypes.create_string_buffer(max(n.value, 1))
+    _check(L.tdt_ply_mesh_write(pv, len(v), pt, len(t), buf, n.value, ctypes.byref(n)))
+    return buf.raw[: n.value]
+
+
 class PlyMesh:
     """tdt_ply_mesh_parse of a byte buffer: vertices (n, 3) float32, triangles (m, 3) uint32 (polygons fan-triangulated),
     faces = the file's polygon count.  Colours are ignored.  Raises ValueError with the reader's message."""

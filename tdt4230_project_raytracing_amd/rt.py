@@ -145,6 +145,23 @@ assert ctypes.sizeof(Fill) == 8
 assert Fill.connectivity.offset == 0 and Fill.material.offset == 4
 
 
+# surface extraction (include/tdt_rt.h): struct tdt_surface, struct tdt_quad
+class Surface(ctypes.Structure):
+    """struct tdt_surface: merge 0 / 1 (one quad per exposed face / runs, then stacks of identical runs), by_material 0 / 1 (faces
+    carry 0 / material + 1)."""
+    _fields_ = [("merge", ctypes.c_int32), ("by_material", ctypes.c_int32)]
+
+
+class Quad(ctypes.Structure):
+    """struct tdt_quad: face 0..5 (-x, +x, -y, +y, -z, +z), material + 1 (or 0), the minimum corner in lattice coordinates, the
+    extent along u = (a + 1) % 3 and v = (a + 2) % 3."""
+    _fields_ = [("face", ctypes.c_int32), ("material", ctypes.c_int32), ("origin", ctypes.c_int32 * 3), ("size", ctypes.c_int32 * 2),
+                ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Surface) == 8 and ctypes.sizeof(Quad) == 32
+
+
 def _exact_ints(a, dtype, name):
     """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
     src = np.asarray(a)
@@ -254,6 +271,7 @@ SYMBOLS = [
     ("tdt_voxelize_triangles_solid", _I, [_P, ctypes.POINTER(Mesh), _I, ctypes.POINTER(Fill), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_edit_triangles_solid", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(Fill), ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_debug_fill_passes", _I, [_P]),
+    ("tdt_octree_extract_surface", _I, [_P, ctypes.POINTER(Surface), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -618,6 +636,30 @@ class Context:
         self._check_edit(lib().tdt_octree_edit_triangles_solid(self.h, int(op), ctypes.byref(mesh), ctypes.byref(f), ctypes.byref(n)), n)
         del keep
         return int(n.value)
+
+    @staticmethod
+    def _surface(merge, by_material):
+        """struct tdt_surface; both fields must fit an int32 (ctypes would wrap them silently); True / False are 1 / 0.  The ranges
+        themselves are the library's to check."""
+        for name, v in (("merge", merge), ("by_material", by_material)):
+            if int(v) != v or not -2**31 <= int(v) <= 2**31 - 1:
+                raise ValueError(f"{name} must be an int32, not {v!r}")
+        return Surface(int(merge), int(by_material))
+
+    def octree_extract_surface(self, merge=True, by_material=True, regions=None):
+        """tdt_octree_extract_surface: the exposed faces of the bound tree's voxels as an (n, 8) int32 array of tdt_quad rows {face,
+        material, origin[3], size[2], pad}, ordered by face, w, u0, v0; merge: runs, then stacks of identical runs (False: one
+        1 x 1 quad per face); by_material: faces carry material + 1 and merge within a material only (False: they carry 0);
+        regions (one Region or a list) limit the voxels whose faces are reported (None: no mask; an empty list: an empty mask).
+        The tree is untouched.  Counts first, fills second: two extractions."""
+        s = self._surface(merge, by_material)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_surface(self.h, ctypes.byref(s), arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 8), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_surface(self.h, ctypes.byref(s), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
 
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
