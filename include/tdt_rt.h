@@ -642,7 +642,10 @@ int tdt_debug_pixel_log(tdt_ctx *ctx, uint32_t *out, size_t n_u32);
  * Mode 17 reads the cells buffer and octree uniforms bound to ctx (max_depth 5 or 6, a tree the whole-depth table serves;
  * TDT_ERR_INVALID_OPERATION otherwise): for every one of the 8^max_depth table positions, what a traversal step decodes from
  * the table's entry (cell corner, cell size, value, LEAF or not) must equal, bit for bit, what the 16-bit entry's decode computes
- * from the position and what the level walk over the packed node table ends on. */
+ * from the position and what the level walk over the packed node table ends on.
+ * Mode 18, on the same bound tree: the table in its plane form (entries that carry three byte offsets into a per-block table of
+ * padded slab planes).  For every position the six planes fetched through the entry's offsets must equal, bit for bit, the planes
+ * the arithmetic form computes from the 16-bit entry, the bound octree corner and scale. */
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches);
 /* A cell_count that is not a power of two (the reference's own: 100000, main.rs:459) takes treeLookup's x index
  * (raytracer.comp:376-378) through two per-cell thresholds on the level's coordinate instead of the float formula (csrc/

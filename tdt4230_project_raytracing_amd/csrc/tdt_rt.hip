@@ -143,6 +143,10 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   // sentinel: the rest of a partial last cell and one more cell (RESIDENT: all EMPTY, see tree_lookup_pow2), or the escape code
   if (threadIdx.x < 16 && P.lds_nodes + threadIdx.x < ((P.lds_nodes + 7u) & ~7u) + 8u)
     s_nodes[P.lds_nodes + threadIdx.x] = (uint16_t)((RESIDENT && POW2) ? 0u : kPackedEscape);
+  // FULL builds, plane form: the padded slab planes of every cell a step can meet (PlaneTable) — a function of the kernel arguments alone
+  constexpr bool kPlanes = FULL && !COUNT && kFullEntryForm == kFullPlanes;
+  __shared__ __attribute__((aligned(8))) float2 s_planes[kPlanes ? PlaneTable::kEntries : 1];
+  if constexpr (kPlanes) build_plane_table<DEPTH, UNIT>(s_planes, P.scale, P.min_x, P.min_y, P.min_z);
   __syncthreads();
   constexpr bool TABLE = FORM == FORM_TABLE;
   static_assert(!TABLE || (SAFEV && !BRICK && !FULL), "per-cell thresholds: the resident walk, or the jump table's bands of a tree outside the LDS table");
@@ -171,6 +175,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   ns.grid_band = FULL ? Grid<5>::kBand : (ns.grid_ok ? (TABLE && kUseGrid ? __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)s_band)) : Grid<GL>::kBand) : 2.0f);
   ns.thr = s_thr; ns.thr_f0max = P.thr_f0max;
   ns.full = P.full_grid;
+  if constexpr (kPlanes) ns.planes = s_planes;
   ns.grid32 = s_grid32; ns.bricks = P.bricks;
   if (BRICK) {
     // the bricks' base address in a VGPR pair: as a scalar pair it was the one value the compiler spilled to a VGPR lane and read back
@@ -260,6 +265,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   float vmin_x, vmin_y, vmin_z;
   if (DEPTH == 0) { vmin_x = P.min_x; vmin_y = P.min_y; vmin_z = P.min_z; }      // (the general kernel has no register to spare)
   else asm volatile("v_mov_b32 %0, %3\n\tv_mov_b32 %1, %4\n\tv_mov_b32 %2, %5" : "=v"(vmin_x), "=v"(vmin_y), "=v"(vmin_z) : "s"(P.min_x), "s"(P.min_y), "s"(P.min_z));
+  if constexpr (kPlanes) { ns.vmin_x = vmin_x; ns.vmin_y = vmin_y; ns.vmin_z = vmin_z; }      // (the walk's planes: see tree_lookup_pow2)
   // The lanes in ST_TRAVERSE and in an event state as wave masks, carried from pass to pass: a traversal step only moves lanes out of
   // the first set into the second, so the masks after the step are mask algebra on the step's own conditions — no compare of `state`
   // in a pass that runs no event code (each v_cmp is a half-rate instruction, and the pass is bound by those: tools/micro/pipe_model.hip).
@@ -313,22 +319,32 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
         float ugx, ugy, ugz; uint32_t value;
         if (COUNT) cnt.iterations++;
         const float ipd_in = inv_pow_depth;          // (kStuckCut)
-        const bool leaf = POW2 ? tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt)
-                               : tree_lookup<COUNT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, cnt);
+        CellPlanes cp;
+        bool leaf;
+        if constexpr (kPlanes) leaf = tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE, UNIT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt, &cp);
+        else leaf = POW2 ? tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt)
+                         : tree_lookup<COUNT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, cnt);
         TDT_MARK(traversal_b);
-        if (!kSlim2) lane_work += kCostStep + (127u - (__float_as_uint(inv_pow_depth) >> 23));   // + tree levels visited (inv_pow_depth = 2^-levels)
-        const float bx = (UNIT ? ugx : ugx * P.scale) + vmin_x, by = (UNIT ? ugy : ugy * P.scale) + vmin_y, bz = (UNIT ? ugz : ugz * P.scale) + vmin_z;
-        const float cs0 = UNIT ? inv_pow_depth : P.scale * inv_pow_depth;
-        // leaf: the exact cell (rc:427-428); empty: padded by -1e-5 / +2e-5 (rc:441-442)
-        // (x + -0.0f is x, bit for bit, for every x: one select on the pad instead of one per coordinate)
-        const float pad = leaf ? -0.0f : -0.00001f;
-        // (kSlim2: the cell's corner and what it holds straight into the registers a hit carries to the event code: they mean nothing while a
-        // lane traverses, so every lane in the octree writes them — no copies in the leaf branch)
-        if (kSlim2) { leaf_box_x = bx + pad; leaf_box_y = by + pad; leaf_box_z = bz + pad; hit_index = value; }
-        const float cx = kSlim2 ? leaf_box_x : bx + pad, cy = kSlim2 ? leaf_box_y : by + pad, cz = kSlim2 ? leaf_box_z : bz + pad;
-        const float cs = leaf ? cs0 : cs0 + 0.00002f;
-        float t_enter, t_exit;
-        cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, t_enter, t_exit);
+        float t_enter, t_exit, cs, cx = 0.f, cy = 0.f, cz = 0.f;      // (cx, cy, cz: the builds that copy the corner in the leaf branch)
+        if constexpr (kPlanes) {
+          // the cell's planes as the table (or the walk) hands them over: nothing of the corner is computed here
+          leaf_box_x = cp.lox; leaf_box_y = cp.loy; leaf_box_z = cp.loz; hit_index = value;
+          cube_slabs_planes(r, ix, iy, iz, cp.lox, cp.loy, cp.loz, cp.hix, cp.hiy, cp.hiz, t_stride, t_octree_max, t_enter, t_exit);
+          cs = UNIT ? inv_pow_depth : P.scale * inv_pow_depth;      // (used by a LEAF alone: its size, rc:427)
+        } else {
+          if (!kSlim2) lane_work += kCostStep + (127u - (__float_as_uint(inv_pow_depth) >> 23));   // + tree levels visited (inv_pow_depth = 2^-levels)
+          const float bx = (UNIT ? ugx : ugx * P.scale) + vmin_x, by = (UNIT ? ugy : ugy * P.scale) + vmin_y, bz = (UNIT ? ugz : ugz * P.scale) + vmin_z;
+          const float cs0 = UNIT ? inv_pow_depth : P.scale * inv_pow_depth;
+          // leaf: the exact cell (rc:427-428); empty: padded by -1e-5 / +2e-5 (rc:441-442)
+          // (x + -0.0f is x, bit for bit, for every x: one select on the pad instead of one per coordinate)
+          const float pad = leaf ? -0.0f : -0.00001f;
+          // (kSlim2: the cell's corner and what it holds straight into the registers a hit carries to the event code: they mean nothing while a
+          // lane traverses, so every lane in the octree writes them — no copies in the leaf branch)
+          if (kSlim2) { leaf_box_x = bx + pad; leaf_box_y = by + pad; leaf_box_z = bz + pad; hit_index = value; }
+          cx = kSlim2 ? leaf_box_x : bx + pad; cy = kSlim2 ? leaf_box_y : by + pad; cz = kSlim2 ? leaf_box_z : bz + pad;
+          cs = leaf ? cs0 : cs0 + 0.00002f;
+          cube_slabs(r, ix, iy, iz, cx, cy, cz, cs, t_stride, t_octree_max, t_enter, t_exit);
+        }
         const bool cube_ok = !(t_exit < t_enter);
         if (leaf) {
           // CubeHit's record (rc:336-354) is deferred to the event code, where the lanes that hit
@@ -823,6 +839,8 @@ __global__ __launch_bounds__(256) void selftest_index_kernel(float inv_cell_coun
 // value a traversal step uses; a PARENT can only be what the last level holds).  Entries of 32 / 64 bits carry, above meta16, the upper
 // fp32 halves of the corner (digit >> (depth - levels)) * 2^-levels of the cell the descent ends in: x alone, or x in w0 and y, z in w1
 // (full_entry_encode).  8^depth entries: 256 KB (depth 5) / 2 MB (depth 6) at 64 bits, 128 KB / 1 MB at 32, 64 KB / 512 KB at 16.
+// The plane form (BITS = kFullPlanes, the product's): the same 64 bits with, in place of the three corner halves, the byte offsets of
+// the cell's (lo, hi) slab planes in the block's plane table (PlaneTable) — the kernel knows level, digits and LEAF or not.
 // *bad is raised when the tree does not fit the claim the table rests on (a PARENT of a level that feeds a later x decision at or
 // above grid_v_bound), a material index does not fit 11 bits, or a corner component has a bit set in the lower half of its fp32
 // (none can for depth <= 6: six significand bits; checked, not argued).
@@ -857,7 +875,7 @@ template <int DEPTH>
 __device__ __forceinline__ uint32_t full_grid_check(uint32_t e, const FullGridEntry *grid, const uint16_t *grid16, const uint16_t *packed, uint32_t lds_nodes) {
   const uint32_t xg = e >> (2 * DEPTH), yg = (e >> DEPTH) & ((1u << DEPTH) - 1u), zg = e & ((1u << DEPTH) - 1u);
   float ax, ay, az, ai, bx, by, bz, bi; uint32_t av, bv;
-  const bool al = full_entry_decode<kFullEntryBits, DEPTH>(grid[e], xg, yg, zg, ax, ay, az, ai, av);
+  const bool al = full_entry_decode<kFullEntryForm, DEPTH>(grid[e], xg, yg, zg, ax, ay, az, ai, av);
   const bool bl = full_entry_decode<16, DEPTH>(grid16[e], xg, yg, zg, bx, by, bz, bi, bv);
   uint32_t bad = (__float_as_uint(ax) != __float_as_uint(bx) || __float_as_uint(ay) != __float_as_uint(by) || __float_as_uint(az) != __float_as_uint(bz) ||
                   __float_as_uint(ai) != __float_as_uint(bi) || av != bv || al != bl) ? 1u : 0u;
@@ -881,6 +899,43 @@ __global__ __launch_bounds__(256) void selftest_full_grid_kernel(int depth, cons
   const uint32_t e = blockIdx.x * 256u + threadIdx.x;
   unsigned long long bad = 0;
   if (e < (1u << (3 * depth))) bad = depth == 5 ? full_grid_check<5>(e, grid, grid16, packed, lds_nodes) : full_grid_check<6>(e, grid, grid16, packed, lds_nodes);
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor((long long)bad, o, 64);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
+}
+
+// tdt_selftest 18: every position of the whole-depth table in its plane form (FullEntry<kFullPlanes>).  The slab planes a step fetches
+// from the block's plane table through the entry's three offsets must be, bit for bit, the planes the arithmetic form computes from
+// the 16-bit entry of the same position: corner from the digits, + the octree's corner, the EMPTY cell's pad, + the size — the
+// expressions of the corner form's step, written out here.  Offsets outside the table or off an 8-byte boundary count as mismatches
+// (and are not read through).
+template <int DEPTH, bool UNIT>
+__global__ __launch_bounds__(256) void selftest_plane_table_kernel(const FullGridEntry64 *__restrict__ grid, const uint16_t *__restrict__ grid16, float scale,
+                                                                  float min_x, float min_y, float min_z, unsigned long long *mismatches) {
+  __shared__ __attribute__((aligned(8))) float2 s_planes[PlaneTable::kEntries];
+  build_plane_table<DEPTH, UNIT>(s_planes, scale, min_x, min_y, min_z);
+  __syncthreads();
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long bad = 0;
+  if (e < (1u << (3 * DEPTH))) {
+    const uint32_t xg = e >> (2 * DEPTH), yg = (e >> DEPTH) & ((1u << DEPTH) - 1u), zg = e & ((1u << DEPTH) - 1u);
+    const FullGridEntry64 g = grid[e];
+    const uint32_t ox = g.w0 >> 16, oy = g.w1 >> 16, oz = g.w1 & 0xFFFFu, kBytes = PlaneTable::kEntries * 8u;
+    if (((ox | oy | oz) & 7u) != 0u || ox >= kBytes || oy >= kBytes || oz >= kBytes) bad = 1;
+    else {
+      CellPlanes cp; float ai, ux, uy, uz, ipd; uint32_t av, value;
+      const bool al = full_entry_planes<DEPTH>(g, s_planes, cp, ai, av);
+      const bool leaf = full_entry_decode<16, DEPTH>(grid16[e], xg, yg, zg, ux, uy, uz, ipd, value);
+      const float bx = (UNIT ? ux : ux * scale) + min_x, by = (UNIT ? uy : uy * scale) + min_y, bz = (UNIT ? uz : uz * scale) + min_z;
+      const float cs0 = UNIT ? ipd : scale * ipd;
+      const float pad = leaf ? -0.0f : -0.00001f;
+      const float cx = bx + pad, cy = by + pad, cz = bz + pad;
+      const float cs = leaf ? cs0 : cs0 + 0.00002f;
+      const float hx = cx + cs, hy = cy + cs, hz = cz + cs;
+      bad = (__float_as_uint(cp.lox) != __float_as_uint(cx) || __float_as_uint(cp.loy) != __float_as_uint(cy) || __float_as_uint(cp.loz) != __float_as_uint(cz) ||
+             __float_as_uint(cp.hix) != __float_as_uint(hx) || __float_as_uint(cp.hiy) != __float_as_uint(hy) || __float_as_uint(cp.hiz) != __float_as_uint(hz) ||
+             __float_as_uint(ai) != __float_as_uint(ipd) || al != leaf || (leaf && av != value)) ? 1u : 0u;
+    }
+  }
   for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor((long long)bad, o, 64);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
 }
@@ -1794,7 +1849,7 @@ int prepare_full_grid(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) 
     if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + 2));      // 8^6 entries and the `bad` word behind them
     uint32_t *bad = reinterpret_cast<uint32_t *>(T.full_grid + ((size_t)1 << 18));
     TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryBits>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
+    hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
     TDT_HIP(ctx, hipGetLastError());
     uint32_t flag = 1;
     TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
@@ -2498,8 +2553,9 @@ int tdt_debug_wave_ends(tdt_ctx *ctx, uint64_t *out, int n) {
 
 /* Exhaustive self-test of the kernels' short correctly-rounded rcp / sqrt / rsq forms against the
  * IEEE expressions on all 2^32 inputs; *mismatches must come back 0 (which: 0 rcp, 1 sqrt, 2 rsq). */
-// tdt_selftest 17 (selftest_full_grid_kernel) on the cells buffer bound to ctx: the tree must be one the whole-depth table serves
-static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
+// tdt_selftest 17 (selftest_full_grid_kernel) and 18 (selftest_plane_table_kernel: the table in its plane form, whatever form the
+// product was built with) on the cells buffer bound to ctx: the tree must be one the whole-depth table serves
+static int selftest_full_grid(tdt_ctx *front, int which, uint64_t *mismatches) {
   tdt_ctx *ctx = front->multi ? tdt::multi_first_member(front) : front;
   TDT_HIP(front, hipSetDevice(ctx->device));
   TraceParams P;
@@ -2514,10 +2570,11 @@ static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
   const uint32_t staged = buf_nodes < tdt::kLdsCells * 8u ? (buf_nodes & ~7u) : tdt::kLdsCells * 8u;
   const size_t entries = (size_t)1 << (3 * P.max_depth);
   tdt::DeviceScratch mem;
-  FullGridEntry *grid = mem.get<FullGridEntry>(entries);
+  FullGridEntry *grid = which == 17 ? mem.get<FullGridEntry>(entries) : nullptr;
+  FullGridEntry64 *grid_planes = which == 18 ? mem.get<FullGridEntry64>(entries) : nullptr;
   uint16_t *grid16 = mem.get<uint16_t>(entries), *packed = mem.get<uint16_t>((size_t)tdt::kLdsCells * 8);
   unsigned long long *words = mem.get<unsigned long long>(4);                // mismatches; bad (two builds); scan results
-  if (!grid || !grid16 || !packed || !words) return tdt::hip_fail(front, hipErrorOutOfMemory, "tdt_selftest 17");
+  if ((!grid && !grid_planes) || !grid16 || !packed || !words) return tdt::hip_fail(front, hipErrorOutOfMemory, "tdt_selftest 17");
   uint32_t *bad = reinterpret_cast<uint32_t *>(words + 1), *scan = reinterpret_cast<uint32_t *>(words + 2);
   TDT_HIP(front, hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), ctx->stream));
   if (staged) hipLaunchKernelGGL(tdt::pack_cells_kernel, dim3((staged + 255) / 256), dim3(256), 0, ctx->stream, cells, cells_dwords, packed, staged);
@@ -2526,7 +2583,8 @@ static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
     hipLaunchKernelGGL(tdt::scan_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, cells, buf_nodes, scan);
   }
   const dim3 blocks((unsigned)((entries + 255) / 256));
-  hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryBits>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid, bad);
+  if (which == 17) hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid, bad);
+  else hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullPlanes>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid_planes, bad);
   hipLaunchKernelGGL(tdt::build_full_grid_kernel<16>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid16, bad + 1);
   TDT_HIP(front, hipGetLastError());
   uint32_t res[4] = {0, 0, 0, 0}, flags[2] = {1, 1};
@@ -2537,7 +2595,14 @@ static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
   const bool served = buf_nodes > 0 && res[2] <= staged && res[1] <= tdt::kPackedMaxValue && res[0] < (1u << 22) && flags[0] == 0 && flags[1] == 0;
   if (!served) return tdt::fail(front, TDT_ERR_INVALID_OPERATION, "tdt_selftest 17: the bound tree is not one the whole-depth table serves");
   const uint32_t lds_nodes = (res[2] + 7u) & ~7u;                            // the live cells alone are staged (classify_tree)
-  hipLaunchKernelGGL(tdt::selftest_full_grid_kernel, blocks, dim3(256), 0, ctx->stream, P.max_depth, grid, grid16, packed, lds_nodes, words);
+  if (which == 17) hipLaunchKernelGGL(tdt::selftest_full_grid_kernel, blocks, dim3(256), 0, ctx->stream, P.max_depth, grid, grid16, packed, lds_nodes, words);
+  else {
+    // the step's own choice between the UNIT and the multiplying build (launch_trace)
+    const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f;
+    auto kernel = P.max_depth == 5 ? (unit ? tdt::selftest_plane_table_kernel<5, true> : tdt::selftest_plane_table_kernel<5, false>)
+                                   : (unit ? tdt::selftest_plane_table_kernel<6, true> : tdt::selftest_plane_table_kernel<6, false>);
+    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, ctx->stream, grid_planes, grid16, P.scale, P.min_x, P.min_y, P.min_z, words);
+  }
   TDT_HIP(front, hipGetLastError());
   TDT_HIP(front, hipMemcpyAsync(mismatches, words, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   TDT_HIP(front, hipStreamSynchronize(ctx->stream));
@@ -2545,8 +2610,8 @@ static int selftest_full_grid(tdt_ctx *front, uint64_t *mismatches) {
 }
 
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches) {
-  if (!ctx || !mismatches || which < 0 || which > 17) return TDT_ERR_INVALID_VALUE;
-  if (which == 17) return selftest_full_grid(ctx, mismatches);
+  if (!ctx || !mismatches || which < 0 || which > 18) return TDT_ERR_INVALID_VALUE;
+  if (which == 17 || which == 18) return selftest_full_grid(ctx, which, mismatches);
   TDT_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->counters) TDT_HIP(ctx, hipMalloc((void **)&ctx->counters, (32 + 16384 + 256) * sizeof(unsigned long long)));
   TDT_HIP(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));

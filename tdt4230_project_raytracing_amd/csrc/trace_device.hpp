@@ -196,6 +196,7 @@ struct NodeSource {
   const void *grid;                                   // top-level jump table (Grid<GL>::Entry[], see build_top_grid), or unusable when !grid_ok
   bool grid_ok; float grid_band;                      // grid_band = kGridBand, or 2 when the table is unusable
   const FullGridEntry *full;                          // FULL builds: the whole-depth table in global memory (see tree_lookup_pow2)
+  const float2 *planes; float vmin_x, vmin_y, vmin_z; // FULL builds, plane form: the block's plane table (LDS, see PlaneTable) and the octree's corner it was filled with
   const uint32_t *grid32; const void *bricks;         // BRICK builds: the 5-level table with brick headers (LDS) and the bricks (global memory, 16-bit entries)
   const float2 *thr; float thr_f0max;                 // FORM_TABLE builds: (F1, F2) per cell (LDS) and the scene-wide bound on F0, see x_thresholds
   __amdgpu_buffer_rsrc_t cells;                       // raw buffer over the cells payload (8-byte granules)
@@ -306,6 +307,20 @@ TDT_DEV void cube_slabs(const Ray &r, float ix, float iy, float iz, float cx, fl
   asm("v_min_f32 %0, %1, %2" : "=v"(x1) : "v"(t_max), "v"(mxx));
   asm("v_min3_f32 %0, %1, %2, %3" : "=v"(x3) : "v"(x1), "v"(mxy), "v"(mxz));
   t_enter = e3; t_exit = x3;      // = hw_max(hw_max(hw_max(t_min, mnx), mny), mnz), hw_min(hw_min(hw_min(t_max, mxx), mxy), mxz)
+}
+// the same test from the planes themselves (the plane form of the FULL builds): c = cube_position, h = cube_position + size
+TDT_DEV void cube_slabs_planes(const Ray &r, float ix, float iy, float iz, float cx, float cy, float cz, float hx, float hy, float hz,
+                               float t_min, float t_max, float &t_enter, float &t_exit) {
+  float lx = (cx + -r.ox) * ix, ly = (cy + -r.oy) * iy, lz = (cz + -r.oz) * iz;
+  float ux = (hx + -r.ox) * ix, uy = (hy + -r.oy) * iy, uz = (hz + -r.oz) * iz;
+  float mnx = hw_min(lx, ux), mny = hw_min(ly, uy), mnz = hw_min(lz, uz);
+  float mxx = hw_max(lx, ux), mxy = hw_max(ly, uy), mxz = hw_max(lz, uz);
+  float e1, e3, x1, x3;                               // (see cube_slabs)
+  asm("v_max_f32 %0, %1, %2" : "=v"(e1) : "v"(t_min), "v"(mnx));
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(e3) : "v"(e1), "v"(mny), "v"(mnz));
+  asm("v_min_f32 %0, %1, %2" : "=v"(x1) : "v"(t_max), "v"(mxx));
+  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(x3) : "v"(x1), "v"(mxy), "v"(mxz));
+  t_enter = e3; t_exit = x3;
 }
 
 // treeLookup rc:359-394: one dependent 8-byte Node load per level
@@ -554,17 +569,67 @@ TDT_DEV int brick_band_exp(int l, uint32_t v) { return (v == 0u ? -40 : (31 - (i
 // fl(v + f) - v for any integer v in [2^e, 2^(e+1)), e <= 21
 TDT_DEV float brick_q(uint32_t e, float f) { const float V = __uint_as_float((127u + e) << 23); return (V + f) - V; }
 constexpr int kFullEntryBits = TDT_FULL_ENTRY_BITS;
+// The plane form of the 64-bit entry (TDT_FULL_ENTRY_PLANES; FullEntry<kFullPlanes>).  What a step does with the corner depends on the
+// cell alone: add the octree's corner, pad an EMPTY cell by -1e-5 / +2e-5 (rc:441-442), add the size — the lower and upper slab plane of
+// each axis.  A tree of depth D has 2^(D+1) - 2 cells per axis (2^m at level m), each of a LEAF and an EMPTY kind: at most 252 (lo, hi)
+// pairs per axis, 6 KB for the three, which every block computes once into LDS with the step's own expressions (slab_planes), so a
+// step fetches them with three ds_read_b64 at the byte offsets the entry carries in place of the corner halves:
+// w0 = off_x << 16 | meta16, w1 = off_y << 16 | off_z.
+constexpr int kFullPlanes = 65;
+constexpr int kFullEntryForm = TDT_FULL_ENTRY_PLANES ? kFullPlanes : kFullEntryBits;
 template <int BITS> struct FullEntry;
 template <> struct FullEntry<16> { typedef uint16_t Type; };
 template <> struct FullEntry<32> { typedef uint32_t Type; };
 template <> struct FullEntry<64> { typedef FullGridEntry64 Type; };
-static_assert(sizeof(FullEntry<kFullEntryBits>::Type) == sizeof(FullGridEntry) && sizeof(FullGridEntry) * 8 == kFullEntryBits, "the table's entry type");
+template <> struct FullEntry<kFullPlanes> { typedef FullGridEntry64 Type; };
+static_assert(sizeof(FullEntry<kFullEntryForm>::Type) == sizeof(FullGridEntry) && sizeof(FullGridEntry) * 8 == kFullEntryBits, "the table's entry type");
+struct PlaneTable {
+  static constexpr uint32_t kCells = 126u;                      // per axis and kind: levels 1..6 (a depth-5 tree fills the first 62)
+  static constexpr uint32_t kPerAxis = 2u * kCells, kEntries = 3u * kPerAxis;
+  // axis a, kind f (1: LEAF), level m >= 1, cell k < 2^m
+  static TDT_DEV uint32_t index(uint32_t a, uint32_t f, uint32_t m, uint32_t k) { return a * kPerAxis + f * kCells + ((1u << m) - 2u) + k; }
+  static TDT_DEV void cell(uint32_t i, uint32_t &a, uint32_t &f, uint32_t &m, uint32_t &k) {
+    a = i / kPerAxis; const uint32_t j = i - a * kPerAxis;
+    f = j >= kCells ? 1u : 0u; const uint32_t c = j - f * kCells + 2u;
+    m = 31u - (uint32_t)__builtin_clz(c); k = c - (1u << m);
+  }
+};
+// One axis of a cell as the slab test meets it: ug = k 2^-levels (treeLookup's grid position), ipd = 2^-levels.  The operations of
+// rc:427-428 / rc:441-442 and of CubeHit's  cube_position + size  (rc:320), in the step's order.
+template <bool UNIT>
+TDT_DEV float2 slab_planes(float ug, float ipd, bool leaf, float scale, float vmin) {
+  const float b = (UNIT ? ug : ug * scale) + vmin;
+  const float lo = b + (leaf ? -0.0f : -0.00001f);     // (x + -0.0f is x, bit for bit, for every x)
+  const float cs0 = UNIT ? ipd : scale * ipd;
+  const float cs = leaf ? cs0 : cs0 + 0.00002f;
+  return make_float2(lo, lo + cs);
+}
+// the table of a depth-DEPTH tree, by the threads of a block (the caller synchronises)
+template <int DEPTH, bool UNIT>
+TDT_DEV void build_plane_table(float2 *t, float scale, float min_x, float min_y, float min_z) {
+  static_assert(DEPTH >= 1 && DEPTH <= 6, "PlaneTable::kCells");
+  for (uint32_t i = threadIdx.x; i < PlaneTable::kEntries; i += blockDim.x) {
+    uint32_t a, f, m, k;
+    PlaneTable::cell(i, a, f, m, k);
+    if (m > (uint32_t)DEPTH) continue;
+    const float ipd = __uint_as_float((127u - m) << 23);
+    t[i] = slab_planes<UNIT>((float)k * ipd, ipd, f != 0u, scale, a == 0u ? min_x : (a == 1u ? min_y : min_z));
+  }
+}
+// what a step hands the slab test (the corner lo is also what a hit carries to CubeHit's record)
+struct CellPlanes { float lox, loy, loz, hix, hiy, hiz; };
 // meta16 = (depth - levels) << 2 | code | value << 5 and the corner (digit >> (depth - levels)) * 2^-levels of the cell the descent
 // from position (xg, yg, zg) ends in, as an entry; false when a corner component does not fit the upper half of its fp32
 template <int BITS>
 TDT_DEV bool full_entry_encode(uint32_t meta16, int depth, uint32_t xg, uint32_t yg, uint32_t zg, typename FullEntry<BITS>::Type &e) {
   if constexpr (BITS == 16) { e = (uint16_t)meta16; return true; }
-  else {
+  else if constexpr (BITS == kFullPlanes) {
+    const uint32_t sh = (meta16 >> 2) & 7u, m = (uint32_t)depth - sh, f = (meta16 & 3u) == 2u ? 1u : 0u;
+    if (depth > 6 || m < 1u) { e.w0 = meta16; e.w1 = 0u; return false; }
+    e.w0 = (PlaneTable::index(0u, f, m, xg >> sh) << 19) | meta16;       // (<< 3: bytes; all three below 2^16)
+    e.w1 = (PlaneTable::index(1u, f, m, yg >> sh) << 19) | (PlaneTable::index(2u, f, m, zg >> sh) << 3);
+    return true;
+  } else {
     const uint32_t sh = (meta16 >> 2) & 7u;
     const float ipd = __uint_as_float(((127u - (uint32_t)depth) << 23) + (sh << 23));        // 2^-levels, as the step computes it
     const uint32_t cx = __float_as_uint((float)(xg >> sh) * ipd), cy = __float_as_uint((float)(yg >> sh) * ipd), cz = __float_as_uint((float)(zg >> sh) * ipd);
@@ -576,9 +641,23 @@ TDT_DEV bool full_entry_encode(uint32_t meta16, int depth, uint32_t xg, uint32_t
 template <int BITS, int DEPTH>
 TDT_DEV bool full_entry_decode(const typename FullEntry<BITS>::Type &g, uint32_t xg, uint32_t Yi, uint32_t Zi, float &gx, float &gy, float &gz, float &ipd, uint32_t &value) {
   uint32_t meta;
-  if constexpr (BITS == 64) meta = g.w0; else meta = g;
+  if constexpr (BITS == 64 || BITS == kFullPlanes) meta = g.w0; else meta = g;
   const uint32_t sh = (meta >> 2) & 7u;                                   // DEPTH - levels (build_full_grid_kernel stores it that way: one subtraction less per step)
   ipd = __uint_as_float(((127u - (uint32_t)DEPTH) << 23) + (sh << 23));   // 2^-levels
+  if constexpr (BITS == kFullPlanes) {
+    // (not what a step does — that is full_entry_planes: the self-test's reading of the offsets.  The cell each of them names must be of
+    // this axis, of the entry's level and kind; its corner is then k 2^-levels.  Anything else comes back as a NaN corner.)
+    const uint32_t off[3] = {g.w0 >> 16, g.w1 >> 16, g.w1 & 0xFFFFu};
+    float c[3];
+    for (uint32_t a = 0; a < 3u; a++) {
+      uint32_t ta, tf, tm, tk;
+      PlaneTable::cell(off[a] >> 3, ta, tf, tm, tk);
+      const bool ok = (off[a] & 7u) == 0u && (off[a] >> 3) < PlaneTable::kEntries && ta == a && tm == (uint32_t)DEPTH - sh && tf == ((meta & 3u) == 2u ? 1u : 0u);
+      c[a] = ok ? (float)tk * ipd : __builtin_nanf("");
+    }
+    gx = c[0]; gy = c[1]; gz = c[2];
+    value = (meta >> 5) & 0x7FFu;
+  } else
   if constexpr (BITS == 16) {
     gx = (float)(xg >> sh) * ipd; gy = (float)(Yi >> sh) * ipd; gz = (float)(Zi >> sh) * ipd;
     value = meta >> 5;
@@ -593,10 +672,26 @@ TDT_DEV bool full_entry_decode(const typename FullEntry<BITS>::Type &g, uint32_t
   }
   return (meta & 3u) == 2u;
 }
-template <bool COUNT, int CL, int DEPTH, bool RESIDENT, bool SAFEV, bool FULL = false, bool BRICK = false, bool TABLE = false>
+// the plane form's step: the cell's slab planes from the block's plane table, its size and a LEAF's value from meta16; true for a LEAF
+template <int DEPTH>
+TDT_DEV bool full_entry_planes(const FullGridEntry64 &g, const float2 *planes, CellPlanes &cp, float &ipd, uint32_t &value) {
+  const char *base = reinterpret_cast<const char *>(planes);
+  const float2 px = *reinterpret_cast<const float2 *>(base + (g.w0 >> 16));
+  const float2 py = *reinterpret_cast<const float2 *>(base + (g.w1 >> 16));
+  const float2 pz = *reinterpret_cast<const float2 *>(base + (g.w1 & 0xFFFFu));
+  cp.lox = px.x; cp.hix = px.y; cp.loy = py.x; cp.hiy = py.y; cp.loz = pz.x; cp.hiz = pz.y;
+  const uint32_t sh = (g.w0 >> 2) & 7u;
+  ipd = __uint_as_float(((127u - (uint32_t)DEPTH) << 23) + (sh << 23));   // 2^-levels
+  value = (g.w0 >> 5) & 0x7FFu;
+  return (g.w0 & 3u) == 2u;
+}
+// UNIT and cp: the plane form of the FULL builds (cp != nullptr there and nowhere else) — *cp gets the cell's planes, from the table or,
+// behind the walk, from slab_planes; gx, gy, gz are then not written
+template <bool COUNT, int CL, int DEPTH, bool RESIDENT, bool SAFEV, bool FULL = false, bool BRICK = false, bool TABLE = false, bool UNIT = false>
 TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float fx, float fy, float fz, float &inv_pow_depth,
-                              float &gx, float &gy, float &gz, uint32_t &value, NodeMemo<CL> &memo, Counters &cnt) {
+                              float &gx, float &gy, float &gz, uint32_t &value, NodeMemo<CL> &memo, Counters &cnt, CellPlanes *cp = nullptr) {
   static_assert(!TABLE || (SAFEV && !BRICK && !FULL), "per-cell thresholds: the resident walk, or (trees outside the LDS table) the jump table's bands only");
+  constexpr bool PLANES = FULL && !COUNT && kFullEntryForm == kFullPlanes;
   const int depth = DEPTH > 0 ? DEPTH : P.max_depth;
   const float scale_d = __uint_as_float((uint32_t)(127 + depth) << 23);     // 2^depth
   const float Yf = fy * scale_d, Zf = fz * scale_d;                        // exact
@@ -618,7 +713,8 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
       // the whole lookup: levels visited, the cell's digits and what it holds (see build_full_grid_kernel)
       const uint32_t xg = (uint32_t)tg;
       const FullGridEntry g = ns.full[(xg << (2 * DEPTH)) | (Yi << DEPTH) | Zi];      // (64 bits: one 8-byte load)
-      return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
+      if constexpr (PLANES) return full_entry_planes<DEPTH>(g, ns.planes, *cp, inv_pow_depth, value);
+      else return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
     }
   } else if constexpr (BRICK && !COUNT) {
     static_assert(!BRICK || (DEPTH >= 6 && DEPTH <= 10 && !RESIDENT && SAFEV), "the 32-bit table: trees of depth 6-10 outside the LDS table");
@@ -788,6 +884,14 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
   qx ^= 1u << m;
   const float ipd = __uint_as_float((uint32_t)(127 - m) << 23);             // 2^-m = inv_pow_depth after m halvings
   const int sh = depth - m;
+  if constexpr (PLANES) {                             // (waves with a lane in a band: the arithmetic the table was filled with)
+    const bool leaf = code == 2u;
+    const float2 px = slab_planes<UNIT>((float)qx * ipd, ipd, leaf, P.scale, ns.vmin_x), py = slab_planes<UNIT>((float)(Yi >> sh) * ipd, ipd, leaf, P.scale, ns.vmin_y),
+                 pz = slab_planes<UNIT>((float)(Zi >> sh) * ipd, ipd, leaf, P.scale, ns.vmin_z);
+    cp->lox = px.x; cp->hix = px.y; cp->loy = py.x; cp->hiy = py.y; cp->loz = pz.x; cp->hiz = pz.y;
+    inv_pow_depth = ipd; value = v;
+    return leaf;
+  }
   gx = (float)qx * ipd; gy = (float)(Yi >> sh) * ipd; gz = (float)(Zi >> sh) * ipd;
   if (DEPTH > 0) {
     inv_pow_depth = ipd;                              // a compile-time depth >= 1: level 1 always runs, m >= 1

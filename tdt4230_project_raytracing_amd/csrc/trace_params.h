@@ -8,7 +8,15 @@
 #ifndef TDT_FULL_ENTRY_BITS
 #define TDT_FULL_ENTRY_BITS 64
 #endif
-struct alignas(8) FullGridEntry64 { uint32_t w0, w1; };       // corner_x_hi16 << 16 | meta16;  corner_y_hi16 << 16 | corner_z_hi16
+// 64-bit entries only: 1 = the three 16-bit fields name the cell's padded slab planes — byte offsets into the plane table every block
+// builds in LDS (PlaneTable, trace_device.hpp) — instead of holding the corner's fp32 halves; -DTDT_FULL_ENTRY_PLANES=0 is the corner form.
+#ifndef TDT_FULL_ENTRY_PLANES
+#define TDT_FULL_ENTRY_PLANES (TDT_FULL_ENTRY_BITS == 64)
+#endif
+#if TDT_FULL_ENTRY_PLANES && TDT_FULL_ENTRY_BITS != 64
+#error "TDT_FULL_ENTRY_PLANES needs the 64-bit entry"
+#endif
+struct alignas(8) FullGridEntry64 { uint32_t w0, w1; };       // corner_x_hi16 << 16 | meta16;  corner_y_hi16 << 16 | corner_z_hi16 (plane form: the planes' byte offsets in their place)
 #if TDT_FULL_ENTRY_BITS == 64
 typedef FullGridEntry64 FullGridEntry;
 #elif TDT_FULL_ENTRY_BITS == 32

@@ -671,7 +671,7 @@ class Context:
 
     def selftest(self, which):
         """Mismatches of the short rcp (0) / sqrt (1) / rsq (2) forms vs IEEE over all 2^32 inputs; the other modes: include/tdt_rt.h
-        (17: the whole-depth table of the bound cells buffer, every position)."""
+        (17: the whole-depth table of the bound cells buffer, every position; 18: its plane form, planes through the offsets vs arithmetic)."""
         n = ctypes.c_uint64(0)
         self.check(lib().tdt_selftest(self.h, which, ctypes.byref(n)))
         return n.value
