@@ -357,6 +357,24 @@ class Octree {
     if (n) ctx.check(tdt_octree_extract_morph(ctx.raw(), &m, r, mask.size(), v.data(), n, &n));
     return v;
   }
+  // NEW: round morphology (tdt_octree_morph_round): r.op (TDT_MORPH_*) with the Euclidean ball of squared radius r.radius2,
+  // inside the union of `mask` (none: everywhere); the bound tree rebuilt in place; returns the number of cells
+  uint32_t morph_round(const Context &ctx, const tdt_round &r, const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_morph_round(ctx.raw(), &r, mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: the signed squared Euclidean distance over the inclusive box lo..hi (tdt_octree_distance_field), x fastest; magnitudes
+  // above max_d2 come back as max_d2 + 1; `nearest` (optional) receives three coordinates per voxel
+  std::vector<int32_t> distance_field(const Context &ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border = 0,
+                                      std::vector<int32_t> *nearest = nullptr) const {
+    size_t n = 0;
+    ctx.check(tdt_octree_distance_field(ctx.raw(), lo, hi, max_d2, border, nullptr, nullptr, 0, &n));
+    std::vector<int32_t> f(n);
+    if (nearest) nearest->assign(3 * n, -1);
+    if (n) ctx.check(tdt_octree_distance_field(ctx.raw(), lo, hi, max_d2, border, f.data(), nearest ? nearest->data() : nullptr, n, &n));
+    return f;
+  }
   // NEW: stamp a triangle mesh (tdt_octree_edit_triangles): op (TDT_REGION_*) over the voxels the closed triangles touch —
   // vertices {x, y, z} fixed point, 64 units per voxel (tdt_mesh_quantize), triangles 3 vertex indices each, material 0..253 for
   // every triangle or, with `materials`, material + 1 per triangle (the highest covering triangle wins).  A surface

@@ -602,6 +602,63 @@ _Static_assert(sizeof(tdt_quad) == 32, "tdt_quad is 32 bytes");
 int tdt_octree_extract_surface(tdt_ctx *ctx, const tdt_surface *opt, const tdt_region *regions, size_t n_regions, tdt_quad *quads,
                                size_t capacity, size_t *n_quads);
 
+/* ---- exact Euclidean distance ----------------------------------------------------------------------------------------------
+ * Round grow, shrink, open, close and hollow, and a distance field.  V = what tdt_octree_extract returns, over the grid
+ * G = [0, N)^3, N = 2^max_depth.  For a voxel q of G and a set S, d2(q, S) = min over p in S of |q - p|^2, in integers; nothing
+ * wraps around the grid.  The NEAREST voxel of q is, of the voxels of S at that minimum, the one with the lowest x, then the
+ * lowest y, then the lowest z.  (The order decomposes over three axis passes taken in any order, each keeping among equal sums
+ * the lexicographically lowest (x, y, z); at radius2 = 1 it is tdt_octree_morph's "first offset in ascending t".)
+ *   B(r2) = { d in Z^3 : |d|^2 <= r2 }, r2 = `radius2` in 1..4096: r * r is the ball of radius r, 2 the 18-neighbourhood, 5 "2 and
+ *     a bit".  R = the smallest integer with R * R >= r2, so R <= 64.
+ *   D(S) = S + { q in G \ S : d2(q, S) <= r2 }.  Voxels of S keep their material; a new q gets `material` when that is >= 0,
+ *     otherwise the material of its nearest voxel of S.
+ *   E_b(S) = { p in S : every lattice point q with |q - p|^2 <= r2 is in S, or lies outside G and b = 1 }.  Materials unchanged.
+ *     With b = 0 the outside of the grid is empty: p survives only if min over axes of min(p_a + 1, N - p_a) exceeds sqrt(r2).
+ *   The ops are the TDT_MORPH_* numbers: DILATE = D(V).  ERODE = E_border(V).  SHELL = V \ E_border(V).  OPEN = D(E_1(V)) and
+ *     CLOSE = E_1(D(V)) ignore `border`, for tdt_octree_morph's reason; OPEN is a subset of V and keeps V's materials, CLOSE's
+ *     new voxels carry what D gave them.
+ *   Mask: as in voxel morphology the result is (op(V) & M) + (V \ M); distances are always taken on the whole tree.
+ * tdt_octree_morph_round / tdt_octree_extract_morph_round behave exactly like tdt_octree_morph / tdt_octree_extract_morph: the
+ * in-place rebuild by tdt_octree_compact's install rule on every replica of a multi-device context, a failure leaving all of
+ * them unchanged, *n_cells on a misfit; the Morton-sorted list by tdt_octree_extract's rules from device_ids[0], the tree, its
+ * counter and its versions untouched.  The number of passes, launches and synchronisations
+ * does not depend on radius2; the domain's margin, the scans' halo and their length grow with R (DESIGN.md has the measured cost).
+ * tdt_octree_distance_field returns the SIGNED squared distance over the inclusive box lo..hi, which must lie inside G and hold
+ * <= 2^26 voxels: field[((z - lo z) * ey + (y - lo y)) * ex + (x - lo x)], e = hi - lo + 1.  An empty voxel q gets +d2(q, V)
+ * (>= 1); an occupied p gets -(the squared distance to the nearest empty lattice point, the points outside the grid counting
+ * when `border` = 0) (<= -1).  A magnitude above `max_d2` (1..4096) is reported as max_d2 + 1, the sign kept.  nearest_xyz is
+ * optional, three int32 per voxel: an empty voxel with a value <= max_d2 gets its nearest voxel of V, an occupied voxel its own
+ * coordinates, any other {-1, -1, -1}.  field == NULL only sets *n_voxels; capacity below the count: TDT_ERR_INVALID_VALUE with
+ * the count set.  The tree, its counter and its versions are untouched; a multi-device context answers from device_ids[0].  An
+ * empty tree is valid: every value is max_d2 + 1, and the round ops install the all-EMPTY root or return an empty list.
+ * Limit, checked on the host before any volume is allocated: the DOMAIN — bbox(V) (round ops) or the requested box (field),
+ * grown by R on every side and clipped to G — must hold <= TDT_ROUND_DOMAIN_CAP voxels.  Over it the unit allocates, per voxel
+ * of the domain's rows rounded out to multiples of 32 in x: 3 bytes of offsets, 3 more for DILATE / CLOSE with an inherited
+ * material, and up to three bit volumes and one count per 32 voxels (0.5 byte): 6.5 bytes at most, 1.75 GiB at the cap for an
+ * aligned domain.  The field form adds 4 (16 with nearest_xyz) bytes per voxel of the box.  |V| and every produced list are
+ * held to 2^26 voxels (TDT_REGION_BRUSH_CAP).
+ * Errors, nothing written: a NULL struct or pointer, a bad op, radius2 or max_d2 outside 1..4096, material outside -1..253,
+ * border outside 0..1, a bad shape, NULL regions with a count above 0, a bad box, a LEAF value >= 254, a limit exceeded:
+ * TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream;
+ * synchronous. */
+#define TDT_ROUND_DOMAIN_CAP (1u << 28)
+typedef struct tdt_round {
+  int32_t op;                  /* TDT_MORPH_* */
+  int32_t radius2;             /* the squared radius, 1..4096 */
+  int32_t material;            /* -1: a new voxel inherits its nearest voxel's; 0..253: every new voxel gets this LEAF value */
+  int32_t border;              /* DILATE / ERODE / SHELL only: 0 = outside the grid is empty, 1 = outside the grid is solid */
+} tdt_round;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_round) == 16, "tdt_round is 16 bytes");
+#else
+_Static_assert(sizeof(tdt_round) == 16, "tdt_round is 16 bytes");
+#endif
+int tdt_octree_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+int tdt_octree_extract_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                                   size_t capacity, size_t *n_voxels);
+int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border, int32_t *field,
+                              int32_t *nearest_xyz, size_t capacity, size_t *n_voxels);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -6,6 +6,7 @@
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
+//            [--morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
@@ -31,6 +32,9 @@
 //   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
 //   change to a box of grid voxels (both corners inclusive).  Applied after the other edits, before the frame; prints the new
 //   cell count.  --cells N: the cells buffer is uploaded padded with zeros to N cells (room for an edit that grows the tree).
+// --morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]: round morphology
+//   (Octree::morph_round) with the Euclidean ball of SQUARED radius R2 (1..4096); new voxels get --material or inherit their
+//   nearest voxel's; --border 1: the outside of the grid is solid.  Applied after --morph; prints the new cell count.
 // --mesh FILE.ply [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]: stamp a triangle mesh (Octree::stamp_mesh):
 //   the ASCII PLY's polygons (tdt_ply_mesh_parse; colours ignored) are fitted into the box of grid voxels (tdt_mesh_fit; default
 //   the whole grid minus a one-voxel margin; with --mesh, --box is this box, not an edit of its own), quantised and applied with
@@ -73,6 +77,8 @@ int main(int argc, char **argv) {
   bool components = false;
   int morph_op = -1, morph_radius = 0, morph_conn = 6;
   std::string morph_name;
+  int round_op = -1, round_r2 = 0, round_border = 0;
+  std::string round_name;
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
@@ -126,6 +132,15 @@ int main(int argc, char **argv) {
       if (morph_op < 0) { std::fprintf(stderr, "--morph dilate|erode|open|close|shell:R\n"); return 2; }
       morph_name = kind;
     }
+    else if (a == "--morph-round") {
+      static const char *names[5] = {"dilate", "erode", "open", "close", "shell"};   // TDT_MORPH_* order
+      char kind[16] = {0};
+      if (std::sscanf(next(), "%15[a-z]:%d", kind, &round_r2) == 2)
+        for (int k = 0; k < 5; k++) if (!std::strcmp(kind, names[k])) round_op = k;
+      if (round_op < 0) { std::fprintf(stderr, "--morph-round dilate|erode|open|close|shell:R2\n"); return 2; }
+      round_name = kind;
+    }
+    else if (a == "--border") { round_border = std::atoi(next()); if (round_border != 0 && round_border != 1) { std::fprintf(stderr, "--border 0|1\n"); return 2; } }
     else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
     else if (a == "--cells") { pad_cells = std::atoll(next()); if (pad_cells < 0) { std::fprintf(stderr, "--cells N\n"); return 2; } }
@@ -287,6 +302,18 @@ int main(int argc, char **argv) {
         regions.push_back(r);
       }
       std::printf("morph %s:%d conn %d cells %u\n", morph_name.c_str(), morph_radius, morph_conn, octree.morph(ctx, m, regions));
+    }
+    if (round_op >= 0) {
+      tdt_round q{};
+      q.op = round_op; q.radius2 = round_r2; q.material = material_given ? material : -1; q.border = round_border;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      std::printf("morph-round %s:%d border %d cells %u\n", round_name.c_str(), round_r2, round_border, octree.morph_round(ctx, q, regions));
     }
     if (fill_enclosed) {
       tdt_fill fill{};

@@ -3,7 +3,7 @@
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
 // tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
-// tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction).
+// tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>

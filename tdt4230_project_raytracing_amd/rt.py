@@ -161,6 +161,18 @@ class Quad(ctypes.Structure):
 
 assert ctypes.sizeof(Surface) == 8 and ctypes.sizeof(Quad) == 32
 
+# exact Euclidean distance (include/tdt_rt.h): struct tdt_round
+ROUND_DOMAIN_CAP = 1 << 28
+
+
+class Round(ctypes.Structure):
+    """struct tdt_round: op MORPH_*, radius2 1..4096 (the squared radius), material -1 (inherit the nearest voxel's) or 0..253,
+    border 0 / 1 (outside the grid empty / solid)."""
+    _fields_ = [("op", ctypes.c_int32), ("radius2", ctypes.c_int32), ("material", ctypes.c_int32), ("border", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Round) == 16
+
 
 def _exact_ints(a, dtype, name):
     """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
@@ -272,6 +284,10 @@ SYMBOLS = [
     ("tdt_octree_edit_triangles_solid", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(Fill), ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_debug_fill_passes", _I, [_P]),
     ("tdt_octree_extract_surface", _I, [_P, ctypes.POINTER(Surface), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_distance_field", _I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
+                                       _P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -660,6 +676,66 @@ class Context:
         if n.value:
             self.check(lib().tdt_octree_extract_surface(self.h, ctypes.byref(s), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
         return out
+
+    @staticmethod
+    def _int32(name, v, allow_bool=False):
+        """v as an int that fits an int32 (ctypes would wrap it silently); a float with a fraction or a bool is not a number here."""
+        if isinstance(v, bool) and not allow_bool:
+            raise ValueError(f"{name} must be an integer, not {v!r}")
+        if int(v) != v or not -2**31 <= int(v) <= 2**31 - 1:
+            raise ValueError(f"{name} must be an int32, not {v!r}")
+        return int(v)
+
+    @classmethod
+    def _round(cls, op, radius2, material, border):
+        """struct tdt_round (material None: inherit).  The ranges themselves are the library's to check."""
+        material = -1 if material is None else material
+        return Round(cls._int32("op", op), cls._int32("radius2", radius2), cls._int32("material", material),
+                     cls._int32("border", border, allow_bool=True))
+
+    def octree_morph_round(self, op, radius2, material=None, border=0, regions=None):
+        """tdt_octree_morph_round: op (MORPH_*) with the Euclidean ball of squared radius `radius2` (1..4096) on the bound tree,
+        rebuilt in place; new voxels inherit the material of their nearest voxel (None) or get `material` 0..253; border 1 treats
+        the outside of the grid as solid; regions: a mask as in octree_morph.  Returns the canonical tree's cell count."""
+        r = self._round(op, radius2, material, border)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_morph_round(self.h, ctypes.byref(r), arr, k, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_morph_round(self, op, radius2, material=None, border=0, regions=None):
+        """tdt_octree_extract_morph_round: what octree_morph_round would leave, as an (n, 4) int32 list {x, y, z, material + 1},
+        Morton-sorted; the tree is untouched.  Counts first, fills second: two transforms."""
+        r = self._round(op, radius2, material, border)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_morph_round(self.h, ctypes.byref(r), arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_morph_round(self.h, ctypes.byref(r), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def octree_distance_field(self, lo, hi, max_d2, border=0, nearest=False):
+        """tdt_octree_distance_field: the signed squared Euclidean distance over the inclusive box lo..hi as an (ez, ey, ex) int32
+        array: +d2 to the nearest voxel for an empty voxel, -d2 to the nearest empty point for an occupied one (border 0: the
+        points outside the grid count), magnitudes above max_d2 (1..4096) reported as max_d2 + 1.  nearest: also an (ez, ey, ex,
+        3) array of the nearest voxel {x, y, z} (an occupied voxel: itself; none within max_d2: -1).  The tree is untouched."""
+        box3 = []
+        for name, c in (("lo", lo), ("hi", hi)):
+            c = list(c)
+            if len(c) != 3:
+                raise ValueError(f"{name} must hold three coordinates")
+            box3.append((ctypes.c_int32 * 3)(*[self._int32(name, v) for v in c]))
+        max_d2, border = self._int32("max_d2", max_d2), self._int32("border", border, allow_bool=True)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_distance_field(self.h, box3[0], box3[1], max_d2, border, None, None, 0, ctypes.byref(n)))
+        ex, ey, ez = (int(box3[1][a]) - int(box3[0][a]) + 1 for a in range(3))
+        field = np.zeros((ez, ey, ex), np.int32)
+        near = np.zeros((ez, ey, ex, 3), np.int32) if nearest else None
+        assert field.size == n.value
+        self.check(lib().tdt_octree_distance_field(self.h, box3[0], box3[1], max_d2, border, field.ctypes.data,
+                                                   near.ctypes.data if nearest else None, field.size, ctypes.byref(n)))
+        return (field, near) if nearest else field
 
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
