@@ -1,13 +1,13 @@
-// Device helpers shared by region edits (tdt_region.hip), connected components (tdt_connect.hip) and voxel morphology
-// (tdt_morph.hip): Morton keys of grid voxels, the exact integer shape test of a tdt_region, and the neighbour lookup in a
-// sorted key list.
+// Device helpers shared by the editing units: Morton keys of grid voxels, the exact integer shape test of a tdt_region, and the
+// neighbour lookup in a sorted key list; and the two host steps every unit with a region list takes: the list's validation
+// with its copy into RegionShapes, and their upload.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdint>
 
-#include "tdt_rt.h"
+#include "tdt_internal.hpp"
 
 namespace tdt {
 
@@ -16,6 +16,29 @@ struct RegionShape {           // a tdt_region with its grid-clipped bounding bo
   int32_t lo[3];
   uint32_t ext[3], lane0;
 };
+
+// a call's region list checked as every entry point checks it; out (may be null): the shapes, shape / a / b copied, the rest 0
+inline int region_shapes(tdt_ctx *ctx, const tdt_region *regions, size_t n_regions, std::vector<RegionShape> *out) {
+  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
+  if (out) out->assign(n_regions, RegionShape{});
+  for (size_t s = 0; s < n_regions; s++) {
+    const tdt_region &g = regions[s];
+    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
+    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
+    if (!out) continue;
+    (*out)[s].shape = g.shape;
+    for (int a = 0; a < 3; a++) { (*out)[s].a[a] = g.a[a]; (*out)[s].b[a] = g.b[a]; }
+  }
+  return TDT_OK;
+}
+// *d = n shapes in device memory of S, queued on st (null when n == 0); no_memory: the caller's out-of-memory text
+inline int upload_shapes(tdt_ctx *front, hipStream_t st, DeviceScratch &S, const RegionShape *shapes, size_t n, const char *no_memory, RegionShape **d) {
+  *d = n ? S.get<RegionShape>(n) : nullptr;
+  if (!n) return TDT_OK;
+  if (!*d) return fail(front, TDT_ERR_HIP, no_memory);
+  TDT_HIP(front, hipMemcpyAsync(*d, shapes, n * sizeof(RegionShape), hipMemcpyHostToDevice, st));
+  return TDT_OK;
+}
 
 __device__ __forceinline__ uint32_t region_spread3(uint32_t v) {   // 10 bits -> every third bit (the builder's spread3)
   v = (v | (v << 16)) & 0x030000FFu;

@@ -156,7 +156,6 @@ int walk_inputs(tdt_ctx *front, tdt_ctx *ctx, int *depth) {
 namespace {
 
 using Scratch = DeviceScratch;
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the octree walk";
 
 struct Walk {

@@ -197,7 +197,6 @@ __global__ __launch_bounds__(256) void connect_select_kernel(const tdt_component
 
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the component labelling";
 
 // the components of V on ctx's stream: *label (nv words, in S), *tab (*n_comp entries, in S).  One host synchronisation.
@@ -254,11 +253,11 @@ struct Selection final : VoxelSelect {
                          (const uint32_t *)keys, nv, depth, (const uint32_t *)label, hit);
     }
     if (!shapes.empty()) {
-      RegionShape *d_shapes = S.get<RegionShape>(shapes.size());
+      RegionShape *d_shapes = nullptr;
       touch = S.get<uint32_t>(nc);
-      if (!d_shapes || !touch) return fail(front, TDT_ERR_HIP, kNoMemory);
+      if (!touch) return fail(front, TDT_ERR_HIP, kNoMemory);
       TDT_HIP(front, hipMemsetAsync(touch, 0, (size_t)nc * sizeof(uint32_t), st));
-      TDT_HIP(front, hipMemcpyAsync(d_shapes, shapes.data(), shapes.size() * sizeof(RegionShape), hipMemcpyHostToDevice, st));
+      if (int rc = upload_shapes(front, st, S, shapes.data(), shapes.size(), kNoMemory, &d_shapes)) return rc;
       hipLaunchKernelGGL(connect_touch_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, v, nv, (const uint32_t *)label,
                          (const RegionShape *)d_shapes, (uint32_t)shapes.size(), touch);
     }
@@ -284,20 +283,10 @@ int make_selection(tdt_ctx *ctx, const tdt_select *sel, const int32_t *seeds, si
   if (sel->min_voxels > sel->max_voxels) return fail(ctx, TDT_ERR_INVALID_VALUE, "min_voxels > max_voxels");
   if (n_seeds && !seeds) return fail(ctx, TDT_ERR_INVALID_VALUE, "null seed list");
   if (n_seeds >= (1ull << 31)) return fail(ctx, TDT_ERR_INVALID_VALUE, "more than 2^31 seeds");
-  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
-  for (size_t s = 0; s < n_regions; s++) {
-    const tdt_region &g = regions[s];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-  }
+  if (int rc = region_shapes(ctx, regions, n_regions, &out.shapes)) return rc;
   out.sel = *sel;
   out.seeds.resize(n_seeds);
   for (size_t s = 0; s < n_seeds; s++) out.seeds[s] = make_int4(seeds[3 * s], seeds[3 * s + 1], seeds[3 * s + 2], 0);
-  out.shapes.assign(n_regions, RegionShape{});
-  for (size_t s = 0; s < n_regions; s++) {
-    out.shapes[s].shape = regions[s].shape;
-    for (int a = 0; a < 3; a++) { out.shapes[s].a[a] = regions[s].a[a]; out.shapes[s].b[a] = regions[s].b[a]; }
-  }
   return TDT_OK;
 }
 

@@ -3,11 +3,12 @@
 // transform of three passes whatever the radius (margin, halo and scan length grow with R); thresholded it is the round grow / shrink / open / close / hollow.
 //
 // The domain is bbox(V) (round ops) or the requested box (field) grown by R = ceil(sqrt(radius2)) and clipped to the grid; it is
-// laid out like tdt_fill.hip's box: x along 32-bit words, rows word-aligned in ABSOLUTE x, so a row is nw words = 32 nw padded
-// voxels, and the byte volumes below use the same padded rows (index = row * 32 nw + x - 32 wx0).
+// laid out as bitvol_device.hpp describes (the layout enclosed space uses too): x along 32-bit words, rows word-aligned in
+// ABSOLUTE x, so a row is nw words = 32 nw padded voxels, and the byte volumes below use the same padded rows
+// (index = row * 32 nw + x - 32 wx0).
 //
-//   rasterise  one lane per voxel of V inside the domain: a vector atomicOr into the occupancy bits, and (Morton key,
-//              material + 1) for the material lookups.                                                dist_rasterise_kernel
+//   bbox, rasterise   tdt_bitvol.hip's: (round ops) bbox(V), then the occupancy bits of the voxels of V inside the domain and every
+//              voxel's (Morton key, material + 1) for the material lookups.
 //   pass x     one lane per padded voxel: the nearest set bit of its row within +-R from a count of leading / trailing zeros
 //              over its word and at most two words either side; of two at the same distance the lower x.  One signed byte
 //              per voxel, -128 = none within R.                                                          dist_pass_x_kernel
@@ -33,12 +34,8 @@
 //   count, emit  per word popc of the selected bits — the result's difference from V inside the mask (the edit forms: a FILL or
 //              CLEAR list for region_edit_source) or V with that difference applied (the extract forms) — exclusive_scan_u32,
 //              then (Morton key, material + 1) per voxel: V's material by lookup in its sorted keys, a new voxel's the fixed
-//              one or its nearest voxel's.  sort_pairs_u32 orders the extract forms.    dist_count_kernel, dist_emit_kernel
-//   bbox       (round ops) one reduction over V: a fixed launch of at most 256 blocks whose lanes stride over the list, wave
-//              shuffles, then one vector atomicMin / atomicMax per wave and axis.  Besides the rasterising OR these are the
-//              unit's only atomics: at most 6144 per call, on integers, so the result does not depend on their order; a second
-//              reduction kernel over per-wave partials would add a launch to save them.  (One wave per 64 voxels, tdt_fill.hip's
-//              form, measured 1.0 ms on config 3's 0.95 M voxels: 90 000 atomics on six words.)                                                                    dist_bbox_kernel
+//              one or its nearest voxel's.  tdt_bitvol.hip's tail writes the list, sorting the extract forms first.
+//                                                                                       dist_count_kernel, dist_emit_kernel
 //   synchronisations per call: the tree walk, the bounding box, the count, the end; none depends on the radius.
 //   memory     per PADDED domain voxel (rows rounded out to whole words; at most 2^28 unpadded): 1 B (pass x) + 2 B (pass
 //              y), + 1 B + 2 B for an inherited DILATE / CLOSE, + 3 bit volumes and a count per word: at most 6.5 B.
@@ -47,8 +44,8 @@
 #include <string>
 #include <vector>
 
+#include "bitvol_device.hpp"
 #include "device_scan.hpp"
-#include "region_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
@@ -59,13 +56,8 @@ constexpr int kDistRows = kDistTile + 2 * kDistMaxR;
 constexpr int kDistNone = -128;                        // pass x: nothing within R
 constexpr unsigned kDistSelf = (128u << 8) | 128u;     // the pair of offsets (0, 0); a pair of 0 = none
 constexpr unsigned long long kDistCap = 1ull << 26;
-constexpr unsigned kDistBboxBlocks = 256;               // the bounding box's launch: 1024 waves, 6 atomics each
 
-struct DistBox {               // the domain and the layout of the volumes over it
-  int32_t lo[3], hi[3];        // inclusive
-  int32_t ey, ez;              // rows per axis
-  int32_t nw, wx0;             // words per row; the absolute word index of word 0
-  uint32_t n_words;            // ey * ez * nw <= 2^25
+struct DistBox : BitBox {      // the domain and the layout of the volumes over it
   int32_t N, R;                // grid side; window
 };
 
@@ -80,14 +72,6 @@ struct DistOut {               // what pass z does with a voxel's squared distan
   int32_t max_d2;
 };
 
-// the bits of word w of a row that lie inside [x0, x1]
-__device__ __forceinline__ uint32_t dist_valid(const DistBox &B, int w) {
-  uint32_t m = 0xFFFFFFFFu;
-  if (w == 0) m &= 0xFFFFFFFFu << (B.lo[0] & 31);
-  if (w == B.nw - 1) m &= 0xFFFFFFFFu >> (31 - (B.hi[0] & 31));
-  return m;
-}
-
 // the bits of word w (any integer, also beyond the row) whose x lies inside the grid
 __device__ __forceinline__ uint32_t dist_grid(const DistBox &B, int w) {
   const int x0 = (B.wx0 + w) * 32;
@@ -100,42 +84,6 @@ __device__ __forceinline__ uint32_t dist_grid(const DistBox &B, int w) {
 __device__ __forceinline__ uint32_t dist_word(const DistBox &B, const uint32_t *src, uint32_t row, int w, int invert) {
   const uint32_t v = (w >= 0 && w < B.nw) ? src[row * (uint32_t)B.nw + (uint32_t)w] : 0u;
   return invert ? ~v & dist_grid(B, w) : v;
-}
-
-__device__ __forceinline__ int dist_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-  return v;
-}
-
-// box[0..2] = min, box[3..5] = max over the list (initialised to INT_MAX / -1)
-// A lane takes every stride-th voxel (stride = the launch's lanes, a multiple of 64, so a wave's trip counts differ by one at
-// most and all its lanes reach the shuffles): the atomics per call are bounded by the launch, not by |V|.
-__global__ __launch_bounds__(256) void dist_bbox_kernel(const int4 *v, uint32_t n, uint32_t stride, int *box) {
-  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
-    const int4 p = v[i];
-    lo[0] = p.x < lo[0] ? p.x : lo[0]; lo[1] = p.y < lo[1] ? p.y : lo[1]; lo[2] = p.z < lo[2] ? p.z : lo[2];
-    hi[0] = p.x > hi[0] ? p.x : hi[0]; hi[1] = p.y > hi[1] ? p.y : hi[1]; hi[2] = p.z > hi[2] ? p.z : hi[2];
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int l = dist_wave_min(lo[a]), h = -dist_wave_min(-hi[a]);
-    if ((threadIdx.x & 63u) == 0 && h >= 0) { atomicMin(box + a, l); atomicMax(box + 3 + a, h); }
-  }
-}
-
-// the voxels of V inside the domain into occ; every voxel's (Morton key, material + 1)
-__global__ __launch_bounds__(256) void dist_rasterise_kernel(const int4 *v, uint32_t n, const DistBox B, uint32_t *occ, uint32_t *keys,
-                                                            uint32_t *vals) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const int4 p = v[i];
-  keys[i] = region_key(p.x, p.y, p.z);
-  vals[i] = (uint32_t)p.w;
-  if (p.x < B.lo[0] || p.x > B.hi[0] || p.y < B.lo[1] || p.y > B.hi[1] || p.z < B.lo[2] || p.z > B.hi[2]) return;
-  const uint32_t row = (uint32_t)(p.z - B.lo[2]) * (uint32_t)B.ey + (uint32_t)(p.y - B.lo[1]);
-  atomicOr(occ + row * (uint32_t)B.nw + (uint32_t)((p.x >> 5) - B.wx0), 1u << (p.x & 31));
 }
 
 __global__ __launch_bounds__(256) void dist_pass_x_kernel(const DistBox B, const uint32_t *src, int invert, signed char *ox) {
@@ -241,7 +189,7 @@ __global__ __launch_bounds__(256) void dist_scan_kernel(const DistBox B, int inv
         if (w < B.nw) {
           const uint32_t g = row * (uint32_t)B.nw + (uint32_t)w;
           const uint32_t q = (uint32_t)(ballot >> lx);
-          O.bits[g] = (O.neg ? ~q : q) & (O.andv ? O.andv[g] : dist_valid(B, w));
+          O.bits[g] = (O.neg ? ~q : q) & (O.andv ? O.andv[g] : bitvol_valid(B, w));
         }
       }
       if (O.oz && live) O.oz[idx] = (signed char)(found ? oa : kDistNone);
@@ -267,20 +215,9 @@ __global__ __launch_bounds__(256) void dist_scan_kernel(const DistBox B, int inv
 // the selected bits of word g: where res differs from occ inside the mask (all = 0), or occ with that difference applied
 __device__ __forceinline__ uint32_t dist_selected(const DistBox &B, const uint32_t *occ, const uint32_t *res, uint32_t g, const RegionShape *shapes,
                                                   uint32_t n_shapes, int masked, int all, int *x0, int *y, int *z) {
-  const int w = (int)(g % (uint32_t)B.nw);
-  const uint32_t row = g / (uint32_t)B.nw;
-  *x0 = (B.wx0 + w) << 5; *y = B.lo[1] + (int)(row % (uint32_t)B.ey); *z = B.lo[2] + (int)(row / (uint32_t)B.ey);
-  uint32_t diff = (occ[g] ^ res[g]) & dist_valid(B, w);
-  if (masked) {
-    uint32_t kept = 0;
-    for (uint32_t b = diff; b; b &= b - 1u) {
-      const int bit = __ffs((int)b) - 1;
-      bool in = false;
-      for (uint32_t s = 0; s < n_shapes && !in; s++) in = region_inside(shapes[s], *x0 + bit, *y, *z);
-      if (in) kept |= 1u << bit;
-    }
-    diff = kept;
-  }
+  const int w = bitvol_word(B, g, x0, y, z);
+  uint32_t diff = (occ[g] ^ res[g]) & bitvol_valid(B, w);
+  if (masked) diff = bitvol_inside(diff, shapes, n_shapes, *x0, *y, *z);
   return all ? occ[g] ^ diff : diff;
 }
 
@@ -291,13 +228,6 @@ __global__ __launch_bounds__(256) void dist_count_kernel(const DistBox B, const 
   if (g == B.n_words) { count[g] = 0; return; }               // the scan's extra item: its slot receives the total
   int x0, y, z;
   count[g] = (uint32_t)__popc(dist_selected(B, occ, res, g, shapes, n_shapes, masked, all, &x0, &y, &z));
-}
-
-// index of key k in the sorted keys[0, n) (k is there)
-__device__ __forceinline__ uint32_t dist_find(const uint32_t *keys, uint32_t n, uint32_t k) {
-  uint32_t lo = 0, hi = n;                                   // keys[lo] <= k < keys[hi]
-  while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (keys[mid] <= k) lo = mid; else hi = mid; }
-  return lo;
 }
 
 // fixed: material + 1 of every new voxel, or 0: that of its nearest voxel of V (xy, oz of the transform of V)
@@ -315,28 +245,20 @@ __global__ __launch_bounds__(256) void dist_emit_kernel(const DistBox B, const u
     const int bit = __ffs((int)b) - 1;
     uint32_t m = fixed;
     if ((o >> bit) & 1u) {
-      m = wvals[dist_find(wkeys, n_w, region_key(x0 + bit, y, z))];
+      m = wvals[bitvol_find(wkeys, n_w, region_key(x0 + bit, y, z))];
     } else if (!m) {
       const uint32_t idx = g * 32u + (uint32_t)bit;
       const int dz = oz[idx];                                // within radius2 of V, so there is one
       const unsigned c = xy[(uint32_t)((int)idx + dz * (int)plane)];
-      m = wvals[dist_find(wkeys, n_w, region_key(x0 + bit + (int)(c & 0xFFu) - 128, y + (int)(c >> 8) - 128, z + dz))];
+      m = wvals[bitvol_find(wkeys, n_w, region_key(x0 + bit + (int)(c & 0xFFu) - 128, y + (int)(c >> 8) - 128, z + dz))];
     }
     keys[pos] = region_key(x0 + bit, y, z); vals[pos] = m;
     pos++;
   }
 }
 
-__global__ __launch_bounds__(256) void dist_list_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, int4 *out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t k = keys[i];
-  out[i] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)vals[i]);
-}
-
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the distance transform";
 
 // what one round call asks for, validated on the host before anything is queued
@@ -353,34 +275,23 @@ int make_request(tdt_ctx *ctx, const tdt_round *r, const tdt_region *regions, si
   if (r->radius2 < 1 || r->radius2 > 4096) return fail(ctx, TDT_ERR_INVALID_VALUE, "radius2 must be 1..4096");
   if (r->material < -1 || r->material > 253) return fail(ctx, TDT_ERR_INVALID_VALUE, "material must be -1 (inherit) or 0..253");
   if (r->border != 0 && r->border != 1) return fail(ctx, TDT_ERR_INVALID_VALUE, "border must be 0 or 1");
-  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
   R.r = *r;
-  R.shapes.assign(n_regions, RegionShape{});
-  for (size_t s = 0; s < n_regions; s++) {
-    const tdt_region &g = regions[s];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-    R.shapes[s].shape = g.shape;
-    for (int a = 0; a < 3; a++) { R.shapes[s].a[a] = g.a[a]; R.shapes[s].b[a] = g.b[a]; }
-  }
-  return TDT_OK;
+  return region_shapes(ctx, regions, n_regions, &R.shapes);
 }
 
 // the domain: lo..hi grown by R, clipped to the grid; held to TDT_ROUND_DOMAIN_CAP before anything is allocated over it
 int make_domain(tdt_ctx *front, const int lo[3], const int hi[3], int depth, int R, DistBox &B) {
-  std::memset(&B, 0, sizeof B);
   B.N = 1 << depth; B.R = R;
+  int glo[3], ghi[3];
   unsigned long long voxels = 1;
   for (int a = 0; a < 3; a++) {
-    B.lo[a] = lo[a] - R < 0 ? 0 : lo[a] - R;
-    B.hi[a] = hi[a] + R > B.N - 1 ? B.N - 1 : hi[a] + R;
-    voxels *= (unsigned long long)(B.hi[a] - B.lo[a] + 1);
+    glo[a] = lo[a] - R < 0 ? 0 : lo[a] - R;
+    ghi[a] = hi[a] + R > B.N - 1 ? B.N - 1 : hi[a] + R;
+    voxels *= (unsigned long long)(ghi[a] - glo[a] + 1);
   }
   if (voxels > TDT_ROUND_DOMAIN_CAP)
     return fail(front, TDT_ERR_INVALID_VALUE, "the distance transform's domain holds " + std::to_string(voxels) + " voxels (more than 2^28)");
-  B.ey = B.hi[1] - B.lo[1] + 1; B.ez = B.hi[2] - B.lo[2] + 1;
-  B.wx0 = B.lo[0] >> 5; B.nw = (B.hi[0] >> 5) - B.wx0 + 1;
-  B.n_words = (uint32_t)B.ey * (uint32_t)B.ez * (uint32_t)B.nw;
+  bitvol_layout(glo, ghi, B);
   return TDT_OK;
 }
 
@@ -394,23 +305,6 @@ void transform(hipStream_t st, const DistBox &B, const uint32_t *src, int invert
                      (const unsigned short *)nullptr, xy, O);
   hipLaunchKernelGGL(dist_scan_kernel<MODE>, dim3(xt, tz * (unsigned)B.ey), dim3(256), 0, st, B, invert, (const signed char *)nullptr,
                      (const unsigned short *)xy, (unsigned short *)nullptr, O);
-}
-
-// V's bounding box (nv > 0); one synchronisation
-int list_bbox(tdt_ctx *front, hipStream_t st, const int4 *v, uint32_t nv, int depth, DeviceScratch &S, int box[6]) {
-  const int init[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
-  int *d_box = S.get<int>(6);
-  if (!d_box) return fail(front, TDT_ERR_HIP, kNoMemory);
-  TDT_HIP(front, hipMemcpyAsync(d_box, init, sizeof init, hipMemcpyHostToDevice, st));
-  const unsigned bbox_blocks = blocks_of(nv) < kDistBboxBlocks ? blocks_of(nv) : kDistBboxBlocks;
-  hipLaunchKernelGGL(dist_bbox_kernel, dim3(bbox_blocks), dim3(256), 0, st, v, nv, bbox_blocks * 256u, d_box);
-  TDT_HIP(front, hipGetLastError());
-  TDT_HIP(front, hipMemcpyAsync(box, d_box, 6 * sizeof(int), hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));
-  const int N = 1 << depth;
-  for (int a = 0; a < 3; a++)
-    if (box[a] < 0 || box[3 + a] >= N || box[a] > box[3 + a]) return fail(front, TDT_ERR_INVALID_VALUE, "a voxel lies outside the grid");
-  return TDT_OK;
 }
 
 // a round op's result on one single-device context, {x, y, z, material + 1} in device memory of ctx (allocated in S; null when
@@ -427,7 +321,7 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
   if (nv > kDistCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
   if (nv == 0) return TDT_OK;                              // every op of the empty set is empty
   int box[6];
-  if (int rc = list_bbox(front, st, v, nv, depth, S, box)) return rc;
+  if (int rc = bitvol_list_bbox(front, st, v, nv, depth, S, kNoMemory, "a voxel lies outside the grid", box)) return rc;
   DistBox B;
   if (int rc = make_domain(front, box, box + 3, depth, window_of(Q.radius2), B)) return rc;
   // ---- volumes ----
@@ -442,13 +336,8 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
   if (!occ || !res || (two && !mid) || !wk || !wv || !ox || (inherit && !oz) || !xy || !xy2) return fail(front, TDT_ERR_HIP, kNoMemory);
   RegionShape *d_shapes = nullptr;
   const uint32_t n_shapes = (uint32_t)R.shapes.size();
-  if (n_shapes) {
-    d_shapes = S.get<RegionShape>(n_shapes);
-    if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
-    TDT_HIP(front, hipMemcpyAsync(d_shapes, R.shapes.data(), n_shapes * sizeof(RegionShape), hipMemcpyHostToDevice, st));
-  }
-  TDT_HIP(front, hipMemsetAsync(occ, 0, (size_t)B.n_words * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(dist_rasterise_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, B, occ, wk, wv);
+  if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
+  if (int rc = bitvol_rasterise(front, st, v, nv, B, occ, wk, wv)) return rc;
   // ---- the op: W(S) = { d2(q, S) <= radius2 }, C = the complement ----
   DistOut O;
   std::memset(&O, 0, sizeof O);
@@ -492,22 +381,12 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
   if (n_out == 0) return TDT_OK;
   // ---- emit, sort ----
   uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
-  int4 *vox = S.get<int4>(n_out);
-  if (!k0 || !v0 || !vox) return fail(front, TDT_ERR_HIP, kNoMemory);
+  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
   hipLaunchKernelGGL(dist_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)res,
                      (const RegionShape *)d_shapes, n_shapes, masked, all, (const uint32_t *)count, Q.material >= 0 ? (uint32_t)Q.material + 1u : 0u,
                      (const unsigned short *)xy, (const signed char *)oz, (const uint32_t *)wk, (const uint32_t *)wv, nv, k0, v0);
-  uint32_t *k = k0, *vv = v0;
-  if (!delta) {
-    uint32_t *k1 = S.get<uint32_t>(n_out), *v1 = S.get<uint32_t>(n_out);
-    uint32_t *hist = S.get<uint32_t>(sort_hist_words(n_out)), *hscr = S.get<uint32_t>(sort_scratch_words(n_out));
-    if (!k1 || !v1 || !hist || !hscr) return fail(front, TDT_ERR_HIP, kNoMemory);
-    TDT_HIP(front, sort_pairs_u32(st, k, vv, k1, v1, n_out, hist, hscr));
-  }
-  hipLaunchKernelGGL(dist_list_kernel, dim3(blocks_of(n_out)), dim3(256), 0, st, (const uint32_t *)k, (const uint32_t *)vv, n_out, vox);
-  TDT_HIP(front, hipGetLastError());
-  TDT_HIP(front, hipStreamSynchronize(st));
-  *out = vox; *n = n_out;
+  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, !delta, S, kNoMemory, out)) return rc;
+  *n = n_out;
   return TDT_OK;
 }
 
@@ -539,7 +418,7 @@ int field_one(tdt_ctx *front, tdt_ctx *ctx, const int32_t lo[3], const int32_t h
   if (capacity < count) return fail(front, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " voxels");
   TDT_HIP(front, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+  Drain drain{st};
   DeviceScratch S;
   int4 *v = nullptr;
   uint32_t nv = 0;
@@ -551,8 +430,7 @@ int field_one(tdt_ctx *front, tdt_ctx *ctx, const int32_t lo[3], const int32_t h
   unsigned short *xy = S.get<unsigned short>(padded);
   int32_t *d_field = S.get<int32_t>((size_t)count), *d_near = nearest ? S.get<int32_t>(3 * (size_t)count) : nullptr;
   if (!occ || !wk || !wv || !ox || !xy || !d_field || (nearest && !d_near)) return fail(front, TDT_ERR_HIP, kNoMemory);
-  TDT_HIP(front, hipMemsetAsync(occ, 0, (size_t)B.n_words * sizeof(uint32_t), st));
-  if (nv) hipLaunchKernelGGL(dist_rasterise_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, B, occ, wk, wv);
+  if (int rc = bitvol_rasterise(front, st, v, nv, B, occ, wk, wv)) return rc;
   DistOut O;
   std::memset(&O, 0, sizeof O);
   O.field = d_field; O.nearest = d_near; O.max_d2 = max_d2;
@@ -592,17 +470,12 @@ int tdt_octree_extract_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_r
   if (int rc = make_request(ctx, r, regions, n_regions, R)) return rc;
   tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
   TDT_HIP(ctx, hipSetDevice(m->device));
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};
+  Drain drain{m->stream};
   DeviceScratch S;
   const int4 *vox = nullptr;
   uint32_t n = 0;
   if (int rc = round_list(ctx, m, R, false, S, &vox, &n)) return rc;
-  *n_voxels = n;
-  if (!voxels_xyzm || n == 0) return TDT_OK;
-  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " voxels");
-  TDT_HIP(ctx, hipMemcpyAsync(voxels_xyzm, vox, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost, m->stream));
-  TDT_HIP(ctx, hipStreamSynchronize(m->stream));
-  return TDT_OK;
+  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border, int32_t *field,

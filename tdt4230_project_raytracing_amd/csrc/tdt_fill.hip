@@ -3,16 +3,14 @@
 // c-neighbours connects to a face of the grid, W being the bound tree's voxels or a mesh's surface voxels.
 //
 // Every other editing unit works on the Morton-sorted list of OCCUPIED voxels; enclosure is a property of the empty ones, which
-// are in no list, so this unit keeps a dense bit volume instead.  It only has to span bbox(W): a voxel outside the bounding box
+// are in no list, so this unit keeps a dense bit volume instead (layout: bitvol_device.hpp; the steps between the list and the
+// volume that exact distance takes too: tdt_bitvol.hip).  It only has to span bbox(W): a voxel outside the bounding box
 // of W is beyond it on some axis, walking away from the box along that axis stays empty up to the grid face, so every voxel
 // outside bbox(W) is outside and E lies inside bbox(W).  An empty voxel on one of the six faces of bbox(W) is either on a grid
 // face or next to a voxel outside the box: those are the seeds, and the flood never has to leave the box.
 //
-//   bbox       one reduction over W: wave shuffles, then one vector atomicMin / atomicMax per wave and axis.     fill_bbox_kernel
-//   rasterise  one lane per voxel of W sets its bit in the occupancy volume with a vector atomicOr and writes its (Morton key,
-//              material + 1).  x runs along the 32-bit word: a row (y, z) of the box is nw <= 32 consecutive words, word w of a
-//              row holding x = 32 (wx0 + w) .. + 31, so rows are word-aligned in ABSOLUTE x and the box itself need not be: the
-//              bits of the first and last word that lie outside [x0, x1] are masked (fill_valid).           fill_rasterise_kernel
+//   bbox, rasterise   tdt_bitvol.hip's: bbox(W) in its bounded launch, then W's occupancy bits and its (Morton key, material + 1);
+//              the box being W's own, the rasteriser's clip never fires.
 //   seed       reach = the empty bits of the rows on the four y / z faces, and the bits x0 and x1 of every other row.  fill_seed_kernel
 //   flood      one block owns a tile of 8 x 8 whole rows, held in LDS with a halo of one row all round (10 x 10 rows); a tile
 //              holds its rows whole, so there is no halo along x.  A round computes, per word,
@@ -36,18 +34,16 @@
 //   emit       (Morton key, material + 1) per enclosed voxel at its word's offset.  Inherit: the first voxel of W in decreasing
 //              x is the highest set occupancy bit below the voxel, in its word (a count of leading zeros) or the words before
 //              it — it exists, or the voxel would reach the box's x0 face and be a seed — and its material is looked up in W's
-//              sorted keys.  The builder's radix sort then orders the pairs (W's own pairs in front of them for the solid mesh
-//              forms), and one lane per pair writes {x, y, z, m}.                                  fill_emit_kernel, fill_list_kernel
+//              sorted keys.  tdt_bitvol.hip's tail then sorts the pairs (W's own pairs in front of them for the solid mesh
+//              forms) and writes the list {x, y, z, m}.                                                       fill_emit_kernel
 //   memory     at the largest box (depth 10, the whole grid: 2^25 words): occupancy 128 MiB + reach 128 MiB + the per-word counts
 //              and their scan 128 MiB (+ 64 KiB of scan scratch), besides W's list (16 B per voxel) and its (key, material)
 //              pairs (8 B), and 32 B per resulting voxel for the pairs, the sort's second pair and the list.
-#include <climits>
-#include <cstring>
 #include <string>
 #include <vector>
 
+#include "bitvol_device.hpp"
 #include "device_scan.hpp"
-#include "region_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
@@ -58,21 +54,6 @@ constexpr int kFillMaxWords = 32;                      // words per row: 2^10 vo
 constexpr int kFillBatch = 8;                          // flood passes per flag read
 constexpr unsigned long long kFillCap = 1ull << 26;
 
-struct FillBox {               // bbox(W) and the layout of the bit volumes over it
-  int32_t lo[3], hi[3];        // inclusive
-  int32_t ey, ez;              // rows per axis
-  int32_t nw, wx0;             // words per row; the absolute word index of word 0
-  uint32_t n_words;            // ey * ez * nw <= 2^25
-};
-
-// the bits of word w of a row that lie inside [x0, x1]
-__device__ __forceinline__ uint32_t fill_valid(const FillBox &B, int w) {
-  uint32_t m = 0xFFFFFFFFu;
-  if (w == 0) m &= 0xFFFFFFFFu << (B.lo[0] & 31);
-  if (w == B.nw - 1) m &= 0xFFFFFFFFu >> (31 - (B.hi[0] & 31));
-  return m;
-}
-
 // every run of set bits of e that holds a bit of s (s a subset of e), whole.  e + s: the lowest seed of a run carries through
 // the run's bits above it and stops in the clear bit behind the run (or leaves the word); a higher seed of the same run stays
 // set in the sum, hence the final | s.
@@ -82,42 +63,13 @@ __device__ __forceinline__ uint32_t fill_runs(uint32_t e, uint32_t s) {
   return up | __brev((eb & ~(eb + sb)) | sb);
 }
 
-__device__ __forceinline__ int fill_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-  return v;
-}
-
-// box[0..2] = min, box[3..5] = max over the list (initialised to INT_MAX / -1)
-__global__ __launch_bounds__(256) void fill_bbox_kernel(const int4 *v, uint32_t n, int *box) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
-  if (i < n) { const int4 p = v[i]; lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z; }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int l = fill_wave_min(lo[a]), h = -fill_wave_min(-hi[a]);
-    if ((threadIdx.x & 63u) == 0 && h >= 0) { atomicMin(box + a, l); atomicMax(box + 3 + a, h); }
-  }
-}
-
-__global__ __launch_bounds__(256) void fill_rasterise_kernel(const int4 *v, uint32_t n, const FillBox B, uint32_t *occ, uint32_t *keys,
-                                                            uint32_t *vals) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const int4 p = v[i];
-  const uint32_t row = (uint32_t)(p.z - B.lo[2]) * (uint32_t)B.ey + (uint32_t)(p.y - B.lo[1]);
-  atomicOr(occ + row * (uint32_t)B.nw + (uint32_t)((p.x >> 5) - B.wx0), 1u << (p.x & 31));
-  keys[i] = region_key(p.x, p.y, p.z);
-  vals[i] = (uint32_t)p.w;
-}
-
-__global__ __launch_bounds__(256) void fill_seed_kernel(const FillBox B, const uint32_t *occ, uint32_t *reach) {
+__global__ __launch_bounds__(256) void fill_seed_kernel(const BitBox B, const uint32_t *occ, uint32_t *reach) {
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   if (g >= B.n_words) return;
   const int w = (int)(g % (uint32_t)B.nw);
   const uint32_t row = g / (uint32_t)B.nw;
   const int y = (int)(row % (uint32_t)B.ey), z = (int)(row / (uint32_t)B.ey);
-  const uint32_t empty = ~occ[g] & fill_valid(B, w);
+  const uint32_t empty = ~occ[g] & bitvol_valid(B, w);
   uint32_t seed = 0xFFFFFFFFu;
   if (y != 0 && y != B.ey - 1 && z != 0 && z != B.ez - 1) {
     seed = 0;
@@ -137,7 +89,7 @@ __device__ __forceinline__ uint32_t fill_spread(const uint32_t *r, int h, int w,
 }
 
 template <int CONN>
-__global__ __launch_bounds__(256) void fill_flood_kernel(const FillBox B, const uint32_t *occ, uint32_t *reach, uint32_t *flag) {
+__global__ __launch_bounds__(256) void fill_flood_kernel(const BitBox B, const uint32_t *occ, uint32_t *reach, uint32_t *flag) {
   __shared__ uint32_t r[kFillHalo * kFillHalo * kFillMaxWords];
   __shared__ uint32_t e[kFillTile * kFillTile * kFillMaxWords];
   const int nw = B.nw;
@@ -150,7 +102,7 @@ __global__ __launch_bounds__(256) void fill_flood_kernel(const FillBox B, const 
   for (int i = (int)threadIdx.x; i < kFillTile * kFillTile * nw; i += 256) {
     const int t = i / nw, w = i - t * nw;
     const int y = ty0 + t % kFillTile, z = tz0 + t / kFillTile;
-    e[i] = (y < B.ey && z < B.ez) ? ~occ[((uint32_t)z * (uint32_t)B.ey + (uint32_t)y) * (uint32_t)nw + (uint32_t)w] & fill_valid(B, w) : 0u;
+    e[i] = (y < B.ey && z < B.ez) ? ~occ[((uint32_t)z * (uint32_t)B.ey + (uint32_t)y) * (uint32_t)nw + (uint32_t)w] & bitvol_valid(B, w) : 0u;
   }
   __syncthreads();
   int any = 0, changed;
@@ -194,26 +146,14 @@ __global__ __launch_bounds__(256) void fill_flood_kernel(const FillBox B, const 
 }
 
 // the enclosed bits of word g that the mask keeps
-__device__ __forceinline__ uint32_t fill_enclosed_bits(const FillBox &B, const uint32_t *occ, const uint32_t *reach, uint32_t g,
+__device__ __forceinline__ uint32_t fill_enclosed_bits(const BitBox &B, const uint32_t *occ, const uint32_t *reach, uint32_t g,
                                                        const RegionShape *shapes, uint32_t n_shapes, int *x0, int *y, int *z) {
-  const int w = (int)(g % (uint32_t)B.nw);
-  const uint32_t row = g / (uint32_t)B.nw;
-  *x0 = (B.wx0 + w) << 5; *y = B.lo[1] + (int)(row % (uint32_t)B.ey); *z = B.lo[2] + (int)(row / (uint32_t)B.ey);
-  uint32_t bits = ~occ[g] & ~reach[g] & fill_valid(B, w);
-  if (n_shapes) {
-    uint32_t kept = 0;
-    for (uint32_t b = bits; b; b &= b - 1u) {
-      const int bit = __ffs((int)b) - 1;
-      bool in = false;
-      for (uint32_t s = 0; s < n_shapes && !in; s++) in = region_inside(shapes[s], *x0 + bit, *y, *z);
-      if (in) kept |= 1u << bit;
-    }
-    bits = kept;
-  }
-  return bits;
+  const int w = bitvol_word(B, g, x0, y, z);
+  const uint32_t bits = ~occ[g] & ~reach[g] & bitvol_valid(B, w);
+  return n_shapes ? bitvol_inside(bits, shapes, n_shapes, *x0, *y, *z) : bits;
 }
 
-__global__ __launch_bounds__(256) void fill_count_kernel(const FillBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
+__global__ __launch_bounds__(256) void fill_count_kernel(const BitBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
                                                         uint32_t n_shapes, uint32_t *count) {
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   if (g > B.n_words) return;
@@ -222,15 +162,8 @@ __global__ __launch_bounds__(256) void fill_count_kernel(const FillBox B, const 
   count[g] = (uint32_t)__popc(fill_enclosed_bits(B, occ, reach, g, shapes, n_shapes, &x0, &y, &z));
 }
 
-// index of key k in the sorted keys[0, n) (k is there)
-__device__ __forceinline__ uint32_t fill_find(const uint32_t *keys, uint32_t n, uint32_t k) {
-  uint32_t lo = 0, hi = n;                                   // keys[lo] <= k < keys[hi]
-  while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (keys[mid] <= k) lo = mid; else hi = mid; }
-  return lo;
-}
-
 // fixed: material + 1 of every enclosed voxel, or 0: inherit along -x from W (wkeys / wvals, n_w sorted pairs)
-__global__ __launch_bounds__(256) void fill_emit_kernel(const FillBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
+__global__ __launch_bounds__(256) void fill_emit_kernel(const BitBox B, const uint32_t *occ, const uint32_t *reach, const RegionShape *shapes,
                                                        uint32_t n_shapes, const uint32_t *excl, uint32_t fixed, const uint32_t *wkeys,
                                                        const uint32_t *wvals, uint32_t n_w, uint32_t *keys, uint32_t *vals) {
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -244,23 +177,15 @@ __global__ __launch_bounds__(256) void fill_emit_kernel(const FillBox B, const u
       uint32_t below = occ[g] & ((1u << bit) - 1u);
       int xw = x0;
       for (uint32_t q = g; !below && xw > (B.wx0 << 5);) { q--; xw -= 32; below = occ[q]; }   // stays in the row: see the header
-      m = below ? wvals[fill_find(wkeys, n_w, region_key(xw + 31 - __clz((int)below), y, z))] : 1u;
+      m = below ? wvals[bitvol_find(wkeys, n_w, region_key(xw + 31 - __clz((int)below), y, z))] : 1u;
     }
     keys[pos] = region_key(x0 + bit, y, z); vals[pos] = m;
     pos++;
   }
 }
 
-__global__ __launch_bounds__(256) void fill_list_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, int4 *out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t k = keys[i];
-  out[i] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)vals[i]);
-}
-
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the enclosed-space fill";
 
 // what one call asks for, validated on the host before anything is queued
@@ -273,17 +198,8 @@ int make_request(tdt_ctx *ctx, const tdt_fill *f, const tdt_region *regions, siz
   if (!f) return fail(ctx, TDT_ERR_INVALID_VALUE, "null tdt_fill pointer");
   if (f->connectivity != 6 && f->connectivity != 26) return fail(ctx, TDT_ERR_INVALID_VALUE, "connectivity must be 6 or 26");
   if (f->material < -1 || f->material > 253) return fail(ctx, TDT_ERR_INVALID_VALUE, "material must be -1 (inherit) or 0..253");
-  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
   R.f = *f;
-  R.shapes.assign(n_regions, RegionShape{});
-  for (size_t s = 0; s < n_regions; s++) {
-    const tdt_region &g = regions[s];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-    R.shapes[s].shape = g.shape;
-    for (int a = 0; a < 3; a++) { R.shapes[s].a[a] = g.a[a]; R.shapes[s].b[a] = g.b[a]; }
-  }
-  return TDT_OK;
+  return region_shapes(ctx, regions, n_regions, &R.shapes);
 }
 
 // E(W, c) within the mask, or (with_walls) W + E(W, c), as {x, y, z, material + 1}, Morton-sorted, in device memory of ctx
@@ -296,29 +212,16 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
   if (n_w == 0) return TDT_OK;                             // nothing encloses anything
   hipStream_t st = ctx->stream;
   // ---- bbox(W) ----
-  int box[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
-  int *d_box = S.get<int>(6);
+  int box[6];
   uint32_t *wk = S.get<uint32_t>(n_w), *wv = S.get<uint32_t>(n_w);
-  if (!d_box || !wk || !wv) return fail(front, TDT_ERR_HIP, kNoMemory);
-  TDT_HIP(front, hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(fill_bbox_kernel, dim3(blocks_of(n_w)), dim3(256), 0, st, w, n_w, d_box);
-  TDT_HIP(front, hipGetLastError());
-  TDT_HIP(front, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the box sizes the volumes
-  const int N = 1 << depth;
-  for (int a = 0; a < 3; a++)
-    if (box[a] < 0 || box[3 + a] >= N || box[a] > box[3 + a]) return fail(front, TDT_ERR_INVALID_VALUE, "a wall voxel lies outside the grid");
-  FillBox B;
-  std::memset(&B, 0, sizeof B);
-  for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }
-  B.ey = B.hi[1] - B.lo[1] + 1; B.ez = B.hi[2] - B.lo[2] + 1;
-  B.wx0 = B.lo[0] >> 5; B.nw = (B.hi[0] >> 5) - B.wx0 + 1;
-  B.n_words = (uint32_t)B.ey * (uint32_t)B.ez * (uint32_t)B.nw;
+  if (!wk || !wv) return fail(front, TDT_ERR_HIP, kNoMemory);
+  if (int rc = bitvol_list_bbox(front, st, w, n_w, depth, S, kNoMemory, "a wall voxel lies outside the grid", box)) return rc;
+  BitBox B;
+  bitvol_layout(box, box + 3, B);
   // ---- occupancy, seeds ----
   uint32_t *occ = S.get<uint32_t>(B.n_words), *reach = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kFillBatch);
   if (!occ || !reach || !flags) return fail(front, TDT_ERR_HIP, kNoMemory);
-  TDT_HIP(front, hipMemsetAsync(occ, 0, (size_t)B.n_words * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(fill_rasterise_kernel, dim3(blocks_of(n_w)), dim3(256), 0, st, w, n_w, B, occ, wk, wv);
+  if (int rc = bitvol_rasterise(front, st, w, n_w, B, occ, wk, wv)) return rc;
   hipLaunchKernelGGL(fill_seed_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, reach);
   TDT_HIP(front, hipGetLastError());
   // ---- flood: a box thinner than 3 rows on an axis is all faces, and seeded whole ----
@@ -342,11 +245,7 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
   // ---- count ----
   RegionShape *d_shapes = nullptr;
   const uint32_t n_shapes = with_walls ? 0u : (uint32_t)R.shapes.size();
-  if (n_shapes) {
-    d_shapes = S.get<RegionShape>(n_shapes);
-    if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
-    TDT_HIP(front, hipMemcpyAsync(d_shapes, R.shapes.data(), n_shapes * sizeof(RegionShape), hipMemcpyHostToDevice, st));
-  }
+  if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
   uint32_t *count = S.get<uint32_t>((size_t)B.n_words + 1), *scr = S.get<uint32_t>(scan_scratch_words((size_t)B.n_words + 1));
   if (!count || !scr) return fail(front, TDT_ERR_HIP, kNoMemory);
   hipLaunchKernelGGL(fill_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
@@ -360,10 +259,8 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
   const uint32_t n_out = n_e + (with_walls ? n_w : 0u);
   if (n_out == 0) return TDT_OK;
   // ---- emit, sort ----
-  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out), *k1 = S.get<uint32_t>(n_out), *v1 = S.get<uint32_t>(n_out);
-  uint32_t *hist = S.get<uint32_t>(sort_hist_words(n_out)), *hscr = S.get<uint32_t>(sort_scratch_words(n_out));
-  int4 *vox = S.get<int4>(n_out);
-  if (!k0 || !v0 || !k1 || !v1 || !hist || !hscr || !vox) return fail(front, TDT_ERR_HIP, kNoMemory);
+  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
+  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
   const uint32_t at = with_walls ? n_w : 0u;
   if (with_walls) {
     TDT_HIP(front, hipMemcpyAsync(k0, wk, (size_t)n_w * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -373,12 +270,8 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
     hipLaunchKernelGGL(fill_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
                        (const RegionShape *)d_shapes, n_shapes, (const uint32_t *)count, R.f.material >= 0 ? (uint32_t)R.f.material + 1u : 0u,
                        (const uint32_t *)wk, (const uint32_t *)wv, n_w, k0 + at, v0 + at);
-  uint32_t *k = k0, *v = v0;
-  TDT_HIP(front, sort_pairs_u32(st, k, v, k1, v1, n_out, hist, hscr));
-  hipLaunchKernelGGL(fill_list_kernel, dim3(blocks_of(n_out)), dim3(256), 0, st, (const uint32_t *)k, (const uint32_t *)v, n_out, vox);
-  TDT_HIP(front, hipGetLastError());
-  TDT_HIP(front, hipStreamSynchronize(st));
-  *out = vox; *n = n_out;
+  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, true, S, kNoMemory, out)) return rc;
+  *n = n_out;
   return TDT_OK;
 }
 
@@ -411,17 +304,12 @@ struct FillSource final : VoxelSource {
 int fill_extract(tdt_ctx *ctx, const Request &R, const tdt_mesh *mesh, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {
   tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
   TDT_HIP(ctx, hipSetDevice(m->device));
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};
+  Drain drain{m->stream};
   DeviceScratch S;
   const int4 *vox = nullptr;
   uint32_t n = 0;
   if (int rc = fill_list(ctx, m, R, mesh, depth, S, &vox, &n)) return rc;
-  *n_out = n;
-  if (!host_out || n == 0) return TDT_OK;
-  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " voxels");
-  TDT_HIP(ctx, hipMemcpyAsync(host_out, vox, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost, m->stream));
-  TDT_HIP(ctx, hipStreamSynchronize(m->stream));
-  return TDT_OK;
+  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", host_out, capacity, n_out);
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 // tdt_multi.hip: the multi-device context; tdt_build.hip: the GPU octree builder; tdt_edit.hip: voxel edits;
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
 // tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
-// tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance).
+// tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance;
+// tdt_bitvol.hip: the dense bit volume the last two share).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,7 +27,7 @@ struct CostSig {
   struct { const void *buffer; unsigned long long version; } slot[kNumSlots];
 };
 
-namespace tdt { struct Multi; struct EditScratch; struct TraceState; }
+namespace tdt { struct Multi; struct EditScratch; struct TraceState; struct BitBox; }
 struct TraceParams;
 
 struct tdt_buffer {
@@ -82,6 +83,22 @@ namespace tdt {
 int fail(tdt_ctx *ctx, int code, const std::string &msg);           // records the message, returns the code
 int hip_fail(tdt_ctx *ctx, hipError_t e, const char *what);
 #define TDT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return tdt::hip_fail((ctx), e_, #call); } while (0)
+
+// blocks of 256 lanes: every kernel of the editing units is launched with these
+inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
+// synchronises the stream when it leaves scope: declared after what the stream's queued work still reads or writes
+struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } };
+// the tail of the calls that list into host memory by tdt_octree_extract's rules: *n_out = n, and when host_out is given and
+// n > 0 the capacity check ("capacity C < n <items>"), the copy of n items of item_bytes and one synchronisation
+inline int list_to_host(tdt_ctx *ctx, hipStream_t st, const void *dev, size_t n, size_t item_bytes, const char *items, void *host_out,
+                        size_t capacity, size_t *n_out) {
+  *n_out = n;
+  if (!host_out || n == 0) return TDT_OK;
+  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " " + items);
+  TDT_HIP(ctx, hipMemcpyAsync(host_out, dev, n * item_bytes, hipMemcpyDeviceToHost, st));
+  TDT_HIP(ctx, hipStreamSynchronize(st));
+  return TDT_OK;
+}
 
 template <class T> void erase_from(std::vector<T *> &v, T *p) {
   for (size_t i = 0; i < v.size(); i++) if (v[i] == p) { v.erase(v.begin() + i); return; }
@@ -193,6 +210,21 @@ int check_mesh(tdt_ctx *ctx, const tdt_mesh *m);
 // the voxels of a mesh that passed check_mesh, {x, y, z, material + 1}, Morton-sorted and unique, in device memory of ctx
 // (allocated in S; null when *n == 0).  Queued on ctx's stream; synchronises.  Errors are reported on `front`.
 int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, DeviceScratch &S, const int4 **out, uint32_t *n);
+
+// ---- tdt_bitvol.hip: the dense bit volume over a box of the grid (layout: bitvol_device.hpp), as enclosed space and exact
+// distance use it.  Everything is queued on `st`; errors are reported on `front`; no_memory is the caller's out-of-memory text ----
+// B over lo..hi (inclusive, inside the grid)
+void bitvol_layout(const int lo[3], const int hi[3], BitBox &B);
+// the bounding box of n > 0 voxels {x, y, z, m} in device memory: box[0..2] = min, box[3..5] = max.  One synchronisation.
+// A voxel outside the grid of side 2^depth: TDT_ERR_INVALID_VALUE with the text `outside`.
+int bitvol_list_bbox(tdt_ctx *front, hipStream_t st, const int4 *v, uint32_t n, int depth, DeviceScratch &S, const char *no_memory,
+                     const char *outside, int box[6]);
+// occ (B.n_words words) cleared, then the bits of the voxels inside B set; keys / vals (n each) = every voxel's Morton key and m
+int bitvol_rasterise(tdt_ctx *front, hipStream_t st, const int4 *v, uint32_t n, const BitBox &B, uint32_t *occ, uint32_t *keys, uint32_t *vals);
+// the end of an emit: n > 0 pairs (Morton key, m) in k / v, sorted by key first if asked, into *out = n voxels {x, y, z, m}
+// allocated in S.  Synchronises.
+int bitvol_emit_list(tdt_ctx *front, hipStream_t st, uint32_t *k, uint32_t *v, uint32_t n, bool sort, DeviceScratch &S, const char *no_memory,
+                     const int4 **out);
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);

@@ -257,7 +257,6 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(const uint32_t *keys, co
 
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the mesh voxelisation";
 
 // level-1 candidates of the whole mesh on a grid of side 2^depth (what mesh_setup_kernel's counts sum to)
@@ -400,17 +399,12 @@ int tdt_voxelize_triangles(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, int32_
   if (int rc = check_mesh(ctx, mesh)) return rc;
   tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
   TDT_HIP(ctx, hipSetDevice(m->device));
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};
+  Drain drain{m->stream};
   DeviceScratch S;
   const int4 *vox = nullptr;
   uint32_t n = 0;
   if (int rc = mesh_voxels(ctx, m, mesh, depth, S, &vox, &n)) return rc;
-  *n_voxels = n;
-  if (!voxels_xyzm || n == 0) return TDT_OK;
-  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " voxels");
-  TDT_HIP(ctx, hipMemcpyAsync(voxels_xyzm, vox, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost, m->stream));
-  TDT_HIP(ctx, hipStreamSynchronize(m->stream));
-  return TDT_OK;
+  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_edit_triangles(tdt_ctx *ctx, int op, const tdt_mesh *mesh, uint32_t *n_cells) {

@@ -177,7 +177,6 @@ __global__ __launch_bounds__(256) void morph_mask_tree_kernel(const int4 *v, con
 
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the voxel morphology";
 
 // a voxel list with its keys; `mem` owns it and the temporaries of the step that made it (kernels of the NEXT step still read
@@ -274,17 +273,8 @@ int make_request(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions, si
   if (m->radius < 1 || m->radius > 64) return fail(ctx, TDT_ERR_INVALID_VALUE, "radius must be 1..64");
   if (m->material < -1 || m->material > 253) return fail(ctx, TDT_ERR_INVALID_VALUE, "material must be -1 (inherit) or 0..253");
   if (m->border != 0 && m->border != 1) return fail(ctx, TDT_ERR_INVALID_VALUE, "border must be 0 or 1");
-  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
   R.m = *m;
-  R.shapes.assign(n_regions, RegionShape{});
-  for (size_t s = 0; s < n_regions; s++) {
-    const tdt_region &g = regions[s];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-    R.shapes[s].shape = g.shape;
-    for (int a = 0; a < 3; a++) { R.shapes[s].a[a] = g.a[a]; R.shapes[s].b[a] = g.b[a]; }
-  }
-  return TDT_OK;
+  return region_shapes(ctx, regions, n_regions, &R.shapes);
 }
 
 // one single-device context: the edit (n_cells) or, host_out / n_out, the result into host memory
@@ -295,7 +285,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
   uint32_t word = 0;
   DeviceScratch S;                                       // V, its keys, the shapes, the combine pass
   std::unique_ptr<List> prev, cur, next;
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};   // before anything above is freed
+  Drain drain{st};                                       // before anything above is freed
   int4 *v0 = nullptr;
   uint32_t nv = 0;
   int depth = 0;
@@ -307,11 +297,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
     uint32_t *k0 = S.get<uint32_t>(nv);
     RegionShape *d_shapes = nullptr;
     if (!k0) return fail(front, TDT_ERR_HIP, kNoMemory);
-    if (!R.shapes.empty()) {
-      d_shapes = S.get<RegionShape>(R.shapes.size());
-      if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
-      TDT_HIP(front, hipMemcpyAsync(d_shapes, R.shapes.data(), R.shapes.size() * sizeof(RegionShape), hipMemcpyHostToDevice, st));
-    }
+    if (int rc = upload_shapes(front, st, S, R.shapes.data(), R.shapes.size(), kNoMemory, &d_shapes)) return rc;
     hipLaunchKernelGGL(morph_keys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v0, nv, k0);
     cur.reset(new List);
     cur->v = v0; cur->k = k0; cur->n = nv;               // (owned by S)
@@ -365,15 +351,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
     }
     if (n_res > kMorphCap) return fail(front, TDT_ERR_INVALID_VALUE, "the result holds " + std::to_string(n_res) + " voxels (more than 2^26)");
   }
-  if (extract) {
-    *n_out = n_res;
-    if (!host_out || n_res == 0) return TDT_OK;
-    if (capacity < n_res)
-      return fail(front, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n_res) + " voxels");
-    TDT_HIP(front, hipMemcpyAsync(host_out, res, (size_t)n_res * sizeof(int4), hipMemcpyDeviceToHost, st));
-    TDT_HIP(front, hipStreamSynchronize(st));
-    return TDT_OK;
-  }
+  if (extract) return list_to_host(front, st, res, n_res, sizeof(int4), "voxels", host_out, capacity, n_out);
   // ---- rebuild and install ----
   tdt_buffer *built = nullptr;
   uint32_t nc = 1;

@@ -146,7 +146,6 @@ __global__ __launch_bounds__(256) void region_gather_kernel(const int4 *slot, co
 
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the region edit";
 
 // what one call asks for, validated on the host before anything is queued
@@ -171,14 +170,9 @@ int check_request(tdt_ctx *ctx, const Request &R) {
           return fail(ctx, TDT_ERR_INVALID_VALUE, "voxel " + std::to_string(i) + ": m must be 1..254");
     return TDT_OK;
   }
-  if (R.n_regions && !R.regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
+  if (R.n_regions && !R.regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");   // (ahead of the material, as ever)
   if (R.material < 0 || R.material > 253) return fail(ctx, TDT_ERR_INVALID_VALUE, "material must be 0..253");
-  for (size_t s = 0; s < R.n_regions; s++) {
-    const tdt_region &g = R.regions[s];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-  }
-  return TDT_OK;
+  return region_shapes(ctx, R.regions, R.n_regions, nullptr);    // clip_shapes makes the shapes, once the depth is known
 }
 
 // the shapes with their bounding boxes clipped to a grid of side N; *lanes = the candidates of all of them
@@ -221,7 +215,7 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
   hipStream_t st = ctx->stream;
   TDT_HIP(front, hipSetDevice(ctx->device));
   uint32_t b_raw = 0, n_res = 0;                          // host words the stream writes: the guard below outlives them
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+  Drain drain{st};
   DeviceScratch S;
   const int4 *src_vox = nullptr;                          // the device-resident list
   uint32_t src_n = 0;
@@ -233,11 +227,7 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
   uint32_t *bk = nullptr, *bv = nullptr, *bk_alt = nullptr, *bv_alt = nullptr, *b_count = nullptr;
   RegionShape *d_shapes = nullptr;
   b_raw = b_cap;
-  if (!shapes.empty()) {
-    d_shapes = S.get<RegionShape>(shapes.size());
-    if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
-    TDT_HIP(front, hipMemcpyAsync(d_shapes, shapes.data(), shapes.size() * sizeof(RegionShape), hipMemcpyHostToDevice, st));
-  }
+  if (int rc = upload_shapes(front, st, S, shapes.data(), shapes.size(), kNoMemory, &d_shapes)) return rc;
   if (build_b && b_cap) {
     bk = S.get<uint32_t>(b_cap); bv = S.get<uint32_t>(b_cap); bk_alt = S.get<uint32_t>(b_cap); bv_alt = S.get<uint32_t>(b_cap);
     b_count = S.get<uint32_t>(2);
@@ -310,15 +300,7 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
     TDT_HIP(front, hipMemcpyAsync(&n_res, keep + n_slots, sizeof n_res, hipMemcpyDeviceToHost, st));
     TDT_HIP(front, hipStreamSynchronize(st));             // the merged count
   }
-  if (R.op == kOpIntersect) {
-    *n_out = n_res;
-    if (!host_out || n_res == 0) return TDT_OK;
-    if (capacity < n_res)
-      return fail(front, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n_res) + " voxels");
-    TDT_HIP(front, hipMemcpyAsync(host_out, res, (size_t)n_res * sizeof(int4), hipMemcpyDeviceToHost, st));
-    TDT_HIP(front, hipStreamSynchronize(st));
-    return TDT_OK;
-  }
+  if (R.op == kOpIntersect) return list_to_host(front, st, res, n_res, sizeof(int4), "voxels", host_out, capacity, n_out);
   // ---- rebuild and install ----
   tdt_buffer *built = nullptr;
   uint32_t nc = 1;

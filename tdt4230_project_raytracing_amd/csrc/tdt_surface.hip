@@ -168,7 +168,6 @@ __global__ __launch_bounds__(256) void surface_quads_kernel(const uint32_t *rk, 
 
 namespace {
 
-inline unsigned blocks_of(unsigned long long lanes) { return (unsigned)((lanes + 255) / 256); }
 const char *kNoMemory = "out of device memory in the surface extraction";
 
 struct Request {
@@ -180,17 +179,8 @@ int make_request(tdt_ctx *ctx, const tdt_surface *s, const tdt_region *regions, 
   if (!s) return fail(ctx, TDT_ERR_INVALID_VALUE, "null tdt_surface pointer");
   if (s->merge != 0 && s->merge != 1) return fail(ctx, TDT_ERR_INVALID_VALUE, "merge must be 0 or 1");
   if (s->by_material != 0 && s->by_material != 1) return fail(ctx, TDT_ERR_INVALID_VALUE, "by_material must be 0 or 1");
-  if (n_regions && !regions) return fail(ctx, TDT_ERR_INVALID_VALUE, "null region list");
   R.s = *s;
-  R.shapes.assign(n_regions, RegionShape{});
-  for (size_t i = 0; i < n_regions; i++) {
-    const tdt_region &g = regions[i];
-    if (g.shape != TDT_SHAPE_BOX && g.shape != TDT_SHAPE_SPHERE) return fail(ctx, TDT_ERR_INVALID_VALUE, "shape must be TDT_SHAPE_BOX or TDT_SHAPE_SPHERE");
-    if (g.shape == TDT_SHAPE_SPHERE && g.b[0] < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "sphere radius must be >= 0");
-    R.shapes[i].shape = g.shape;
-    for (int a = 0; a < 3; a++) { R.shapes[i].a[a] = g.a[a]; R.shapes[i].b[a] = g.b[a]; }
-  }
-  return TDT_OK;
+  return region_shapes(ctx, regions, n_regions, &R.shapes);
 }
 
 struct Pass {
@@ -242,11 +232,7 @@ int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch 
   RegionShape *d_shapes = nullptr;
   if (!keys || !mask || !cnt || !scr || !d_bounds) return fail(front, TDT_ERR_HIP, kNoMemory);
   const uint32_t n_shapes = (uint32_t)R.shapes.size();
-  if (n_shapes) {
-    d_shapes = S.get<RegionShape>(n_shapes);
-    if (!d_shapes) return fail(front, TDT_ERR_HIP, kNoMemory);
-    TDT_HIP(front, hipMemcpyAsync(d_shapes, R.shapes.data(), n_shapes * sizeof(RegionShape), hipMemcpyHostToDevice, st));
-  }
+  if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
   hipLaunchKernelGGL(surface_keys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, keys);
   hipLaunchKernelGGL(surface_probe_kernel, dim3(blocks_of(stride)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)keys, nv, depth,
                      (const RegionShape *)d_shapes, n_shapes, mask, cnt);
@@ -320,16 +306,11 @@ int tdt_octree_extract_surface(tdt_ctx *ctx, const tdt_surface *opt, const tdt_r
   tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
   TDT_HIP(ctx, hipSetDevice(m->device));
   DeviceScratch S;
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{m->stream};   // before S is freed
+  Drain drain{m->stream};                                // before S is freed
   const int4 *d_quads = nullptr;
   uint32_t n = 0;
   if (int rc = surface_quads(ctx, m, R, S, &d_quads, &n)) return rc;
-  *n_quads = n;
-  if (!quads || n == 0) return TDT_OK;
-  if (capacity < n) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " quads");
-  TDT_HIP(ctx, hipMemcpyAsync(quads, d_quads, (size_t)n * sizeof(tdt_quad), hipMemcpyDeviceToHost, m->stream));
-  TDT_HIP(ctx, hipStreamSynchronize(m->stream));
-  return TDT_OK;
+  return list_to_host(ctx, m->stream, d_quads, n, sizeof(tdt_quad), "quads", quads, capacity, n_quads);
 }
 
 }  // extern "C"

@@ -57,8 +57,7 @@ def test_distance_kernels_have_no_scratch_and_no_spills():
     import kernel_resources
     rows = kernel_resources.collect("tdt_distance.hip")
     names = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in rows}
-    assert {"dist_bbox_kernel", "dist_rasterise_kernel", "dist_pass_x_kernel", "dist_scan_kernel", "dist_count_kernel", "dist_emit_kernel",
-            "dist_list_kernel"} <= names
+    assert {"dist_pass_x_kernel", "dist_scan_kernel", "dist_count_kernel", "dist_emit_kernel"} <= names     # the shared steps: test_bitvol_api.py
     assert sum("dist_scan_kernel<" in r["name"] for r in rows) == 3          # pass y, pass z into bits, pass z into the field
     for r in rows:
         assert r["ScratchSize [bytes/lane]"] == 0, r["name"]

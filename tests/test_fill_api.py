@@ -49,8 +49,7 @@ def test_fill_kernels_have_no_scratch_and_no_spills():
     import kernel_resources
     rows = kernel_resources.collect("tdt_fill.hip")
     names = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in rows}
-    assert {"fill_bbox_kernel", "fill_rasterise_kernel", "fill_seed_kernel", "fill_flood_kernel", "fill_count_kernel", "fill_emit_kernel",
-            "fill_list_kernel"} <= names
+    assert {"fill_seed_kernel", "fill_flood_kernel", "fill_count_kernel", "fill_emit_kernel"} <= names     # the shared steps: test_bitvol_api.py
     assert sum("fill_flood_kernel<" in r["name"] for r in rows) == 2         # connectivity 6 and 26
     for r in rows:
         assert r["ScratchSize [bytes/lane]"] == 0, r["name"]

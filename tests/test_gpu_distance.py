@@ -13,6 +13,7 @@ import pytest
 import distance_model as dm
 import morph_model as mm
 from test_gpu_connect import bind_tree, block
+from test_gpu_fill import strided_bbox_tree
 from test_gpu_region_edit import bind_cells, built_cells, padded, sort_vox
 from tdt4230_project_raytracing_amd import build, host, rt
 
@@ -439,3 +440,21 @@ def test_demo_morph_round_leaves_the_model_tree(tmp_path):
                        timeout=300)
     assert p.returncode == 0, p.stderr
     assert re.search(rf"morph-round dilate:5 border 1 cells {n}\b", p.stdout), p.stdout
+
+
+# ---- 8. a list longer than one trip of the bounding box's strided loop ---------------------------------------------------------
+def test_list_longer_than_the_bounding_box_launch(ctx):
+    """The tree of test_gpu_fill.py whose bounding box is owed to the later trips of tdt_bitvol.hip's strided loop: a round op
+    sizes its domain by that box, the field rasterises the same long list into a box of its own."""
+    depth, V, _ = strided_bbox_tree()
+    bind_tree(ctx, V, depth)
+    for material in (None, 9):
+        want = dm.round_op(V, depth, rt.MORPH_DILATE, 1, material)
+        assert len(want) > len(V) and set(want[:, 3]) == ({int(V[0, 3])} if material is None else {int(V[0, 3]), material + 1})
+        same(ctx.octree_extract_morph_round(rt.MORPH_DILATE, 1, material), want, material)
+    lo, hi = (5, 6, 7), (14, 12, 13)                            # across the shell's corner: outside, wall and cavity
+    f, near = ctx.octree_distance_field(lo, hi, 9, nearest=True)
+    wf, wn = dm.field(V, depth, lo, hi, 9)
+    assert (wf < 0).any() and (wf > 0).any()
+    same(f, wf, "field")
+    same(near, wn, "nearest")

@@ -3,6 +3,7 @@ tdt_octree_edit_triangles_solid): the voxel lists must equal the numpy model (te
 faces on a dense grid) or the closed forms of the definition element for element, and the edit forms must leave in the bound
 cells buffer exactly what tdt_octree_edit_voxels of those lists leaves."""
 import ctypes
+import functools
 import re
 import subprocess
 
@@ -699,3 +700,37 @@ def test_demo_solid_mesh_and_fill_enclosed(oracle, tmp_path):
     assert re.search(rf"fill-enclosed conn 26 voxels {len(E)} cells {len(refilled) // 16}\b", p.stdout), p.stdout
     ref = oracle.render(host.Scene({**scene.blobs, 0: padded(refilled, 64 * room)}), cam, threads=8)
     assert (read_pfm(out).view(np.uint32) == ref.view(np.uint32)).all()
+
+
+# ---- 9. a list longer than one trip of the bounding box's strided loop ---------------------------------------------------------
+BBOX_LAUNCH = 256 * 256                                        # lanes of tdt_bitvol.hip's bounding-box launch: a lane's first trip covers these
+
+
+@functools.lru_cache(maxsize=None)
+def strided_bbox_tree():
+    """(depth, V, the voxels the shell encloses): a shell two voxels thick from (8,8,8) to (119,119,119), its cavity (10..117)^3,
+    and two stray voxels in far corners of the grid, one material throughout.  Made once; callers do not write to it."""
+    depth, m = 7, 6
+    shell = block((8, 8, 8), (119, 119, 119), m)
+    shell = shell[((shell[:, :3] < 10) | (shell[:, :3] > 117)).any(1)]
+    V = sort_vox(np.concatenate([shell, [[127, 127, 0, m], [127, 127, 127, m]]]))
+    V.setflags(write=False)
+    return depth, V, block((10, 10, 10), (117, 117, 117), m)
+
+
+def test_bounding_box_of_a_list_longer_than_its_launch(ctx):
+    """bbox(V) needs the later trips of the strided loop: one axis minimum and one axis maximum lie beyond the first 65 536
+    voxels of the Morton-sorted list, so a kernel that stopped after a lane's first voxel would size the volume wrongly."""
+    depth, V, inside = strided_bbox_tree()
+    assert len(V) == 145218 > 2 * BBOX_LAUNCH
+    head = V[:BBOX_LAUNCH, :3]
+    assert (head[:, 0].min(), head[:, 0].max(), head[:, 2].min(), head[:, 2].max()) == (8, 63, 8, 119)
+    assert (V[:, 0].min(), V[:, 0].max(), V[:, 2].min(), V[:, 2].max()) == (8, 127, 0, 127)
+    want = {conn: fm.enclosed(V, depth, conn) for conn in (6, 26)}
+    for conn in (6, 26):
+        assert len(want[conn]) == 108 ** 3
+        same(want[conn], sort_vox(inside), "the cavity, whole")
+    bind_tree(ctx, V, depth)
+    for conn in (6, 26):
+        same(ctx.octree_extract_enclosed(conn), want[conn], conn)
+    same(ctx.octree_extract(), V, "the tree is untouched")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""csrc/tdt_distance.hip — kernels and host code, unchanged — compiled for the CPU and run against an all-pairs brute force and
-the ops' definitions, under AddressSanitizer and UBSan.  No GPU, no HIP: hip/hip_runtime.h here (on top of tools/fill_hostsim's)
+"""csrc/tdt_distance.hip and the bit-volume unit it shares with enclosed space, csrc/tdt_bitvol.hip — kernels and host code,
+unchanged — compiled for the CPU and run against an all-pairs brute force and the ops' definitions, under AddressSanitizer and
+UBSan.  No GPU, no HIP: hip/hip_runtime.h here (on top of tools/fill_hostsim's)
 stands in for the constructs the unit uses, tools/fill_hostsim/device_scan.hpp for the scan, and main.cpp supplies the pieces of
 the sibling units the unit calls (the slot check, the tree's voxel list, the sort, the edit that takes the delta list) and the
 cases, about twenty, hand-picked because a block is 256 real threads and every case costs seconds: one sparse and one dense random
@@ -26,13 +27,15 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         # the unit is compiled from a copy next to the stand-in headers, so that its quoted includes find those first
         shutil.copy(os.path.join(CSRC, "tdt_distance.hip"), os.path.join(tmp, "distance_unit.cpp"))
-        shutil.copy(os.path.join(CSRC, "region_device.hpp"), tmp)
+        shutil.copy(os.path.join(CSRC, "tdt_bitvol.hip"), os.path.join(tmp, "bitvol_unit.cpp"))
+        for f in ("region_device.hpp", "bitvol_device.hpp"):
+            shutil.copy(os.path.join(CSRC, f), tmp)
         shutil.copy(os.path.join(FILL, "device_scan.hpp"), tmp)
         shutil.copy(os.path.join(HERE, "main.cpp"), tmp)
         exe = os.path.join(tmp, "distance_hostsim")
         subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
                         "-I", tmp, "-I", HERE, "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-x", "c++",
-                        os.path.join(tmp, "distance_unit.cpp"), os.path.join(tmp, "main.cpp"), "-o", exe], check=True)
+                        os.path.join(tmp, "distance_unit.cpp"), os.path.join(tmp, "bitvol_unit.cpp"), os.path.join(tmp, "main.cpp"), "-o", exe], check=True)
         return subprocess.run([exe] + sys.argv[1:]).returncode
 
 
