@@ -375,6 +375,25 @@ class Octree {
     if (n) ctx.check(tdt_octree_distance_field(ctx.raw(), lo, hi, max_d2, border, f.data(), nearest ? nearest->data() : nullptr, n, &n));
     return f;
   }
+  // NEW: move, turn, mirror, rotate or scale a selection (tdt_octree_transform): x is the destination -> source map (the
+  // tdt_xform_* builders of tdt_host.h make one from a forward transform); the voxels of the tree inside the union of `mask`
+  // (none: all of it) are resampled through it and applied with op (TDT_REGION_*) as a voxel list that never leaves the device.
+  // The source voxels stay where they are.  Returns the number of cells.
+  uint32_t transform(const Context &ctx, const tdt_xform &x, int op = TDT_REGION_SET, const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_transform(ctx.raw(), &x, op, mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: the transformed selection itself, voxels {x, y, z, material + 1} in Morton order, the tree untouched
+  // (tdt_octree_extract_transform): the preview, and with a CLEAR of the source in between, the move
+  std::vector<int32_t> extract_transform(const Context &ctx, const tdt_xform &x, const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_transform(ctx.raw(), &x, r, mask.size(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_transform(ctx.raw(), &x, r, mask.size(), v.data(), n, &n));
+    return v;
+  }
   // NEW: stamp a triangle mesh (tdt_octree_edit_triangles): op (TDT_REGION_*) over the voxels the closed triangles touch —
   // vertices {x, y, z} fixed point, 64 units per voxel (tdt_mesh_quantize), triangles 3 vertex indices each, material 0..253 for
   // every triangle or, with `materials`, material + 1 per triangle (the highest covering triangle wins).  A surface

@@ -196,6 +196,42 @@ int tdt_quads_to_mesh(const int32_t *quads, size_t n_quads, int32_t *vertices, s
 int tdt_ply_mesh_write(const int32_t *vertices, size_t n_vertices, const uint32_t *triangles, size_t n_triangles, char *buffer,
                        size_t capacity, size_t *bytes);
 
+/* ---------------------------------------------------------------- affine transforms ---------- */
+/* Builders of struct tdt_xform (include/tdt_rt.h: the DESTINATION -> SOURCE map s = (a (2 p + 1) + t) >> 17 of
+ * tdt_octree_transform / tdt_octree_extract_transform) from the FORWARD transform a caller thinks in.  Each fills *out with
+ * material = -1 (keep the source voxel's) and dst = the whole grid (lo 0, hi INT32_MAX); set those two afterwards.  Returns 0,
+ * or 0x0501 with a message in tdt_host_last_error and *out untouched: a NULL pointer, a bad axis, an entry beyond the struct's
+ * limits (|a| <= 2^20, |t| <= 2^40), a singular matrix.
+ * pivot2 is a fixed point of the transform in DOUBLED coordinates: 2 c + 1 is the centre of voxel c, 2 c its low corner; (N, N, N)
+ * is the centre of a grid of side N.  The integer builders are exact: with R the forward matrix and P = pivot2,
+ * a = 65536 R^-1 and t = 65536 (P - R^-1 P).
+ *   identity        a = 65536 I, t = 0: s = p.
+ *   translate       the selection moves by d voxels (|d| <= 2^23): t = -d 2^17.
+ *   quarter_turns   k quarter turns (any integer, taken mod 4) about `axis` (0 x, 1 y, 2 z) through pivot2; k = 1 takes axis
+ *                   (axis + 1) % 3 towards axis (axis + 2) % 3: about z, x towards y, which with pivot2 = (N, N, N) is
+ *                   numpy.rot90(grid, 1, axes=(0, 1)) of a grid indexed [x, y, z].  A quarter turn is a bijection of the grid
+ *                   (and of the voxel lattice) exactly when the pivot2 components on the two turned axes have EQUAL PARITY;
+ *                   with unequal parity voxel centres land on voxel faces and the floor picks a side: still defined, no
+ *                   longer one to one.  Half turns (k = 2) and mirrors are bijections of the lattice for every pivot2.
+ *   mirror          the reflection of `axis` about the plane through pivot2[axis] (the other two components are not read).
+ *   scale           per axis by num / den (both >= 1) about pivot2: a = 65536 den / num rounded to nearest (halves up; exact
+ *                   when num divides 65536 den), t = (65536 - a) P, so the pivot stays fixed whatever the rounding.
+ *   from_affine     the forward map x' = F x + f on CONTINUOUS coordinates, where voxel c occupies [c, c + 1):
+ *                   fwd[4 i + j] = F_ij (j < 3), fwd[4 i + 3] = f_i.  F is inverted in double (adjugate / determinant) and
+ *                   a = rint(65536 F^-1), t = rint(-2^17 F^-1 f).  The maps above given as exact doubles reproduce the integer
+ *                   builders; in general the last bit rests on the platform's arithmetic and is not pinned.
+ *   rotate          by `degrees` about the line through `pivot` (continuous coordinates; the centre of voxel c is c + 1/2) along
+ *                   `axis` (any non-zero length), counter-clockwise seen against the axis: Rodrigues' matrix through
+ *                   from_affine; cos and sin come from libm, so the last bit is not pinned. */
+typedef struct tdt_xform tdt_xform;
+int tdt_xform_identity(tdt_xform *out);
+int tdt_xform_translate(const int32_t d[3], tdt_xform *out);
+int tdt_xform_quarter_turns(int axis, int k, const int32_t pivot2[3], tdt_xform *out);
+int tdt_xform_mirror(int axis, const int32_t pivot2[3], tdt_xform *out);
+int tdt_xform_scale(const int32_t num[3], const int32_t den[3], const int32_t pivot2[3], tdt_xform *out);
+int tdt_xform_from_affine(const double fwd[12], tdt_xform *out);
+int tdt_xform_rotate(const double axis[3], double degrees, const double pivot[3], tdt_xform *out);
+
 /* ---------------------------------------------------------------- pick-to-edit --------------- */
 /* The DeltaNode (8 floats: the 32-byte std430 stride of octree_update.comp:41-48) for a click on the voxel face a ray query found
  * (tdt_ray_hit, include/tdt_rt.h) — what the reference's click handler (main.rs:551-568) hands Octree::update_vbo, aimed at the

@@ -659,6 +659,53 @@ int tdt_octree_extract_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_r
 int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border, int32_t *field,
                               int32_t *nearest_xyz, size_t capacity, size_t *n_voxels);
 
+/* ---- affine transforms of voxel selections -------------------------------------------------------------------------------
+ * Move, turn, mirror, rotate and scale a selection by resampling.  N = 2^max_depth, G = [0, N)^3, V = what tdt_octree_extract
+ * returns, S = the voxels of V inside the mask: all of V with n_regions == 0, otherwise those inside the union of the regions
+ * (tdt_region shapes, the exact integer test of region edits).  The transform is given DESTINATION -> SOURCE, which makes the
+ * result onto by construction: no holes under a rotation or an enlargement.  For a destination voxel p, in int64,
+ *     q = 2 p + 1                                   (its doubled centre)
+ *     s_i = (a[3 i] q_x + a[3 i + 1] q_y + a[3 i + 2] q_z + t_i) >> 17,   i = x, y, z
+ * with >> the arithmetic shift (a floor, never a truncating divide), `a` in Q16 (TDT_XFORM_ONE = 65536 is 1.0) and `t` in units
+ * of 2^-17 voxel.  The result is
+ *     T = { (p, m) : p in G, dst_lo <= p <= dst_hi, s(p) in G, s(p) in S },
+ * m = the material + 1 of s(p) when `material` is -1, or `material` + 1 for 0..253; Morton-sorted by p by tdt_octree_extract's
+ * rules.  The identity is a = 65536 I, t = 0; a translation by d is t = -d 2^17; a = 32768 I doubles the selection about the
+ * corner of the grid.  include/tdt_host.h has builders (tdt_xform_translate, _quarter_turns, _mirror, _scale, _rotate,
+ * _from_affine) that fill the struct.
+ * tdt_octree_extract_transform returns T by tdt_octree_extract's rules (voxels_xyzm == NULL only counts; capacity < the count:
+ * TDT_ERR_INVALID_VALUE with *n_voxels set; a multi-device context answers from device_ids[0]) and leaves the tree, its counter
+ * and its versions untouched.  tdt_octree_transform is tdt_octree_edit_voxels with the list T, taken from the tree BEFORE the
+ * edit and never leaving the device: op TDT_REGION_SET / FILL / PAINT / CLEAR, the in-place rebuild by tdt_octree_compact's
+ * install rule on every replica of a multi-device context, a failure leaving all of them unchanged, *n_cells on a misfit.  The
+ * source voxels are not removed: a move is tdt_octree_extract_transform, tdt_octree_edit_region(CLEAR), tdt_octree_edit_voxels.
+ * Limits, checked on the host before anything is queued: |a[k]| <= 2^20 and |t_i| <= 2^40 (the sum then stays below 2^41),
+ * det(a) != 0, material -1..253, pad 0.  |V| and T are held to 2^26 voxels (TDT_REGION_BRUSH_CAP); T's size is known after the
+ * count pass and checked before the list is allocated.
+ * Errors, nothing written: a NULL struct or pointer, a limit exceeded, a bad op, a bad shape, NULL regions with a count above
+ * 0, a LEAF value >= 254: TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  An empty tree, mask or dst box is
+ * valid: T is empty.  Ordered after work queued on the context's stream; synchronous.
+ * tdt_debug_xform_bricks: of the context's last transform call, out = {the aligned 8 x 8 x 8 bricks of the destination domain
+ * (dst & G & a bounding box of the preimage of S's bounding box), those whose exact source box met S's bounding box and went
+ * through the count and emit passes}; DESIGN.md has the scheme. */
+#define TDT_XFORM_ONE 65536
+typedef struct tdt_xform {
+  int64_t t[3];                /* units of 2^-17 voxel, |t| <= 2^40 */
+  int32_t a[9];                /* row-major, destination -> source, Q16, |a| <= 2^20 */
+  int32_t material;            /* -1: the source voxel's; 0..253: this LEAF value */
+  int32_t dst_lo[3], dst_hi[3];  /* inclusive box the result is clipped to (then to the grid); lo > hi on an axis: empty */
+  int32_t pad[2];              /* must be 0 */
+} tdt_xform;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_xform) == 96, "tdt_xform is 96 bytes");
+#else
+_Static_assert(sizeof(tdt_xform) == 96, "tdt_xform is 96 bytes");
+#endif
+int tdt_octree_extract_transform(tdt_ctx *ctx, const tdt_xform *xf, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                                 size_t capacity, size_t *n_voxels);
+int tdt_octree_transform(tdt_ctx *ctx, const tdt_xform *xf, int op, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+int tdt_debug_xform_bricks(const tdt_ctx *ctx, uint32_t out[2]);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -37,15 +37,15 @@ def _run(cmd):
 def build_host(force=False):
     out = os.path.join(_HERE, "libtdthost.so")
     srcs = [os.path.join(CSRC, "host_scene.cpp"), os.path.join(CSRC, "host_view.cpp"), os.path.join(CSRC, "host_mesh.cpp"),
-            os.path.join(INCLUDE, "tdt_host.h"), os.path.join(INCLUDE, "tdt_rt.h"), os.path.abspath(__file__)]
+            os.path.join(CSRC, "host_xform.cpp"), os.path.join(INCLUDE, "tdt_host.h"), os.path.join(INCLUDE, "tdt_rt.h"), os.path.abspath(__file__)]
     if force or _newer(out, srcs):
-        _run(["g++"] + HOST_FLAGS + ["-I", INCLUDE] + srcs[:3] + ["-o", out, "-lz"])      # zlib: the PNG writer (§8f-4)
+        _run(["g++"] + HOST_FLAGS + ["-I", INCLUDE] + srcs[:4] + ["-o", out, "-lz"])      # zlib: the PNG writer (§8f-4)
     return out
 
 
 DEVICE_UNITS = ("tdt_rt.hip", "tdt_multi.hip", "tdt_build.hip", "tdt_edit.hip", "tdt_query.hip", "tdt_compact.hip",
                 "tdt_region.hip", "tdt_connect.hip", "tdt_morph.hip", "tdt_mesh.hip", "tdt_fill.hip", "tdt_surface.hip",
-                "tdt_distance.hip", "tdt_bitvol.hip")
+                "tdt_distance.hip", "tdt_bitvol.hip", "tdt_xform.hip")
 DEVICE_HEADERS = ("trace_device.hpp", "trace_params.h", "tdt_internal.hpp", "device_scan.hpp", "region_device.hpp", "bitvol_device.hpp")
 
 

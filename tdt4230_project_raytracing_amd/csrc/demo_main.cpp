@@ -7,6 +7,8 @@
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
 //            [--morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]]
+//            [--transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG [--pivot X,Y,Z] [--op ..]
+//             [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
@@ -35,6 +37,11 @@
 // --morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]: round morphology
 //   (Octree::morph_round) with the Euclidean ball of SQUARED radius R2 (1..4096); new voxels get --material or inherit their
 //   nearest voxel's; --border 1: the outside of the grid is solid.  Applied after --morph; prints the new cell count.
+// --transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG [--pivot X,Y,Z] [--op set|fill|paint|clear]
+//   [--material K] [--mask x0,y0,z0,x1,y1,z1]: move, turn (K quarter turns about AXIS 0 / 1 / 2), mirror, scale or rotate (DEG
+//   degrees about the axis AX,AY,AZ) the tree's voxels, those inside the --mask box only, about the voxel corner --pivot (default
+//   the centre of the grid) and apply the result with `op` (Octree::transform, the tdt_xform_* builders); the voxels keep their
+//   material or get K; the source voxels stay.  Applied after --morph-round; prints the new cell count.
 // --mesh FILE.ply [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]: stamp a triangle mesh (Octree::stamp_mesh):
 //   the ASCII PLY's polygons (tdt_ply_mesh_parse; colours ignored) are fitted into the box of grid voxels (tdt_mesh_fit; default
 //   the whole grid minus a one-voxel margin; with --mesh, --box is this box, not an edit of its own), quantised and applied with
@@ -79,6 +86,9 @@ int main(int argc, char **argv) {
   std::string morph_name;
   int round_op = -1, round_r2 = 0, round_border = 0;
   std::string round_name;
+  std::string xform_kind;
+  double xform_arg[4] = {0, 0, 0, 0};
+  std::vector<int32_t> pivot;
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
@@ -140,6 +150,22 @@ int main(int argc, char **argv) {
       if (round_op < 0) { std::fprintf(stderr, "--morph-round dilate|erode|open|close|shell:R2\n"); return 2; }
       round_name = kind;
     }
+    else if (a == "--transform") {
+      char kind[16] = {0};
+      const char *v = next();
+      const char *colon = std::strchr(v, ':');
+      bool good = colon && std::sscanf(v, "%15[a-z]:", kind) == 1;
+      xform_kind = kind;
+      double *g = xform_arg;
+      if (good && xform_kind == "translate") good = std::sscanf(colon + 1, "%lf,%lf,%lf", g, g + 1, g + 2) == 3;
+      else if (good && xform_kind == "turn") good = std::sscanf(colon + 1, "%lf,%lf", g, g + 1) == 2;
+      else if (good && xform_kind == "mirror") good = std::sscanf(colon + 1, "%lf", g) == 1;
+      else if (good && xform_kind == "scale") good = std::sscanf(colon + 1, "%lf/%lf", g, g + 1) == 2;
+      else if (good && xform_kind == "rotate") good = std::sscanf(colon + 1, "%lf,%lf,%lf,%lf", g, g + 1, g + 2, g + 3) == 4;
+      else good = false;
+      if (!good) { std::fprintf(stderr, "--transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG\n"); return 2; }
+    }
+    else if (a == "--pivot") { int32_t v[3]; if (std::sscanf(next(), "%d,%d,%d", v, v + 1, v + 2) != 3) { std::fprintf(stderr, "--pivot X,Y,Z\n"); return 2; } pivot.assign(v, v + 3); }
     else if (a == "--border") { round_border = std::atoi(next()); if (round_border != 0 && round_border != 1) { std::fprintf(stderr, "--border 0|1\n"); return 2; } }
     else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
@@ -314,6 +340,34 @@ int main(int argc, char **argv) {
         regions.push_back(r);
       }
       std::printf("morph-round %s:%d border %d cells %u\n", round_name.c_str(), round_r2, round_border, octree.morph_round(ctx, q, regions));
+    }
+    if (!xform_kind.empty()) {
+      const int32_t half = 1 << (ints[0] - 1);
+      const int32_t corner[3] = {pivot.empty() ? half : pivot[0], pivot.empty() ? half : pivot[1], pivot.empty() ? half : pivot[2]};
+      const int32_t pivot2[3] = {2 * corner[0], 2 * corner[1], 2 * corner[2]};             // a voxel corner, doubled
+      const double *g = xform_arg;
+      tdt_xform x;
+      int rc = 0;
+      if (xform_kind == "translate") { const int32_t d[3] = {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2]}; rc = tdt_xform_translate(d, &x); }
+      else if (xform_kind == "turn") rc = tdt_xform_quarter_turns((int)g[0], (int)g[1], pivot2, &x);
+      else if (xform_kind == "mirror") rc = tdt_xform_mirror((int)g[0], pivot2, &x);
+      else if (xform_kind == "scale") {
+        const int32_t num[3] = {(int32_t)g[0], (int32_t)g[0], (int32_t)g[0]}, den[3] = {(int32_t)g[1], (int32_t)g[1], (int32_t)g[1]};
+        rc = tdt_xform_scale(num, den, pivot2, &x);
+      } else {
+        const double centre[3] = {(double)corner[0], (double)corner[1], (double)corner[2]};
+        rc = tdt_xform_rotate(g, g[3], centre, &x);
+      }
+      if (rc != 0) { std::fprintf(stderr, "--transform: %s\n", tdt_host_last_error()); return 2; }
+      x.material = material_given ? material : -1;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      std::printf("transform %s cells %u\n", xform_kind.c_str(), octree.transform(ctx, x, op, regions));
     }
     if (fill_enclosed) {
       tdt_fill fill{};

@@ -471,6 +471,77 @@ def ply_mesh_write(vertices, triangles):
     return buf.raw[: n.value]
 
 
+# ---------------------------------------------------------------- affine transforms ---
+def _xform_call(name, argtypes, *args):
+    """One tdt_xform_* builder: a fresh rt.Xform filled by the library; ValueError with its message otherwise."""
+    from . import rt
+    L = lib()
+    f = getattr(L, name)
+    f.argtypes = list(argtypes) + [ctypes.POINTER(rt.Xform)]
+    out = rt.Xform()
+    rc = f(*args, ctypes.byref(out))
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return out
+
+
+def _i3(name, v):
+    v = list(v)
+    if len(v) != 3 or any(isinstance(e, (bool, np.bool_)) or int(e) != e or not -2**31 <= int(e) <= 2**31 - 1 for e in v):
+        raise ValueError(f"{name} must hold three int32 values, not {v!r}")
+    return (ctypes.c_int32 * 3)(*[int(e) for e in v])
+
+
+def _d(name, v, count):
+    v = [float(e) for e in np.asarray(v, np.float64).reshape(-1)]
+    if len(v) != count:
+        raise ValueError(f"{name} must hold {count} numbers")
+    return (ctypes.c_double * count)(*v)
+
+
+_I3 = ctypes.POINTER(ctypes.c_int32)
+_D = ctypes.POINTER(ctypes.c_double)
+
+
+def xform_identity():
+    """tdt_xform_identity: s = p."""
+    return _xform_call("tdt_xform_identity", [])
+
+
+def xform_translate(d):
+    """tdt_xform_translate: the selection moves by d = (dx, dy, dz) voxels."""
+    return _xform_call("tdt_xform_translate", [_I3], _i3("d", d))
+
+
+def xform_quarter_turns(axis, k, pivot2):
+    """tdt_xform_quarter_turns: k quarter turns about `axis` (0 x, 1 y, 2 z) through pivot2 (doubled coordinates: 2 c + 1 is the
+    centre of voxel c); k = 1 about z takes x towards y: numpy.rot90(grid, 1, axes=(0, 1)) when pivot2 = (N, N, N).  A bijection
+    of the grid exactly when pivot2's components on the two turned axes have equal parity."""
+    return _xform_call("tdt_xform_quarter_turns", [ctypes.c_int, ctypes.c_int, _I3], int(axis), int(k), _i3("pivot2", pivot2))
+
+
+def xform_mirror(axis, pivot2):
+    """tdt_xform_mirror: the reflection of `axis` about the plane through pivot2[axis] (doubled coordinates)."""
+    return _xform_call("tdt_xform_mirror", [ctypes.c_int, _I3], int(axis), _i3("pivot2", pivot2))
+
+
+def xform_scale(num, den, pivot2):
+    """tdt_xform_scale: per axis by num / den (integers >= 1) about pivot2 (doubled coordinates)."""
+    return _xform_call("tdt_xform_scale", [_I3, _I3, _I3], _i3("num", num), _i3("den", den), _i3("pivot2", pivot2))
+
+
+def xform_from_affine(fwd):
+    """tdt_xform_from_affine: the forward map x' = F x + f on continuous coordinates (voxel c occupies [c, c + 1)) as a (3, 4)
+    array [F | f]; inverted and rounded to the struct's fixed point."""
+    return _xform_call("tdt_xform_from_affine", [_D], _d("fwd", fwd, 12))
+
+
+def xform_rotate(axis, degrees, pivot):
+    """tdt_xform_rotate: by `degrees` about the line through `pivot` (continuous coordinates; the centre of voxel c is c + 0.5)
+    along `axis`."""
+    return _xform_call("tdt_xform_rotate", [_D, ctypes.c_double, _D], _d("axis", axis, 3), float(degrees), _d("pivot", pivot, 3))
+
+
 class PlyMesh:
     """tdt_ply_mesh_parse of a byte buffer: vertices (n, 3) float32, triangles (m, 3) uint32 (polygons fan-triangulated),
     faces = the file's polygon count.  Colours are ignored.  Raises ValueError with the reader's message."""

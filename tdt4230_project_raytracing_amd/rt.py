@@ -174,6 +174,21 @@ class Round(ctypes.Structure):
 assert ctypes.sizeof(Round) == 16
 
 
+# affine transforms of voxel selections (include/tdt_rt.h): struct tdt_xform
+XFORM_ONE = 65536
+
+
+class Xform(ctypes.Structure):
+    """struct tdt_xform: the destination -> source map s = (a (2 p + 1) + t) >> 17: t three int64 in units of 2^-17 voxel, a nine
+    int32 row-major in Q16 (XFORM_ONE = 1.0), material -1 (the source voxel's) or 0..253, dst_lo / dst_hi the inclusive box the
+    result is clipped to, pad 0.  host.xform_* build one from a forward transform."""
+    _fields_ = [("t", ctypes.c_int64 * 3), ("a", ctypes.c_int32 * 9), ("material", ctypes.c_int32), ("dst_lo", ctypes.c_int32 * 3),
+                ("dst_hi", ctypes.c_int32 * 3), ("pad", ctypes.c_int32 * 2)]
+
+
+assert ctypes.sizeof(Xform) == 96
+
+
 def _exact_ints(a, dtype, name):
     """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
     src = np.asarray(a)
@@ -288,6 +303,9 @@ SYMBOLS = [
     ("tdt_octree_extract_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_distance_field", _I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                                        _P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_extract_transform", _I, [_P, ctypes.POINTER(Xform), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_transform", _I, [_P, ctypes.POINTER(Xform), _I, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_debug_xform_bricks", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -736,6 +754,67 @@ class Context:
         self.check(lib().tdt_octree_distance_field(self.h, box3[0], box3[1], max_d2, border, field.ctypes.data,
                                                    near.ctypes.data if nearest else None, field.size, ctypes.byref(n)))
         return (field, near) if nearest else field
+
+    @classmethod
+    def _xform(cls, xf):
+        """A checked copy of an Xform, or one built from a dict / keywords-like mapping with the keys t, a, material (None: -1),
+        dst_lo, dst_hi.  Every entry must be an integer that fits its field (ctypes would wrap it silently); a bool is not a number
+        here.  The ranges themselves are the library's to check."""
+        if isinstance(xf, Xform):
+            get = lambda k, d: getattr(xf, k)                                # noqa: E731
+        elif isinstance(xf, dict):
+            get = lambda k, d: xf.get(k, d)                                  # noqa: E731
+        else:
+            raise ValueError(f"xf must be an rt.Xform or a dict, not {type(xf).__name__}")
+
+        def ints(name, v, count, bits):
+            v = list(v)
+            if len(v) != count:
+                raise ValueError(f"{name} must hold {count} entries")
+            for e in v:
+                if isinstance(e, (bool, np.bool_)) or int(e) != e or not -2 ** (bits - 1) <= int(e) <= 2 ** (bits - 1) - 1:
+                    raise ValueError(f"{name} must hold int{bits} values, not {e!r}")
+            return [int(e) for e in v]
+        material = get("material", -1)
+        out = Xform()
+        out.t[:] = ints("t", get("t", (0, 0, 0)), 3, 64)
+        out.a[:] = ints("a", get("a", (XFORM_ONE, 0, 0, 0, XFORM_ONE, 0, 0, 0, XFORM_ONE)), 9, 32)
+        out.material = cls._int32("material", -1 if material is None else material)
+        out.dst_lo[:] = ints("dst_lo", get("dst_lo", (0, 0, 0)), 3, 32)
+        out.dst_hi[:] = ints("dst_hi", get("dst_hi", (2 ** 31 - 1,) * 3), 3, 32)
+        out.pad[:] = ints("pad", get("pad", (0, 0)), 2, 32)
+        return out
+
+    def octree_transform(self, xf, op=REGION_SET, regions=None):
+        """tdt_octree_transform: octree_edit_voxels(op, octree_extract_transform(xf, regions)) with the list taken from the tree
+        before the edit and never leaving the device; xf an Xform (host.xform_*) or a dict of its fields.  The source voxels stay:
+        a move clears them with octree_edit_region first.  Returns the canonical tree's cell count."""
+        x = self._xform(xf)
+        op = self._int32("op", op)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_transform(self.h, ctypes.byref(x), op, arr, k, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_transform(self, xf, regions=None):
+        """tdt_octree_extract_transform: the transformed selection as an (n, 4) int32 list {x, y, z, material + 1}, Morton-sorted:
+        every destination voxel p of the grid and of xf's dst box whose source voxel (a (2 p + 1) + t) >> 17 is a voxel of the
+        tree inside `regions` (None: the whole tree; an empty list: nothing).  The tree is untouched.  Counts first, fills
+        second: two resamplings."""
+        x = self._xform(xf)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_transform(self.h, ctypes.byref(x), arr, k, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_transform(self.h, ctypes.byref(x), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def xform_bricks(self):
+        """tdt_debug_xform_bricks: (bricks of the last transform's destination domain, bricks its count and emit passes ran on)."""
+        out = (ctypes.c_uint32 * 2)()
+        self.check(lib().tdt_debug_xform_bricks(self.h, out))
+        return int(out[0]), int(out[1])
 
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
