@@ -711,14 +711,19 @@ int tdt_debug_xform_bricks(const tdt_ctx *ctx, uint32_t out[2]);
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this
  * lets a test tell a scene that fell back to the general kernel from one that runs its specialised build. */
 int tdt_debug_last_variant(const tdt_ctx *ctx, int out[6]);
+/* the launch geometry of that build: out = {threads per block, blocks that share a CU}.  1024 x 1 (four waves per SIMD) for every
+ * build but the whole-depth ones, which run 256 x 5 (five waves per SIMD) unless TDT_FOUR_WAVES=1 was set when the context was
+ * created. */
+int tdt_debug_last_geometry(const tdt_ctx *ctx, int out[2]);
 /* every scene-specialised build of the trace kernel the library holds, six ints per build in the order above; needs no context or
  * device.  *count receives the number of builds; the first min(capacity, *count) are written to rows (capacity 0: count only). */
 int tdt_debug_trace_variants(int *rows, int capacity, int *count);
 /* pass / lane statistics of the PRODUCT trace kernels (how many traversal and event passes the waves ran, how many lanes were live in
  * each code region: the STAT_* rows of csrc/tdt_rt.hip) since the last reset — collected only by a -DTDT_STATS build of the library
  * (tools/loss_budget.py builds one beside the product library; the product library answers TDT_ERR_INVALID_OPERATION).  The first
- * call switches the collection on; reset != 0 clears the totals after reading them.  out: n_words entries (0: the 32 totals) —
- * 32 totals, then the time (100 MHz ticks) the first wave met the end of the pixel queue, then up to 8192 per-wave end times. */
+ * call switches the collection on; reset != 0 clears the totals after reading them.  out: n_words entries (0: the 34 totals) —
+ * 34 totals (the last two: traversal passes of a whole-depth build that took the level walk, and the lanes in a band that sent them
+ * there), then the time (100 MHz ticks) the first wave met the end of the pixel queue, then up to 8192 per-wave end times. */
 int tdt_debug_stats(tdt_ctx *ctx, uint64_t *out, int n_words, int reset);
 /* lane-utilisation diagnostics of the last tdt_dispatch_counted of this context (32 totals; layout in
  * csrc/trace_device.hpp `Counters`); development aid */

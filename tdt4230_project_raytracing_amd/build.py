@@ -75,6 +75,19 @@ def build_device(force=False, extra_flags=(), out=None):
     return out
 
 
+STATS_LIB = os.path.join(_HERE, "libtdtrt_stats.so")
+
+
+def build_stats(force=False):
+    """libtdtrt_stats.so: the same library compiled with -DTDT_STATS, whose product trace kernels count their passes (tdt_debug_stats;
+    tools/loss_budget.py, tests/test_gpu_five_waves.py load it through TDT_LIB in a process of their own).  Never the product library."""
+    hdrs = [os.path.join(CSRC, f) for f in DEVICE_HEADERS] + [os.path.join(INCLUDE, "tdt_rt.h"), os.path.abspath(__file__)]
+    srcs = [os.path.join(CSRC, f) for f in DEVICE_UNITS]
+    if force or _newer(STATS_LIB, srcs + hdrs):
+        build_device(extra_flags=("-DTDT_STATS",), out=STATS_LIB)
+    return STATS_LIB
+
+
 def build_demo(force=False):
     """tdt_demo: the reference's main.rs, headless, written against include/renderer.hpp (C++ host mirror)."""
     out = os.path.join(_HERE, "tdt_demo")
@@ -101,4 +114,9 @@ def build_selftest(force=False):
 
 
 def build_all(force=False):
-    return build_host(force), build_device(force), build_demo(force), build_selftest(force)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(2) as pool:               # (the two device libraries side by side: each is bound by the trace unit's compile)
+        stats = pool.submit(build_stats, force)
+        host_lib, device_lib = build_host(force), build_device(force)
+        stats_lib = stats.result()
+    return host_lib, device_lib, build_demo(force), build_selftest(force), stats_lib

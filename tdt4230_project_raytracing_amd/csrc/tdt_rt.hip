@@ -18,16 +18,18 @@
 #include "trace_device.hpp"
 #include "trace_params.h"
 
+// Launch geometry is a property of the build (trace_kernel's BLOCK and PER_CU, a row's block / per_cu in kTraceVariants): persistent
+// blocks of BLOCK threads, PER_CU of them sharing a CU.  1024 x 1 = four waves per SIMD everywhere but in the whole-depth builds,
+// whose default is 256 x 5 (see kCold in trace_kernel).
 #ifndef TDT_BLOCK
-#define TDT_BLOCK 1024      // threads per persistent block; TDT_BLOCKS_PER_CU of them share a CU
-#define TDT_BLOCKS_PER_CU 1
+#define TDT_BLOCK 1024      // (-DTDT_BLOCK: the geometry of every build but the five-wave ones, for occupancy experiments)
 #endif
 // ============================================================================ kernels ======
 namespace tdt {
 
 // ---- work decomposition ------------------------------------------------------------------
-// Persistent 1024-thread blocks, one per CU (the block's LDS holds the top of the octree, see
-// NodeSource).  Pixels are NOT bound to threads: the covered image is a single global queue of
+// Persistent blocks: 1024 threads, one per CU (the block's LDS holds the top of the octree, see
+// NodeSource), or 256 threads, five per CU (the whole-depth builds).  Pixels are NOT bound to threads: the covered image is a single global queue of
 // pixel slots q = k * 1024 + p — k-th 32x32 work-group owned by this rank (row-major group index
 // t = rank + k * world: SURVEY §8e), p-th pixel inside it in 8x8-tile-major order — and every lane
 // pulls its next pixel from it (one atomic per wave: ballot + prefix count) when it has finished
@@ -84,6 +86,26 @@ template <> struct HitOwed<false> {
   TDT_DEV bool new_record() const { return (bits & 2u) != 0u; }
 };
 
+// Per-lane LDS slots of the five-wave builds (trace_kernel's kCold): the per-pixel state that no traversal pass reads or writes.
+// Structure of arrays — word w of thread t at w * BLOCK + t — so the 64 lanes of a wave read 64 consecutive words: no bank conflict,
+// and one address register with the word in the instruction's offset field.  The budget beside the 6 KB plane table in a block's
+// 32 KB is 26 words (26 x 256 lanes x 4 B = 26 624 B); these 21 reach 96 VGPRs without a spill.  (The path's own event-only state —
+// attenuation, sample index, bounce count — in slots as well was measured slower than four waves: HISTORY.md.)
+enum : int { COLD_ROOT = 0, COLD_ROOT_T = 7, COLD_LEAF = 8,      // the two hit records (HitTmp: nx ny nz px py pz ff) and the root call site's t
+             COLD_SUM = 15, COLD_WORK = 18, COLD_X = 19, COLD_Y = 20,      // running sums, lane_work, pixel coordinates
+             COLD_WORDS = 21 };
+template <int BLOCK> struct ColdSlots {
+  uint32_t *lane;                                    // &slots[threadIdx.x]
+  TDT_DEV uint32_t u(int w) const { return lane[w * BLOCK]; }
+  TDT_DEV float f(int w) const { return __uint_as_float(lane[w * BLOCK]); }
+  TDT_DEV void u(int w, uint32_t v) const { lane[w * BLOCK] = v; }
+  TDT_DEV void f(int w, float v) const { lane[w * BLOCK] = __float_as_uint(v); }
+  TDT_DEV void put(int w, const HitTmp &h) const {
+    f(w, h.nx); f(w + 1, h.ny); f(w + 2, h.nz); f(w + 3, h.px); f(w + 4, h.py); f(w + 5, h.pz); u(w + 6, h.ff ? 1u : 0u);
+  }
+  TDT_DEV HitTmp get(int w) const { return {f(w), f(w + 1), f(w + 2), f(w + 3), f(w + 4), f(w + 5), u(w + 6) != 0u}; }
+};
+
 // -DTDT_STATS builds (tools/loss_budget.py; never the product library): what the passes of the product kernels carry — how many
 // traversal / event passes a wave runs and how many lanes are live in each code region — summed per wave in LDS (one lane writes its
 // wave's row) and added to P.stats when the wave ends.  Together with the static instruction counts of the regions
@@ -92,7 +114,9 @@ enum : int { STAT_TRAV_PASS = 0, STAT_TRAV_LANES, STAT_INSIDE_LANES, STAT_ALIVE_
              STAT_LAMB_PASS, STAT_LAMB_LANES, STAT_METAL_PASS, STAT_METAL_LANES, STAT_DIEL_PASS, STAT_DIEL_LANES, STAT_END_PASS, STAT_END_LANES,
              STAT_PIXEL_END_PASS, STAT_PIXEL_END_LANES, STAT_FETCH_PASS, STAT_FETCH_LANES, STAT_PRIMARY_PASS, STAT_PRIMARY_LANES,
              STAT_NEWRAY_PASS, STAT_NEWRAY_LANES, STAT_GATE_WAIT_LANES, STAT_DRAINED_TRAV_PASS, STAT_DRAINED_EVENT_PASS, STAT_LOOP_PASS, STAT_WAVE_TICKS, STAT_WAVES,
-             STAT_T_FIRST, STAT_T_LAST, STAT_COUNT = 32 };
+             STAT_T_FIRST, STAT_T_LAST,
+             STAT_FALLBACK_PASS = 32, STAT_FALLBACK_LANES,      // whole-depth builds: traversal passes that took the level walk (a lane in a band), and the lanes in a band
+             STAT_COUNT = 34 };
 #ifdef TDT_STATS
 TDT_DEV void stat_add(uint32_t *row, int i, unsigned long long mask) {      // mask: the lanes (of those executing this) that are live in the region
   const unsigned long long m = __ballot(1);
@@ -111,8 +135,10 @@ TDT_DEV void stat_add(uint32_t *row, int i, unsigned long long mask) {      // m
 // FORM: how treeLookup's x index is computed — FORM_LITERAL the float formula as written; FORM_POW2 the exact-comparison form
 // for cell_count = 2^k (see tree_lookup_pow2); FORM_TABLE the same walk with per-cell thresholds for any other cell_count (the
 // reference's own 100000), see build_thresholds_kernel.
-template <bool COUNT, int FORM, int DEPTH = 0, bool RESIDENT = false, bool SAFEV = false, bool FULL = false, bool UNIT = false, bool BRICK = false>
-__global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
+// BLOCK, PER_CU: the launch geometry this build is compiled for (threads per block, blocks that share a CU).
+template <bool COUNT, int FORM, int DEPTH = 0, bool RESIDENT = false, bool SAFEV = false, bool FULL = false, bool UNIT = false, bool BRICK = false,
+          int BLOCK = TDT_BLOCK, int PER_CU = 1>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_per_eu((BLOCK * PER_CU + 255) / 256))) void trace_kernel(const TraceParams P) {
   constexpr bool POW2 = FORM != FORM_LITERAL;        // the exact forms (integer digits, one-compare box test)
   // round 4's second batch of step slimming (see the uses): the scene-specialised builds; the general kernel, with its nine-level node
   // memo, sits at the register cap and keeps the plain forms
@@ -137,12 +163,24 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
 #else
   constexpr bool kSharedNorm = kSlim2;                // (scatter<>: one normalize() behind the three material branches)
 #endif
-  __shared__ __attribute__((aligned(16))) uint16_t s_nodes[(BRICK ? kBrickLdsCells : kLdsCells) * 8 + 8];   // + the sentinel slot (BRICK: the host stages no more than fit)
-  for (uint32_t i = threadIdx.x * 8u; i < P.lds_nodes; i += (uint32_t)TDT_BLOCK * 8u)      // one cell (8 x u16) per lane and trip
-    *reinterpret_cast<uint4 *>(&s_nodes[i]) = *reinterpret_cast<const uint4 *>(&P.packed[i]);
-  // sentinel: the rest of a partial last cell and one more cell (RESIDENT: all EMPTY, see tree_lookup_pow2), or the escape code
-  if (threadIdx.x < 16 && P.lds_nodes + threadIdx.x < ((P.lds_nodes + 7u) & ~7u) + 8u)
-    s_nodes[P.lds_nodes + threadIdx.x] = (uint16_t)((RESIDENT && POW2) ? 0u : kPackedEscape);
+  // kCold: the five-wave builds (256 x 5; whole-depth plane form only).  Five blocks share the CU's 160 KB of LDS and its register
+  // file, so a block has 32 KB and a lane 96 VGPRs: no node table in LDS — the walk of a wave with a lane in a band reads the cells
+  // from global memory, without a memo — and the per-pixel state that only event passes touch lives in per-lane LDS slots
+  // (ColdSlots), loaded where the event code uses it and stored where it produces it.
+  constexpr bool kCold = PER_CU > 1;
+  static_assert(!kCold || (FULL && !COUNT && !BRICK && RESIDENT && SAFEV && DEPTH > 0 && kFullEntryForm == kFullPlanes && BLOCK * PER_CU == 1280),
+                "five waves per SIMD: the whole-depth plane-form builds");
+  __shared__ __attribute__((aligned(16))) uint16_t s_nodes[(kCold ? 0u : (BRICK ? kBrickLdsCells : kLdsCells)) * 8 + 8];   // + the sentinel slot (BRICK: the host stages no more than fit)
+  if constexpr (!kCold) {
+    for (uint32_t i = threadIdx.x * 8u; i < P.lds_nodes; i += (uint32_t)BLOCK * 8u)      // one cell (8 x u16) per lane and trip
+      *reinterpret_cast<uint4 *>(&s_nodes[i]) = *reinterpret_cast<const uint4 *>(&P.packed[i]);
+    // sentinel: the rest of a partial last cell and one more cell (RESIDENT: all EMPTY, see tree_lookup_pow2), or the escape code
+    if (threadIdx.x < 16 && P.lds_nodes + threadIdx.x < ((P.lds_nodes + 7u) & ~7u) + 8u)
+      s_nodes[P.lds_nodes + threadIdx.x] = (uint16_t)((RESIDENT && POW2) ? 0u : kPackedEscape);
+  }
+  __shared__ uint32_t s_cold[kCold ? COLD_WORDS * BLOCK : 1];
+  const ColdSlots<BLOCK> cold = {&s_cold[kCold ? threadIdx.x : 0]};
+  if constexpr (kCold) cold.u(COLD_WORK, 0u);      // (read by every lane in every event pass, the first included; the other words are written at fetch before any read)
   // FULL builds, plane form: the padded slab planes of every cell a step can meet (PlaneTable) — a function of the kernel arguments alone
   constexpr bool kPlanes = FULL && !COUNT && kFullEntryForm == kFullPlanes;
   __shared__ __attribute__((aligned(8))) float2 s_planes[kPlanes ? PlaneTable::kEntries : 1];
@@ -154,7 +192,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   __shared__ __attribute__((aligned(8))) float2 s_thr[kThrCells + 1];      // FORM_TABLE: x_thresholds of the cells PARENT nodes point at (trees outside the LDS table: of the top cells)
   __shared__ uint32_t s_band;
   if (TABLE) {
-    for (uint32_t i = threadIdx.x; i <= kThrCells; i += (uint32_t)TDT_BLOCK)
+    for (uint32_t i = threadIdx.x; i <= kThrCells; i += (uint32_t)BLOCK)
       s_thr[i] = i < P.thr_cells ? reinterpret_cast<const float2 *>(P.thr)[i] : make_float2(2.0f, 2.0f);
     __syncthreads();
   }
@@ -165,7 +203,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   if (kUseGrid) build_top_grid<GL, TABLE>(s_nodes, P.lds_nodes, DEPTH, s_grid, &s_grid_ok, s_thr, P.thr_cells, P.thr_f0max, &s_band);
   __shared__ __attribute__((aligned(16))) uint32_t s_grid32[BRICK ? (1 << 15) : 4];     // BRICK: build_bricks_kernel's table, copied as it is
   if (BRICK) {
-    for (uint32_t i = threadIdx.x * 4u; i < (1u << 15); i += (uint32_t)TDT_BLOCK * 4u)
+    for (uint32_t i = threadIdx.x * 4u; i < (1u << 15); i += (uint32_t)BLOCK * 4u)
       *reinterpret_cast<uint4 *>(&s_grid32[i]) = *reinterpret_cast<const uint4 *>(&P.brick_grid[i]);
     __syncthreads();
   }
@@ -194,9 +232,10 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   MatSource ms_regs;
   if (!kColdArgs) ms_regs = material_source(P);
 #ifdef TDT_STATS
-  __shared__ uint32_t s_stats[(TDT_BLOCK / 64) * STAT_COUNT];
+  __shared__ uint32_t s_stats[(BLOCK / 64) * STAT_COUNT];
   uint32_t *const s_stat_row = &s_stats[(threadIdx.x >> 6) * STAT_COUNT];
   if ((threadIdx.x & 63) < STAT_COUNT) s_stat_row[threadIdx.x & 63] = 0u;
+  ns.stat_fallback = &s_stat_row[STAT_FALLBACK_PASS];
   const unsigned long long stat_t0 = __builtin_amdgcn_s_memrealtime();
   bool stat_drained = false;
 #endif
@@ -215,7 +254,8 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   // node-memo levels (2 VGPRs each): the brick builds' level walk is the fallback of the few per cent of their steps that have a lane in a
   // band — three levels' worth of memo instead of nine pays for the octree corner in VGPRs and the hit flags in a VGPR there too
   // (4K/256^3 -1.9 %, 1080p/512^3 -3.3 %; one or two levels: -1.0 / -2.9 %)
-  constexpr int kMemo = BRICK ? kBrickMemoLevels : kMemoLevels;
+  // (kCold: none — two VGPRs a level that only the band fallback's global walk would use; three levels measured 1.5 ... 2 % slower)
+  constexpr int kMemo = BRICK ? kBrickMemoLevels : (kCold ? 0 : kMemoLevels);
   NodeMemo<kMemo> memo;
 #pragma unroll
   for (int l = 0; l < kMemo; l++) { memo.key[l] = 0x3FFFFFFFu; memo.val[l] = 0u; }
@@ -321,7 +361,8 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
         const float ipd_in = inv_pow_depth;          // (kStuckCut)
         CellPlanes cp;
         bool leaf;
-        if constexpr (kPlanes) leaf = tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE, UNIT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt, &cp);
+        if constexpr (kCold) leaf = tree_lookup_pow2<COUNT, kMemo, DEPTH, false, SAFEV, FULL, BRICK, TABLE, UNIT, true>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt, &cp);
+        else if constexpr (kPlanes) leaf = tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE, UNIT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt, &cp);
         else leaf = POW2 ? tree_lookup_pow2<COUNT, kMemo, DEPTH, RESIDENT, SAFEV, FULL, BRICK, TABLE>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, memo, cnt)
                          : tree_lookup<COUNT>(P, ns, lx, ly, lz, inv_pow_depth, ugx, ugy, ugz, value, cnt);
         TDT_MARK(traversal_b);
@@ -401,8 +442,10 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
     // of the ray that ends here — `it` counted them (the step that finds a leaf does not advance it: + 1) — added once per ray, in the event
     // pass, instead of three instructions in every traversal step.  (The tree levels a step visited used to be part of it; with one table or
     // brick read per step whatever the depth they no longer say what a step costs.)
+    if constexpr (kCold) lane_work = cold.u(COLD_WORK);
     if (kSlim2) lane_work += (state == ST_HIT || state == ST_END) ? kCostEvent + kCostRayStep * ((uint32_t)it + 1u) : ((state > ST_TRAVERSE) ? kCostEvent : 0u);
     else lane_work += (state > ST_TRAVERSE) ? kCostEvent : 0u;
+    if constexpr (kCold) cold.u(COLD_WORK, lane_work);
     if (COUNT) lane_E += (state > ST_TRAVERSE) ? 1u : 0u;
     if (state == ST_HIT) {                            // RayColor loop body rc:272-295
       if (COUNT) { cnt.scatter_slots += slot64(); cnt.scatter_active++; }
@@ -414,9 +457,17 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
       } else ms = ms_regs;
       const MatRef mat = material_fetch(ms, hit_index);
       TDT_ST(STAT_LAMB_PASS, __ballot(mat.type == 0u)); TDT_ST(STAT_METAL_PASS, __ballot(mat.type == 1u)); TDT_ST(STAT_DIEL_PASS, __ballot(mat.type == 2u));
-      if (owed.new_record()) { cube_hit_record(r, t_stride, leaf_box_x, leaf_box_y, leaf_box_z, inv_pow_depth, pc.leaf); if (COUNT) cnt.leaf_records++; }
+      if (owed.new_record()) {
+        cube_hit_record(r, t_stride, leaf_box_x, leaf_box_y, leaf_box_z, inv_pow_depth, pc.leaf); if (COUNT) cnt.leaf_records++;
+        if constexpr (kCold) cold.put(COLD_LEAF, pc.leaf);
+      }
       loop_count += 1;
-      const HitTmp &src = owed.leaf_site() ? pc.leaf : pc.root;
+      HitTmp cold_rec = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, false};
+      if constexpr (kCold) {                          // (the record of either call site, as the slots hold it now)
+        const ColdSlots<BLOCK> site = {cold.lane + (owed.leaf_site() ? COLD_LEAF * BLOCK : COLD_ROOT * BLOCK)};
+        cold_rec = site.get(0);
+      }
+      const HitTmp &src = kCold ? cold_rec : (owed.leaf_site() ? pc.leaf : pc.root);
       Hit h;
       h.px = src.px; h.py = src.py; h.pz = src.pz; h.nx = src.nx; h.ny = src.ny; h.nz = src.nz; h.ff = src.ff;
       h.index = hit_index;
@@ -438,6 +489,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
     TDT_ST(STAT_END_PASS, __ballot(state == ST_END));
     if (state == ST_END) {                            // rc:297-301, rc:246
       float cr, cg, cb;
+      if constexpr (kCold) { sr = cold.f(COLD_SUM); sg = cold.f(COLD_SUM + 1); sb = cold.f(COLD_SUM + 2); }
       if (loop_count > 0) { cr = ar; cg = ag; cb = ab; }
       else {
         const float yp = r.dy + 1.0f;
@@ -446,14 +498,17 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
       }
       sr = sr + cr; sg = sg + cg; sb = sb + cb;
       s++;
+      if constexpr (kCold) { cold.f(COLD_SUM, sr); cold.f(COLD_SUM + 1, sg); cold.f(COLD_SUM + 2, sb); }
       if (s < s_end) state = ST_PRIMARY;
       else {
         TDT_MARK(pixel_end);
         TDT_ST(STAT_PIXEL_END_PASS, __ballot(1));
+        if constexpr (kCold) { int x_, y_; bool in_; decode_pixel(P, (int)(pixel_slot >> 10), pixel_slot & 1023u, x_, y_, pix, in_); }      // (recomputed: not kept across the passes)
         float4 *dst = reinterpret_cast<float4 *>(P.image) + pix;
         if (P.accumulate) {
           *dst = make_float4(sr, sg, sb, 0.f);
           if (P.carry && !P.carry_final) {           // (the last launch of a two-phase frame: nobody will read the records again)
+            if constexpr (kCold) { pc.root = cold.get(COLD_ROOT); pc.root_t = cold.f(COLD_ROOT_T); pc.leaf = cold.get(COLD_LEAF); }
             float4 *c = reinterpret_cast<float4 *>(P.carry) + pix * 4;
             c[0] = make_float4(pc.root.nx, pc.root.ny, pc.root.nz, pc.root.px);
             c[1] = make_float4(pc.root.py, pc.root.pz, pc.root.ff ? 1.f : 0.f, pc.root_t);
@@ -472,13 +527,13 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
 #ifdef TDT_STATS
         if (P.stats && P.pixel_log) {                 // (-DTDT_STATS builds with TDT_PIXEL_LOG set: when each pixel of a PRODUCT launch started and ended, and on which wave)
           uint32_t *L = P.pixel_log + (size_t)pixel_slot * 8;
-          L[0] = lane_work; L[3] = stat_pix_t0; L[4] = (uint32_t)__builtin_amdgcn_s_memrealtime(); L[5] = blockIdx.x * 16 + (threadIdx.x >> 6); L[7] = (uint32_t)threshold;
+          L[0] = lane_work; L[3] = stat_pix_t0; L[4] = (uint32_t)__builtin_amdgcn_s_memrealtime(); L[5] = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); L[7] = (uint32_t)threshold;
         }
 #endif
         if (COUNT && P.pixel_log) {
           uint32_t *L = P.pixel_log + (size_t)pixel_slot * 8;
           L[0] = lane_S; L[1] = lane_E; L[2] = pass_no - pixel_pass0; L[3] = (uint32_t)(pixel_rt0 - P.counters[23]);
-          L[4] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - P.counters[23]); L[5] = blockIdx.x * 16 + (threadIdx.x >> 6); L[6] = evpass_no - pixel_evpass0; L[7] = (uint32_t)threshold;
+          L[4] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - P.counters[23]); L[5] = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); L[6] = evpass_no - pixel_evpass0; L[7] = (uint32_t)threshold;
         }
         if (COUNT) {
           const unsigned long long d = (__builtin_amdgcn_s_memrealtime() - pixel_rt0) / 10000ull;   // 0.1 ms bins
@@ -534,6 +589,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
             pixel_slot = q;
             decode_pixel(P, (int)(pixel_slot >> 10), pixel_slot & 1023u, x, y, pix, inside);
             lane_work = 0u;
+            if constexpr (kCold) cold.u(COLD_WORK, 0u);
             if (inside) {                             // outside the covered image: ask again next time
               n_pixels++;
               sr = 0.f; sg = 0.f; sb = 0.f; s = P.spp_begin;
@@ -547,6 +603,11 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
                   pc.root = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z != 0.f}; pc.root_t = c1.w;
                   pc.leaf = {c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z != 0.f};
                 }
+              }
+              if constexpr (kCold) {
+                cold.put(COLD_ROOT, pc.root); cold.f(COLD_ROOT_T, pc.root_t); cold.put(COLD_LEAF, pc.leaf);
+                cold.f(COLD_SUM, sr); cold.f(COLD_SUM + 1, sg); cold.f(COLD_SUM + 2, sb);
+                cold.u(COLD_X, (uint32_t)x); cold.u(COLD_Y, (uint32_t)y);
               }
               if (s < s_end) state = ST_PRIMARY;
               else if (!P.accumulate) {               // zero samples: main() still stores sqrt(0/0) clamped
@@ -563,6 +624,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
     TDT_MARK(primary);
     TDT_ST(STAT_PRIMARY_PASS, __ballot(state == ST_PRIMARY));
     if (state == ST_PRIMARY) {                        // rc:240-245
+      if constexpr (kCold) { x = (int)cold.u(COLD_X); y = (int)cold.u(COLD_Y); }
       r = primary_ray(P, x, y, s);
       loop_count = 0; ar = 1.f; ag = 1.f; ab = 1.f;
       state = ST_NEWRAY;
@@ -596,9 +658,11 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
         const float t_enter = hw_max(hw_max(hw_max(mnx, 0.0003f), mny), mnz);
         const float t_exit = hw_min(hw_min(hw_min(mxx, inf), mxy), mxz);
         t_octree_max = inf;
+        if constexpr (kCold) pc.root_t = cold.f(COLD_ROOT_T);
         if (t_exit >= t_enter) {
           cube_hit_record(r, t_enter, P.min_x, P.min_y, P.min_z, P.scale, pc.root);
           pc.root_t = t_enter;
+          if constexpr (kCold) { cold.put(COLD_ROOT, pc.root); cold.f(COLD_ROOT_T, t_enter); }
           t_octree_max = t_exit;
         }
         t_stride = pc.root_t;
@@ -618,10 +682,10 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
   if (P.stats) {
     const unsigned long long stat_t1 = __builtin_amdgcn_s_memrealtime();
     const uint32_t lane = threadIdx.x & 63u;
-    if (lane < (uint32_t)STAT_WAVE_TICKS) { const uint32_t v = s_stat_row[lane]; if (v) atomicAdd(&P.stats[lane], (unsigned long long)v); }
+    if (lane < (uint32_t)STAT_WAVE_TICKS || (lane >= (uint32_t)STAT_FALLBACK_PASS && lane < (uint32_t)STAT_COUNT)) { const uint32_t v = s_stat_row[lane]; if (v) atomicAdd(&P.stats[lane], (unsigned long long)v); }
     if (lane == 0) { atomicAdd(&P.stats[STAT_WAVE_TICKS], stat_t1 - stat_t0); atomicAdd(&P.stats[STAT_WAVES], 1ull);
                      atomicMin(&P.stats[STAT_T_FIRST], stat_t0); atomicMax(&P.stats[STAT_T_LAST], stat_t1);
-                     const uint32_t w = blockIdx.x * (TDT_BLOCK / 64) + (threadIdx.x >> 6);      // per-wave end times (100 MHz ticks) of the last launch
+                     const uint32_t w = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);      // per-wave end times (100 MHz ticks) of the last launch
                      if (w < 8192u) P.stats[STAT_COUNT + 1 + w] = stat_t1; }
   }
 #endif
@@ -632,7 +696,7 @@ __global__ __launch_bounds__(TDT_BLOCK) void trace_kernel(const TraceParams P) {
       const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
       atomicMin(&P.counters[18], wave_t0); atomicMax(&P.counters[19], t_end);
       atomicAdd(&P.counters[20], t_end - wave_t0); atomicAdd(&P.counters[21], 1ull);
-      P.counters[32 + blockIdx.x * (TDT_BLOCK / 64) + (threadIdx.x >> 6)] = t_end;   // per-wave end time (grid <= 256 blocks... see kWaveLog)
+      P.counters[32 + blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)] = t_end;   // per-wave end time (grid <= 256 blocks... see kWaveLog)
     }
     if ((threadIdx.x & 63) == 0) for (int i = 0; i < 7; i++) atomicAdd(&P.counters[24 + i], tacc[i]);
     uint32_t v[18] = {n_pixels, cnt.octree_hit_calls, cnt.iterations, cnt.node_loads,
@@ -1402,9 +1466,12 @@ void make_sig(const tdt_ctx *ctx, const tdt_compute *c, const Cover &k, const td
 // The scene-specialised builds of the trace kernel (all SAFEV, COUNT = false), looked up by what the dispatch found out about the
 // scene.  One row per instantiation; a build that is not listed does not exist, and launch_trace() falls back to the general kernel.
 using TraceFn = void (*)(const TraceParams);
-struct TraceVariant { int form, depth; bool resident, full, brick, unit; TraceFn fn; };
-#define TDT_V1(FORM, D, R, F, B, U) {tdt::FORM, D, R, F, B, U, tdt::trace_kernel<false, tdt::FORM, D, R, true, F, U, B>}
+// block x per_cu: the geometry the build is compiled for and launched with (threads per block, blocks that share a CU)
+struct TraceVariant { int form, depth; bool resident, full, brick, unit; TraceFn fn; int block, per_cu; };
+#define TDT_V1(FORM, D, R, F, B, U) {tdt::FORM, D, R, F, B, U, tdt::trace_kernel<false, tdt::FORM, D, R, true, F, U, B>, TDT_BLOCK, 1}
 #define TDT_V(FORM, D, R, F, B) TDT_V1(FORM, D, R, F, B, false), TDT_V1(FORM, D, R, F, B, true)
+#define TDT_V5_1(D, U) {tdt::FORM_POW2, D, true, true, false, U, tdt::trace_kernel<false, tdt::FORM_POW2, D, true, true, true, U, false, 256, 5>, 256, 5}
+#define TDT_V5(D) TDT_V5_1(D, false), TDT_V5_1(D, true)
 const TraceVariant kTraceVariants[] = {
   // trees outside the LDS table, depth 6-10: the 32-bit level-5 table with per-position bands (+ bricks for depths 6-9) ...
   TDT_V(FORM_POW2, 6, false, false, true), TDT_V(FORM_POW2, 7, false, false, true), TDT_V(FORM_POW2, 8, false, false, true),
@@ -1412,7 +1479,11 @@ const TraceVariant kTraceVariants[] = {
   // ... or, when that table cannot be built for the tree (or is switched off), the 16-bit 5-level table built per block and the memo walk
   TDT_V(FORM_POW2, 6, false, false, false), TDT_V(FORM_POW2, 7, false, false, false), TDT_V(FORM_POW2, 8, false, false, false),
   TDT_V(FORM_POW2, 9, false, false, false), TDT_V(FORM_POW2, 10, false, false, false),
-  // small trees inside the LDS table: the whole-depth table
+  // small trees inside the LDS table: the whole-depth table, at five waves per SIMD (256 x 5: no LDS node table, cold state in LDS
+  // slots) ...
+  TDT_V5(5), TDT_V5(6),
+  // ... and its four-wave form (1024 x 1), which TDT_FOUR_WAVES=1 selects: the control of an A/B.  Same six properties: find_variant
+  // tells the two apart by per_cu, tdt_debug_trace_variants lists the pair once
   TDT_V(FORM_POW2, 5, true, true, false), TDT_V(FORM_POW2, 6, true, true, false),
   // trees inside the LDS table: 4-level jump table (depth >= 4) + whole-cell LDS reads
   TDT_V(FORM_POW2, 3, true, false, false), TDT_V(FORM_POW2, 4, true, false, false), TDT_V(FORM_POW2, 5, true, false, false),
@@ -1427,11 +1498,15 @@ const TraceVariant kTraceVariants[] = {
   TDT_V(FORM_TABLE, 6, false, false, false), TDT_V(FORM_TABLE, 7, false, false, false), TDT_V(FORM_TABLE, 8, false, false, false),
   TDT_V(FORM_TABLE, 9, false, false, false), TDT_V(FORM_TABLE, 10, false, false, false),
 };
+#undef TDT_V5
+#undef TDT_V5_1
 #undef TDT_V
 #undef TDT_V1
-TraceFn find_variant(int form, int depth, bool resident, bool full, bool brick, bool unit) {
+// (four_waves: skip the builds that share a CU between several blocks)
+const TraceVariant *find_variant(int form, int depth, bool resident, bool full, bool brick, bool unit, bool four_waves) {
   for (const TraceVariant &v : kTraceVariants)
-    if (v.form == form && v.depth == depth && v.resident == resident && v.full == full && v.brick == brick && v.unit == unit) return v.fn;
+    if (v.form == form && v.depth == depth && v.resident == resident && v.full == full && v.brick == brick && v.unit == unit &&
+        !(four_waves && v.per_cu > 1)) return &v;
   return nullptr;
 }
 
@@ -1471,6 +1546,7 @@ struct tdt::TraceState {
     bool no_prepass = env_set("TDT_NO_PREPASS");              // never run the miss pre-pass
     bool no_order_reuse = env_set("TDT_NO_ORDER_REUSE");      // sort every frame
     bool no_full = env_set("TDT_NO_FULL_GRID");               // whole-depth lookup table off
+    bool four_waves = env_one("TDT_FOUR_WAVES");              // whole-depth builds: the 1024 x 1 form instead of 256 x 5 (A/B testing)
     bool no_table_form = env_set("TDT_NO_TABLE_FORM");        // FORM_TABLE builds off
     bool no_bricks = env_set("TDT_NO_BRICKS");                // BRICK builds off (also set when the bricks cannot be allocated)
     float max_share = env_float("TDT_MAX_SHARE", 1.0f);
@@ -1521,6 +1597,7 @@ struct tdt::TraceState {
   uint32_t *pixel_log = nullptr; size_t pixel_log_u32 = 0;   // TDT_PIXEL_LOG diagnostics (instrumented dispatches only)
   unsigned long long *stats = nullptr;   // tdt_debug_stats: pass statistics of -DTDT_STATS builds (null otherwise)
   int last_variant[6] = {};     // tdt_debug_last_variant: the build the last trace launch ran
+  int last_geometry[2] = {};    // tdt_debug_last_geometry: its threads per block and blocks per CU
 
   ~TraceState() { if (phase_timing) for (auto &e : phase_ev) (void)hipEventDestroy(e); }
   template <class T> hipError_t alloc(T *&p, size_t n) { p = mem.get<T>(n); return p ? hipSuccess : hipErrorOutOfMemory; }
@@ -1699,7 +1776,7 @@ int refresh_packed(tdt_ctx *ctx, TraceState &S, TraceParams &P) {
 // cost-feedback hand-out order (see order_scatter_kernel): what the launch hands out and where it records its costs
 struct HandOut { const uint32_t *slot_order = nullptr, *plan = nullptr; uint32_t *slot_cost = nullptr; };
 
-int plan_order(tdt_ctx *ctx, TraceState &S, const CostSig &sig, const LaunchRequest &rq, int owned, HandOut &out) {
+int plan_order(tdt_ctx *ctx, TraceState &S, const CostSig &sig, const LaunchRequest &rq, int owned, uint32_t lanes, HandOut &out) {
   TraceState::CostOrder &O = S.order;
   const TraceState::Switches &env = S.env;
   const size_t n = (size_t)owned * 1024;
@@ -1747,7 +1824,6 @@ int plan_order(tdt_ctx *ctx, TraceState &S, const CostSig &sig, const LaunchRequ
     const uint32_t og = tdt::kOrderBits;
     // two sets of sort counters alternate: the plan kernel of this pass zeroes the set of the next one
     uint32_t *hist = O.hist + 1024u * O.parity, *hist_next = O.hist + 1024u * (O.parity ^ 1u), *plan = O.hist + 2048;
-    const uint32_t lanes = (uint32_t)ctx->num_cus * TDT_BLOCKS_PER_CU * TDT_BLOCK;
     hipLaunchKernelGGL(tdt::order_hist_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, O.slot_cost, O.slot_acc, n_slots, hist, og, smooth, keep_costs ? 1 : 0, blend);
     hipLaunchKernelGGL(tdt::order_plan_kernel, dim3(1), dim3(512), 0, ctx->stream, hist, og, lanes, env.max_share, plan, smooth, hist_next, plan + 4);
     hipLaunchKernelGGL(tdt::order_scatter_kernel, dim3(n_chunks), dim3(1024), 0, ctx->stream, O.slot_cost, O.slot_acc, n_slots,
@@ -1899,29 +1975,39 @@ int prepare_bricks(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) {
   return TDT_OK;
 }
 
-// choose the build and launch it: one persistent block per CU (fewer when there is less work than lanes)
-int launch_trace(tdt_ctx *ctx, TraceState &S, const LaunchRequest &rq, const TreeForm &f, int owned, const TraceParams &P) {
-  unsigned nblk = (unsigned)(((long)owned * 1024 + 1023) / 1024);
-  if (nblk > (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU) nblk = (unsigned)ctx->num_cus * TDT_BLOCKS_PER_CU;
-  const dim3 grid(nblk, 1, 1), block(TDT_BLOCK, 1, 1);
-  bool launched = false;
+// the build a launch runs, chosen from what the dispatch found out about the tree; fn == nullptr: a general kernel
+struct TraceBuild { TraceFn fn = nullptr; int block = TDT_BLOCK, per_cu = 1; int v[6] = {}; };
+TraceBuild choose_build(const TraceState &S, const LaunchRequest &rq, const TreeForm &f, const TraceParams &P) {
+  TraceBuild b;
+  b.v[0] = f.pow2 ? tdt::FORM_POW2 : tdt::FORM_LITERAL;
   if (!rq.counts_out && (f.pow2 || f.table_form) && f.safev && !S.env.no_specialise) {
     // UNIT builds do not multiply by a scale of exactly 1.0f (x * 1.0f is x).  The probe launch of a two-phase frame runs the build
     // that multiplies — the same bits, and the short launch then has a row of its own in profiler statistics instead of halving the
     // average of the launches that do the work
     const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f && !rq.probe;      // (a zero corner component: see the in-octree test)
     const int form = f.pow2 ? tdt::FORM_POW2 : tdt::FORM_TABLE;
-    TraceFn fn = nullptr;
-    if (f.brick) fn = find_variant(form, P.max_depth, false, false, true, unit);
-    if (!fn && f.full) fn = find_variant(form, P.max_depth, true, true, false, unit);
-    if (!fn) fn = find_variant(form, P.max_depth, f.resident, false, false, unit);
-    if (fn) {
-      hipLaunchKernelGGL(fn, grid, block, 0, ctx->stream, P); launched = true;
+    const TraceVariant *tv = nullptr;
+    if (f.brick) tv = find_variant(form, P.max_depth, false, false, true, unit, S.env.four_waves);
+    if (!tv && f.full) tv = find_variant(form, P.max_depth, true, true, false, unit, S.env.four_waves);
+    if (!tv) tv = find_variant(form, P.max_depth, f.resident, false, false, unit, S.env.four_waves);
+    if (tv) {
+      b.fn = tv->fn; b.block = tv->block; b.per_cu = tv->per_cu;
       const int v[6] = {form, P.max_depth, (f.brick || !f.resident) ? 0 : 1, (!f.brick && f.full) ? 1 : 0, f.brick ? 1 : 0, unit ? 1 : 0};
-      std::memcpy(S.last_variant, v, sizeof v);
+      std::memcpy(b.v, v, sizeof v);
     }
   }
-  if (!launched) { const int v[6] = {f.pow2 ? tdt::FORM_POW2 : tdt::FORM_LITERAL, 0, 0, 0, 0, 0}; std::memcpy(S.last_variant, v, sizeof v); }
+  return b;
+}
+
+// launch the chosen build: per_cu persistent blocks per CU (fewer when there is less work than lanes)
+int launch_trace(tdt_ctx *ctx, TraceState &S, const LaunchRequest &rq, const TreeForm &f, const TraceBuild &b, int owned, const TraceParams &P) {
+  unsigned nblk = (unsigned)(((long)owned * 1024 + b.block - 1) / b.block);
+  if (nblk > (unsigned)ctx->num_cus * (unsigned)b.per_cu) nblk = (unsigned)ctx->num_cus * (unsigned)b.per_cu;
+  const dim3 grid(nblk, 1, 1), block((unsigned)b.block, 1, 1);
+  bool launched = false;
+  if (b.fn) { hipLaunchKernelGGL(b.fn, grid, block, 0, ctx->stream, P); launched = true; }
+  std::memcpy(S.last_variant, b.v, sizeof b.v);
+  S.last_geometry[0] = b.block; S.last_geometry[1] = b.per_cu;
 #define TDT_LAUNCH(C) do { if (f.pow2) hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_POW2>), grid, block, 0, ctx->stream, P); \
                            else hipLaunchKernelGGL((tdt::trace_kernel<C, tdt::FORM_LITERAL>), grid, block, 0, ctx->stream, P); } while (0)
   if (!launched && rq.counts_out && getenv("TDT_COUNT_SPECIALISED") && f.pow2 && f.safev && f.resident && P.max_depth == 6) {
@@ -1949,21 +2035,23 @@ int launch(tdt_compute *c, int width, int height, int depth, const LaunchRequest
   if (t.owned > 0) {
     if (int rc = bind_queue(ctx, S.queue, S.mem, P)) return rc;
     if (int rc = refresh_packed(ctx, S, P)) return rc;
-    if (!S.env.no_cost_order) {      // TDT_NO_COST_ORDER=1: image order
-      CostSig sig; HandOut h;
-      make_sig(ctx, c, k, ctx->image0, &sig);
-      if (int rc = plan_order(ctx, S, sig, rq, t.owned, h)) return rc;
-      P.slot_order = h.slot_order; P.plan = h.plan; P.slot_cost = h.slot_cost;
-    }
-    if (rq.prepass_ran && !rq.counts_out)
-      if (int rc = filter_done(ctx, S.miss, t.owned, P.slot_order)) return rc;
+    // (the build before the hand-out order: the order's plan counts the lanes of the geometry that will run)
     TreeForm f = classify_tree(S, P);
     if (!rq.counts_out) {
       if (int rc = prepare_thresholds(ctx, S, f, P)) return rc;
       if (int rc = prepare_full_grid(ctx, S, f, P)) return rc;
       if (int rc = prepare_bricks(ctx, S, f, P)) return rc;
     }
-    if (int rc = launch_trace(ctx, S, rq, f, t.owned, P)) return rc;
+    const TraceBuild build = choose_build(S, rq, f, P);
+    if (!S.env.no_cost_order) {      // TDT_NO_COST_ORDER=1: image order
+      CostSig sig; HandOut h;
+      make_sig(ctx, c, k, ctx->image0, &sig);
+      if (int rc = plan_order(ctx, S, sig, rq, t.owned, (uint32_t)ctx->num_cus * (uint32_t)(build.per_cu * build.block), h)) return rc;
+      P.slot_order = h.slot_order; P.plan = h.plan; P.slot_cost = h.slot_cost;
+    }
+    if (rq.prepass_ran && !rq.counts_out)
+      if (int rc = filter_done(ctx, S.miss, t.owned, P.slot_order)) return rc;
+    if (int rc = launch_trace(ctx, S, rq, f, build, t.owned, P)) return rc;
   }
   if (rq.counts_out) {
     TDT_HIP(ctx, hipMemcpyAsync(rq.counts_out, ctx->counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -2486,12 +2574,21 @@ int tdt_debug_last_variant(const tdt_ctx *ctx, int out[6]) {
   return TDT_OK;
 }
 
+/* threads per block and blocks per CU of that launch: a property of the build (kTraceVariants) */
+int tdt_debug_last_geometry(const tdt_ctx *ctx, int out[2]) {
+  if (!ctx || !out) return TDT_ERR_INVALID_VALUE;
+  if (ctx->multi) ctx = tdt::multi_first_member(const_cast<tdt_ctx *>(ctx));
+  std::memcpy(out, ctx->trace->last_geometry, 2 * sizeof(int));
+  return TDT_OK;
+}
+
 /* the scene-specialised builds the library holds (kTraceVariants), six ints per build in tdt_debug_last_variant's order; *count is
  * the number of builds, of which the first min(capacity, *count) are written — so that a test's list of builds cannot fall behind */
 int tdt_debug_trace_variants(int *rows, int capacity, int *count) {
   if (!count || capacity < 0 || (capacity > 0 && !rows)) return TDT_ERR_INVALID_VALUE;
   int n = 0;
   for (const TraceVariant &v : kTraceVariants) {
+    if (v.per_cu == 1 && find_variant(v.form, v.depth, v.resident, v.full, v.brick, v.unit, false) != &v) continue;      // (the four-wave form of a build listed already)
     if (n < capacity) {
       const int r[6] = {v.form, v.depth, v.resident ? 1 : 0, v.full ? 1 : 0, v.brick ? 1 : 0, v.unit ? 1 : 0};
       std::memcpy(rows + 6 * n, r, sizeof r);

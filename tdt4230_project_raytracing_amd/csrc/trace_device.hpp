@@ -200,6 +200,9 @@ struct NodeSource {
   const uint32_t *grid32; const void *bricks;         // BRICK builds: the 5-level table with brick headers (LDS) and the bricks (global memory, 16-bit entries)
   const float2 *thr; float thr_f0max;                 // FORM_TABLE builds: (F1, F2) per cell (LDS) and the scene-wide bound on F0, see x_thresholds
   __amdgpu_buffer_rsrc_t cells;                       // raw buffer over the cells payload (8-byte granules)
+#ifdef TDT_STATS
+  uint32_t *stat_fallback;                            // -DTDT_STATS builds: the wave's STAT_FALLBACK_PASS / _LANES rows (LDS)
+#endif
 };
 
 // returns the node's value; code = 0 EMPTY, 2 LEAF, 1 otherwise (rc:384-386 only distinguishes these)
@@ -413,6 +416,7 @@ TDT_DEV float4 x_thresholds(uint32_t v, float inv_cell_count, int32_t cell_count
 // key = node index (29 bits) | code << 30.
 template <int CL>
 struct NodeMemo { uint32_t key[CL]; uint32_t val[CL]; };
+template <> struct NodeMemo<0> { uint32_t key[1]; uint32_t val[1]; };      // (no level keeps a memo: never read)
 // Top-level jump table (kGridLevels = 4 levels).  The y and z child digits of treeLookup are exact integer digits
 // (tree_lookup_pow2); the x decision of a level is  a = fl(v + f) - v > 0.5  (and b = ... == 1), which differs from the
 // plain binary digit floor(2 f) only when f lies within ulp(v + f) above 1/2 or below 1: <= 2^-17 for a cell index
@@ -687,10 +691,12 @@ TDT_DEV bool full_entry_planes(const FullGridEntry64 &g, const float2 *planes, C
 }
 // UNIT and cp: the plane form of the FULL builds (cp != nullptr there and nowhere else) — *cp gets the cell's planes, from the table or,
 // behind the walk, from slab_planes; gx, gy, gz are then not written
-template <bool COUNT, int CL, int DEPTH, bool RESIDENT, bool SAFEV, bool FULL = false, bool BRICK = false, bool TABLE = false, bool UNIT = false>
+// GLOBAL: no LDS node table (ns.lds is not read): every level of the walk reads the cells from global memory, range-checked
+template <bool COUNT, int CL, int DEPTH, bool RESIDENT, bool SAFEV, bool FULL = false, bool BRICK = false, bool TABLE = false, bool UNIT = false, bool GLOBAL = false>
 TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float fx, float fy, float fz, float &inv_pow_depth,
                               float &gx, float &gy, float &gz, uint32_t &value, NodeMemo<CL> &memo, Counters &cnt, CellPlanes *cp = nullptr) {
   static_assert(!TABLE || (SAFEV && !BRICK && !FULL), "per-cell thresholds: the resident walk, or (trees outside the LDS table) the jump table's bands only");
+  static_assert(!GLOBAL || (FULL && !RESIDENT && !COUNT), "the walk from global memory: behind the whole-depth table");
   constexpr bool PLANES = FULL && !COUNT && kFullEntryForm == kFullPlanes;
   const int depth = DEPTH > 0 ? DEPTH : P.max_depth;
   const float scale_d = __uint_as_float((uint32_t)(127 + depth) << 23);     // 2^depth
@@ -716,6 +722,12 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
       if constexpr (PLANES) return full_entry_planes<DEPTH>(g, ns.planes, *cp, inv_pow_depth, value);
       else return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
     }
+#ifdef TDT_STATS
+    {                                                 // the wave takes the level walk: one pass, and the lanes in a band that sent it there
+      const unsigned long long in_band = __ballot(!safe);
+      if ((threadIdx.x & 63) == (uint32_t)__builtin_ctzll(__ballot(1))) { ns.stat_fallback[0] += 1u; ns.stat_fallback[1] += (uint32_t)__popcll(in_band); }
+    }
+#endif
   } else if constexpr (BRICK && !COUNT) {
     static_assert(!BRICK || (DEPTH >= 6 && DEPTH <= 10 && !RESIDENT && SAFEV), "the 32-bit table: trees of depth 6-10 outside the LDS table");
     constexpr int BL = (int)brick_levels(DEPTH);      // levels a brick covers: all of them below the table (depths 6-9), or no bricks (depth 10)
@@ -840,7 +852,7 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
     // a sentinel: EMPTY (0) when the whole buffer is resident — a read past the end of the buffer IS 0
     // (robust access) — and the escape code otherwise, which sends the lane to the range-checked HBM path.
     bool resident = false;
-    if (RESIDENT || l < kNoProbeFrom) {
+    if (!GLOBAL && (RESIDENT || l < kNoProbeFrom)) {
       const uint32_t li = idx < ns.lds_nodes ? idx : ns.lds_nodes;
       const uint32_t n = ns.lds[li];
       resident = RESIDENT || (n != kPackedEscape);

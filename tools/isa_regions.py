@@ -20,12 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tdt4230_project_raytracing_amd import build as b   # noqa: E402
 
-# the builds the bench frames run (tests/test_gpu_variants.py pins them): <COUNT, FORM, DEPTH, RESIDENT, SAFEV, FULL, UNIT, BRICK>
+# the builds the bench frames run (tests/test_gpu_variants.py pins them): <COUNT, FORM, DEPTH, RESIDENT, SAFEV, FULL, UNIT, BRICK, BLOCK, PER_CU>
 KERNELS = {
-    "config2_64cube_full": "_ZN3tdt12trace_kernelILb0ELi1ELi6ELb1ELb1ELb1ELb1ELb0EEEv11TraceParams",
-    "config3_256cube_brick8": "_ZN3tdt12trace_kernelILb0ELi1ELi8ELb0ELb1ELb0ELb1ELb1EEEv11TraceParams",
-    "config5_512cube_brick9": "_ZN3tdt12trace_kernelILb0ELi1ELi9ELb0ELb1ELb0ELb1ELb1EEEv11TraceParams",
-    "config0_demo_table10": "_ZN3tdt12trace_kernelILb0ELi2ELi10ELb1ELb1ELb0ELb1ELb0EEEv11TraceParams",
+    "config2_64cube_full": "_ZN3tdt12trace_kernelILb0ELi1ELi6ELb1ELb1ELb1ELb1ELb0ELi256ELi5EEEv11TraceParams",
+    "config3_256cube_brick8": "_ZN3tdt12trace_kernelILb0ELi1ELi8ELb0ELb1ELb0ELb1ELb1ELi1024ELi1EEEv11TraceParams",
+    "config5_512cube_brick9": "_ZN3tdt12trace_kernelILb0ELi1ELi9ELb0ELb1ELb0ELb1ELb1ELi1024ELi1EEEv11TraceParams",
+    "config0_demo_table10": "_ZN3tdt12trace_kernelILb0ELi2ELi10ELb1ELb1ELb0ELb1ELb0ELi1024ELi1EEEv11TraceParams",
 }
 TRANS = re.compile(r"v_(rcp|rsq|sqrt|exp|log|sin|cos)_")
 

@@ -60,6 +60,7 @@ if __name__ == "__main__":
     dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r04_kernel_resources.txt")
     rows = collect()
     head = ("# hipcc -Rpass-analysis=kernel-resource-usage over csrc/tdt_rt.hip with the build's flags (tools/kernel_resources.py).\n"
-            "# trace_kernel<COUNT, FORM (0 literal / 1 pow2 / 2 table), DEPTH, RESIDENT, SAFEV, FULL, UNIT, BRICK>; 1024-thread blocks: 128 VGPRs = 4 waves/SIMD is the cap.\n")
+            "# trace_kernel<COUNT, FORM (0 literal / 1 pow2 / 2 table), DEPTH, RESIDENT, SAFEV, FULL, UNIT, BRICK, BLOCK, PER_CU>; 1024 x 1 blocks: 128 VGPRs = 4 waves/SIMD is the cap;\n"
+            "# 256 x 5 blocks (the whole-depth builds): 96 VGPRs and 32 768 B of LDS = 5 waves/SIMD.\n")
     open(dst, "w").write(head + table(rows))
     print(table(rows))

@@ -3,14 +3,14 @@
 
 Three sources, one frame each (the main launch of a history-free frame, or a replay):
   * pass statistics of the PRODUCT kernels from a -DTDT_STATS build of the library (`collect`, on the GPU box, run with
-    TDT_LIB=build_ab/lib_stats.so TDT_STATS_SKIP_PROBE=1): traversal / event passes per wave and live lanes per code region;
+    TDT_LIB=tdt4230_project_raytracing_amd/libtdtrt_stats.so TDT_STATS_SKIP_PROBE=1): traversal / event passes per wave and live lanes per code region;
   * the SQ counters of the same frame under the product library (tools/profile_r0x.sh -> profiles/r0x_pmc_summary.json);
   * static VALU counts of the event regions (tools/isa_regions.py -> profiles/r04_isa_regions.json).
 `report` combines them:  VALU wave-instructions of the event regions = passes x size; the traversal step's = SQ_INSTS_VALU minus
 those (per loop pass: cross-checked against the hand count of the fast path); active lane-instructions likewise from
 SQ_THREAD_CYCLES_VALU.  The budget is in units of SIMD lane-slots: 1024 SIMDs x launch time x clock / 2 cycles x 64 lanes.
 
-    TDT_LIB=build_ab/lib_stats.so TDT_STATS_SKIP_PROBE=1 python tools/loss_budget.py collect --config 2 --mode fresh > stats.json
+    TDT_LIB=tdt4230_project_raytracing_amd/libtdtrt_stats.so TDT_STATS_SKIP_PROBE=1 python tools/loss_budget.py collect --config 2 --mode fresh > stats.json
     python tools/loss_budget.py report --stats-dir gpurun_out/r04/ --pmc profiles/r04_pmc_summary.json
 """
 import argparse, glob, json, os, sys
