@@ -394,6 +394,68 @@ class Octree {
     if (n) ctx.check(tdt_octree_extract_transform(ctx.raw(), &x, r, mask.size(), v.data(), n, &n));
     return v;
   }
+  // NEW: geodesic distance (tdt_octree_edit_geodesic): apply `op` (TDT_REGION_*) to the reach set of `g` — every voxel of g.medium
+  // whose cheapest path of face / edge / corner steps (costs g.w) from one of `seeds_xyz` (x, y, z triples), staying inside the
+  // medium and inside the union of `mask` (none: anywhere), costs at most g.max_cost — in material g.material (-1: the voxel's
+  // own, the SOLID medium only).  The soft selection and the pouring tool.  Returns the number of cells.
+  uint32_t reach(const Context &ctx, int op, const tdt_geodesic &g, const std::vector<int32_t> &seeds_xyz, const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_geodesic(ctx.raw(), op, &g, seeds_xyz.empty() ? nullptr : seeds_xyz.data(), seeds_xyz.size() / 3,
+                                       mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: a reach click: pick pixel (x, y) of the raytracer's camera (sample 0) and on a hit run reach() from the grid voxel behind
+  // the face (the SOLID medium) or in front of it (the EMPTY medium) (tdt_pick_grid_voxel).  Returns whether an edit ran; *hit
+  // receives the pick, *n_cells the size.
+  bool reach(const ComputeShader &raytracer, int x, int y, int op, const tdt_geodesic &g, const std::vector<tdt_region> &mask = {},
+             tdt_ray_hit *hit = nullptr, uint32_t *n_cells = nullptr) const {
+    const tdt_ray_hit h = raytracer.pick({{{x, y}}}, 0)[0];
+    if (hit) *hit = h;
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    int32_t c[3];
+    if (tdt_pick_grid_voxel(&h, floats, ints, g.medium == TDT_MEDIUM_EMPTY ? 1 : 0, c) != 0) return false;   // miss / stale record / outside
+    const uint32_t n = reach(raytracer.context(), op, g, {c[0], c[1], c[2]}, mask);
+    if (n_cells) *n_cells = n;
+    return true;
+  }
+  // NEW: the reach set itself, voxels {x, y, z, material + 1} in Morton order, the tree untouched (tdt_octree_extract_geodesic)
+  std::vector<int32_t> extract_reach(const Context &ctx, const tdt_geodesic &g, const std::vector<int32_t> &seeds_xyz,
+                                     const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const int32_t *s = seeds_xyz.empty() ? nullptr : seeds_xyz.data();
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_geodesic(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_geodesic(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), v.data(), n, &n));
+    return v;
+  }
+  // NEW: the geodesic distance over the inclusive box lo..hi (tdt_octree_geodesic_field), x fastest; -1 where a voxel is not in
+  // the medium, unreachable or beyond g.max_cost
+  std::vector<int32_t> reach_field(const Context &ctx, const tdt_geodesic &g, const std::vector<int32_t> &seeds_xyz, const int32_t lo[3],
+                                   const int32_t hi[3], const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const int32_t *s = seeds_xyz.empty() ? nullptr : seeds_xyz.data();
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_geodesic_field(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), lo, hi, nullptr, 0, &n));
+    std::vector<int32_t> f(n);
+    if (n) ctx.check(tdt_octree_geodesic_field(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), lo, hi, f.data(), n, &n));
+    return f;
+  }
+  // NEW: the canonical shortest path from `goal` back to the seed it reaches, x, y, z triples with the goal first
+  // (tdt_octree_geodesic_path); *cost receives its cost.  A goal outside the reach set: no points, cost -1.
+  std::vector<int32_t> path(const Context &ctx, const tdt_geodesic &g, const std::vector<int32_t> &seeds_xyz, const int32_t goal[3],
+                            const std::vector<tdt_region> &mask = {}, int32_t *cost = nullptr) const {
+    size_t n = 0;
+    int32_t c = -1;
+    const int32_t *s = seeds_xyz.empty() ? nullptr : seeds_xyz.data();
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_geodesic_path(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), goal, nullptr, 0, &n, &c));
+    std::vector<int32_t> p(3 * n);
+    if (n) ctx.check(tdt_octree_geodesic_path(ctx.raw(), &g, s, seeds_xyz.size() / 3, r, mask.size(), goal, p.data(), n, &n, &c));
+    if (cost) *cost = c;
+    return p;
+  }
   // NEW: stamp a triangle mesh (tdt_octree_edit_triangles): op (TDT_REGION_*) over the voxels the closed triangles touch —
   // vertices {x, y, z} fixed point, 64 units per voxel (tdt_mesh_quantize), triangles 3 vertex indices each, material 0..253 for
   // every triangle or, with `materials`, material + 1 per triangle (the highest covering triangle wins).  A surface

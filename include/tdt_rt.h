@@ -706,6 +706,73 @@ int tdt_octree_extract_transform(tdt_ctx *ctx, const tdt_xform *xf, const tdt_re
 int tdt_octree_transform(tdt_ctx *ctx, const tdt_xform *xf, int op, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
 int tdt_debug_xform_bricks(const tdt_ctx *ctx, uint32_t out[2]);
 
+/* ---- geodesic distance --------------------------------------------------------------------------------------------------------
+ * How far is it from here if you must stay inside the object, or walk round the walls: reach fields, reach edits and shortest
+ * paths.  N = 2^max_depth (slot 7), G = [0, N)^3, V = what tdt_octree_extract returns; nothing wraps around the grid.
+ *   Medium P, the voxels a path may visit: TDT_MEDIUM_EMPTY = G \ V; TDT_MEDIUM_SOLID = V when `match` is -1, with `match` in
+ *     0..253 only the voxels of V whose LEAF value is `match`.  With n_regions > 0, P is further intersected with the union M of
+ *     the regions (tdt_region shapes, the exact integer test of region edits): here the mask constrains the PATHS, not only the
+ *     report.  n_regions == 0: no mask.
+ *   Steps: an offset d in {-1, 0, 1}^3 \ {0} has class k(d) = |dx| + |dy| + |dz| - 1 (0 across a face, 1 an edge, 2 a corner) and
+ *     order t(d) = 9 (dx + 1) + 3 (dy + 1) + (dz + 1), tdt_octree_morph's.  A step p -> p + d is allowed when both ends are in P
+ *     and w[k(d)] > 0, and costs w[k(d)].  w[0] is in 1..255, w[1] and w[2] in 0..255, 0 meaning no such step; no ordering between
+ *     the three is assumed.  A diagonal step may pass between two voxels that are not in P: the project's meaning of
+ *     26-connectivity, as in connected components and enclosed space.  {1, 0, 0} are 6-steps, {1, 1, 1} 26-steps, {3, 4, 5} the
+ *     chamfer metric (about 3 x the Euclidean path length).
+ *   Distance: seeds are {x, y, z} triples; one off the grid or not in P is ignored.  g(q), q in P, is the minimum over paths of
+ *     allowed steps from any seed to q of the summed cost; a seed has g = 0.  g is a fixed point of the grid alone, so it does
+ *     not depend on scheduling and compares bit for bit.  `max_cost` is in 0..2^30; the reach set is R = { q in P : g(q) <= max_cost }.
+ *   Canonical shortest path from a goal q0 in R: while g(q_i) > 0, q_(i+1) = q_i + d for the first d in ascending t(d) whose step
+ *     is allowed and has g(q_i + d) + w[k(d)] == g(q_i).  It ends on a seed.
+ * tdt_octree_geodesic_field covers the inclusive box lo..hi, which must lie inside G and hold <= 2^26 voxels, in the layout and by
+ * the count / capacity rules of tdt_octree_distance_field (field == NULL only sets *n_voxels; capacity below the count:
+ * TDT_ERR_INVALID_VALUE with the count set): g(q) for q in R, -1 everywhere else (not in P, unreachable, beyond max_cost).
+ * tdt_octree_extract_geodesic returns R as {x, y, z, m}, Morton-sorted, by tdt_octree_extract's rules; m is the voxel's own
+ * material + 1 when `material` is -1 (SOLID only: with TDT_MEDIUM_EMPTY it is an error), else `material` + 1.  The tree, its
+ * counter and its versions are untouched.
+ * tdt_octree_edit_geodesic is tdt_octree_edit_voxels(op, that list), taken from the tree BEFORE the edit and never leaving the
+ * device: all four ops, tdt_octree_compact's install rule on every replica of a multi-device context, a failure leaving all of
+ * them unchanged, *n_cells on a misfit, exactly like tdt_octree_transform.
+ * tdt_octree_geodesic_path returns the canonical path, path[0] = goal and the last point the seed reached, *cost = g(goal).  A
+ * goal not in R: *n_points = 0, *cost = -1, TDT_OK.  path_xyz == NULL only counts; capacity below the count:
+ * TDT_ERR_INVALID_VALUE with the count set.
+ * Domain: the unit works on the box D = G cut by the bounding box of the regions' union (when masked), by bbox(V) (SOLID), and by
+ * the bounding box of the in-grid seeds grown by floor(max_cost / w_min) on every side, w_min the smallest positive weight (a
+ * step moves at most 1 per axis and costs at least w_min, so nothing outside is in R).  D must hold <= TDT_GEODESIC_DOMAIN_CAP
+ * voxels, checked on the host before any volume over it is allocated (for TDT_MEDIUM_EMPTY before the tree is walked).  Over D
+ * the unit allocates 4.5 bytes per voxel of its rows rounded out to multiples of 32 in x.  An empty D, no valid seed, an empty
+ * tree or an empty mask are valid: R is empty.
+ * Errors, nothing written: a NULL struct or required pointer, a bad medium / match / weight / max_cost / material / pad / op /
+ * shape / box, NULL seeds or regions with a count above 0, a LEAF value >= 254, |V| or |R| above 2^26, the domain cap exceeded:
+ * TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream;
+ * synchronous.  The query forms answer from device_ids[0]. */
+enum { TDT_MEDIUM_EMPTY = 0, TDT_MEDIUM_SOLID = 1 };
+#define TDT_GEODESIC_DOMAIN_CAP (1u << 27)
+typedef struct tdt_geodesic {
+  int32_t medium;              /* TDT_MEDIUM_* */
+  int32_t match;               /* SOLID: -1 any voxel, 0..253 this LEAF value only; EMPTY: must be -1 */
+  int32_t w[3];                /* cost of a face / edge / corner step */
+  int32_t max_cost;            /* 0..2^30 */
+  int32_t material;            /* list and edit forms: -1 = the voxel's own (SOLID only), 0..253 = this LEAF value */
+  int32_t pad;                 /* must be 0 */
+} tdt_geodesic;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_geodesic) == 32, "tdt_geodesic is 32 bytes");
+#else
+_Static_assert(sizeof(tdt_geodesic) == 32, "tdt_geodesic is 32 bytes");
+#endif
+int tdt_octree_geodesic_field(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t *seeds_xyz, size_t n_seeds, const tdt_region *regions,
+                              size_t n_regions, const int32_t lo[3], const int32_t hi[3], int32_t *field, size_t capacity, size_t *n_voxels);
+int tdt_octree_extract_geodesic(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t *seeds_xyz, size_t n_seeds, const tdt_region *regions,
+                                size_t n_regions, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+int tdt_octree_edit_geodesic(tdt_ctx *ctx, int op, const tdt_geodesic *g, const int32_t *seeds_xyz, size_t n_seeds, const tdt_region *regions,
+                             size_t n_regions, uint32_t *n_cells);
+int tdt_octree_geodesic_path(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t *seeds_xyz, size_t n_seeds, const tdt_region *regions,
+                             size_t n_regions, const int32_t goal[3], int32_t *path_xyz, size_t capacity, size_t *n_points, int32_t *cost);
+/* the relaxation passes of the context's last geodesic call that changed the volume (0: the seeds were the fixed point, or D was
+ * empty); the host queues passes in batches of 8, so up to 8 more ran idle.  Measurement only. */
+int tdt_debug_geodesic_passes(const tdt_ctx *ctx);
+
 /* which build of the trace kernel the context's last trace launch ran: out = {form: 0 the literal float index, 1 the exact form of a
  * power-of-two cell_count, 2 per-cell thresholds (any other count); compile-time depth (0 = the general kernel); tree inside the LDS
  * table; whole-depth table; bricks; the build that skips multiplications by a scale of 1.0f}.  Every build writes the same pixels; this

@@ -5,6 +5,7 @@
 //   tdt_demo [--size WxH] [--spp N] [--bounce N] [--settings camera.ron] [--move KEYS] [--edit x,y,z,type,value]
 //            [--pick X,Y [--click left|right] [--material N]] [--brush sphere:R|box:R] [--box x0,y0,z0,x1,y1,z1]
 //            [--op set|fill|paint|clear] [--flood paint|clear] [--match any|material] [--connect 6|26] [--components]
+//            [--reach COST [--steps 6|26|345] [--medium solid|empty] [--match-material] [--op ..] [--material K] [--mask ..]]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
 //            [--morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG [--pivot X,Y,Z] [--op ..]
@@ -29,6 +30,12 @@
 //   tool (Octree::flood): the connected component that holds the grid voxel behind the picked face is painted with material N
 //   or removed (neighbours by face, 6, the default, or also by edge and corner, 26; any voxel, the default, or only the same
 //   material).  Prints the pick and the new cell count.
+// --reach COST [--steps 6|26|345] [--medium solid|empty] [--match-material] [--op set|fill|paint|clear] [--material K]
+//   [--mask x0,y0,z0,x1,y1,z1]: with --pick, the soft selection / pouring tool (Octree::reach): every voxel within geodesic cost
+//   COST of the picked voxel — walking through the object (solid, the default: from the voxel behind the picked face, through
+//   voxels of its material only with --match-material) or through the air (empty: from the voxel in front of it), by face steps
+//   (6, the default), face / edge / corner steps of cost 1 (26) or the chamfer weights 3 / 4 / 5 (345), inside the --mask box
+//   only — is applied with `op` in material K (solid: default the voxel's own).  Prints the pick and the new cell count.
 // --components [--connect 6|26] [--match any|material]: prints the component count and the largest component's size.
 // --morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]: voxel morphology (Octree::morph) of R steps with
 //   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
@@ -82,6 +89,8 @@ int main(int argc, char **argv) {
   int brush_shape = -1, brush_size = 0, op = TDT_REGION_SET;
   int flood_op = -1, connect = 6, match = TDT_MATCH_ANY;
   bool components = false;
+  int reach_cost = -1, reach_steps = 6, reach_medium = TDT_MEDIUM_SOLID;
+  bool reach_match = false;
   int morph_op = -1, morph_radius = 0, morph_conn = 6;
   std::string morph_name;
   int round_op = -1, round_r2 = 0, round_border = 0;
@@ -134,6 +143,14 @@ int main(int argc, char **argv) {
     }
     else if (a == "--connect") { connect = std::atoi(next()); if (connect != 6 && connect != 26) { std::fprintf(stderr, "--connect 6|26\n"); return 2; } }
     else if (a == "--components") components = true;
+    else if (a == "--reach") { reach_cost = std::atoi(next()); if (reach_cost < 0) { std::fprintf(stderr, "--reach COST\n"); return 2; } }
+    else if (a == "--steps") { reach_steps = std::atoi(next()); if (reach_steps != 6 && reach_steps != 26 && reach_steps != 345) { std::fprintf(stderr, "--steps 6|26|345\n"); return 2; } }
+    else if (a == "--medium") {
+      const std::string v = next();
+      if (v == "solid") reach_medium = TDT_MEDIUM_SOLID; else if (v == "empty") reach_medium = TDT_MEDIUM_EMPTY;
+      else { std::fprintf(stderr, "--medium solid|empty\n"); return 2; }
+    }
+    else if (a == "--match-material") reach_match = true;
     else if (a == "--morph") {
       char kind[16] = {0};
       static const char *names[5] = {"dilate", "erode", "open", "close", "shell"};
@@ -294,7 +311,29 @@ int main(int argc, char **argv) {
       for (int a = 0; a < 3; a++) { r.a[a] = box[a]; r.b[a] = box[3 + a]; }
       std::printf("box cells %u\n", octree.edit_region(ctx, op, {r}, material));
     }
-    if (pick_x >= 0 && flood_op >= 0) {                                                  // a flood click at the pixel
+    if (pick_x >= 0 && reach_cost >= 0) {                                                // a reach click at the pixel
+      tdt_ray_hit h;
+      uint32_t cells = 0;
+      tdt_geodesic g{};
+      g.medium = reach_medium; g.match = -1; g.max_cost = reach_cost;
+      g.w[0] = reach_steps == 345 ? 3 : 1; g.w[1] = reach_steps == 345 ? 4 : reach_steps == 26 ? 1 : 0; g.w[2] = reach_steps == 345 ? 5 : reach_steps == 26 ? 1 : 0;
+      g.material = (material_given || reach_medium == TDT_MEDIUM_EMPTY) ? material : -1;
+      if (reach_match) {                                                                 // only the picked voxel's own material
+        const tdt_ray_hit first = raytrace_program.pick({{{pick_x, pick_y}}}, 0)[0];
+        if (first.status == TDT_RAY_HIT) g.match = (int32_t)first.material;
+      }
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      const bool edited = octree.reach(raytrace_program, pick_x, pick_y, op, g, regions, &h, &cells);
+      std::printf("pick %d,%d status %d material %u t %.9g point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d reach %d steps %d medium %s %s cells %u\n",
+                  pick_x, pick_y, h.status, h.material, h.t, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1], h.normal[2], h.fresh_record,
+                  reach_cost, reach_steps, reach_medium == TDT_MEDIUM_SOLID ? "solid" : "empty", edited ? "applied" : "none", cells);
+    } else if (pick_x >= 0 && flood_op >= 0) {                                           // a flood click at the pixel
       tdt_ray_hit h;
       uint32_t cells = 0;
       tdt_select sel{};

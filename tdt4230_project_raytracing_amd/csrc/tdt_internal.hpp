@@ -4,7 +4,8 @@
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
 // tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
 // tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance;
-// tdt_bitvol.hip: the dense bit volume the last two and tdt_xform.hip share; tdt_xform.hip: affine transforms of selections).
+// tdt_bitvol.hip: the dense bit volume the last two, tdt_xform.hip and tdt_geodesic.hip share; tdt_xform.hip: affine transforms
+// of selections; tdt_geodesic.hip: geodesic distance).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,6 +65,7 @@ struct tdt_ctx {
   void *query = nullptr; size_t query_bytes = 0;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
+  uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
   std::vector<tdt_buffer *> buffers;
   std::vector<tdt_image *> images;
   std::vector<tdt_compute *> computes;

@@ -188,6 +188,22 @@ class Xform(ctypes.Structure):
 
 assert ctypes.sizeof(Xform) == 96
 
+# geodesic distance (include/tdt_rt.h): media, step-weight presets and struct tdt_geodesic
+MEDIUM_EMPTY, MEDIUM_SOLID = 0, 1
+GEODESIC_DOMAIN_CAP = 1 << 27
+STEPS_6, STEPS_26, CHAMFER_345 = (1, 0, 0), (1, 1, 1), (3, 4, 5)
+
+
+class Geodesic(ctypes.Structure):
+    """struct tdt_geodesic: medium MEDIUM_*, match -1 (any voxel) or 0..253 (SOLID: that LEAF value only), w the cost of a face /
+    edge / corner step (w[0] 1..255, the others 0..255 with 0 = no such step), max_cost 0..2^30, material -1 (the voxel's own,
+    SOLID only) or 0..253 for the list and edit forms, pad 0."""
+    _fields_ = [("medium", ctypes.c_int32), ("match", ctypes.c_int32), ("w", ctypes.c_int32 * 3), ("max_cost", ctypes.c_int32),
+                ("material", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Geodesic) == 32
+
 
 def _exact_ints(a, dtype, name):
     """a as a contiguous array of an integer dtype, refusing what the cast would change (a wrapped index would be a valid one)."""
@@ -307,6 +323,13 @@ SYMBOLS = [
     ("tdt_octree_extract_transform", _I, [_P, ctypes.POINTER(Xform), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_transform", _I, [_P, ctypes.POINTER(Xform), _I, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_debug_xform_bricks", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_geodesic_field", _I, [_P, ctypes.POINTER(Geodesic), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                       _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_extract_geodesic", _I, [_P, ctypes.POINTER(Geodesic), _P, _S, _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_geodesic", _I, [_P, _I, ctypes.POINTER(Geodesic), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_geodesic_path", _I, [_P, ctypes.POINTER(Geodesic), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_int32), _P, _S,
+                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]),
+    ("tdt_debug_geodesic_passes", _I, [_P]),
     ("tdt_selftest", _I, [_P, _I, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_selftest_index", _I, [_P, ctypes.c_int32, _F, ctypes.c_uint32, _I, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
 ]
@@ -816,6 +839,90 @@ class Context:
         out = (ctypes.c_uint32 * 2)()
         self.check(lib().tdt_debug_xform_bricks(self.h, out))
         return int(out[0]), int(out[1])
+
+    @classmethod
+    def _geodesic(cls, medium, steps, max_cost, match, material, seeds):
+        """(struct tdt_geodesic, the seed array, its count) of a geodesic call: steps three weights (STEPS_6, STEPS_26, CHAMFER_345
+        or any other), match / material None = -1.  Every entry must fit an int32 (ctypes would wrap it silently); the ranges
+        themselves are the library's to check.  Seeds: an (n, 3) array; none is a valid call with an empty result."""
+        steps = list(steps)
+        if len(steps) != 3:
+            raise ValueError("steps must hold three weights")
+        g = Geodesic(cls._int32("medium", medium), cls._int32("match", -1 if match is None else match),
+                     (ctypes.c_int32 * 3)(*[cls._int32("steps", v) for v in steps]), cls._int32("max_cost", max_cost),
+                     cls._int32("material", -1 if material is None else material), 0)
+        s = np.ascontiguousarray(_exact_ints(np.asarray(seeds).reshape(-1, 3) if len(seeds) else np.zeros((0, 3), np.int32), np.int32, "seeds"))
+        return g, s, len(s)
+
+    def octree_geodesic_field(self, seeds, lo, hi, medium=MEDIUM_SOLID, steps=STEPS_6, max_cost=1 << 30, match=None, regions=None):
+        """tdt_octree_geodesic_field: the geodesic distance g from the seeds ((n, 3) voxel coordinates) through the medium
+        (MEDIUM_SOLID: the tree's voxels, of LEAF value `match` only when given; MEDIUM_EMPTY: the empty voxels), a step across a
+        face / an edge / a corner costing steps[0..2] (0: no such step), over the inclusive box lo..hi as an (ez, ey, ex) int32
+        array; -1 where a voxel is not in the medium, unreachable or beyond max_cost.  regions (one Region or a list) confine the
+        PATHS (None: no mask; an empty list: an empty mask, so nothing is reached).  The tree is untouched."""
+        g, s, k = self._geodesic(medium, steps, max_cost, match, None, seeds)
+        arr, kr = _touch_regions(regions)
+        box3 = []
+        for name, c in (("lo", lo), ("hi", hi)):
+            c = list(c)
+            if len(c) != 3:
+                raise ValueError(f"{name} must hold three coordinates")
+            box3.append((ctypes.c_int32 * 3)(*[self._int32(name, v) for v in c]))
+        n = ctypes.c_size_t(0)
+        sp = s.ctypes.data if k else None
+        self.check(lib().tdt_octree_geodesic_field(self.h, ctypes.byref(g), sp, k, arr, kr, box3[0], box3[1], None, 0, ctypes.byref(n)))
+        ex, ey, ez = (int(box3[1][a]) - int(box3[0][a]) + 1 for a in range(3))
+        field = np.zeros((ez, ey, ex), np.int32)
+        assert field.size == n.value
+        self.check(lib().tdt_octree_geodesic_field(self.h, ctypes.byref(g), sp, k, arr, kr, box3[0], box3[1], field.ctypes.data, field.size,
+                                                   ctypes.byref(n)))
+        return field
+
+    def octree_extract_geodesic(self, seeds, medium=MEDIUM_SOLID, steps=STEPS_6, max_cost=1 << 30, match=None, material=None, regions=None):
+        """tdt_octree_extract_geodesic: the reach set { g <= max_cost } of octree_geodesic_field's distance as an (n, 4) int32 list
+        {x, y, z, material + 1}, Morton-sorted; material None: the voxel's own (MEDIUM_SOLID only), or 0..253.  The tree is
+        untouched.  Counts first, fills second: two relaxations."""
+        g, s, k = self._geodesic(medium, steps, max_cost, match, material, seeds)
+        arr, kr = _touch_regions(regions)
+        n = ctypes.c_size_t(0)
+        sp = s.ctypes.data if k else None
+        self.check(lib().tdt_octree_extract_geodesic(self.h, ctypes.byref(g), sp, k, arr, kr, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_extract_geodesic(self.h, ctypes.byref(g), sp, k, arr, kr, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def octree_edit_geodesic(self, op, seeds, medium=MEDIUM_SOLID, steps=STEPS_6, max_cost=1 << 30, match=None, material=None, regions=None):
+        """tdt_octree_edit_geodesic: octree_edit_voxels(op, octree_extract_geodesic(...)) with the list taken from the tree before
+        the edit and never leaving the device; returns the canonical tree's cell count."""
+        g, s, k = self._geodesic(medium, steps, max_cost, match, material, seeds)
+        op = self._int32("op", op)
+        arr, kr = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_geodesic(self.h, op, ctypes.byref(g), s.ctypes.data if k else None, k, arr, kr, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_geodesic_path(self, seeds, goal, medium=MEDIUM_SOLID, steps=STEPS_6, max_cost=1 << 30, match=None, regions=None):
+        """tdt_octree_geodesic_path: (the canonical shortest path from `goal` back to the seed it reaches as an (n, 3) int32 array,
+        path[0] = goal; g(goal)).  A goal outside the reach set: (an empty array, -1)."""
+        g, s, k = self._geodesic(medium, steps, max_cost, match, None, seeds)
+        arr, kr = _touch_regions(regions)
+        goal = list(goal)
+        if len(goal) != 3:
+            raise ValueError("goal must hold three coordinates")
+        q = (ctypes.c_int32 * 3)(*[self._int32("goal", v) for v in goal])
+        n, cost = ctypes.c_size_t(0), ctypes.c_int32(-1)
+        sp = s.ctypes.data if k else None
+        self.check(lib().tdt_octree_geodesic_path(self.h, ctypes.byref(g), sp, k, arr, kr, q, None, 0, ctypes.byref(n), ctypes.byref(cost)))
+        out = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            self.check(lib().tdt_octree_geodesic_path(self.h, ctypes.byref(g), sp, k, arr, kr, q, out.ctypes.data, n.value, ctypes.byref(n),
+                                                      ctypes.byref(cost)))
+        return out, int(cost.value)
+
+    def geodesic_passes(self):
+        """tdt_debug_geodesic_passes: the relaxation passes of the last geodesic call that changed the volume."""
+        return int(lib().tdt_debug_geodesic_passes(self.h))
 
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
