@@ -1,8 +1,10 @@
-// The dense bit volume over a box of the grid that enclosed space (tdt_fill.hip) and exact Euclidean distance (tdt_distance.hip)
-// share: the steps that take a Morton-sorted voxel list into the volume and a selection of its bits back into a list.  The
-// layout and the device helpers of the units' own count and emit kernels are bitvol_device.hpp's; the declarations are in
-// tdt_internal.hpp.  A kernel is launched from the unit that defines it, so the kernels here are reached through the host
-// functions below only.
+// The dense bit volume over a box of the grid that enclosed space (tdt_fill.hip), exact Euclidean distance (tdt_distance.hip),
+// affine transforms (tdt_xform.hip) and geodesic distance (tdt_geodesic.hip) share: the steps that take the tree's
+// Morton-sorted voxel list into the volume and a selection of its bits back into a list.  The layout, the device helpers of
+// the units' own count and emit kernels, and the host steps around those kernels (the pass loop, the list's tail from the
+// count to the list, a field's box: templates over what queues the unit's kernel) are bitvol_device.hpp's; the declarations
+// are in tdt_internal.hpp.  A kernel is launched from the unit that defines it, so the kernels here are reached through the
+// host functions below only.
 //
 //   bbox       one reduction over the list: a fixed launch of at most 256 blocks whose lanes stride over the list, wave
 //              shuffles, then one vector atomicMin / atomicMax per wave and axis: at most 6144 per call, on integers, so the
@@ -63,6 +65,12 @@ void bitvol_layout(const int lo[3], const int hi[3], BitBox &B) {
   B.ey = B.hi[1] - B.lo[1] + 1; B.ez = B.hi[2] - B.lo[2] + 1;
   B.wx0 = B.lo[0] >> 5; B.nw = (B.hi[0] >> 5) - B.wx0 + 1;
   B.n_words = (uint32_t)B.ey * (uint32_t)B.ez * (uint32_t)B.nw;
+}
+
+int bitvol_tree_voxels(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
+  if (int rc = tree_voxels(front, ctx, 254u, S, out, n, depth)) return rc;
+  if (*n > kBitvolCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(*n) + " voxels (more than 2^26)");
+  return TDT_OK;
 }
 
 int bitvol_list_bbox(tdt_ctx *front, hipStream_t st, const int4 *v, uint32_t n, int depth, DeviceScratch &S, const char *no_memory,

@@ -55,7 +55,6 @@ constexpr int kDistMaxR = 64;
 constexpr int kDistRows = kDistTile + 2 * kDistMaxR;
 constexpr int kDistNone = -128;                        // pass x: nothing within R
 constexpr unsigned kDistSelf = (128u << 8) | 128u;     // the pair of offsets (0, 0); a pair of 0 = none
-constexpr unsigned long long kDistCap = 1ull << 26;
 
 struct DistBox : BitBox {      // the domain and the layout of the volumes over it
   int32_t N, R;                // grid side; window
@@ -317,8 +316,7 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
-  if (nv > kDistCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
   if (nv == 0) return TDT_OK;                              // every op of the empty set is empty
   int box[6];
   if (int rc = bitvol_list_bbox(front, st, v, nv, depth, S, kNoMemory, "a voxel lies outside the grid", box)) return rc;
@@ -366,35 +364,26 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
       break;
   }
   TDT_HIP(front, hipGetLastError());
-  // ---- count ----
+  // ---- count, emit, sort ----
   const int all = delta ? 0 : 1, masked = n_shapes ? 1 : 0;
-  uint32_t *count = S.get<uint32_t>((size_t)B.n_words + 1), *scr = S.get<uint32_t>(scan_scratch_words((size_t)B.n_words + 1));
-  if (!count || !scr) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(dist_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)res,
-                     (const RegionShape *)d_shapes, n_shapes, masked, all, count);
-  TDT_HIP(front, exclusive_scan_u32(st, count, count, B.n_words + 1u, scr));
-  TDT_HIP(front, hipGetLastError());
-  uint32_t n_out = 0;                                      // <= 2^30: 32 per word
-  TDT_HIP(front, hipMemcpyAsync(&n_out, count + B.n_words, sizeof n_out, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the count
-  if (n_out > kDistCap) return fail(front, TDT_ERR_INVALID_VALUE, "the result holds " + std::to_string(n_out) + " voxels (more than 2^26)");
-  if (n_out == 0) return TDT_OK;
-  // ---- emit, sort ----
-  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
-  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(dist_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)res,
-                     (const RegionShape *)d_shapes, n_shapes, masked, all, (const uint32_t *)count, Q.material >= 0 ? (uint32_t)Q.material + 1u : 0u,
-                     (const unsigned short *)xy, (const signed char *)oz, (const uint32_t *)wk, (const uint32_t *)wv, nv, k0, v0);
-  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, !delta, S, kNoMemory, out)) return rc;
-  *n = n_out;
-  return TDT_OK;
+  auto count = [&](uint32_t *cnt) {
+    hipLaunchKernelGGL(dist_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)res,
+                       (const RegionShape *)d_shapes, n_shapes, masked, all, cnt);
+  };
+  auto emit = [&](const uint32_t *excl, uint32_t *keys, uint32_t *vals) {
+    hipLaunchKernelGGL(dist_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)res,
+                       (const RegionShape *)d_shapes, n_shapes, masked, all, excl, Q.material >= 0 ? (uint32_t)Q.material + 1u : 0u,
+                       (const unsigned short *)xy, (const signed char *)oz, (const uint32_t *)wk, (const uint32_t *)wv, nv, keys, vals);
+  };
+  return bitvol_list_tail(front, st, B.n_words, count, emit, "the result", !delta, nullptr, nullptr, 0u, S, kNoMemory, out, n);
 }
 
 struct RoundSource final : VoxelSource {
   const Request &R;
-  explicit RoundSource(const Request &r) : R(r) {}
+  const bool delta;              // the edit's difference from V, or the extract's whole result
+  RoundSource(const Request &r, bool d) : R(r), delta(d) {}
   int run(tdt_ctx *front, tdt_ctx *ctx, int, DeviceScratch &S, const int4 **vox, uint32_t *n) override {
-    return round_list(front, ctx, R, true, S, vox, n);
+    return round_list(front, ctx, R, delta, S, vox, n);
   }
 };
 
@@ -404,26 +393,18 @@ int field_one(tdt_ctx *front, tdt_ctx *ctx, const int32_t lo[3], const int32_t h
   // everything the host can check comes first: the count-only call walks no tree and queues nothing
   int depth = 0;
   if (int rc = walk_inputs(front, ctx, &depth)) return rc;
-  const int N = 1 << depth;
-  unsigned long long count = 1;
-  for (int a = 0; a < 3; a++) {
-    if (lo[a] < 0 || hi[a] >= N || lo[a] > hi[a]) return fail(front, TDT_ERR_INVALID_VALUE, "the box must satisfy 0 <= lo <= hi < 2^max_depth");
-    count *= (unsigned long long)(hi[a] - lo[a] + 1);
-  }
-  if (count > kDistCap) return fail(front, TDT_ERR_INVALID_VALUE, "the box holds " + std::to_string(count) + " voxels (more than 2^26)");
   DistBox B;
-  if (int rc = make_domain(front, lo, hi, depth, window_of(max_d2), B)) return rc;
-  *n_voxels = (size_t)count;
+  auto domain = [&] { return make_domain(front, lo, hi, depth, window_of(max_d2), B); };
+  if (int rc = bitvol_field_box(front, depth, lo, hi, domain, field != nullptr, capacity, n_voxels)) return rc;
   if (!field) return TDT_OK;
-  if (capacity < count) return fail(front, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " voxels");
+  const size_t count = *n_voxels;
   TDT_HIP(front, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   Drain drain{st};
   DeviceScratch S;
   int4 *v = nullptr;
   uint32_t nv = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) { *n_voxels = 0; return rc; }
-  if (nv > kDistCap) { *n_voxels = 0; return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)"); }
+  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) { *n_voxels = 0; return rc; }
   const size_t padded = (size_t)B.n_words * 32;
   uint32_t *occ = S.get<uint32_t>(B.n_words), *wk = S.get<uint32_t>(nv), *wv = S.get<uint32_t>(nv);
   signed char *ox = S.get<signed char>(padded);
@@ -455,7 +436,7 @@ int tdt_octree_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_region *r
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   Request R;
   if (int rc = make_request(ctx, r, regions, n_regions, R)) return rc;
-  RoundSource src(R);
+  RoundSource src(R, true);
   const bool grows = r->op == TDT_MORPH_DILATE || r->op == TDT_MORPH_CLOSE;
   return region_edit_source(ctx, grows ? TDT_REGION_FILL : TDT_REGION_CLEAR, src, n_cells);
 }
@@ -468,14 +449,8 @@ int tdt_octree_extract_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_r
   *n_voxels = 0;
   Request R;
   if (int rc = make_request(ctx, r, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
-  TDT_HIP(ctx, hipSetDevice(m->device));
-  Drain drain{m->stream};
-  DeviceScratch S;
-  const int4 *vox = nullptr;
-  uint32_t n = 0;
-  if (int rc = round_list(ctx, m, R, false, S, &vox, &n)) return rc;
-  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
+  RoundSource src(R, false);
+  return region_extract_source(ctx, src, 0, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border, int32_t *field,

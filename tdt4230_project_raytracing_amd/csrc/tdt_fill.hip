@@ -27,10 +27,9 @@
 //              and found its tile stable: that is the fixed point.
 //              Passes: information crosses one tile boundary per pass at least, so the number of passes is bounded by 1 + the
 //              length, in tiles entered, of the longest shortest path from a seed through empties (the longest corridor).  The
-//              host queues kFillBatch passes, each with a flag word of its own, and reads the flags with ONE synchronisation per
-//              batch; it stops when the last pass of a batch changed nothing, so at most kFillBatch - 1 passes run idle.
+//              host queues them in batches with one flag read per batch (bitvol_pass_loop).
 //   count      per word popc(empty & ~reach & in-mask), the mask being the exact integer test of region edits per set bit;
-//              exclusive_scan_u32 over the words; the total is read (one synchronisation) and held to 2^26.  fill_count_kernel
+//              bitvol_list_tail scans the counts, reads the total (one synchronisation) and holds it to 2^26.  fill_count_kernel
 //   emit       (Morton key, material + 1) per enclosed voxel at its word's offset.  Inherit: the first voxel of W in decreasing
 //              x is the highest set occupancy bit below the voxel, in its word (a count of leading zeros) or the words before
 //              it — it exists, or the voxel would reach the box's x0 face and be a seed — and its material is looked up in W's
@@ -51,8 +50,6 @@ namespace tdt {
 constexpr int kFillTile = 8;                           // rows per tile side, in y and in z
 constexpr int kFillHalo = kFillTile + 2;
 constexpr int kFillMaxWords = 32;                      // words per row: 2^10 voxels / 32
-constexpr int kFillBatch = 8;                          // flood passes per flag read
-constexpr unsigned long long kFillCap = 1ull << 26;
 
 // every run of set bits of e that holds a bit of s (s a subset of e), whole.  e + s: the lowest seed of a run carries through
 // the run's bits above it and stops in the clear bit behind the run (or leaves the word); a higher seed of the same run stays
@@ -219,7 +216,7 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
   BitBox B;
   bitvol_layout(box, box + 3, B);
   // ---- occupancy, seeds ----
-  uint32_t *occ = S.get<uint32_t>(B.n_words), *reach = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kFillBatch);
+  uint32_t *occ = S.get<uint32_t>(B.n_words), *reach = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kBitvolBatch);
   if (!occ || !reach || !flags) return fail(front, TDT_ERR_HIP, kNoMemory);
   if (int rc = bitvol_rasterise(front, st, w, n_w, B, occ, wk, wv)) return rc;
   hipLaunchKernelGGL(fill_seed_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, reach);
@@ -227,52 +224,26 @@ int enclosed_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *w, uint32_t n_w, i
   // ---- flood: a box thinner than 3 rows on an axis is all faces, and seeded whole ----
   if (B.ey > 2 && B.ez > 2 && B.hi[0] - B.lo[0] > 1) {
     const dim3 tiles((unsigned)((B.ey + kFillTile - 1) / kFillTile), (unsigned)((B.ez + kFillTile - 1) / kFillTile));
-    uint32_t h_flags[kFillBatch], queued = 0;
-    do {
-      TDT_HIP(front, hipMemsetAsync(flags, 0, sizeof h_flags, st));
-      for (int p = 0; p < kFillBatch; p++) {
-        if (R.f.connectivity == 6) hipLaunchKernelGGL(fill_flood_kernel<6>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flags + p);
-        else hipLaunchKernelGGL(fill_flood_kernel<26>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flags + p);
-      }
-      TDT_HIP(front, hipGetLastError());
-      TDT_HIP(front, hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
-      TDT_HIP(front, hipStreamSynchronize(st));            // one per batch of passes
-      for (int p = kFillBatch - 1; p >= 0; p--)
-        if (h_flags[p]) { front->fill_passes = queued + (uint32_t)p + 1u; break; }   // the last pass that changed the volume
-      queued += kFillBatch;
-    } while (h_flags[kFillBatch - 1]);
+    auto flood = [&](uint32_t *flag) {
+      if (R.f.connectivity == 6) hipLaunchKernelGGL(fill_flood_kernel<6>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flag);
+      else hipLaunchKernelGGL(fill_flood_kernel<26>, tiles, dim3(256), 0, st, B, (const uint32_t *)occ, reach, flag);
+    };
+    if (int rc = bitvol_pass_loop(front, st, flags, flood, &front->fill_passes)) return rc;
   }
-  // ---- count ----
+  // ---- count, emit, sort: W's own pairs in front for the solid forms; the cap is on the enclosed voxels alone ----
   RegionShape *d_shapes = nullptr;
   const uint32_t n_shapes = with_walls ? 0u : (uint32_t)R.shapes.size();
   if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
-  uint32_t *count = S.get<uint32_t>((size_t)B.n_words + 1), *scr = S.get<uint32_t>(scan_scratch_words((size_t)B.n_words + 1));
-  if (!count || !scr) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(fill_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
-                     (const RegionShape *)d_shapes, n_shapes, count);
-  TDT_HIP(front, exclusive_scan_u32(st, count, count, B.n_words + 1u, scr));
-  TDT_HIP(front, hipGetLastError());
-  uint32_t n_e = 0;                                        // <= 2^30: 32 per word
-  TDT_HIP(front, hipMemcpyAsync(&n_e, count + B.n_words, sizeof n_e, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the enclosed count
-  if (n_e > kFillCap) return fail(front, TDT_ERR_INVALID_VALUE, "the enclosed space holds " + std::to_string(n_e) + " voxels (more than 2^26)");
-  const uint32_t n_out = n_e + (with_walls ? n_w : 0u);
-  if (n_out == 0) return TDT_OK;
-  // ---- emit, sort ----
-  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
-  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
-  const uint32_t at = with_walls ? n_w : 0u;
-  if (with_walls) {
-    TDT_HIP(front, hipMemcpyAsync(k0, wk, (size_t)n_w * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    TDT_HIP(front, hipMemcpyAsync(v0, wv, (size_t)n_w * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  }
-  if (n_e)
+  auto count = [&](uint32_t *cnt) {
+    hipLaunchKernelGGL(fill_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
+                       (const RegionShape *)d_shapes, n_shapes, cnt);
+  };
+  auto emit = [&](const uint32_t *excl, uint32_t *keys, uint32_t *vals) {
     hipLaunchKernelGGL(fill_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)occ, (const uint32_t *)reach,
-                       (const RegionShape *)d_shapes, n_shapes, (const uint32_t *)count, R.f.material >= 0 ? (uint32_t)R.f.material + 1u : 0u,
-                       (const uint32_t *)wk, (const uint32_t *)wv, n_w, k0 + at, v0 + at);
-  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, true, S, kNoMemory, out)) return rc;
-  *n = n_out;
-  return TDT_OK;
+                       (const RegionShape *)d_shapes, n_shapes, excl, R.f.material >= 0 ? (uint32_t)R.f.material + 1u : 0u, (const uint32_t *)wk,
+                       (const uint32_t *)wv, n_w, keys, vals);
+  };
+  return bitvol_list_tail(front, st, B.n_words, count, emit, "the enclosed space", true, wk, wv, with_walls ? n_w : 0u, S, kNoMemory, out, n);
 }
 
 // the list a call produces on one single-device context: the tree form (mesh == null: E(V, c) within the mask) or the solid mesh
@@ -285,9 +256,7 @@ int fill_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, const tdt_mesh *me
   }
   int4 *v = nullptr;
   uint32_t nv = 0;
-  // (as in the sibling units the cap is checked on the expanded list: 16 B per voxel of the tree before it can fail)
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
-  if (nv > kFillCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
   return enclosed_voxels(front, ctx, v, nv, depth, R, false, S, out, n);
 }
 
@@ -299,18 +268,6 @@ struct FillSource final : VoxelSource {
     return fill_list(front, ctx, R, mesh, depth, S, vox, n);
   }
 };
-
-// the list into host memory by tdt_octree_extract's rules, from device_ids[0] of a multi-device context
-int fill_extract(tdt_ctx *ctx, const Request &R, const tdt_mesh *mesh, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
-  TDT_HIP(ctx, hipSetDevice(m->device));
-  Drain drain{m->stream};
-  DeviceScratch S;
-  const int4 *vox = nullptr;
-  uint32_t n = 0;
-  if (int rc = fill_list(ctx, m, R, mesh, depth, S, &vox, &n)) return rc;
-  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", host_out, capacity, n_out);
-}
 
 }  // namespace
 }  // namespace tdt
@@ -325,7 +282,8 @@ int tdt_octree_extract_enclosed(tdt_ctx *ctx, const tdt_fill *f, const tdt_regio
   *n_voxels = 0;
   Request R;
   if (int rc = make_request(ctx, f, regions, n_regions, R)) return rc;
-  return fill_extract(ctx, R, nullptr, 0, voxels_xyzm, capacity, n_voxels);
+  FillSource src(R, nullptr);
+  return region_extract_source(ctx, src, 0, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_fill_enclosed(tdt_ctx *ctx, const tdt_fill *f, const tdt_region *regions, size_t n_regions, uint32_t *n_cells) {
@@ -347,7 +305,8 @@ int tdt_voxelize_triangles_solid(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, 
   if (int rc = check_mesh(ctx, mesh)) return rc;
   Request R;
   if (int rc = make_request(ctx, f, nullptr, 0, R)) return rc;
-  return fill_extract(ctx, R, mesh, depth, voxels_xyzm, capacity, n_voxels);
+  FillSource src(R, mesh);
+  return region_extract_source(ctx, src, depth, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_edit_triangles_solid(tdt_ctx *ctx, int op, const tdt_mesh *mesh, const tdt_fill *f, uint32_t *n_cells) {

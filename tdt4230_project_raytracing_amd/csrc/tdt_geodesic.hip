@@ -29,10 +29,10 @@
 //              lane that reads a neighbour's entry (in LDS within a round, or in memory for its halo) sees an old or a new
 //              value, both no smaller than the fixed point and both the cost of a real path; and a pass whose flag stays clear
 //              changed nothing anywhere, so every block saw the final volume and found its tile stable: that is the fixed point,
-//              which is g cut at max_cost.  The host queues kGeoBatch passes, each with a flag word of its own, and reads the
-//              flags with ONE synchronisation per batch.
+//              which is g cut at max_cost.  The host queues the passes in batches with one flag read per batch
+//              (bitvol_pass_loop).
 //   reach      per padded voxel (cost < kGeoFar), a wave's ballot is two words of the reach volume.            geo_reach_kernel
-//   count      per word popc of the reach bits, exclusive_scan_u32, the total read and held to 2^26.           geo_count_kernel
+//   count      per word popc of the reach bits; bitvol_list_tail scans them, reads the total, holds it to 2^26.  geo_count_kernel
 //   emit       (Morton key, material + 1) per reached voxel at its word's offset, the material the fixed one or the voxel's own
 //              by lookup in V's sorted keys; tdt_bitvol.hip's tail sorts the pairs and writes the list.         geo_emit_kernel
 //   field      a gather over the requested box: the cost, or -1 outside D and where it is not finite.          geo_field_kernel
@@ -55,10 +55,8 @@ namespace tdt {
 constexpr int kGeoTile = 8;                              // rows per tile side, in y and in z; a tile is one word wide in x
 constexpr int kGeoHX = 34, kGeoHY = kGeoTile + 2, kGeoHZ = kGeoTile + 2;
 constexpr int kGeoCells = kGeoHX * kGeoHY * kGeoHZ;      // 3400 entries
-constexpr int kGeoBatch = 8;                             // relaxation passes per flag read
 constexpr uint32_t kGeoFar = 0x7FFFFFFEu;                // in P, not reached
 constexpr uint32_t kGeoWall = 0x7FFFFFFFu;               // not in P, or padding
-constexpr unsigned long long kGeoCap = 1ull << 26;
 
 struct GeoSteps {
   uint32_t w[3];               // face / edge / corner; 0: no such step
@@ -360,8 +358,7 @@ int solve(tdt_ctx *front, tdt_ctx *ctx, const Request &R, int depth_known, Devic
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
-  if (nv > kGeoCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
   if (!host_domain(R, depth, lo, hi, seeds_in)) return TDT_OK;
   if (solid) {
     if (nv == 0) return TDT_OK;
@@ -379,7 +376,7 @@ int solve(tdt_ctx *front, tdt_ctx *ctx, const Request &R, int depth_known, Devic
   bitvol_layout(ilo, ihi, B);
   // ---- volumes ----
   const size_t padded = (size_t)B.n_words * 32;            // < 2^28: the cap, and at most 62 voxels of padding per row
-  uint32_t *occ = S.get<uint32_t>(B.n_words), *medium = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kGeoBatch);
+  uint32_t *occ = S.get<uint32_t>(B.n_words), *medium = S.get<uint32_t>(B.n_words), *flags = S.get<uint32_t>(kBitvolBatch);
   uint32_t *cost = S.get<uint32_t>(padded);
   Z.wk = S.get<uint32_t>(nv); Z.wv = S.get<uint32_t>(nv);
   int32_t *d_seeds = S.get<int32_t>(seeds_in.size());
@@ -399,17 +396,8 @@ int solve(tdt_ctx *front, tdt_ctx *ctx, const Request &R, int depth_known, Devic
   TDT_HIP(front, hipGetLastError());
   // ---- relax ----
   const dim3 tiles((unsigned)B.nw * (unsigned)((B.ey + kGeoTile - 1) / kGeoTile), (unsigned)((B.ez + kGeoTile - 1) / kGeoTile));
-  uint32_t h_flags[kGeoBatch], queued = 0;
-  do {
-    TDT_HIP(front, hipMemsetAsync(flags, 0, sizeof h_flags, st));
-    for (int p = 0; p < kGeoBatch; p++) hipLaunchKernelGGL(geo_relax_kernel, tiles, dim3(256), 0, st, B, cost, Z.W, flags + p);
-    TDT_HIP(front, hipGetLastError());
-    TDT_HIP(front, hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
-    TDT_HIP(front, hipStreamSynchronize(st));              // one per batch of passes
-    for (int p = kGeoBatch - 1; p >= 0; p--)
-      if (h_flags[p]) { front->geodesic_passes = queued + (uint32_t)p + 1u; break; }   // the last pass that changed the volume
-    queued += kGeoBatch;
-  } while (h_flags[kGeoBatch - 1]);
+  auto relax = [&](uint32_t *flag) { hipLaunchKernelGGL(geo_relax_kernel, tiles, dim3(256), 0, st, B, cost, Z.W, flag); };
+  if (int rc = bitvol_pass_loop(front, st, flags, relax, &front->geodesic_passes)) return rc;
   Z.cost = cost; Z.nv = nv; Z.have = true;
   return TDT_OK;
 }
@@ -422,25 +410,17 @@ int geodesic_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, int depth_know
   if (!Z.have) return TDT_OK;
   hipStream_t st = ctx->stream;
   const BitBox &B = Z.B;
-  uint32_t *reach = S.get<uint32_t>(B.n_words), *count = S.get<uint32_t>((size_t)B.n_words + 1);
-  uint32_t *scr = S.get<uint32_t>(scan_scratch_words((size_t)B.n_words + 1));
-  if (!reach || !count || !scr) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(geo_reach_kernel, dim3(blocks_of((unsigned long long)B.n_words * 32u)), dim3(256), 0, st, B, (const uint32_t *)Z.cost, reach);
-  hipLaunchKernelGGL(geo_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)reach, count);
-  TDT_HIP(front, exclusive_scan_u32(st, count, count, B.n_words + 1u, scr));
-  TDT_HIP(front, hipGetLastError());
-  uint32_t n_out = 0;                                      // <= 2^27: the domain cap
-  TDT_HIP(front, hipMemcpyAsync(&n_out, count + B.n_words, sizeof n_out, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the count
-  if (n_out > kGeoCap) return fail(front, TDT_ERR_INVALID_VALUE, "the reach set holds " + std::to_string(n_out) + " voxels (more than 2^26)");
-  if (n_out == 0) return TDT_OK;
-  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
-  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(geo_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)reach, (const uint32_t *)count,
-                     R.g.material >= 0 ? (uint32_t)R.g.material + 1u : 0u, (const uint32_t *)Z.wk, (const uint32_t *)Z.wv, Z.nv, k0, v0);
-  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, true, S, kNoMemory, out)) return rc;
-  *n = n_out;
-  return TDT_OK;
+  uint32_t *reach = S.get<uint32_t>(B.n_words);
+  if (!reach) return fail(front, TDT_ERR_HIP, kNoMemory);
+  auto count = [&](uint32_t *cnt) {
+    hipLaunchKernelGGL(geo_reach_kernel, dim3(blocks_of((unsigned long long)B.n_words * 32u)), dim3(256), 0, st, B, (const uint32_t *)Z.cost, reach);
+    hipLaunchKernelGGL(geo_count_kernel, dim3(blocks_of((size_t)B.n_words + 1)), dim3(256), 0, st, B, (const uint32_t *)reach, cnt);
+  };
+  auto emit = [&](const uint32_t *excl, uint32_t *keys, uint32_t *vals) {
+    hipLaunchKernelGGL(geo_emit_kernel, dim3(blocks_of(B.n_words)), dim3(256), 0, st, B, (const uint32_t *)reach, excl,
+                       R.g.material >= 0 ? (uint32_t)R.g.material + 1u : 0u, (const uint32_t *)Z.wk, (const uint32_t *)Z.wv, Z.nv, keys, vals);
+  };
+  return bitvol_list_tail(front, st, B.n_words, count, emit, "the reach set", true, nullptr, nullptr, 0u, S, kNoMemory, out, n);
 }
 
 struct GeodesicSource final : VoxelSource {
@@ -469,16 +449,9 @@ int tdt_octree_geodesic_field(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t
   // everything the host can check comes first: the count-only call walks no tree and queues nothing
   int depth = 0;
   if (int rc = walk_inputs(ctx, m, &depth)) return rc;
-  const int N = 1 << depth;
-  unsigned long long count = 1;
-  for (int a = 0; a < 3; a++) {
-    if (lo[a] < 0 || hi[a] >= N || lo[a] > hi[a]) return fail(ctx, TDT_ERR_INVALID_VALUE, "the box must satisfy 0 <= lo <= hi < 2^max_depth");
-    count *= (unsigned long long)(hi[a] - lo[a] + 1);
-  }
-  if (count > kGeoCap) return fail(ctx, TDT_ERR_INVALID_VALUE, "the box holds " + std::to_string(count) + " voxels (more than 2^26)");
-  *n_voxels = (size_t)count;
+  if (int rc = bitvol_field_box(ctx, depth, lo, hi, [] { return TDT_OK; }, field != nullptr, capacity, n_voxels)) return rc;
   if (!field) return TDT_OK;
-  if (capacity < count) return fail(ctx, TDT_ERR_INVALID_VALUE, "capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " voxels");
+  const size_t count = *n_voxels;
   TDT_HIP(ctx, hipSetDevice(m->device));
   hipStream_t st = m->stream;
   Drain drain{st};
@@ -507,13 +480,8 @@ int tdt_octree_extract_geodesic(tdt_ctx *ctx, const tdt_geodesic *g, const int32
   tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
   int depth = 0;
   if (int rc = walk_inputs(ctx, m, &depth)) return rc;
-  TDT_HIP(ctx, hipSetDevice(m->device));
-  Drain drain{m->stream};
-  DeviceScratch S;
-  const int4 *vox = nullptr;
-  uint32_t n = 0;
-  if (int rc = geodesic_list(ctx, m, R, depth, S, &vox, &n)) return rc;
-  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
+  GeodesicSource src(R);
+  return region_extract_source(ctx, src, depth, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_edit_geodesic(tdt_ctx *ctx, int op, const tdt_geodesic *g, const int32_t *seeds_xyz, size_t n_seeds, const tdt_region *regions,

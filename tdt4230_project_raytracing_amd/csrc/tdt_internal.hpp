@@ -4,8 +4,9 @@
 // tdt_query.hip: ray queries; tdt_compact.hip: voxel extraction and compaction; tdt_region.hip: region edits;
 // tdt_connect.hip: connected components; tdt_morph.hip: voxel morphology; tdt_mesh.hip: triangle-mesh voxelisation;
 // tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance;
-// tdt_bitvol.hip: the dense bit volume the last two, tdt_xform.hip and tdt_geodesic.hip share; tdt_xform.hip: affine transforms
-// of selections; tdt_geodesic.hip: geodesic distance).
+// tdt_bitvol.hip: the dense bit volume that tdt_fill.hip, tdt_distance.hip, tdt_xform.hip and tdt_geodesic.hip stand on, from
+// the tree's list to the result's (its templates over a unit's own kernels: bitvol_device.hpp); tdt_xform.hip: affine
+// transforms of selections; tdt_geodesic.hip: geodesic distance).
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -206,6 +207,18 @@ struct VoxelSource {
 };
 // tdt_octree_edit_voxels(op, the source's list) on every replica (the caller has checked op)
 int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells);
+// the source's list on device_ids[0] (depth: what its run() is given; no tree need be bound) into host memory, by
+// tdt_octree_extract's rules
+inline int region_extract_source(tdt_ctx *ctx, VoxelSource &src, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {
+  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  TDT_HIP(ctx, hipSetDevice(m->device));
+  Drain drain{m->stream};
+  DeviceScratch S;
+  const int4 *vox = nullptr;
+  uint32_t n = 0;
+  if (int rc = src.run(ctx, m, depth, S, &vox, &n)) return rc;
+  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", host_out, capacity, n_out);
+}
 
 // ---- tdt_mesh.hip: what the solid forms (tdt_fill.hip) start from ----
 // everything about a mesh that does not depend on the grid, checked on the host before anything is queued
@@ -214,8 +227,13 @@ int check_mesh(tdt_ctx *ctx, const tdt_mesh *m);
 // (allocated in S; null when *n == 0).  Queued on ctx's stream; synchronises.  Errors are reported on `front`.
 int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, DeviceScratch &S, const int4 **out, uint32_t *n);
 
-// ---- tdt_bitvol.hip: the dense bit volume over a box of the grid (layout: bitvol_device.hpp), as enclosed space and exact
-// distance use it.  Everything is queued on `st`; errors are reported on `front`; no_memory is the caller's out-of-memory text ----
+// ---- tdt_bitvol.hip: the dense bit volume over a box of the grid (layout: bitvol_device.hpp), as enclosed space, exact distance,
+// transforms and geodesic distance use it.  Everything is queued on `st`; errors are reported on `front`; no_memory is the
+// caller's out-of-memory text ----
+constexpr unsigned long long kBitvolCap = 1ull << 26;   // voxels of the tree's list, of a result and of a field's box
+// tree_voxels with the leaf limit of the editing units (254), held to kBitvolCap (checked on the expanded list: 16 B per voxel
+// of the tree before it can fail)
+int bitvol_tree_voxels(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth);
 // B over lo..hi (inclusive, inside the grid)
 void bitvol_layout(const int lo[3], const int hi[3], BitBox &B);
 // the bounding box of n > 0 voxels {x, y, z, m} in device memory: box[0..2] = min, box[3..5] = max.  One synchronisation.

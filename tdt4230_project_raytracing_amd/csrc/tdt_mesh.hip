@@ -397,14 +397,8 @@ int tdt_voxelize_triangles(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, int32_
   *n_voxels = 0;
   if (depth < 1 || depth > 10) return fail(ctx, TDT_ERR_INVALID_VALUE, "depth must be 1..10");
   if (int rc = check_mesh(ctx, mesh)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
-  TDT_HIP(ctx, hipSetDevice(m->device));
-  Drain drain{m->stream};
-  DeviceScratch S;
-  const int4 *vox = nullptr;
-  uint32_t n = 0;
-  if (int rc = mesh_voxels(ctx, m, mesh, depth, S, &vox, &n)) return rc;
-  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
+  MeshSource src(mesh);
+  return region_extract_source(ctx, src, depth, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_octree_edit_triangles(tdt_ctx *ctx, int op, const tdt_mesh *mesh, uint32_t *n_cells) {

@@ -21,7 +21,7 @@
 //              exclusive_scan_u32 over the waves the emit pass repeats the test and writes (key, material + 1) at the wave's
 //              offset + the lane's rank in the ballot, the material by bitvol_find in the sorted pairs.
 //                                                                                     xform_count_kernel, xform_emit_kernel
-//   list       tdt_bitvol.hip's bitvol_emit_list, without its sort.
+//   list       bitvol_list_tail around the two (an item is a wave of a kept brick), without the sort.
 //   synchronisations per call: the tree walk, the bounding box, the brick count, the voxel count, the end.
 #include <cstring>
 #include <string>
@@ -32,8 +32,6 @@
 #include "tdt_internal.hpp"
 
 namespace tdt {
-
-constexpr unsigned long long kXformCap = 1ull << 26;   // TDT_REGION_BRUSH_CAP: the tree's list and the result
 
 struct XformParams {
   BitBox B;                    // the source box and the layout of the occupancy bits over it
@@ -175,11 +173,11 @@ int xform_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch &S,
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
-  if (nv > kXformCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
   if (nv == 0) return TDT_OK;
   const long long N = 1ll << depth;
-  // ---- the source box: bbox(V) & the shapes' bounding box ----
+  // ---- the source box: bbox(V) & the shapes' bounding box (each shape clipped to the grid, the ones that leave it dropped;
+  // tdt_geodesic.hip's host_domain unions first and clips after, which gives its domain another box: the two stay apart) ----
   int box[6];
   if (int rc = bitvol_list_bbox(front, st, v, nv, depth, S, kNoMemory, "a voxel lies outside the grid", box)) return rc;
   if (R.masked) {
@@ -262,27 +260,16 @@ int xform_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch &S,
   hipLaunchKernelGGL(xform_brick_kernel, dim3(blocks_of(nb1)), dim3(256), 0, st, P, (const uint32_t *)flag, bk);
   TDT_HIP(front, hipMemsetAsync(bv, 0, (size_t)n_active * sizeof(uint32_t), st));   // the sort's values: unused
   TDT_HIP(front, sort_pairs_u32(st, bk, bv, bk1, bv1, n_active, hist, hscr));
-  // ---- count ----
-  const size_t nw1 = (size_t)n_active * 8 + 1;
-  uint32_t *count = S.get<uint32_t>(nw1), *cscr = S.get<uint32_t>(scan_scratch_words(nw1));
-  if (!count || !cscr) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(xform_count_kernel, dim3(n_active * 2u), dim3(256), 0, st, P, (const uint32_t *)occ, (const RegionShape *)d_shapes,
-                     (const uint32_t *)bk, n_active, count);
-  TDT_HIP(front, exclusive_scan_u32(st, count, count, (uint32_t)nw1, cscr));
-  TDT_HIP(front, hipGetLastError());
-  uint32_t n_out = 0;                                      // <= 2^30: 512 per brick
-  TDT_HIP(front, hipMemcpyAsync(&n_out, count + (nw1 - 1), sizeof n_out, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the count
-  if (n_out > kXformCap) return fail(front, TDT_ERR_INVALID_VALUE, "the result holds " + std::to_string(n_out) + " voxels (more than 2^26)");
-  if (n_out == 0) return TDT_OK;
-  // ---- emit ----
-  uint32_t *k0 = S.get<uint32_t>(n_out), *v0 = S.get<uint32_t>(n_out);
-  if (!k0 || !v0) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(xform_emit_kernel, dim3(n_active * 2u), dim3(256), 0, st, P, (const uint32_t *)occ, (const RegionShape *)d_shapes,
-                     (const uint32_t *)bk, (const uint32_t *)count, (const uint32_t *)wk, (const uint32_t *)wv, nv, k0, v0);
-  if (int rc = bitvol_emit_list(front, st, k0, v0, n_out, false, S, kNoMemory, out)) return rc;
-  *n = n_out;
-  return TDT_OK;
+  // ---- count, emit: 8 waves per kept brick ----
+  auto count = [&](uint32_t *cnt) {
+    hipLaunchKernelGGL(xform_count_kernel, dim3(n_active * 2u), dim3(256), 0, st, P, (const uint32_t *)occ, (const RegionShape *)d_shapes,
+                       (const uint32_t *)bk, n_active, cnt);
+  };
+  auto emit = [&](const uint32_t *excl, uint32_t *keys, uint32_t *vals) {
+    hipLaunchKernelGGL(xform_emit_kernel, dim3(n_active * 2u), dim3(256), 0, st, P, (const uint32_t *)occ, (const RegionShape *)d_shapes,
+                       (const uint32_t *)bk, excl, (const uint32_t *)wk, (const uint32_t *)wv, nv, keys, vals);
+  };
+  return bitvol_list_tail(front, st, (size_t)n_active * 8, count, emit, "the result", false, nullptr, nullptr, 0u, S, kNoMemory, out, n);
 }
 
 struct XformSource final : VoxelSource {
@@ -314,14 +301,8 @@ int tdt_octree_extract_transform(tdt_ctx *ctx, const tdt_xform *x, const tdt_reg
   *n_voxels = 0;
   Request R;
   if (int rc = make_request(ctx, x, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
-  TDT_HIP(ctx, hipSetDevice(m->device));
-  Drain drain{m->stream};
-  DeviceScratch S;
-  const int4 *vox = nullptr;
-  uint32_t n = 0;
-  if (int rc = xform_list(ctx, m, R, S, &vox, &n)) return rc;
-  return list_to_host(ctx, m->stream, vox, n, sizeof(int4), "voxels", voxels_xyzm, capacity, n_voxels);
+  XformSource src(R);
+  return region_extract_source(ctx, src, 0, voxels_xyzm, capacity, n_voxels);
 }
 
 int tdt_debug_xform_bricks(const tdt_ctx *ctx, uint32_t out[2]) {

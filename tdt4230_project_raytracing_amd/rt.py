@@ -463,14 +463,19 @@ class Context:
         self.check(lib().tdt_octree_census(self.h, out))
         return dict(zip(self.CENSUS_FIELDS, [int(v) for v in out]))
 
+    def _list(self, fn, *args, width=4, tail=()):
+        """The two-call list protocol of fn(ctx, *args, array, capacity, &n, *tail): a call without an array for the count, then an
+        (n, width) int32 array that a second call fills when n > 0."""
+        n = ctypes.c_size_t(0)
+        self.check(fn(self.h, *args, None, 0, ctypes.byref(n), *tail))
+        out = np.zeros((n.value, width), np.int32)
+        if n.value:
+            self.check(fn(self.h, *args, out.ctypes.data, n.value, ctypes.byref(n), *tail))
+        return out
+
     def octree_extract(self):
         """tdt_octree_extract: the bound tree's voxels as an (n, 4) int32 array {x, y, z, material + 1}, sorted by Morton key."""
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract(self.h, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract(self.h, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract)
 
     def octree_compact(self):
         """tdt_octree_compact: rewrite the bound cells buffer in place into the canonical tree of its voxels; returns its cell count."""
@@ -505,12 +510,7 @@ class Context:
     def octree_extract_region(self, regions):
         """tdt_octree_extract_region: the bound tree's voxels inside the union of `regions`, (n, 4) int32, Morton-sorted."""
         arr, k = _regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_region(self.h, arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_region(self.h, arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_region, arr, k)
 
     def _voxel_count(self):
         """The bound tree's voxel count from a walk alone (tdt_octree_extract with a null array), without labelling anything."""
@@ -605,12 +605,7 @@ class Context:
         (a DILATE grows the list), so this counts first and fills second: two runs of the steps."""
         m = self._morph(op, radius, connectivity, material, border)
         arr, k = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_morph(self.h, ctypes.byref(m), arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_morph(self.h, ctypes.byref(m), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_morph, ctypes.byref(m), arr, k)
 
     def voxelize_triangles(self, vertices, triangles, depth, materials=None, material=0):
         """tdt_voxelize_triangles: the voxels of the grid [0, 2^depth)^3 the closed triangles touch, as an (n, 4) int32 list
@@ -618,11 +613,7 @@ class Context:
         triangles (m, 3) indices, materials None or (m,) material + 1 per triangle (the highest covering triangle wins).
         Needs no bound tree.  Counts first, fills second: two rasterisations."""
         mesh, keep = _mesh(vertices, triangles, materials, material)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_voxelize_triangles(self.h, ctypes.byref(mesh), int(depth), None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_voxelize_triangles(self.h, ctypes.byref(mesh), int(depth), out.ctypes.data, n.value, ctypes.byref(n)))
+        out = self._list(lib().tdt_voxelize_triangles, ctypes.byref(mesh), int(depth))
         del keep
         return out
 
@@ -654,12 +645,7 @@ class Context:
         an empty list: an empty mask).  The tree is untouched.  Counts first, fills second: two floods."""
         f = self._fill(connectivity, material)
         arr, k = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_enclosed(self.h, ctypes.byref(f), arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_enclosed(self.h, ctypes.byref(f), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_enclosed, ctypes.byref(f), arr, k)
 
     def octree_fill_enclosed(self, connectivity=6, material=None, regions=None):
         """tdt_octree_fill_enclosed: octree_edit_voxels(REGION_FILL, octree_extract_enclosed(...)) without the list leaving the
@@ -676,12 +662,7 @@ class Context:
         Needs no bound tree.  Counts first, fills second."""
         mesh, keep = _mesh(vertices, triangles, materials, material)
         f = self._fill(connectivity, fill_material)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_voxelize_triangles_solid(self.h, ctypes.byref(mesh), int(depth), ctypes.byref(f), None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_voxelize_triangles_solid(self.h, ctypes.byref(mesh), int(depth), ctypes.byref(f), out.ctypes.data, n.value,
-                                                          ctypes.byref(n)))
+        out = self._list(lib().tdt_voxelize_triangles_solid, ctypes.byref(mesh), int(depth), ctypes.byref(f))
         del keep
         return out
 
@@ -712,12 +693,7 @@ class Context:
         The tree is untouched.  Counts first, fills second: two extractions."""
         s = self._surface(merge, by_material)
         arr, k = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_surface(self.h, ctypes.byref(s), arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 8), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_surface(self.h, ctypes.byref(s), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_surface, ctypes.byref(s), arr, k, width=8)
 
     @staticmethod
     def _int32(name, v, allow_bool=False):
@@ -727,6 +703,17 @@ class Context:
         if int(v) != v or not -2**31 <= int(v) <= 2**31 - 1:
             raise ValueError(f"{name} must be an int32, not {v!r}")
         return int(v)
+
+    @classmethod
+    def _box3(cls, lo, hi):
+        """The corners of an inclusive box as two checked int32[3] arrays."""
+        box3 = []
+        for name, c in (("lo", lo), ("hi", hi)):
+            c = list(c)
+            if len(c) != 3:
+                raise ValueError(f"{name} must hold three coordinates")
+            box3.append((ctypes.c_int32 * 3)(*[cls._int32(name, v) for v in c]))
+        return box3
 
     @classmethod
     def _round(cls, op, radius2, material, border):
@@ -750,24 +737,14 @@ class Context:
         Morton-sorted; the tree is untouched.  Counts first, fills second: two transforms."""
         r = self._round(op, radius2, material, border)
         arr, k = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_morph_round(self.h, ctypes.byref(r), arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_morph_round(self.h, ctypes.byref(r), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_morph_round, ctypes.byref(r), arr, k)
 
     def octree_distance_field(self, lo, hi, max_d2, border=0, nearest=False):
         """tdt_octree_distance_field: the signed squared Euclidean distance over the inclusive box lo..hi as an (ez, ey, ex) int32
         array: +d2 to the nearest voxel for an empty voxel, -d2 to the nearest empty point for an occupied one (border 0: the
         points outside the grid count), magnitudes above max_d2 (1..4096) reported as max_d2 + 1.  nearest: also an (ez, ey, ex,
         3) array of the nearest voxel {x, y, z} (an occupied voxel: itself; none within max_d2: -1).  The tree is untouched."""
-        box3 = []
-        for name, c in (("lo", lo), ("hi", hi)):
-            c = list(c)
-            if len(c) != 3:
-                raise ValueError(f"{name} must hold three coordinates")
-            box3.append((ctypes.c_int32 * 3)(*[self._int32(name, v) for v in c]))
+        box3 = self._box3(lo, hi)
         max_d2, border = self._int32("max_d2", max_d2), self._int32("border", border, allow_bool=True)
         n = ctypes.c_size_t(0)
         self.check(lib().tdt_octree_distance_field(self.h, box3[0], box3[1], max_d2, border, None, None, 0, ctypes.byref(n)))
@@ -827,12 +804,7 @@ class Context:
         second: two resamplings."""
         x = self._xform(xf)
         arr, k = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
-        self.check(lib().tdt_octree_extract_transform(self.h, ctypes.byref(x), arr, k, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_transform(self.h, ctypes.byref(x), arr, k, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_transform, ctypes.byref(x), arr, k)
 
     def xform_bricks(self):
         """tdt_debug_xform_bricks: (bricks of the last transform's destination domain, bricks its count and emit passes ran on)."""
@@ -862,12 +834,7 @@ class Context:
         PATHS (None: no mask; an empty list: an empty mask, so nothing is reached).  The tree is untouched."""
         g, s, k = self._geodesic(medium, steps, max_cost, match, None, seeds)
         arr, kr = _touch_regions(regions)
-        box3 = []
-        for name, c in (("lo", lo), ("hi", hi)):
-            c = list(c)
-            if len(c) != 3:
-                raise ValueError(f"{name} must hold three coordinates")
-            box3.append((ctypes.c_int32 * 3)(*[self._int32(name, v) for v in c]))
+        box3 = self._box3(lo, hi)
         n = ctypes.c_size_t(0)
         sp = s.ctypes.data if k else None
         self.check(lib().tdt_octree_geodesic_field(self.h, ctypes.byref(g), sp, k, arr, kr, box3[0], box3[1], None, 0, ctypes.byref(n)))
@@ -884,13 +851,8 @@ class Context:
         untouched.  Counts first, fills second: two relaxations."""
         g, s, k = self._geodesic(medium, steps, max_cost, match, material, seeds)
         arr, kr = _touch_regions(regions)
-        n = ctypes.c_size_t(0)
         sp = s.ctypes.data if k else None
-        self.check(lib().tdt_octree_extract_geodesic(self.h, ctypes.byref(g), sp, k, arr, kr, None, 0, ctypes.byref(n)))
-        out = np.zeros((n.value, 4), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_extract_geodesic(self.h, ctypes.byref(g), sp, k, arr, kr, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return self._list(lib().tdt_octree_extract_geodesic, ctypes.byref(g), sp, k, arr, kr)
 
     def octree_edit_geodesic(self, op, seeds, medium=MEDIUM_SOLID, steps=STEPS_6, max_cost=1 << 30, match=None, material=None, regions=None):
         """tdt_octree_edit_geodesic: octree_edit_voxels(op, octree_extract_geodesic(...)) with the list taken from the tree before
@@ -911,13 +873,9 @@ class Context:
         if len(goal) != 3:
             raise ValueError("goal must hold three coordinates")
         q = (ctypes.c_int32 * 3)(*[self._int32("goal", v) for v in goal])
-        n, cost = ctypes.c_size_t(0), ctypes.c_int32(-1)
-        sp = s.ctypes.data if k else None
-        self.check(lib().tdt_octree_geodesic_path(self.h, ctypes.byref(g), sp, k, arr, kr, q, None, 0, ctypes.byref(n), ctypes.byref(cost)))
-        out = np.zeros((n.value, 3), np.int32)
-        if n.value:
-            self.check(lib().tdt_octree_geodesic_path(self.h, ctypes.byref(g), sp, k, arr, kr, q, out.ctypes.data, n.value, ctypes.byref(n),
-                                                      ctypes.byref(cost)))
+        cost = ctypes.c_int32(-1)
+        out = self._list(lib().tdt_octree_geodesic_path, ctypes.byref(g), s.ctypes.data if k else None, k, arr, kr, q, width=3,
+                         tail=(ctypes.byref(cost),))
         return out, int(cost.value)
 
     def geodesic_passes(self):

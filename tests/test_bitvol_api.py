@@ -1,6 +1,7 @@
-"""The dense bit-volume layer that enclosed space and exact distance share (csrc/tdt_bitvol.hip, csrc/bitvol_device.hpp) without
-a GPU: its three kernels cross-compile without scratch or spills, and what the editing units used to keep a copy of each — the
-layer's pieces and the host helpers of tdt_internal.hpp / region_device.hpp — has exactly one definition under csrc/."""
+"""The dense bit-volume layer that four units share — enclosed space, exact distance, affine transforms and geodesic distance
+(csrc/tdt_bitvol.hip, csrc/bitvol_device.hpp) — without a GPU: its three kernels cross-compile without scratch or spills, and what
+the editing units used to keep a copy of each — the layer's pieces, from the tree's list to the result's, and the host helpers of
+tdt_internal.hpp / region_device.hpp — has exactly one definition under csrc/."""
 import os
 import re
 import sys
@@ -33,6 +34,12 @@ ONE_DEFINITION = {
     "blocks_of": (r"\(lanes \+ 255\) / 256", "tdt_internal.hpp"),
     "the drain guard": (r"~\w+\(\) \{ \(void\)hipStreamSynchronize\(", "tdt_internal.hpp"),
     "the shape check": (r"shape must be TDT_SHAPE_BOX", "region_device.hpp"),
+    "the list tail's total read": (r"hipMemcpyAsync\(&\w+, count \+ ", "bitvol_device.hpp"),
+    "the pass loop's last-flag test": (r"while \(h_flags\[k\w+ - 1\]\)", "bitvol_device.hpp"),
+    # (tdt_morph.hip and tdt_surface.hip, voxel-list units outside the layer, hold the same text against caps of their own)
+    "the tree cap": (r"k(Fill|Dist|Xform|Geo|Bitvol)Cap\b.*\"the tree holds \"", "tdt_bitvol.hip"),
+    "the field box": (r"\"the box holds \"", "bitvol_device.hpp"),
+    "the extract frame": (r"list_to_host\(ctx, m->stream, vox, n, sizeof\(int4\), \"voxels\"", "tdt_internal.hpp"),
 }
 
 

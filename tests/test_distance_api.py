@@ -175,5 +175,5 @@ def test_field_of_the_model_by_hand():
 
 
 def test_the_unit_compiled_for_the_cpu_runs_clean_under_the_sanitizers():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "distance_hostsim", "run.py")], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "hostsim", "run.py"), "distance"], capture_output=True, text=True)
     assert r.returncode == 0 and "all ok" in r.stdout and "MISMATCH" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-3000:]

@@ -243,5 +243,5 @@ def test_geodesic_kernels_have_no_scratch_and_no_spills():
 
 
 def test_the_unit_compiled_for_the_cpu_runs_clean_under_the_sanitizers():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "geodesic_hostsim", "run.py")], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "hostsim", "run.py"), "geodesic"], capture_output=True, text=True)
     assert r.returncode == 0 and "all ok" in r.stdout and "MISMATCH" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-3000:]

@@ -248,5 +248,5 @@ def test_rotate_is_within_one_unit_of_the_rounded_closed_form(axis, degrees, piv
 
 
 def test_the_unit_compiled_for_the_cpu_runs_clean_under_the_sanitizers():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "xform_hostsim", "run.py")], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "hostsim", "run.py"), "xform"], capture_output=True, text=True)
     assert r.returncode == 0 and "all ok" in r.stdout and "MISMATCH" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-3000:]

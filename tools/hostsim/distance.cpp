@@ -1,56 +1,7 @@
-// drives the real entry points of distance_unit.cpp on lists made here, against an all-pairs brute force and the ops' definitions
-#include <algorithm>
+// exact distance: drives the real entry points of tdt_distance.hip on lists made here, against an all-pairs brute force and
+// the ops' definitions
 #include <array>
-#include <cstdio>
-#include <random>
-#include "tdt_internal.hpp"
-static std::vector<int4> g_list; static int g_depth;
-static std::vector<int4> g_delta; static int g_delta_op;
-namespace tdt {
-int fail(tdt_ctx *c, int code, const std::string &m) { c->err = m; std::fprintf(stderr, "fail: %s\n", m.c_str()); return code; }
-int hip_fail(tdt_ctx *c, hipError_t, const char *w) { return fail(c, TDT_ERR_HIP, w); }
-tdt_ctx *multi_first_member(tdt_ctx *f) { return f; }
-size_t sort_hist_words(uint32_t) { return 1; }
-size_t sort_scratch_words(uint32_t) { return 1; }
-hipError_t sort_pairs_u32(hipStream_t, uint32_t *&k, uint32_t *&v, uint32_t *, uint32_t *, uint32_t n, uint32_t *, uint32_t *) {
-  std::vector<std::pair<uint32_t, uint32_t>> p(n);
-  for (uint32_t i = 0; i < n; i++) p[i] = {k[i], v[i]};
-  std::stable_sort(p.begin(), p.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  for (uint32_t i = 0; i < n; i++) { k[i] = p[i].first; v[i] = p[i].second; }
-  return 0;
-}
-int walk_inputs(tdt_ctx *, tdt_ctx *, int *depth) { *depth = g_depth; return 0; }
-int tree_voxels(tdt_ctx *, tdt_ctx *, uint32_t, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
-  *depth = g_depth; *n = (uint32_t)g_list.size(); *out = nullptr;
-  if (g_list.empty()) return 0;
-  *out = S.get<int4>(g_list.size()); std::memcpy(*out, g_list.data(), g_list.size() * sizeof(int4)); return 0;
-}
-// the edit form: keep the delta list and the op it would be applied with
-int region_edit_source(tdt_ctx *c, int op, VoxelSource &src, uint32_t *) {
-  DeviceScratch S;
-  const int4 *v = nullptr; uint32_t n = 0;
-  g_delta.clear(); g_delta_op = op;
-  if (int rc = src.run(c, c, g_depth, S, &v, &n)) return rc;
-  g_delta.assign(v, v + n);
-  return 0;
-}
-}
-// Morton key of the library's lists: spread3(x) << 2 | spread3(y) << 1 | spread3(z)
-static uint32_t key(int x, int y, int z) {
-  uint32_t k = 0;
-  for (int b = 0; b < 10; b++)
-    k |= ((x >> b) & 1u) << (3 * b + 2) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b);
-  return k;
-}
-
-struct Grid {
-  int N;
-  std::vector<int> m;            // material + 1, 0: empty; [x][y][z]
-  explicit Grid(int n) : N(n), m((size_t)n * n * n, 0) {}
-  int &at(int x, int y, int z) { return m[((size_t)x * N + y) * N + z]; }
-  int get(int x, int y, int z) const { return m[((size_t)x * N + y) * N + z]; }
-  bool in(int x, int y, int z) const { return x >= 0 && y >= 0 && z >= 0 && x < N && y < N && z < N; }
-};
+#include "siblings.hpp"
 
 // the set voxels, in lexicographic (x, y, z) order
 static std::vector<std::array<int, 3>> points(const Grid &g) {
@@ -106,25 +57,6 @@ static Grid apply(const Grid &g, int op, int r2, int material, int border) {
     default: { Grid e = erode(g, r2, border), o = g; for (size_t i = 0; i < o.m.size(); i++) if (e.m[i]) o.m[i] = 0; return o; }
   }
 }
-static bool region_has(const tdt_region &r, int x, int y, int z) {
-  if (r.shape == TDT_SHAPE_BOX) return x >= r.a[0] && x <= r.b[0] && y >= r.a[1] && y <= r.b[1] && z >= r.a[2] && z <= r.b[2];
-  const long dx = x - r.a[0], dy = y - r.a[1], dz = z - r.a[2];
-  return dx * dx + dy * dy + dz * dz <= (long)r.b[0] * r.b[0];
-}
-static std::vector<int4> sorted_list(const Grid &g) {
-  std::vector<std::pair<uint32_t, int4>> v;
-  for (int x = 0; x < g.N; x++) for (int y = 0; y < g.N; y++) for (int z = 0; z < g.N; z++)
-    if (g.get(x, y, z)) v.push_back({key(x, y, z), int4{x, y, z, g.get(x, y, z)}});
-  std::sort(v.begin(), v.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  std::vector<int4> o;
-  for (auto &p : v) o.push_back(p.second);
-  return o;
-}
-static bool same(const std::vector<int4> &a, const std::vector<int4> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); i++) if (a[i].x != b[i].x || a[i].y != b[i].y || a[i].z != b[i].z || a[i].w != b[i].w) return false;
-  return true;
-}
 
 static int run_round(const char *name, int depth, const Grid &g, int op, int r2, int material, int border, const std::vector<tdt_region> &mask) {
   g_list = sorted_list(g); g_depth = depth;
@@ -137,12 +69,11 @@ static int run_round(const char *name, int depth, const Grid &g, int op, int r2,
     }
   tdt_ctx ctx{};
   tdt_round q{op, r2, material, border};
-  size_t n = 0;
-  int rc = tdt_octree_extract_morph_round(&ctx, &q, mask.data(), mask.size(), nullptr, 0, &n);
-  std::vector<int32_t> got(4 * n + 4);
-  if (!rc && n) rc = tdt_octree_extract_morph_round(&ctx, &q, mask.data(), mask.size(), got.data(), n, &n);
-  std::vector<int4> gl(n);
-  for (size_t i = 0; i < n; i++) gl[i] = int4{got[4 * i], got[4 * i + 1], got[4 * i + 2], got[4 * i + 3]};
+  std::vector<int4> gl;
+  int rc = extract_list([&](int32_t *dst, size_t capacity, size_t *n) {
+    return tdt_octree_extract_morph_round(&ctx, &q, mask.data(), mask.size(), dst, capacity, n);
+  }, gl);
+  const size_t n = gl.size();
   const auto wl = sorted_list(want);
   bool ok = rc == 0 && same(gl, wl);
   // the edit form's delta: exactly the voxels that differ, new ones with their material, for the right op
@@ -151,12 +82,8 @@ static int run_round(const char *name, int depth, const Grid &g, int op, int r2,
   const bool grows = op == TDT_MORPH_DILATE || op == TDT_MORPH_CLOSE;
   Grid diff(g.N);
   for (size_t i = 0; i < diff.m.size(); i++) if ((g.m[i] != 0) != (want.m[i] != 0)) diff.m[i] = grows ? want.m[i] : g.m[i];
-  std::vector<std::pair<uint32_t, int4>> d;
-  for (auto &p : g_delta) d.push_back({key(p.x, p.y, p.z), p});
-  std::sort(d.begin(), d.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  std::vector<int4> dl;
-  for (auto &p : d) dl.push_back(p.second);
-  const bool dok = rc == 0 && g_delta_op == (grows ? TDT_REGION_FILL : TDT_REGION_CLEAR) && same(dl, sorted_list(diff));
+  const std::vector<int4> dl = morton_sorted(g_edit);
+  const bool dok = rc == 0 && g_edit_op == (grows ? TDT_REGION_FILL : TDT_REGION_CLEAR) && same(dl, sorted_list(diff));
   std::printf("%-22s depth %d op %d r2 %4d mat %3d border %d mask %zu: |V| %zu want %zu got %zu delta %zu %s\n", name, depth, op, r2, material,
               border, mask.size(), g_list.size(), wl.size(), n, dl.size(), ok && dok ? "OK" : "MISMATCH");
   return ok && dok ? 0 : 1;

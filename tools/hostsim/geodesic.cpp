@@ -1,67 +1,8 @@
-// drives the real entry points of geodesic_unit.cpp on lists made here, against a brute-force Dijkstra on a dense grid
-#include <algorithm>
+// geodesic distance: drives the real entry points of tdt_geodesic.hip on lists made here, against a brute-force Dijkstra on a
+// dense grid
 #include <array>
-#include <cstdio>
 #include <queue>
-#include <random>
-#include "tdt_internal.hpp"
-static std::vector<int4> g_list; static int g_depth;
-static std::vector<int4> g_edit; static int g_edit_op;
-namespace tdt {
-int fail(tdt_ctx *c, int code, const std::string &m) { c->err = m; std::fprintf(stderr, "fail: %s\n", m.c_str()); return code; }
-int hip_fail(tdt_ctx *c, hipError_t, const char *w) { return fail(c, TDT_ERR_HIP, w); }
-tdt_ctx *multi_first_member(tdt_ctx *f) { return f; }
-size_t sort_hist_words(uint32_t) { return 1; }
-size_t sort_scratch_words(uint32_t) { return 1; }
-hipError_t sort_pairs_u32(hipStream_t, uint32_t *&k, uint32_t *&v, uint32_t *, uint32_t *, uint32_t n, uint32_t *, uint32_t *) {
-  std::vector<std::pair<uint32_t, uint32_t>> p(n);
-  for (uint32_t i = 0; i < n; i++) p[i] = {k[i], v[i]};
-  std::stable_sort(p.begin(), p.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  for (uint32_t i = 0; i < n; i++) { k[i] = p[i].first; v[i] = p[i].second; }
-  return 0;
-}
-int walk_inputs(tdt_ctx *, tdt_ctx *, int *depth) { *depth = g_depth; return 0; }
-int tree_voxels(tdt_ctx *, tdt_ctx *, uint32_t, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
-  *depth = g_depth; *n = (uint32_t)g_list.size(); *out = nullptr;
-  if (g_list.empty()) return 0;
-  *out = S.get<int4>(g_list.size()); std::memcpy(*out, g_list.data(), g_list.size() * sizeof(int4)); return 0;
-}
-// the edit form: keep the list and the op it would be applied with
-int region_edit_source(tdt_ctx *c, int op, VoxelSource &src, uint32_t *) {
-  DeviceScratch S;
-  const int4 *v = nullptr; uint32_t n = 0;
-  g_edit.clear(); g_edit_op = op;
-  if (int rc = src.run(c, c, g_depth, S, &v, &n)) return rc;
-  g_edit.assign(v, v + n);
-  return 0;
-}
-}
-// Morton key of the library's lists: spread3(x) << 2 | spread3(y) << 1 | spread3(z)
-static uint32_t key(int x, int y, int z) {
-  uint32_t k = 0;
-  for (int b = 0; b < 10; b++)
-    k |= ((x >> b) & 1u) << (3 * b + 2) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b);
-  return k;
-}
-
-struct Grid {
-  int N;
-  std::vector<int> m;            // material + 1, 0: empty; [x][y][z]
-  explicit Grid(int n) : N(n), m((size_t)n * n * n, 0) {}
-  size_t cell(int x, int y, int z) const { return ((size_t)x * N + y) * N + z; }
-  int &at(int x, int y, int z) { return m[cell(x, y, z)]; }
-  int get(int x, int y, int z) const { return m[cell(x, y, z)]; }
-};
-static bool region_has(const tdt_region &r, long x, long y, long z) {
-  if (r.shape == TDT_SHAPE_BOX) return x >= r.a[0] && x <= r.b[0] && y >= r.a[1] && y <= r.b[1] && z >= r.a[2] && z <= r.b[2];
-  const long dx = x - r.a[0], dy = y - r.a[1], dz = z - r.a[2];
-  return dx * dx + dy * dy + dz * dz <= (long)r.b[0] * r.b[0];
-}
-static bool same(const std::vector<int4> &a, const std::vector<int4> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); i++) if (a[i].x != b[i].x || a[i].y != b[i].y || a[i].z != b[i].z || a[i].w != b[i].w) return false;
-  return true;
-}
+#include "siblings.hpp"
 
 struct Case {
   const char *name;
@@ -77,14 +18,7 @@ struct Case {
 
 static int run(const Grid &g, const Case &c) {
   const int N = g.N;
-  std::vector<int4> list;
-  {
-    std::vector<std::pair<uint32_t, int4>> v;
-    for (int x = 0; x < N; x++) for (int y = 0; y < N; y++) for (int z = 0; z < N; z++)
-      if (g.get(x, y, z)) v.push_back({key(x, y, z), int4{x, y, z, g.get(x, y, z)}});
-    std::sort(v.begin(), v.end(), [](auto &a, auto &b) { return a.first < b.first; });
-    for (auto &p : v) list.push_back(p.second);
-  }
+  const std::vector<int4> list = sorted_list(g);
   g_list = list; g_depth = c.depth;
   // ---- the brute force: P, then a heap Dijkstra over the 26 offsets ----
   std::vector<char> P((size_t)N * N * N, 0);
@@ -116,13 +50,9 @@ static int run(const Grid &g, const Case &c) {
   }
   auto reached = [&](int x, int y, int z) { return d[g.cell(x, y, z)] <= c.q.max_cost; };
   std::vector<int4> want;
-  {
-    std::vector<std::pair<uint32_t, int4>> v;
-    for (int x = 0; x < N; x++) for (int y = 0; y < N; y++) for (int z = 0; z < N; z++)
-      if (reached(x, y, z)) v.push_back({key(x, y, z), int4{x, y, z, c.q.material >= 0 ? c.q.material + 1 : g.get(x, y, z)}});
-    std::sort(v.begin(), v.end(), [](auto &a, auto &b) { return a.first < b.first; });
-    for (auto &p : v) want.push_back(p.second);
-  }
+  for (int x = 0; x < N; x++) for (int y = 0; y < N; y++) for (int z = 0; z < N; z++)
+    if (reached(x, y, z)) want.push_back(int4{x, y, z, c.q.material >= 0 ? c.q.material + 1 : g.get(x, y, z)});
+  want = morton_sorted(want);
   std::vector<std::array<int, 3>> want_path;
   long want_cost = -1;
   {

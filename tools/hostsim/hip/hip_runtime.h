@@ -1,4 +1,5 @@
-// host stand-in for the HIP constructs tdt_fill.hip uses: one block at a time, 256 real threads, a pthread barrier
+// host stand-in for the HIP constructs the bit-volume units use: one block at a time, 256 real threads, a pthread barrier;
+// the block-wide or, the wave shuffle and the wave ballot are called by every thread of the block together
 #pragma once
 #include <pthread.h>
 #include <cstdint>
@@ -45,6 +46,16 @@ inline int __syncthreads_or(int p) {
   return r;
 }
 inline int __shfl_xor(int v, int o, int) { sim::slot[threadIdx.x] = v; sim::sync(); const int r = sim::slot[threadIdx.x ^ (unsigned)o]; sim::sync(); return r; }
+inline unsigned long long __ballot(int p) {
+  sim::slot[threadIdx.x] = p != 0;
+  sim::sync();
+  unsigned long long r = 0;
+  const unsigned w = threadIdx.x & ~63u;
+  for (unsigned i = 0; i < 64; i++) r |= (unsigned long long)sim::slot[w + i] << i;
+  sim::sync();
+  return r;
+}
+inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 inline unsigned atomicOr(unsigned *p, unsigned v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
 inline int atomicMin(int *p, int v) { int o = __atomic_load_n(p, __ATOMIC_SEQ_CST); while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {} return o; }
 inline int atomicMax(int *p, int v) { int o = __atomic_load_n(p, __ATOMIC_SEQ_CST); while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {} return o; }

@@ -1,72 +1,6 @@
-// drives the real entry points of xform_unit.cpp on lists made here, against a brute force over every destination voxel
-#include <algorithm>
-#include <cstdio>
-#include <random>
-#include "tdt_internal.hpp"
-static std::vector<int4> g_list; static int g_depth;
-static std::vector<int4> g_edit; static int g_edit_op;
-namespace tdt {
-int fail(tdt_ctx *c, int code, const std::string &m) { c->err = m; std::fprintf(stderr, "fail: %s\n", m.c_str()); return code; }
-int hip_fail(tdt_ctx *c, hipError_t, const char *w) { return fail(c, TDT_ERR_HIP, w); }
-tdt_ctx *multi_first_member(tdt_ctx *f) { return f; }
-size_t sort_hist_words(uint32_t) { return 1; }
-size_t sort_scratch_words(uint32_t) { return 1; }
-hipError_t sort_pairs_u32(hipStream_t, uint32_t *&k, uint32_t *&v, uint32_t *, uint32_t *, uint32_t n, uint32_t *, uint32_t *) {
-  std::vector<std::pair<uint32_t, uint32_t>> p(n);
-  for (uint32_t i = 0; i < n; i++) p[i] = {k[i], v[i]};
-  std::stable_sort(p.begin(), p.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  for (uint32_t i = 0; i < n; i++) { k[i] = p[i].first; v[i] = p[i].second; }
-  return 0;
-}
-int tree_voxels(tdt_ctx *, tdt_ctx *, uint32_t, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
-  *depth = g_depth; *n = (uint32_t)g_list.size(); *out = nullptr;
-  if (g_list.empty()) return 0;
-  *out = S.get<int4>(g_list.size()); std::memcpy(*out, g_list.data(), g_list.size() * sizeof(int4)); return 0;
-}
-// the edit form: keep the list and the op it would be applied with
-int region_edit_source(tdt_ctx *c, int op, VoxelSource &src, uint32_t *) {
-  DeviceScratch S;
-  const int4 *v = nullptr; uint32_t n = 0;
-  g_edit.clear(); g_edit_op = op;
-  if (int rc = src.run(c, c, g_depth, S, &v, &n)) return rc;
-  g_edit.assign(v, v + n);
-  return 0;
-}
-}
-// Morton key of the library's lists: spread3(x) << 2 | spread3(y) << 1 | spread3(z)
-static uint32_t key(int x, int y, int z) {
-  uint32_t k = 0;
-  for (int b = 0; b < 10; b++)
-    k |= ((x >> b) & 1u) << (3 * b + 2) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b);
-  return k;
-}
-
-struct Grid {
-  int N;
-  std::vector<int> m;            // material + 1, 0: empty; [x][y][z]
-  explicit Grid(int n) : N(n), m((size_t)n * n * n, 0) {}
-  int &at(int x, int y, int z) { return m[((size_t)x * N + y) * N + z]; }
-  int get(int x, int y, int z) const { return m[((size_t)x * N + y) * N + z]; }
-};
-static bool region_has(const tdt_region &r, long x, long y, long z) {
-  if (r.shape == TDT_SHAPE_BOX) return x >= r.a[0] && x <= r.b[0] && y >= r.a[1] && y <= r.b[1] && z >= r.a[2] && z <= r.b[2];
-  const long dx = x - r.a[0], dy = y - r.a[1], dz = z - r.a[2];
-  return dx * dx + dy * dy + dz * dz <= (long)r.b[0] * r.b[0];
-}
-static std::vector<int4> sorted_list(const Grid &g) {
-  std::vector<std::pair<uint32_t, int4>> v;
-  for (int x = 0; x < g.N; x++) for (int y = 0; y < g.N; y++) for (int z = 0; z < g.N; z++)
-    if (g.get(x, y, z)) v.push_back({key(x, y, z), int4{x, y, z, g.get(x, y, z)}});
-  std::sort(v.begin(), v.end(), [](auto &a, auto &b) { return a.first < b.first; });
-  std::vector<int4> o;
-  for (auto &p : v) o.push_back(p.second);
-  return o;
-}
-static bool same(const std::vector<int4> &a, const std::vector<int4> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); i++) if (a[i].x != b[i].x || a[i].y != b[i].y || a[i].z != b[i].z || a[i].w != b[i].w) return false;
-  return true;
-}
+// affine transforms: drives the real entry points of tdt_xform.hip on lists made here, against a brute force over every
+// destination voxel
+#include "siblings.hpp"
 // floor(v / 2^17) by a division and a correction, where the unit shifts
 static __int128 floor17(__int128 v) { __int128 q = v / 131072; if (v % 131072 < 0) q--; return q; }
 
@@ -105,12 +39,11 @@ static int run(const char *name, int depth, const Grid &g, tdt_xform x, const st
   tdt_ctx ctx{};
   const tdt_region *regions = masked ? mask.data() : nullptr;
   const size_t n_regions = masked ? mask.size() : 0;
-  size_t n = 0;
-  int rc = tdt_octree_extract_transform(&ctx, &x, regions, n_regions, nullptr, 0, &n);
-  std::vector<int32_t> got(4 * n + 4);
-  if (!rc && n) rc = tdt_octree_extract_transform(&ctx, &x, regions, n_regions, got.data(), n, &n);
-  std::vector<int4> gl(n);
-  for (size_t i = 0; i < n; i++) gl[i] = int4{got[4 * i], got[4 * i + 1], got[4 * i + 2], got[4 * i + 3]};
+  std::vector<int4> gl;
+  int rc = extract_list([&](int32_t *dst, size_t capacity, size_t *n) {
+    return tdt_octree_extract_transform(&ctx, &x, regions, n_regions, dst, capacity, n);
+  }, gl);
+  const size_t n = gl.size();
   uint32_t bricks[2] = {0, 0};
   tdt_debug_xform_bricks(&ctx, bricks);
   bool ok = rc == 0 && same(gl, wl) && wl.size() >= min_results && bricks[1] <= bricks[0];
