@@ -72,18 +72,28 @@ TDT_DEV uint32_t wave_sum(uint32_t v) {
 // of operations for its own pixel, in the same order (bit-identical sums).
 enum : int { ST_DONE = -1, ST_TRAVERSE = 0, ST_HIT = 1, ST_END = 2, ST_FETCH = 3, ST_PRIMARY = 4, ST_NEWRAY = 5 };   // events are the positive states
 
-template <bool AS_MASKS> struct HitOwed;             // (see its use in trace_kernel)
-template <> struct HitOwed<true> {
+enum : int { OWED_MASKS = 0, OWED_BITS = 1, OWED_CUBE = 2 };
+template <int OWED_FORM> struct HitOwed;              // (see its use in trace_kernel; later_step: the hit was found after the first iteration)
+template <> struct HitOwed<OWED_MASKS> {
   bool use_leaf = false, leaf_rec = false;
   TDT_DEV void set(bool later_step, bool cube_ok) { use_leaf = later_step; leaf_rec = later_step && cube_ok; }
-  TDT_DEV bool leaf_site() const { return use_leaf; }
-  TDT_DEV bool new_record() const { return leaf_rec; }
+  TDT_DEV bool leaf_site(bool) const { return use_leaf; }
+  TDT_DEV bool new_record(bool) const { return leaf_rec; }
 };
-template <> struct HitOwed<false> {
+template <> struct HitOwed<OWED_BITS> {
   uint32_t bits = 0u;
   TDT_DEV void set(bool later_step, bool cube_ok) { bits = later_step ? (cube_ok ? 3u : 1u) : 0u; }
-  TDT_DEV bool leaf_site() const { return (bits & 1u) != 0u; }
-  TDT_DEV bool new_record() const { return (bits & 2u) != 0u; }
+  TDT_DEV bool leaf_site(bool) const { return (bits & 1u) != 0u; }
+  TDT_DEV bool new_record(bool) const { return (bits & 2u) != 0u; }
+};
+// The step records the slab test alone, in one select: 0 while the lane traverses (reset with every new ray), 1 + cube_ok once it has
+// found its leaf — so the word also says, to the one compare at the step's end, who still traverses and, to the event pass, who left
+// through a leaf.  The iteration count does not move after the hit: the event code asks `later_step` where it reads the record.
+template <> struct HitOwed<OWED_CUBE> {
+  uint32_t cube = 0u;
+  TDT_DEV void set(bool, bool cube_ok) { cube = cube_ok ? 2u : 1u; }
+  TDT_DEV bool leaf_site(bool later_step) const { return later_step; }
+  TDT_DEV bool new_record(bool later_step) const { return later_step && cube == 2u; }
 };
 
 // Per-lane LDS slots of the five-wave builds (trace_kernel's kCold): the per-pixel state that no traversal pass reads or writes.
@@ -143,6 +153,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
   // round 4's second batch of step slimming (see the uses): the scene-specialised builds; the general kernel, with its nine-level node
   // memo, sits at the register cap and keeps the plain forms
   constexpr bool kSlim2 = DEPTH > 0;
+  // the step's bookkeeping as lane masks (see k_trav): no write and no compare of `state` in a traversal pass, the hit's debt in one
+  // select, the iterations counted down against an inline constant.  The instrumented builds keep the plain forms their counters read.
+  constexpr bool kMaskStep = kSlim2 && !COUNT;
 #ifdef TDT_THRESHOLD_EVERY
   constexpr uint32_t kThresholdEvery = kSlim2 ? TDT_THRESHOLD_EVERY : 1u;
 #else
@@ -271,12 +284,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
   float ar = 1.f, ag = 1.f, ab = 1.f;                // accumulative_attenuation rc:267
   float sr = 0.f, sg = 0.f, sb = 0.f;                // color rc:237
   float t_stride = 0.f, t_octree_max = 0.f, inv_pow_depth = 0.5f;
-  int it = 0;                                        // OctreeHit's i rc:410
+  // OctreeHit's i rc:410.  kMaskStep: the steps still allowed — max_iter less ONE per step in the octree, the step that finds the leaf
+  // included (the reference's i does not count that one: the event pass, which knows who hit, adds it back) — so the step decrements it
+  // outside the leaf / no-leaf split and tests it against zero
+  int it = kMaskStep ? P.max_iter : 0;
   // what the hit found by the traversal step still owes the event code: bit 0 = the record is the leaf call site's (it > 0), bit 1 = that
   // call site writes a new record (its slab test hit).  As two bools the compiler keeps them as lane masks in scalar register pairs and
   // updates those with a dozen s_and / s_andn2 / s_or per pass; as an integer in a VGPR the pass is 16 scalar instructions shorter — which
   // is worth 0.8 % where registers are to spare (round 3: not in the brick builds; round 4 freed theirs by shortening the node memo)
-  HitOwed<DEPTH == 0> owed;      // (as lane masks in the general kernel, which sits at the register cap)
+  HitOwed<DEPTH == 0 ? OWED_MASKS : (kMaskStep ? OWED_CUBE : OWED_BITS)> owed;      // (as lane masks in the general kernel, which sits at the register cap)
   uint32_t hit_index = 0;
   float leaf_box_x = 0.f, leaf_box_y = 0.f, leaf_box_z = 0.f;
   Carry pc;
@@ -314,6 +330,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
   unsigned long long k_trav = 0ull, k_event = ~0ull;       // (every lane starts in ST_FETCH)
   int th_now = threshold;
   for (;;) {
+    TDT_MARK(step_head);
     if (COUNT) pass_no++;
     TDT_ST1(STAT_LOOP_PASS, 1);
     // ------------------------------------------------------------ one traversal step rc:410-447
@@ -324,7 +341,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
       const bool trav = __builtin_amdgcn_inverse_ballot_w64(k_trav);
       const unsigned long long k_trav0 = k_trav;
       if (COUNT && trav) { lane_S++; cnt.trav_slots += slot64(); cnt.trav_active++; }
-      const bool go = trav && (it < P.max_iter) && (t_stride < t_octree_max);      // else: OctreeHit returns false rc:449
+      // (kMaskStep: `it` counts down, so the limit is a compare with an inline constant — a VALU compare with a scalar operand is the dearest
+      // half-rate kind — and each condition is taken as the lane mask its compare writes)
+      const bool c_iter = kMaskStep ? (it > 0) : (it < P.max_iter), c_ahead = t_stride < t_octree_max;
+      unsigned long long k_inside = 0ull;
+      if constexpr (kMaskStep) k_inside = k_trav & __ballot(c_iter) & __ballot(c_ahead);
+      const bool go = trav && c_iter && c_ahead;      // else: OctreeHit returns false rc:449
       // rc:412 max(1e-4 (inv_pow_depth + 0.1), 1e-6): in the exact forms inv_pow_depth of a traversing lane is 2^-levels > 0, so the first
       // operand is >= 1e-5 and the max returns it (lanes in other states carry other things in that register; their value is never used)
       const float adv = POW2 ? 0.0001f * (inv_pow_depth + 0.1f) : f_max(0.0001f * (inv_pow_depth + 0.1f), 0.000001f);
@@ -350,7 +372,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
         const float ex = f_fract(lx) + -lx, ey = f_fract(ly) + -ly, ez = f_fract(lz) + -lz;
         in_box = !((__builtin_fabsf(ez) + __builtin_fabsf(ey)) != -__builtin_fabsf(ex));
       }
-      const bool inside = go && in_box;
+      if constexpr (kMaskStep) k_inside &= __ballot(in_box);
+      const bool inside = kMaskStep ? __builtin_amdgcn_inverse_ballot_w64(k_inside) : (go && in_box);
       TDT_ST(STAT_TRAV_PASS, __ballot(trav)); TDT_ST1(STAT_INSIDE_LANES, __popcll(__ballot(inside))); TDT_ST1(STAT_ALIVE_LANES, __popcll(__ballot(state != ST_DONE)));
 #ifdef TDT_STATS
       TDT_ST1(STAT_DRAINED_TRAV_PASS, stat_drained ? 1 : 0);
@@ -358,6 +381,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
       if (inside) {
         float ugx, ugy, ugz; uint32_t value;
         if (COUNT) cnt.iterations++;
+        if constexpr (kMaskStep) it--;
         const float ipd_in = inv_pow_depth;          // (kStuckCut)
         CellPlanes cp;
         bool leaf;
@@ -394,7 +418,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
           if (!kSlim2) { leaf_box_x = cx; leaf_box_y = cy; leaf_box_z = cz; hit_index = value; }
           inv_pow_depth = cs; t_stride = t_enter;
           owed.set(it > 0, cube_ok);
-          state = ST_HIT;
+          // (kMaskStep leaves one select on either side of this split, which the compiler would flatten into selects under the leaf mask:
+          // two more half-rate instructions.  The empty statement keeps the two exec regions: bench frame -1.2 % against -0.6 % flat)
+          if constexpr (kMaskStep) asm volatile("");
+          else state = ST_HIT;
         } else {
           const float ts_new = cube_ok ? t_exit : t_octree_max;
           if (kStuckCut) {
@@ -407,13 +434,20 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
             const bool stuck = __float_as_uint(ts_new) == __float_as_uint(t_stride) && __float_as_uint(inv_pow_depth) == __float_as_uint(ipd_in);
             t_stride = stuck ? t_octree_max : ts_new;
           } else t_stride = ts_new;
-          it++;
+          if constexpr (!kMaskStep) it++;
         }
       }
-      state = (trav && !inside) ? ST_END : state;       // left the octree / ran out of iterations
-      // (ONE compare of `state` per pass: who still traverses; whoever left has an event to be served.  A ballot of the step's own conditions
-      //  — inside && !leaf — would need none, but the compiler lowers the ballot of a boolean that is not a compare to v_cndmask + v_cmp)
-      k_trav &= __ballot(state == ST_TRAVERSE);
+      if constexpr (kMaskStep) {
+        // who still traverses: inside the octree and no leaf found — the masks of the step's own compares and ONE compare of the hit's word
+        // (the leaf branch's exec mask would need none, but a wave-uniform value that leaves a divergent branch is a divergent phi to the
+        // compiler: it moves the mask pair through VGPRs).  `state` is neither written nor read: the event pass works it out for whoever left.
+        k_trav = k_inside & __ballot(owed.cube == 0u);
+      } else {
+        state = (trav && !inside) ? ST_END : state;       // left the octree / ran out of iterations
+        // (ONE compare of `state` per pass: who still traverses; whoever left has an event to be served.  A ballot of the step's own conditions
+        //  — inside && !leaf — would need none, but the compiler lowers the ballot of a boolean that is not a compare to v_cndmask + v_cmp)
+        k_trav &= __ballot(state == ST_TRAVERSE);
+      }
       k_event = ~k_trav & (k_event | k_trav0);
     }
 
@@ -430,6 +464,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
     TDT_ST1(STAT_GATE_WAIT_LANES, __popcll(m_event));      // (every pass: lanes parked at the gate or about to be served)
     if ((int)__popcll(m_event) < th_now && m_trav != 0ull) { TDT_TICK(1); continue; }
     TDT_TICK(1);
+    if constexpr (kMaskStep) {
+      // the lanes that left the traversal since the last event pass still read ST_TRAVERSE: through a leaf (the hit's word is set) or out of
+      // the octree / of iterations
+      const bool left = __builtin_amdgcn_inverse_ballot_w64(m_event) && state == ST_TRAVERSE;
+      state = left ? (owed.cube != 0u ? ST_HIT : ST_END) : state;
+    }
+    int it_done = it;                                 // OctreeHit's i of a ray that has ended (nothing of it moves after the hit)
+    if constexpr (kMaskStep) it_done = P.max_iter - it - (owed.cube != 0u ? 1 : 0);
     TDT_ST(STAT_EVENT_PASS, m_event); TDT_ST(STAT_HIT_PASS, __ballot(state == ST_HIT));
 #ifdef TDT_STATS
     TDT_ST1(STAT_DRAINED_EVENT_PASS, stat_drained ? 1 : 0);
@@ -443,7 +485,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
     // pass, instead of three instructions in every traversal step.  (The tree levels a step visited used to be part of it; with one table or
     // brick read per step whatever the depth they no longer say what a step costs.)
     if constexpr (kCold) lane_work = cold.u(COLD_WORK);
-    if (kSlim2) lane_work += (state == ST_HIT || state == ST_END) ? kCostEvent + kCostRayStep * ((uint32_t)it + 1u) : ((state > ST_TRAVERSE) ? kCostEvent : 0u);
+    if (kSlim2) lane_work += (state == ST_HIT || state == ST_END) ? kCostEvent + kCostRayStep * ((uint32_t)it_done + 1u) : ((state > ST_TRAVERSE) ? kCostEvent : 0u);
     else lane_work += (state > ST_TRAVERSE) ? kCostEvent : 0u;
     if constexpr (kCold) cold.u(COLD_WORK, lane_work);
     if (COUNT) lane_E += (state > ST_TRAVERSE) ? 1u : 0u;
@@ -457,17 +499,17 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
       } else ms = ms_regs;
       const MatRef mat = material_fetch(ms, hit_index);
       TDT_ST(STAT_LAMB_PASS, __ballot(mat.type == 0u)); TDT_ST(STAT_METAL_PASS, __ballot(mat.type == 1u)); TDT_ST(STAT_DIEL_PASS, __ballot(mat.type == 2u));
-      if (owed.new_record()) {
+      if (owed.new_record(it_done > 0)) {
         cube_hit_record(r, t_stride, leaf_box_x, leaf_box_y, leaf_box_z, inv_pow_depth, pc.leaf); if (COUNT) cnt.leaf_records++;
         if constexpr (kCold) cold.put(COLD_LEAF, pc.leaf);
       }
       loop_count += 1;
       HitTmp cold_rec = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, false};
       if constexpr (kCold) {                          // (the record of either call site, as the slots hold it now)
-        const ColdSlots<BLOCK> site = {cold.lane + (owed.leaf_site() ? COLD_LEAF * BLOCK : COLD_ROOT * BLOCK)};
+        const ColdSlots<BLOCK> site = {cold.lane + (owed.leaf_site(it_done > 0) ? COLD_LEAF * BLOCK : COLD_ROOT * BLOCK)};
         cold_rec = site.get(0);
       }
-      const HitTmp &src = kCold ? cold_rec : (owed.leaf_site() ? pc.leaf : pc.root);
+      const HitTmp &src = kCold ? cold_rec : (owed.leaf_site(it_done > 0) ? pc.leaf : pc.root);
       Hit h;
       h.px = src.px; h.py = src.py; h.pz = src.pz; h.nx = src.nx; h.ny = src.ny; h.nz = src.nz; h.ff = src.ff;
       h.index = hit_index;
@@ -667,7 +709,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
         }
         t_stride = pc.root_t;
         inv_pow_depth = 0.5f;
-        it = 0;
+        if constexpr (kMaskStep) { it = P.max_iter; owed.cube = 0u; } else it = 0;
         state = ST_TRAVERSE;
       }
     }

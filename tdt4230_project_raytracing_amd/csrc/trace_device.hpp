@@ -718,7 +718,12 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
     if (__builtin_expect(__ballot(!safe) == 0ull, 1)) {
       // the whole lookup: levels visited, the cell's digits and what it holds (see build_full_grid_kernel)
       const uint32_t xg = (uint32_t)tg;
-      const FullGridEntry g = ns.full[(xg << (2 * DEPTH)) | (Yi << DEPTH) | Zi];      // (64 bits: one 8-byte load)
+      // (64 bits: one 8-byte load.  The byte offset — below 2 MB at depth 6 — formed in 32 bits beside the table's scalar base: no 64-bit add)
+      constexpr int kEntryShift = sizeof(FullGridEntry) == 8 ? 3 : (sizeof(FullGridEntry) == 4 ? 2 : 1);
+      static_assert(sizeof(FullGridEntry) == (1u << kEntryShift) && 3 * DEPTH + kEntryShift < 32, "the table's byte offset in 32 bits");
+      // (a sum of disjoint bit fields)
+      const uint32_t off = (xg << (2 * DEPTH + kEntryShift)) + ((Yi << (DEPTH + kEntryShift)) + (Zi << kEntryShift));
+      const FullGridEntry g = *reinterpret_cast<const FullGridEntry *>(reinterpret_cast<const char *>(ns.full) + off);
       if constexpr (PLANES) return full_entry_planes<DEPTH>(g, ns.planes, *cp, inv_pow_depth, value);
       else return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
     }

@@ -3,9 +3,13 @@
 
 Compiles csrc/tdt_rt.hip with -DTDT_MARKERS (assembler comments at the region boundaries, see TDT_MARK in trace_device.hpp), cuts
 the compiler's assembly of the builds the bench frames run at those comments and counts VALU / transcendental / SALU / LDS / VMEM
-instructions per region.  Blocks the compiler laid out after the main loop (the `__builtin_expect`-unlikely paths: band fallbacks, the
-IEEE forms of rcp / sqrt outside the exponent window, the literal normal) are reported as `cold`.  The marker build is not the
-product build (an `asm volatile` is a scheduling boundary), but the counts per region are the source's, to a few instructions.
+instructions per region.  Blocks the compiler laid out behind the loop's last region (the `__builtin_expect`-unlikely paths: band
+fallbacks, the IEEE forms of rcp / sqrt outside the exponent window, the literal normal) are reported as `cold`: they follow the
+unconditional branch that closes `newray`.  `step_head` is the loop's header block: the compiler lays the traversal step's first
+instructions (position, in-octree test, loop condition — plain arithmetic, which no marker holds in place) out between the
+`loop_tail` marker and the `step_head` / `traversal` markers, behind two scalar instructions of loop control (builds whose loop ends
+with the `loop_tail` marker have their unlikely blocks there instead, and the step's first instructions under `traversal`).  The marker build is
+not the product build (an `asm volatile` is a scheduling boundary), but the counts per region are the source's, to a few instructions.
 
     python tools/isa_regions.py [out.json]         # default: profiles/r04_isa_regions.json
 """
@@ -41,12 +45,23 @@ def regions(asm, symbol):
         t = line.strip()
         m = re.match(r";\s*TDT_MARK (\w+)", t)
         if m:
-            cur = {"after_loop": "epilogue", "loop_tail": "cold"}.get(m.group(1), m.group(1))
+            name = m.group(1)
+            if cur == "after_loop_tail":              # what followed the loop's last marker: the header block, or blocks laid out behind the loop
+                tail = out.pop(cur, None)
+                if tail:
+                    into = out.setdefault("step_head" if name in ("step_head", "traversal") else "cold", dict(valu=0, trans=0, salu=0, lds=0, vmem=0))
+                    for k, v in tail.items():
+                        into[k] += v
+            cur = {"after_loop": "epilogue", "loop_tail": "after_loop_tail"}.get(name, name)
             continue
         if not t or t[0] in ";." or t.endswith(":"):
             continue
         op = t.split()[0]
         r = out.setdefault(cur, dict(valu=0, trans=0, salu=0, lds=0, vmem=0))
+        if op == "s_branch" and cur == "newray":      # the loop's last block jumps back: what follows was laid out behind the loop
+            r["salu"] += 1
+            cur = "cold"
+            continue
         if op.startswith("v_"):
             r["valu"] += 1
             if TRANS.match(op):
@@ -72,7 +87,7 @@ def main():
         if r.returncode != 0:
             raise SystemExit("compile failed:\n" + r.stderr[-3000:])
         asm = open(s_path).read()
-    res = {"note": "static instruction counts per code region of the -DTDT_MARKERS build (tools/isa_regions.py); `cold` = blocks laid out at the end of the loop (unlikely paths; in the demo kernel, whose loop the compiler rotated, they follow `newray` and are counted there); `walk` = treeLookup level by level",
+    res = {"note": "static instruction counts per code region of the -DTDT_MARKERS build (tools/isa_regions.py); `step_head` = the loop's header block (the traversal step's first instructions); `cold` = blocks laid out behind the loop's last region (unlikely paths); `walk` = treeLookup level by level",
            "kernels": {}}
     for name, sym in KERNELS.items():
         reg = regions(asm, sym)
