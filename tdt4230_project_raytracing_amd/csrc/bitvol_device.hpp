@@ -104,8 +104,7 @@ int bitvol_list_tail(tdt_ctx *front, hipStream_t st, size_t n_items, Count &&cou
   TDT_HIP(front, exclusive_scan_u32(st, count, count, (uint32_t)(n_items + 1), scr));
   TDT_HIP(front, hipGetLastError());
   uint32_t n_sel = 0;                                      // <= 2^30 in every unit
-  TDT_HIP(front, hipMemcpyAsync(&n_sel, count + n_items, sizeof n_sel, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the count
+  if (int rc = read_word(front, st, count + n_items, &n_sel)) return rc;   // the count
   if (n_sel > kBitvolCap)
     return fail(front, TDT_ERR_INVALID_VALUE, std::string(noun) + " holds " + std::to_string(n_sel) + " voxels (more than 2^26)");
   const uint32_t n_out = n_sel + n_head;

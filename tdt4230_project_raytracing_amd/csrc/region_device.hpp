@@ -1,5 +1,5 @@
-// Device helpers shared by the editing units: Morton keys of grid voxels, the exact integer shape test of a tdt_region, and the
-// neighbour lookup in a sorted key list; and the two host steps every unit with a region list takes: the list's validation
+// Device helpers shared by the editing units: Morton keys of grid voxels and a key's voxel, the exact integer shape test of a
+// tdt_region, the lower- and upper-bound searches of the rank merges and the neighbour lookup in a sorted key list; and the two host steps every unit with a region list takes: the list's validation
 // with its copy into RegionShapes, and their upload.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,14 +40,16 @@ inline int upload_shapes(tdt_ctx *front, hipStream_t st, DeviceScratch &S, const
   return TDT_OK;
 }
 
-__device__ __forceinline__ uint32_t region_spread3(uint32_t v) {   // 10 bits -> every third bit (the builder's spread3)
+constexpr uint32_t kDroppedKey = 0xFFFFFFFFu;   // key of a voxel outside the grid: sorts behind everything, and the unique drops it
+
+__device__ __forceinline__ uint32_t region_spread3(uint32_t v) {   // 10 bits -> every third bit
   v = (v | (v << 16)) & 0x030000FFu;
   v = (v | (v << 8)) & 0x0300F00Fu;
   v = (v | (v << 4)) & 0x030C30C3u;
   v = (v | (v << 2)) & 0x09249249u;
   return v;
 }
-__device__ __forceinline__ uint32_t region_compact3(uint32_t v) {
+__device__ __forceinline__ uint32_t region_compact3(uint32_t v) {  // every third bit -> 10 bits
   v &= 0x09249249u;
   v = (v | (v >> 2)) & 0x030C30C3u;
   v = (v | (v >> 4)) & 0x0300F00Fu;
@@ -71,6 +73,22 @@ __device__ __forceinline__ bool region_inside(const RegionShape &s, int x, int y
   return d2 <= (unsigned long long)(r * r);
 }
 
+// the voxel of Morton key k, with w = m
+__device__ __forceinline__ int4 region_voxel(uint32_t k, int m) {
+  return make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), m);
+}
+
+// the number of keys below k (lower) / at or below k (upper) in the sorted keys[0, n): the index of the first that is not
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *keys, uint32_t n, uint32_t k) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (keys[mid] < k) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+__device__ __forceinline__ uint32_t upper_bound_u32(const uint32_t *keys, uint32_t n, uint32_t k) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (keys[mid] <= k) lo = mid + 1; else hi = mid; }
+  return lo;
+}
 // index of key kn in keys[0, n), or -1: a gallop from i (keys[i] = k != kn) toward kn, then a binary search
 __device__ __forceinline__ int gallop_find(const uint32_t *keys, int n, int i, uint32_t k, uint32_t kn) {
   if (kn > k) {

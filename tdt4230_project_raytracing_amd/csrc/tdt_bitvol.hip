@@ -56,8 +56,7 @@ __global__ __launch_bounds__(256) void bitvol_rasterise_kernel(const int4 *v, ui
 __global__ __launch_bounds__(256) void bitvol_list_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, int4 *out) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  const uint32_t k = keys[i];
-  out[i] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)vals[i]);
+  out[i] = region_voxel(keys[i], (int)vals[i]);
 }
 
 void bitvol_layout(const int lo[3], const int hi[3], BitBox &B) {
@@ -65,12 +64,6 @@ void bitvol_layout(const int lo[3], const int hi[3], BitBox &B) {
   B.ey = B.hi[1] - B.lo[1] + 1; B.ez = B.hi[2] - B.lo[2] + 1;
   B.wx0 = B.lo[0] >> 5; B.nw = (B.hi[0] >> 5) - B.wx0 + 1;
   B.n_words = (uint32_t)B.ey * (uint32_t)B.ez * (uint32_t)B.nw;
-}
-
-int bitvol_tree_voxels(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
-  if (int rc = tree_voxels(front, ctx, 254u, S, out, n, depth)) return rc;
-  if (*n > kBitvolCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(*n) + " voxels (more than 2^26)");
-  return TDT_OK;
 }
 
 int bitvol_list_bbox(tdt_ctx *front, hipStream_t st, const int4 *v, uint32_t n, int depth, DeviceScratch &S, const char *no_memory,

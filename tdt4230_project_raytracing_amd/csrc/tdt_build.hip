@@ -23,11 +23,11 @@
 #include <vector>
 
 #include "device_scan.hpp"
+#include "region_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
 
-constexpr uint32_t kDropped = 0xFFFFFFFFu;   // key of a voxel outside the grid: sorts behind everything
 constexpr uint32_t kMixed = 0xFFu;           // host_scene.cpp MIXED
 constexpr uint32_t kSortTile = 2048;         // items per 256-thread block and pass
 
@@ -39,16 +39,8 @@ struct KeyArgs {
   const uint32_t *pal_keys; uint32_t n_pal; const uint32_t *pal_rank;   // null: voxel[3] is material + 1 already
 };
 
-__device__ __forceinline__ uint32_t spread3(uint32_t v) {      // 10 bits -> every third bit
-  v = (v | (v << 16)) & 0x030000FFu;
-  v = (v | (v << 8)) & 0x0300F00Fu;
-  v = (v | (v << 4)) & 0x030C30C3u;
-  v = (v | (v << 2)) & 0x09249249u;
-  return v;
-}
 __device__ __forceinline__ int pal_find(const uint32_t *keys, uint32_t n, uint32_t k) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (keys[mid] < k) lo = mid + 1; else hi = mid; }
+  const uint32_t lo = lower_bound_u32(keys, n, k);
   return (lo < n && keys[lo] == k) ? (int)lo : -1;
 }
 
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(256) void build_keys_kernel(const KeyArgs A, uint32
   if (A.pal_keys) { const int p = pal_find(A.pal_keys, A.n_pal, (uint32_t)v[3]); m = p < 0 ? 0u : 1u + A.pal_rank[p]; }
   else m = (uint32_t)v[3];
   const bool ok = x >= 0 && y >= 0 && z >= 0 && x < N && y < N && z < N && m >= 1u && m < kMixed;
-  keys[i] = ok ? ((spread3((uint32_t)x) << 2) | (spread3((uint32_t)y) << 1) | spread3((uint32_t)z)) : kDropped;
+  keys[i] = ok ? region_key((int)x, (int)y, (int)z) : kDroppedKey;
   vals[i] = m;
 }
 
@@ -132,20 +124,6 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t *keys,
     s_off[threadIdx.x] += s_wave[0][threadIdx.x] + s_wave[1][threadIdx.x] + s_wave[2][threadIdx.x] + s_wave[3][threadIdx.x];
     __syncthreads();
   }
-}
-
-// ---- leaf level: of every run of equal keys keep the LAST (file order: Grid::set overwrites) ---------------------------
-__global__ __launch_bounds__(256) void build_last_flags_kernel(const uint32_t *keys, uint32_t n, uint32_t *flag /* n + 1 */) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i > n) return;
-  flag[i] = (i < n && keys[i] != kDropped && (i + 1u == n || keys[i + 1u] != keys[i])) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void build_compact_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, const uint32_t *excl /* n + 1 */,
-                                                           uint32_t *lk, uint32_t *lv, uint32_t *count) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) *count = excl[n];
-  if (i >= n) return;
-  if (excl[i + 1u] != excl[i]) { lk[excl[i]] = keys[i]; lv[excl[i]] = vals[i]; }
 }
 
 // ---- one level up: children (keys ck, values cv, *c_count of them) -> parents ------------------------------------------
@@ -223,29 +201,18 @@ hipError_t sort_pairs_u32(hipStream_t st, uint32_t *&k, uint32_t *&v, uint32_t *
 
 namespace {
 
-struct DeviceArena {          // temporaries of one build, freed together
-  tdt_ctx *ctx; std::vector<void *> ptrs;
-  explicit DeviceArena(tdt_ctx *c) : ctx(c) {}
-  ~DeviceArena() { for (void *p : ptrs) (void)hipFree(p); }
-  template <class T> T *get(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-};
-#define TDT_ALLOC(var, T, n) T *var = arena.get<T>(n); if (!var) return fail(ctx, TDT_ERR_HIP, "out of device memory in the octree builder")
-inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
+const char *kNoMemory = "out of device memory in the octree builder";
+#define TDT_ALLOC(var, T, n) T *var = arena.get<T>(n); if (!var) return fail(ctx, TDT_ERR_HIP, kNoMemory)   // arena: the build's DeviceScratch
 
 // voxels already on the device -> a cells buffer; pal_* null: vox[3] is material + 1
 int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const KeyArgs &key_args, tdt_buffer **out, uint32_t *n_cells_out) {
   hipStream_t st = ctx->stream;
   const int D = key_args.depth;
-  DeviceArena arena(ctx);
+  DeviceScratch arena;
   TDT_ALLOC(k0, uint32_t, n); TDT_ALLOC(k1, uint32_t, n); TDT_ALLOC(v0, uint32_t, n); TDT_ALLOC(v1, uint32_t, n);
   KeyArgs A = key_args; A.vox = d_vox; A.n = n;
-  hipLaunchKernelGGL(build_keys_kernel, dim3(blocks(n)), dim3(256), 0, st, A, k0, v0);
-  // sort
+  hipLaunchKernelGGL(build_keys_kernel, dim3(blocks_of(n)), dim3(256), 0, st, A, k0, v0);
+  // sort (queued ahead of the allocations below, which the host makes while the GPU sorts)
   TDT_ALLOC(hist, uint32_t, sort_hist_words(n));
   TDT_ALLOC(hscr, uint32_t, sort_scratch_words(n));
   TDT_HIP(ctx, sort_pairs_u32(st, k0, v0, k1, v1, n, hist, hscr));
@@ -255,19 +222,19 @@ int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const Key
   std::vector<uint32_t *> lk(D + 1, nullptr), lv(D + 1, nullptr), par(D + 1, nullptr);
   for (int l = 1; l <= D; l++) {
     lk[l] = arena.get<uint32_t>(cap[l]); lv[l] = arena.get<uint32_t>(cap[l]); par[l] = arena.get<uint32_t>(cap[l]);
-    if (!lk[l] || !lv[l] || !par[l]) return fail(ctx, TDT_ERR_HIP, "out of device memory in the octree builder");
+    if (!lk[l] || !lv[l] || !par[l]) return fail(ctx, TDT_ERR_HIP, kNoMemory);
   }
   TDT_ALLOC(count, uint32_t, D + 2);
   TDT_ALLOC(flag, uint32_t, (size_t)n + 1); TDT_ALLOC(fscr, uint32_t, scan_scratch_words((size_t)n + 1));
-  hipLaunchKernelGGL(build_last_flags_kernel, dim3(blocks((size_t)n + 1)), dim3(256), 0, st, (const uint32_t *)k0, n, flag);
+  // the leaf level: of every run of equal keys the LAST (file order: Grid::set overwrites)
+  voxlist_last_flags(st, k0, n, flag);
   TDT_HIP(ctx, exclusive_scan_u32(st, flag, flag, n + 1u, fscr));
-  hipLaunchKernelGGL(build_compact_kernel, dim3(blocks(n)), dim3(256), 0, st, (const uint32_t *)k0, (const uint32_t *)v0, n, (const uint32_t *)flag,
-                     lk[D], lv[D], count + D);
+  voxlist_unique(st, k0, v0, n, flag, lk[D], lv[D], count + D);
   for (int l = D - 1; l >= 1; l--) {
     const uint32_t cc = cap[l + 1];
-    hipLaunchKernelGGL(build_head_flags_kernel, dim3(blocks((size_t)cc + 1)), dim3(256), 0, st, (const uint32_t *)lk[l + 1], (const uint32_t *)(count + l + 1), cc, flag);
+    hipLaunchKernelGGL(build_head_flags_kernel, dim3(blocks_of((size_t)cc + 1)), dim3(256), 0, st, (const uint32_t *)lk[l + 1], (const uint32_t *)(count + l + 1), cc, flag);
     TDT_HIP(ctx, exclusive_scan_u32(st, flag, flag, cc + 1u, fscr));
-    hipLaunchKernelGGL(build_reduce_kernel, dim3(blocks(cc)), dim3(256), 0, st, (const uint32_t *)lk[l + 1], (const uint32_t *)lv[l + 1], (const uint32_t *)(count + l + 1), cc,
+    hipLaunchKernelGGL(build_reduce_kernel, dim3(blocks_of(cc)), dim3(256), 0, st, (const uint32_t *)lk[l + 1], (const uint32_t *)lv[l + 1], (const uint32_t *)(count + l + 1), cc,
                        (const uint32_t *)flag, par[l + 1], lk[l], lv[l], count + l);
   }
   // breadth-first numbers: one prefix sum over the MIXED flags of levels 1..D-1 laid end to end
@@ -277,12 +244,11 @@ int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const Key
   TDT_ALLOC(mixed, uint32_t, total_cap + 1); TDT_ALLOC(mscr, uint32_t, scan_scratch_words(total_cap + 1));
   TDT_HIP(ctx, hipMemsetAsync(mixed + total_cap, 0, sizeof(uint32_t), st));
   for (int l = 1; l < D; l++)
-    hipLaunchKernelGGL(build_mixed_flags_kernel, dim3(blocks(cap[l])), dim3(256), 0, st, (const uint32_t *)lv[l], (const uint32_t *)(count + l), cap[l], mixed + off[l]);
+    hipLaunchKernelGGL(build_mixed_flags_kernel, dim3(blocks_of(cap[l])), dim3(256), 0, st, (const uint32_t *)lv[l], (const uint32_t *)(count + l), cap[l], mixed + off[l]);
   TDT_HIP(ctx, exclusive_scan_u32(st, mixed, mixed, (uint32_t)(total_cap + 1), mscr));
   TDT_HIP(ctx, hipGetLastError());
   uint32_t n_mixed = 0;
-  TDT_HIP(ctx, hipMemcpyAsync(&n_mixed, mixed + total_cap, sizeof n_mixed, hipMemcpyDeviceToHost, st));
-  TDT_HIP(ctx, hipStreamSynchronize(st));             // the one thing the host must know: how large the cells buffer is
+  if (int rc = read_word(ctx, st, mixed + total_cap, &n_mixed)) return rc;   // the one thing the host must know: how large the cells buffer is
   const uint32_t n_cells = 1u + n_mixed;
   const size_t bytes = (size_t)n_cells * 64;
   void *d_cells = nullptr;
@@ -290,7 +256,7 @@ int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const Key
   hipError_t e = hipMemsetAsync(d_cells, 0, bytes + 16, st);
   if (e != hipSuccess) { (void)hipFree(d_cells); return hip_fail(ctx, e, "hipMemsetAsync"); }
   for (int l = 1; l <= D; l++)
-    hipLaunchKernelGGL(build_emit_kernel, dim3(blocks(cap[l])), dim3(256), 0, st, (const uint32_t *)lk[l], (const uint32_t *)lv[l], (const uint32_t *)(count + l),
+    hipLaunchKernelGGL(build_emit_kernel, dim3(blocks_of(cap[l])), dim3(256), 0, st, (const uint32_t *)lk[l], (const uint32_t *)lv[l], (const uint32_t *)(count + l),
                        (const uint32_t *)(l > 1 ? par[l] : nullptr), (const uint32_t *)(l > 1 ? lv[l - 1] : nullptr),
                        (const uint32_t *)(l > 1 ? mixed + off[l - 1] : nullptr), (const uint32_t *)(l < D ? mixed + off[l] : nullptr),
                        (uint32_t *)d_cells, n_cells);
@@ -303,9 +269,9 @@ int build_cells_device(tdt_ctx *ctx, const int32_t *d_vox, uint32_t n, const Key
   return TDT_OK;
 }
 
-int upload_voxels(tdt_ctx *ctx, DeviceArena &arena, const int32_t *host, size_t n, int32_t **dev) {
+int upload_voxels(tdt_ctx *ctx, DeviceScratch &arena, const int32_t *host, size_t n, int32_t **dev) {
   *dev = arena.get<int32_t>(n * 4);
-  if (!*dev) return fail(ctx, TDT_ERR_HIP, "out of device memory in the octree builder");
+  if (!*dev) return fail(ctx, TDT_ERR_HIP, kNoMemory);
   TDT_HIP(ctx, hipMemcpyAsync(*dev, host, n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   return TDT_OK;
 }
@@ -353,7 +319,7 @@ int tdt_octree_build_cells(tdt_ctx *ctx, const int32_t *voxels_xyzm, size_t n_vo
     if (n_cells) *n_cells = 1;
     return tdt_buffer_create(ctx, zero, sizeof zero, cells);
   }
-  DeviceArena arena(ctx);
+  DeviceScratch arena;
   int32_t *d_vox = nullptr;
   int rc = upload_voxels(ctx, arena, voxels_xyzm, n_voxels, &d_vox);
   if (rc != TDT_OK) return rc;
@@ -376,10 +342,10 @@ int tdt_octree_build_from_points(tdt_ctx *ctx, const int32_t *voxels_xyzk, size_
   if (n_voxels >= (1ull << 31) || n_palette >= (1ull << 24)) return fail(ctx, TDT_ERR_INVALID_VALUE, "voxel list or palette too large");
   for (size_t i = 1; i < n_palette; i++)
     if (palette_keys[i] <= palette_keys[i - 1]) return fail(ctx, TDT_ERR_INVALID_VALUE, "palette keys must be strictly ascending");
-  tdt_ctx *dev_ctx = ctx->multi ? multi_first_member(ctx) : ctx;          // kernels run here; buffers are created on `ctx`
+  tdt_ctx *dev_ctx = first_member(ctx);          // kernels run here; buffers are created on `ctx`
   TDT_HIP(ctx, hipSetDevice(dev_ctx->device));
   hipStream_t st = dev_ctx->stream;
-  DeviceArena arena(dev_ctx);
+  DeviceScratch arena;
   const uint32_t n = (uint32_t)n_voxels, np = (uint32_t)n_palette;
   int32_t *d_vox = nullptr;
   int rc = upload_voxels(dev_ctx, arena, voxels_xyzk, n_voxels, &d_vox);
@@ -388,7 +354,7 @@ int tdt_octree_build_from_points(tdt_ctx *ctx, const int32_t *voxels_xyzk, size_
   TDT_ALLOC(d_mx, int32_t, 3);
   const int32_t lowest[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
   TDT_HIP(ctx, hipMemcpyAsync(d_mx, lowest, sizeof lowest, hipMemcpyHostToDevice, st));
-  unsigned nb = blocks(n); if (nb > 1024) nb = 1024;
+  unsigned nb = blocks_of(n); if (nb > 1024) nb = 1024;
   hipLaunchKernelGGL(build_extent_kernel, dim3(nb), dim3(256), 0, st, (const int32_t *)d_vox, n, d_mx);
   // palette entries in use -> material index = rank among them (ascending key, as the host's std::map iterates)
   TDT_ALLOC(d_pk, uint32_t, np); TDT_ALLOC(d_rgb, uint8_t, (size_t)np * 3);
@@ -398,7 +364,7 @@ int tdt_octree_build_from_points(tdt_ctx *ctx, const int32_t *voxels_xyzk, size_
   TDT_HIP(ctx, hipMemcpyAsync(d_rgb, palette_rgb, (size_t)np * 3, hipMemcpyHostToDevice, st));
   TDT_HIP(ctx, hipMemsetAsync(d_used, 0, ((size_t)np + 1) * sizeof(uint32_t), st));
   TDT_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(build_palette_mark_kernel, dim3(blocks(n)), dim3(256), 0, st, (const int32_t *)d_vox, n, (const uint32_t *)d_pk, np, d_used, d_err);
+  hipLaunchKernelGGL(build_palette_mark_kernel, dim3(blocks_of(n)), dim3(256), 0, st, (const int32_t *)d_vox, n, (const uint32_t *)d_pk, np, d_used, d_err);
   TDT_HIP(ctx, exclusive_scan_u32(st, d_used, d_rank, np + 1u, d_pscr));
   int32_t mx[3]; uint32_t n_colours = 0, err = 0;
   TDT_HIP(ctx, hipMemcpyAsync(mx, d_mx, sizeof mx, hipMemcpyDeviceToHost, st));
@@ -434,7 +400,7 @@ int tdt_octree_build_from_points(tdt_ctx *ctx, const int32_t *voxels_xyzk, size_
   if (e == hipSuccess) e = hipMemsetAsync(d_mat, 0, tab_bytes + 16, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_alb, 0, tab_bytes + 16, st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(build_materials_kernel, dim3(blocks(np)), dim3(256), 0, st, (const uint32_t *)d_used, (const uint32_t *)d_rank, (const uint8_t *)d_rgb, np,
+    hipLaunchKernelGGL(build_materials_kernel, dim3(blocks_of(np)), dim3(256), 0, st, (const uint32_t *)d_used, (const uint32_t *)d_rank, (const uint8_t *)d_rgb, np,
                        (uint32_t *)d_mat, (float *)d_alb);
     e = hipGetLastError();
   }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "device_scan.hpp"
+#include "region_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
@@ -121,15 +122,6 @@ __global__ __launch_bounds__(256) void compact_counts_kernel(const uint32_t *ord
   vc[i] = i < n ? 1u << (3 * (depth - (int)leaf_lvl[order[i]])) : 0u;
 }
 
-__device__ __forceinline__ uint32_t compact3(uint32_t v) {     // every third bit -> 10 bits (inverse of the builder's spread3)
-  v &= 0x09249249u;
-  v = (v | (v >> 2)) & 0x030C30C3u;
-  v = (v | (v >> 4)) & 0x0300F00Fu;
-  v = (v | (v >> 8)) & 0x030000FFu;
-  v = (v | (v >> 16)) & 0x000003FFu;
-  return v;
-}
-
 // one lane per voxel: its leaf record is the last one whose voxel offset is <= the lane (offsets strictly increase)
 __global__ __launch_bounds__(256) void compact_expand_kernel(const uint32_t *start, const uint32_t *order, const uint32_t *voff, uint32_t n_leaves,
                                                             const uint32_t *leaf_val, uint32_t n_vox, int4 *out) {
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(256) void compact_expand_kernel(const uint32_t *sta
   uint32_t lo = 0, hi = n_leaves;                           // invariant: voff[lo] <= v < voff[hi]
   while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (voff[mid] <= v) lo = mid; else hi = mid; }
   const uint32_t key = start[lo] + (v - voff[lo]);
-  out[v] = make_int4((int)compact3(key >> 2), (int)compact3(key >> 1), (int)compact3(key), (int)(leaf_val[order[lo]] + 1u));
+  out[v] = region_voxel(key, (int)(leaf_val[order[lo]] + 1u));
 }
 
 // the bound slots 0 / 7 of ctx (a single-device context); errors are reported on `front`
@@ -267,8 +259,6 @@ int expand_voxels(tdt_ctx *front, tdt_ctx *ctx, Walk &W, Scratch &S, int4 **out)
   return TDT_OK;
 }
 
-tdt_ctx *walk_member(tdt_ctx *ctx) { return ctx->multi ? multi_first_member(ctx) : ctx; }
-
 }  // namespace
 
 int tree_voxels(tdt_ctx *front, tdt_ctx *ctx, uint32_t leaf_limit, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
@@ -313,22 +303,12 @@ namespace {
 
 // compaction of one single-device context
 int compact_one(tdt_ctx *front, tdt_ctx *ctx, uint32_t *n_cells) {
-  tdt_buffer *built = nullptr;
-  uint32_t nc = 1;
-  {
-    Scratch S;
-    int4 *vox = nullptr;
-    uint32_t nv = 0;
-    int depth = 0;
-    if (int rc = tree_voxels(front, ctx, 254u, S, &vox, &nv, &depth)) return rc;
-    if (nv) {
-      const int rc = build_cells_from_device(ctx, (const int32_t *)vox, nv, depth, &built, &nc);
-      if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
-    }
-  }
-  if (int rc = install_cells(front, ctx, built, nc)) return rc;
-  *n_cells = nc;
-  return TDT_OK;
+  Scratch S;
+  int4 *vox = nullptr;
+  uint32_t nv = 0;
+  int depth = 0;
+  if (int rc = tree_voxels(front, ctx, 254u, S, &vox, &nv, &depth)) return rc;
+  return rebuild_install(front, ctx, vox, nv, depth, false, n_cells, [&] { S.release(); });   // *n_cells only once installed
 }
 
 }  // namespace
@@ -341,7 +321,7 @@ int tdt_octree_census(tdt_ctx *ctx, int64_t out[6]) {
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   if (!out) return fail(ctx, TDT_ERR_INVALID_VALUE, "null out pointer");
   Walk W;
-  if (int rc = walk_tree(ctx, walk_member(ctx), false, W)) return rc;
+  if (int rc = walk_tree(ctx, first_member(ctx), false, W)) return rc;
   out[0] = (int64_t)W.meta.reach; out[1] = (int64_t)W.meta.leaves; out[2] = (int64_t)W.meta.voxels;
   out[3] = (int64_t)W.meta.max_cell; out[4] = (int64_t)W.buffer_cells; out[5] = W.counter;
   return TDT_OK;
@@ -352,7 +332,7 @@ int tdt_octree_extract(tdt_ctx *ctx, int32_t *voxels_xyzm, size_t capacity, size
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   if (!n_voxels) return fail(ctx, TDT_ERR_INVALID_VALUE, "null n_voxels pointer");
   *n_voxels = 0;
-  tdt_ctx *m = walk_member(ctx);
+  tdt_ctx *m = first_member(ctx);
   Walk W;
   if (int rc = walk_tree(ctx, m, voxels_xyzm != nullptr, W)) return rc;
   *n_voxels = (size_t)W.meta.voxels;
@@ -371,23 +351,9 @@ int tdt_octree_extract(tdt_ctx *ctx, int32_t *voxels_xyzm, size_t capacity, size
 int tdt_octree_compact(tdt_ctx *ctx, uint32_t *n_cells) {
   using namespace tdt;
   if (!ctx) return TDT_ERR_INVALID_VALUE;
-  uint32_t nc = 0;
-  if (!ctx->multi) {
-    if (int rc = compact_one(ctx, ctx, &nc)) return rc;
-  } else {
-    // an edit changes every replica identically (multi_dispatch_compute), so does this; a failure leaves the replicas as they were
-    // (the checks fail on the first member, before anything is written, and the others hold the same bytes)
-    if (!ctx->ssbo[TDT_SLOT_CELLS] || !ctx->ssbo[TDT_SLOT_OCTREE_INTS])
-      return fail(ctx, TDT_ERR_INCOMPLETE, std::string("no buffer bound to shader-storage slot ") + (ctx->ssbo[TDT_SLOT_CELLS] ? "7" : "0"));
-    tdt_ctx *m0 = multi_first_member(ctx);
-    for (tdt_ctx *m : multi_members(ctx)) {
-      uint32_t k = 0;
-      if (int rc = compact_one(ctx, m, &k)) return rc;
-      if (m == m0) nc = k;
-    }
-  }
-  if (n_cells) *n_cells = nc;
-  return TDT_OK;
+  // an edit changes every replica identically (multi_dispatch_compute), so does this; a failure leaves the replicas as they were,
+  // and *n_cells too
+  return edit_replicas(ctx, false, n_cells, [&](tdt_ctx *m, uint32_t *nc) { return compact_one(ctx, m, nc); });
 }
 
 }  // extern "C"

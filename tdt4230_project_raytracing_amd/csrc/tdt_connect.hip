@@ -161,8 +161,7 @@ __global__ __launch_bounds__(256) void connect_seed_kernel(const int4 *seeds, ui
   const int N = 1 << depth;
   if (q.x < 0 || q.y < 0 || q.z < 0 || q.x >= N || q.y >= N || q.z >= N) return;
   const uint32_t k = region_key(q.x, q.y, q.z);
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (keys[mid] < k) lo = mid + 1; else hi = mid; }
+  const uint32_t lo = lower_bound_u32(keys, n, k);
   if (lo < n && keys[lo] == k) hit[label[lo]] = 1u;
 }
 
@@ -217,8 +216,7 @@ int label_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *v, uint32_t nv, int d
   hipLaunchKernelGGL(connect_flatten_kernel, dim3(blocks_of((size_t)nv + 1)), dim3(256), 0, st, parent, nv, label, flag);
   TDT_HIP(front, exclusive_scan_u32(st, flag, flag, nv + 1u, fscr));
   uint32_t nc = 0;
-  TDT_HIP(front, hipMemcpyAsync(&nc, flag + nv, sizeof nc, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));               // the component count
+  if (int rc = read_word(front, st, flag + nv, &nc)) return rc;   // the component count
   tdt_component *tab = S.get<tdt_component>(nc);
   if (!tab) return fail(front, TDT_ERR_HIP, kNoMemory);
   hipLaunchKernelGGL(connect_table_init_kernel, dim3(blocks_of(nc)), dim3(256), 0, st, tab, nc);
@@ -302,7 +300,7 @@ int tdt_octree_components(tdt_ctx *ctx, int connectivity, int match, uint32_t *l
   if (!n_voxels || !n_components) return fail(ctx, TDT_ERR_INVALID_VALUE, "null count pointer");
   *n_voxels = 0; *n_components = 0;
   if (int rc = check_kind(ctx, connectivity, match)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   TDT_HIP(ctx, hipSetDevice(m->device));
   DeviceScratch S;
   int4 *v = nullptr;

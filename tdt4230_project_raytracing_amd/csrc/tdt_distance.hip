@@ -316,7 +316,7 @@ int round_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, bool delta, Devic
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
   if (nv == 0) return TDT_OK;                              // every op of the empty set is empty
   int box[6];
   if (int rc = bitvol_list_bbox(front, st, v, nv, depth, S, kNoMemory, "a voxel lies outside the grid", box)) return rc;
@@ -404,7 +404,7 @@ int field_one(tdt_ctx *front, tdt_ctx *ctx, const int32_t lo[3], const int32_t h
   DeviceScratch S;
   int4 *v = nullptr;
   uint32_t nv = 0;
-  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) { *n_voxels = 0; return rc; }
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) { *n_voxels = 0; return rc; }
   const size_t padded = (size_t)B.n_words * 32;
   uint32_t *occ = S.get<uint32_t>(B.n_words), *wk = S.get<uint32_t>(nv), *wv = S.get<uint32_t>(nv);
   signed char *ox = S.get<signed char>(padded);
@@ -462,7 +462,7 @@ int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t h
   if (!lo || !hi) return fail(ctx, TDT_ERR_INVALID_VALUE, "null box pointer");
   if (max_d2 < 1 || max_d2 > 4096) return fail(ctx, TDT_ERR_INVALID_VALUE, "max_d2 must be 1..4096");
   if (border != 0 && border != 1) return fail(ctx, TDT_ERR_INVALID_VALUE, "border must be 0 or 1");
-  return field_one(ctx, ctx->multi ? multi_first_member(ctx) : ctx, lo, hi, max_d2, border, field, nearest_xyz, capacity, n_voxels);
+  return field_one(ctx, first_member(ctx), lo, hi, max_d2, border, field, nearest_xyz, capacity, n_voxels);
 }
 
 }  // extern "C"

@@ -256,7 +256,7 @@ int fill_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, const tdt_mesh *me
   }
   int4 *v = nullptr;
   uint32_t nv = 0;
-  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
   return enclosed_voxels(front, ctx, v, nv, depth, R, false, S, out, n);
 }
 

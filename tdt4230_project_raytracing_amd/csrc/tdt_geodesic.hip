@@ -358,7 +358,7 @@ int solve(tdt_ctx *front, tdt_ctx *ctx, const Request &R, int depth_known, Devic
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
   if (!host_domain(R, depth, lo, hi, seeds_in)) return TDT_OK;
   if (solid) {
     if (nv == 0) return TDT_OK;
@@ -445,7 +445,7 @@ int tdt_octree_geodesic_field(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t
   if (!lo || !hi) return fail(ctx, TDT_ERR_INVALID_VALUE, "null box pointer");
   Request R;
   if (int rc = make_request(ctx, g, false, seeds_xyz, n_seeds, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   // everything the host can check comes first: the count-only call walks no tree and queues nothing
   int depth = 0;
   if (int rc = walk_inputs(ctx, m, &depth)) return rc;
@@ -477,7 +477,7 @@ int tdt_octree_extract_geodesic(tdt_ctx *ctx, const tdt_geodesic *g, const int32
   *n_voxels = 0;
   Request R;
   if (int rc = make_request(ctx, g, true, seeds_xyz, n_seeds, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   int depth = 0;
   if (int rc = walk_inputs(ctx, m, &depth)) return rc;
   GeodesicSource src(R);
@@ -504,7 +504,7 @@ int tdt_octree_geodesic_path(tdt_ctx *ctx, const tdt_geodesic *g, const int32_t 
   if (!goal) return fail(ctx, TDT_ERR_INVALID_VALUE, "null goal pointer");
   Request R;
   if (int rc = make_request(ctx, g, false, seeds_xyz, n_seeds, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   int depth = 0;
   if (int rc = walk_inputs(ctx, m, &depth)) return rc;
   TDT_HIP(ctx, hipSetDevice(m->device));

@@ -6,7 +6,9 @@
 // tdt_fill.hip: enclosed space; tdt_surface.hip: surface extraction; tdt_distance.hip: exact Euclidean distance;
 // tdt_bitvol.hip: the dense bit volume that tdt_fill.hip, tdt_distance.hip, tdt_xform.hip and tdt_geodesic.hip stand on, from
 // the tree's list to the result's (its templates over a unit's own kernels: bitvol_device.hpp); tdt_xform.hip: affine
-// transforms of selections; tdt_geodesic.hip: geodesic distance).
+// transforms of selections; tdt_geodesic.hip: geodesic distance; tdt_voxlist.hip: the Morton-sorted voxel list the list-based units
+// share: the capped tree list, keys, last-of-run unique, scan-gather-count).  The host helpers around a call that every editing unit
+// repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,6 +144,36 @@ int multi_dispatch_counted(tdt_compute *c, int width, int height, int depth, uin
 int multi_forget_costs(tdt_ctx *ctx);
 tdt_ctx *multi_first_member(tdt_ctx *front);
 const std::vector<tdt_ctx *> &multi_members(tdt_ctx *front);
+// the single-device context a call that only reads runs on: a multi-device front's first member, or ctx itself
+inline tdt_ctx *first_member(tdt_ctx *ctx) { return ctx->multi ? multi_first_member(ctx) : ctx; }
+// an edit on every replica: one(member, &cells) on the context itself or on each member in turn, the first failure ending it (the
+// checks fail on the first member, before anything is written, and the others hold the same bytes).  *n_cells (may be null) = the
+// first member's count; after a failure only where cells_on_failure is set and that count is non-zero (a misfit's size to grow to).
+template <class One> int edit_replicas(tdt_ctx *ctx, bool cells_on_failure, uint32_t *n_cells, One one) {
+  uint32_t nc = 0;
+  if (!ctx->multi) {
+    const int rc = one(ctx, &nc);
+    if (n_cells && (rc == TDT_OK || (cells_on_failure && nc))) *n_cells = nc;
+    return rc;
+  }
+  if (!ctx->ssbo[TDT_SLOT_CELLS] || !ctx->ssbo[TDT_SLOT_OCTREE_INTS])
+    return fail(ctx, TDT_ERR_INCOMPLETE, std::string("no buffer bound to shader-storage slot ") + (ctx->ssbo[TDT_SLOT_CELLS] ? "7" : "0"));
+  tdt_ctx *m0 = multi_first_member(ctx);
+  for (tdt_ctx *m : multi_members(ctx)) {
+    uint32_t k = 0;
+    const int rc = one(m, &k);
+    if (m == m0) nc = k;
+    if (rc != TDT_OK) { if (n_cells && cells_on_failure && nc) *n_cells = nc; return rc; }
+  }
+  if (n_cells) *n_cells = nc;
+  return TDT_OK;
+}
+// one device word into *host: the copy queued on st, then ONE host synchronisation (hipGetLastError stays with the caller)
+inline int read_word(tdt_ctx *front, hipStream_t st, const uint32_t *dev, uint32_t *host) {
+  TDT_HIP(front, hipMemcpyAsync(host, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  TDT_HIP(front, hipStreamSynchronize(st));
+  return TDT_OK;
+}
 
 // ---- tdt_edit.hip ----
 int launch_update(tdt_compute *c, int width, int height, int depth);
@@ -180,6 +212,41 @@ int tree_voxels(tdt_ctx *front, tdt_ctx *ctx, uint32_t leaf_limit, DeviceScratch
 // the fit check and in-place install of compaction: nc cells of `built` (null: one all-EMPTY root) over the bound cells
 // buffer, tail zeroed, counter = nc, versions bumped.  Too large: TDT_ERR_INVALID_VALUE, nothing written.  Takes `built`.
 int install_cells(tdt_ctx *front, tdt_ctx *ctx, tdt_buffer *built, uint32_t nc);
+// the end of an edit: the n_res voxels of res (device memory of ctx; 0: the empty tree, one cell) rebuilt, a member's error text
+// forwarded to `front`, release() freeing the caller's scratch, then the install.  *n_cells is written after the install, and with
+// cells_on_misfit before it too: the size the caller must grow the buffer to.
+template <class Release>
+int rebuild_install(tdt_ctx *front, tdt_ctx *ctx, const int4 *res, uint32_t n_res, int depth, bool cells_on_misfit, uint32_t *n_cells, Release release) {
+  tdt_buffer *built = nullptr;
+  uint32_t nc = 1;
+  if (n_res) {
+    const int rc = build_cells_from_device(ctx, (const int32_t *)res, n_res, depth, &built, &nc);
+    if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
+  }
+  release();
+  if (cells_on_misfit) *n_cells = nc;
+  if (int rc = install_cells(front, ctx, built, nc)) return rc;
+  *n_cells = nc;
+  return TDT_OK;
+}
+
+// ---- tdt_voxlist.hip: the steps the list-based units take on a Morton-sorted voxel list.  Everything is queued on `st`; errors are
+// reported on `front`; no_memory is the caller's out-of-memory text ----
+constexpr unsigned long long kVoxelListCap = TDT_REGION_BRUSH_CAP;   // voxels of the tree's list: what the 2^26 caps of the units equal
+// tree_voxels with the leaf limit of the editing units (254), held to kVoxelListCap (checked on the expanded list: 16 B per voxel
+// of the tree before it can fail)
+int tree_voxels_capped(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth);
+// k[i] = the Morton key of voxel i, n > 0
+void voxlist_keys(hipStream_t st, const int4 *v, uint32_t n, uint32_t *k);
+// behind a stable sort of n > 0 pairs by key: flag[i] = i is the LAST of its run of equal keys and not the all-ones key, over n + 1
+// lanes (flag[n] = 0); then, excl being the scanned flags, the flagged pairs into (uk, uv) in order and *count = their number
+void voxlist_last_flags(hipStream_t st, const uint32_t *keys, uint32_t n, uint32_t *flag);
+void voxlist_unique(hipStream_t st, const uint32_t *keys, const uint32_t *vals, uint32_t n, const uint32_t *excl, uint32_t *uk, uint32_t *uv,
+                    uint32_t *count);
+// the end of a pass of keep flags: keep (n + 1 words, keep[n] = 0; n > 0) scanned in place (scr: its scratch), the kept voxels of v, and
+// their keys where k / ok are given, gathered in order into ov / ok, hipGetLastError, and *total (host) = their number: ONE synchronisation
+int scan_gather_count(tdt_ctx *front, hipStream_t st, const int4 *v, const uint32_t *k, uint32_t *keep, uint32_t n, uint32_t *scr, int4 *ov,
+                      uint32_t *ok, uint32_t *total);
 
 // ---- tdt_region.hip: the V-only path of region edits (PAINT / CLEAR / intersect) driven by a per-voxel membership ----
 struct VoxelSelect {
@@ -210,7 +277,7 @@ int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells
 // the source's list on device_ids[0] (depth: what its run() is given; no tree need be bound) into host memory, by
 // tdt_octree_extract's rules
 inline int region_extract_source(tdt_ctx *ctx, VoxelSource &src, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   TDT_HIP(ctx, hipSetDevice(m->device));
   Drain drain{m->stream};
   DeviceScratch S;
@@ -230,10 +297,7 @@ int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, Devi
 // ---- tdt_bitvol.hip: the dense bit volume over a box of the grid (layout: bitvol_device.hpp), as enclosed space, exact distance,
 // transforms and geodesic distance use it.  Everything is queued on `st`; errors are reported on `front`; no_memory is the
 // caller's out-of-memory text ----
-constexpr unsigned long long kBitvolCap = 1ull << 26;   // voxels of the tree's list, of a result and of a field's box
-// tree_voxels with the leaf limit of the editing units (254), held to kBitvolCap (checked on the expanded list: 16 B per voxel
-// of the tree before it can fail)
-int bitvol_tree_voxels(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth);
+constexpr unsigned long long kBitvolCap = kVoxelListCap;   // voxels of a result and of a field's box, as of the tree's list
 // B over lo..hi (inclusive, inside the grid)
 void bitvol_layout(const int lo[3], const int hi[3], BitBox &B);
 // the bounding box of n > 0 voxels {x, y, z, m} in device memory: box[0..2] = min, box[3..5] = max.  One synchronisation.

@@ -251,8 +251,7 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(const uint32_t *keys, co
                                                        const uint32_t *mat, int4 *out) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n || excl[i + 1u] == excl[i]) return;
-  const uint32_t k = keys[i];
-  out[excl[i]] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)mat[tri[i]]);
+  out[excl[i]] = region_voxel(keys[i], (int)mat[tri[i]]);
 }
 
 namespace {
@@ -331,8 +330,7 @@ int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, Devi
   hipLaunchKernelGGL(mesh_tiles_kernel, dim3(blocks_of((size_t)nc + 1)), dim3(256), 0, st, (const MeshTri *)tris, (const uint32_t *)first, nt, nc, flag);
   TDT_HIP(front, exclusive_scan_u32(st, flag, flag, nc + 1u, scr2));
   uint32_t np = 0;
-  TDT_HIP(front, hipMemcpyAsync(&np, flag + nc, sizeof np, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the surviving pairs
+  if (int rc = read_word(front, st, flag + nc, &np)) return rc;   // the surviving pairs
   if (np == 0) return TDT_OK;
   uint2 *pairs = S.get<uint2>(np);
   uint32_t *counts = S.get<uint32_t>((size_t)np + 1), *scr3 = S.get<uint32_t>(scan_scratch_words((size_t)np + 1));
@@ -369,8 +367,7 @@ int mesh_voxels(tdt_ctx *front, tdt_ctx *ctx, const tdt_mesh *m, int depth, Devi
                      (const uint32_t *)mat, vox);
   TDT_HIP(front, hipGetLastError());
   uint32_t nu = 0;
-  TDT_HIP(front, hipMemcpyAsync(&nu, last + nk, sizeof nu, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the voxel count
+  if (int rc = read_word(front, st, last + nk, &nu)) return rc;   // the voxel count
   *out = vox; *n = nu;
   return TDT_OK;
 }

@@ -28,12 +28,6 @@
 namespace tdt {
 
 constexpr uint32_t kMorphOutside = 1u << 13;       // probe word: a neighbour outside the grid
-constexpr unsigned long long kMorphCap = TDT_REGION_BRUSH_CAP;
-
-__global__ __launch_bounds__(256) void morph_keys_kernel(const int4 *v, uint32_t n, uint32_t *k) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) { const int4 p = v[i]; k[i] = region_key(p.x, p.y, p.z); }
-}
 
 // mask[i]: absent in-grid neighbours by t, kMorphOutside; cnt[i]: dilate popc(absent), erode keep (border: outside is solid);
 // cnt[n] = 0 (an exclusive scan over n + 1 leaves the total in [n])
@@ -59,15 +53,6 @@ __global__ __launch_bounds__(256) void morph_probe_kernel(const int4 *v, const u
   mask[i] = m;
   const uint32_t absent = m & ~kMorphOutside;
   cnt[i] = erode ? ((absent == 0u && (border || !(m & kMorphOutside))) ? 1u : 0u) : (uint32_t)__popc(absent);
-}
-
-// the kept voxels and their keys, in order
-__global__ __launch_bounds__(256) void morph_gather_kernel(const int4 *v, const uint32_t *k, const uint32_t *excl, uint32_t n, int4 *ov,
-                                                           uint32_t *ok) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n || excl[i + 1u] == excl[i]) return;
-  ov[excl[i]] = v[i];
-  if (ok) ok[excl[i]] = k[i];
 }
 
 // lane i writes its candidates at excl[i].., ascending t: (key of p + d, (26 - t(d)) << 8 | material + 1)
@@ -112,19 +97,15 @@ __global__ __launch_bounds__(256) void morph_merge_list_kernel(const int4 *v, co
                                                                int4 *ov, uint32_t *ok) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= nv) return;
-  const uint32_t k = kv[i];
-  uint32_t lo = 0, hi = nu;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (uk[mid] < k) lo = mid + 1; else hi = mid; }
+  const uint32_t k = kv[i], lo = lower_bound_u32(uk, nu, k);
   ov[i + lo] = v[i]; ok[i + lo] = k;
 }
 __global__ __launch_bounds__(256) void morph_merge_new_kernel(const uint32_t *kv, uint32_t nv, const uint32_t *uk, const uint32_t *uv, uint32_t nu,
                                                               int4 *ov, uint32_t *ok) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= nu) return;
-  const uint32_t k = uk[j];
-  uint32_t lo = 0, hi = nv;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (kv[mid] <= k) lo = mid + 1; else hi = mid; }
-  ov[j + lo] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)uv[j]);
+  const uint32_t k = uk[j], lo = upper_bound_u32(kv, nv, k);
+  ov[j + lo] = region_voxel(k, (int)uv[j]);
   ok[j + lo] = k;
 }
 
@@ -141,9 +122,7 @@ __global__ __launch_bounds__(256) void morph_select_kernel(const int4 *v, const 
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i > nv) return;
   if (i == nv) { keep[nv] = 0u; return; }
-  const uint32_t k = kv[i];
-  uint32_t lo = 0, hi = ne;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (ke[mid] < k) lo = mid + 1; else hi = mid; }
+  const uint32_t k = kv[i], lo = lower_bound_u32(ke, ne, k);
   const bool found = lo < ne && ke[lo] == k;
   keep[i] = (found == (want != 0) || !morph_in_mask(shapes, n_shapes, v[i])) ? 1u : 0u;
 }
@@ -154,9 +133,7 @@ __global__ __launch_bounds__(256) void morph_mask_result_kernel(const int4 *r, c
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i > nr) return;
   if (i == nr) { keep[nr + nv] = 0u; return; }
-  const uint32_t k = kr[i];
-  uint32_t lo = 0, hi = nv;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (kv[mid] < k) lo = mid + 1; else hi = mid; }
+  const uint32_t lo = lower_bound_u32(kv, nv, kr[i]);
   const int4 p = r[i];
   const bool in = morph_in_mask(shapes, n_shapes, p);
   keep[i + lo] = in ? 1u : 0u;
@@ -166,9 +143,7 @@ __global__ __launch_bounds__(256) void morph_mask_tree_kernel(const int4 *v, con
                                                               const RegionShape *shapes, uint32_t n_shapes, int4 *slot, uint32_t *keep) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= nv) return;
-  const uint32_t k = kv[j];
-  uint32_t lo = 0, hi = nr;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (kr[mid] <= k) lo = mid + 1; else hi = mid; }
+  const uint32_t lo = upper_bound_u32(kr, nr, kv[j]);
   const int4 p = v[j];
   const bool in = morph_in_mask(shapes, n_shapes, p);
   keep[j + lo] = in ? 0u : 1u;
@@ -192,9 +167,7 @@ struct Step {
 
   int read_word(const uint32_t *dev) {
     TDT_HIP(front, hipGetLastError());
-    TDT_HIP(front, hipMemcpyAsync(host_word, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TDT_HIP(front, hipStreamSynchronize(st));
-    return TDT_OK;
+    return tdt::read_word(front, st, dev, host_word);
   }
   void probe(const List &in, bool erode, int border, uint32_t *mask, uint32_t *cnt) {
     const dim3 g(blocks_of((size_t)in.n + 1)), b(256);
@@ -210,10 +183,7 @@ struct Step {
     out.v = S.get<int4>(in.n); out.k = S.get<uint32_t>(in.n);
     if (!mask || !cnt || !scr || !out.v || !out.k) return fail(front, TDT_ERR_HIP, kNoMemory);
     probe(in, true, border, mask, cnt);
-    TDT_HIP(front, exclusive_scan_u32(st, cnt, cnt, in.n + 1u, scr));
-    hipLaunchKernelGGL(morph_gather_kernel, dim3(blocks_of(in.n)), dim3(256), 0, st, (const int4 *)in.v, (const uint32_t *)in.k, (const uint32_t *)cnt,
-                       in.n, out.v, out.k);
-    if (int rc = read_word(cnt + in.n)) return rc;
+    if (int rc = scan_gather_count(front, st, in.v, in.k, cnt, in.n, scr, out.v, out.k, host_word)) return rc;
     out.n = *host_word;
     return TDT_OK;
   }
@@ -226,7 +196,7 @@ struct Step {
     TDT_HIP(front, exclusive_scan_u32(st, cnt, cnt, in.n + 1u, scr));
     if (int rc = read_word(cnt + in.n)) return rc;
     const uint32_t nc = *host_word;                      // candidates: at most 26 * 2^26 < 2^32
-    if (nc > kMorphCap) return fail(front, TDT_ERR_INVALID_VALUE, "a dilate step emits " + std::to_string(nc) + " candidate voxels (more than 2^26)");
+    if (nc > kVoxelListCap) return fail(front, TDT_ERR_INVALID_VALUE, "a dilate step emits " + std::to_string(nc) + " candidate voxels (more than 2^26)");
     uint32_t nu = 0, *uk = nullptr, *uv = nullptr;
     if (nc) {
       uint32_t *ck = S.get<uint32_t>(nc), *cv = S.get<uint32_t>(nc), *ck_alt = S.get<uint32_t>(nc), *cv_alt = S.get<uint32_t>(nc);
@@ -246,7 +216,7 @@ struct Step {
       nu = *host_word;
     }
     const unsigned long long total = (unsigned long long)in.n + nu;
-    if (total > kMorphCap) return fail(front, TDT_ERR_INVALID_VALUE, "a dilate step grows the list to " + std::to_string(total) + " voxels (more than 2^26)");
+    if (total > kVoxelListCap) return fail(front, TDT_ERR_INVALID_VALUE, "a dilate step grows the list to " + std::to_string(total) + " voxels (more than 2^26)");
     out.n = (uint32_t)total;
     out.v = S.get<int4>(out.n); out.k = S.get<uint32_t>(out.n);
     if (!out.v || !out.k) return fail(front, TDT_ERR_HIP, kNoMemory);
@@ -289,8 +259,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
   int4 *v0 = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v0, &nv, &depth)) return rc;
-  if (nv > kMorphCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = tree_voxels_capped(front, ctx, S, &v0, &nv, &depth)) return rc;
   const int4 *res = nullptr;
   uint32_t n_res = 0;
   if (nv) {
@@ -298,7 +267,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
     RegionShape *d_shapes = nullptr;
     if (!k0) return fail(front, TDT_ERR_HIP, kNoMemory);
     if (int rc = upload_shapes(front, st, S, R.shapes.data(), R.shapes.size(), kNoMemory, &d_shapes)) return rc;
-    hipLaunchKernelGGL(morph_keys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v0, nv, k0);
+    voxlist_keys(st, v0, nv, k0);
     cur.reset(new List);
     cur->v = v0; cur->k = k0; cur->n = nv;               // (owned by S)
     Step T{front, ctx, st, depth, M.connectivity, &word};
@@ -325,10 +294,7 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
       if (!keep || !scr || !out) return fail(front, TDT_ERR_HIP, kNoMemory);
       hipLaunchKernelGGL(morph_select_kernel, dim3(blocks_of((size_t)nv + 1)), dim3(256), 0, st, (const int4 *)v0, (const uint32_t *)k0, nv,
                          (const uint32_t *)cur->k, cur->n, M.op == TDT_MORPH_OPEN ? 1 : 0, (const RegionShape *)d_shapes, n_shapes, keep);
-      TDT_HIP(front, exclusive_scan_u32(st, keep, keep, nv + 1u, scr));
-      hipLaunchKernelGGL(morph_gather_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v0, (const uint32_t *)nullptr,
-                         (const uint32_t *)keep, nv, out, (uint32_t *)nullptr);
-      if (int rc = T.read_word(keep + nv)) return rc;
+      if (int rc = scan_gather_count(front, st, v0, nullptr, keep, nv, scr, out, nullptr, &word)) return rc;
       res = out; n_res = word;
     } else if (n_shapes) {
       const uint32_t nr = cur->n;
@@ -340,28 +306,17 @@ int morph_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells,
                          (const uint32_t *)k0, nv, (const RegionShape *)d_shapes, n_shapes, slot, keep);
       hipLaunchKernelGGL(morph_mask_tree_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v0, (const uint32_t *)k0, nv,
                          (const uint32_t *)cur->k, nr, (const RegionShape *)d_shapes, n_shapes, slot, keep);
-      TDT_HIP(front, exclusive_scan_u32(st, keep, keep, (uint32_t)n_slots + 1u, scr));
-      hipLaunchKernelGGL(morph_gather_kernel, dim3(blocks_of(n_slots)), dim3(256), 0, st, (const int4 *)slot, (const uint32_t *)nullptr,
-                         (const uint32_t *)keep, (uint32_t)n_slots, out, (uint32_t *)nullptr);
-      if (int rc = T.read_word(keep + n_slots)) return rc;
+      if (int rc = scan_gather_count(front, st, slot, nullptr, keep, (uint32_t)n_slots, scr, out, nullptr, &word)) return rc;
       res = out; n_res = word;
     } else {
       TDT_HIP(front, hipGetLastError());
       TDT_HIP(front, hipStreamSynchronize(st));           // a dilate step's merge may still be running
     }
-    if (n_res > kMorphCap) return fail(front, TDT_ERR_INVALID_VALUE, "the result holds " + std::to_string(n_res) + " voxels (more than 2^26)");
+    if (n_res > kVoxelListCap) return fail(front, TDT_ERR_INVALID_VALUE, "the result holds " + std::to_string(n_res) + " voxels (more than 2^26)");
   }
   if (extract) return list_to_host(front, st, res, n_res, sizeof(int4), "voxels", host_out, capacity, n_out);
   // ---- rebuild and install ----
-  tdt_buffer *built = nullptr;
-  uint32_t nc = 1;
-  if (n_res) {
-    const int rc = build_cells_from_device(ctx, (const int32_t *)res, n_res, depth, &built, &nc);
-    if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
-  }
-  prev.reset(); cur.reset(); S.release();
-  *n_cells = nc;                                          // also on a misfit: the size the caller must grow the buffer to
-  return install_cells(front, ctx, built, nc);
+  return rebuild_install(front, ctx, res, n_res, depth, true, n_cells, [&] { prev.reset(); cur.reset(); S.release(); });
 }
 
 }  // namespace
@@ -374,25 +329,8 @@ int tdt_octree_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   Request R;
   if (int rc = make_request(ctx, m, regions, n_regions, R)) return rc;
-  uint32_t nc = 0;
-  if (!ctx->multi) {
-    const int rc = morph_one(ctx, ctx, R, &nc, false, nullptr, 0, nullptr);
-    if (n_cells && (rc == TDT_OK || nc)) *n_cells = nc;
-    return rc;
-  }
-  // every replica, as region edits do: the checks fail on the first member, before anything is written, and the others hold
-  // the same bytes
-  if (!ctx->ssbo[TDT_SLOT_CELLS] || !ctx->ssbo[TDT_SLOT_OCTREE_INTS])
-    return fail(ctx, TDT_ERR_INCOMPLETE, std::string("no buffer bound to shader-storage slot ") + (ctx->ssbo[TDT_SLOT_CELLS] ? "7" : "0"));
-  tdt_ctx *m0 = multi_first_member(ctx);
-  for (tdt_ctx *mem : multi_members(ctx)) {
-    uint32_t k = 0;
-    const int rc = morph_one(ctx, mem, R, &k, false, nullptr, 0, nullptr);
-    if (mem == m0) nc = k;
-    if (rc != TDT_OK) { if (n_cells && nc) *n_cells = nc; return rc; }
-  }
-  if (n_cells) *n_cells = nc;
-  return TDT_OK;
+  // every replica, as region edits do, a misfit reporting the size to grow to
+  return edit_replicas(ctx, true, n_cells, [&](tdt_ctx *mem, uint32_t *nc) { return morph_one(ctx, mem, R, nc, false, nullptr, 0, nullptr); });
 }
 
 int tdt_octree_extract_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
@@ -403,7 +341,7 @@ int tdt_octree_extract_morph(tdt_ctx *ctx, const tdt_morph *m, const tdt_region 
   *n_voxels = 0;
   Request R;
   if (int rc = make_request(ctx, m, regions, n_regions, R)) return rc;
-  return morph_one(ctx, ctx->multi ? multi_first_member(ctx) : ctx, R, nullptr, true, voxels_xyzm, capacity, n_voxels);
+  return morph_one(ctx, first_member(ctx), R, nullptr, true, voxels_xyzm, capacity, n_voxels);
 }
 
 }  // extern "C"

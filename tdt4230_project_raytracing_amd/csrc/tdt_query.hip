@@ -130,9 +130,6 @@ __global__ __launch_bounds__(kQueryBlock) void raycast_kernel(const TraceParams 
 
 namespace {
 
-// a multi-device context answers from its first member (whose slots hold the replicas of the bound buffers)
-tdt_ctx *query_member(tdt_ctx *ctx) { return ctx->multi ? multi_first_member(ctx) : ctx; }
-
 // the kernel arguments a query needs: slots 0, 6, 7 of the member context; errors are reported on `front`
 int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P) {
   static const int required[] = {TDT_SLOT_CELLS, TDT_SLOT_OCTREE_FLOATS, TDT_SLOT_OCTREE_INTS};
@@ -188,7 +185,7 @@ int tdt_raycast(tdt_ctx *ctx, const float *rays, size_t n, tdt_ray_hit *out) {
   if (!ctx) return TDT_ERR_INVALID_VALUE;
   if (n == 0) return TDT_OK;
   if (!rays || !out) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "null rays / out pointer");
-  tdt_ctx *m = tdt::query_member(ctx);
+  tdt_ctx *m = tdt::first_member(ctx);   // (its slots hold the replicas of the bound buffers)
   TraceParams P;
   if (int rc = tdt::query_params(ctx, m, P)) return rc;
   if (n > (~size_t(0)) / 128) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "too many rays");
@@ -210,7 +207,7 @@ int tdt_raycast_device(tdt_ctx *ctx, const void *rays_dev, size_t n, void *hits_
   if (!rays_dev || !hits_dev) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "null rays / hits pointer");
   if (((uintptr_t)rays_dev & 3u) || ((uintptr_t)hits_dev & 15u))
     return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "rays must be 4-byte and hits 16-byte aligned");
-  tdt_ctx *m = tdt::query_member(ctx);
+  tdt_ctx *m = tdt::first_member(ctx);   // (its slots hold the replicas of the bound buffers)
   TraceParams P;
   if (int rc = tdt::query_params(ctx, m, P)) return rc;
   TDT_HIP(ctx, hipSetDevice(m->device));

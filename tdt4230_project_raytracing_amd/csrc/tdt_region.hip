@@ -25,9 +25,7 @@
 
 namespace tdt {
 
-constexpr uint32_t kRegionDropped = 0xFFFFFFFFu;   // key of a voxel outside the grid: sorts behind everything
 constexpr int kOpIntersect = 4;                    // extract_region: keep V inside the shapes
-constexpr unsigned long long kBrushCap = 1ull << 26;
 
 // one lane per candidate voxel of every shape's clipped box; hits -> (key, m) behind one atomic per wave
 __global__ __launch_bounds__(256) void region_brush_kernel(const RegionShape *shapes, uint32_t n_shapes, uint32_t n_lanes, uint32_t m,
@@ -62,27 +60,8 @@ __global__ __launch_bounds__(256) void region_list_keys_kernel(const int4 *vox, 
   const int4 v = vox[i];
   const int N = 1 << depth;
   const bool ok = v.x >= 0 && v.y >= 0 && v.z >= 0 && v.x < N && v.y < N && v.z < N;
-  keys[i] = ok ? region_key(v.x, v.y, v.z) : kRegionDropped;
+  keys[i] = ok ? region_key(v.x, v.y, v.z) : kDroppedKey;
   vals[i] = clear ? 0u : (uint32_t)v.w;
-}
-
-// of every run of equal sorted keys keep the LAST (the stable sort kept list order); flag[n] = 0
-__global__ __launch_bounds__(256) void region_last_flags_kernel(const uint32_t *keys, uint32_t n, uint32_t *flag) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i > n) return;
-  flag[i] = (i < n && keys[i] != kRegionDropped && (i + 1u == n || keys[i + 1u] != keys[i])) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void region_unique_kernel(const uint32_t *keys, const uint32_t *vals, uint32_t n, const uint32_t *excl,
-                                                           uint32_t *uk, uint32_t *uv, uint32_t *count) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) *count = excl[n];
-  if (i >= n || excl[i + 1u] == excl[i]) return;
-  uk[excl[i]] = keys[i]; uv[excl[i]] = vals[i];
-}
-
-__global__ __launch_bounds__(256) void region_vkeys_kernel(const int4 *v, uint32_t n, uint32_t *kv) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) { const int4 p = v[i]; kv[i] = region_key(p.x, p.y, p.z); }
 }
 
 struct MergeArgs {
@@ -102,9 +81,7 @@ __global__ __launch_bounds__(256) void region_merge_v_kernel(const MergeArgs A) 
   bool in = false;
   uint32_t pos = i, bm = A.m;
   if (A.kb) {
-    const uint32_t k = A.kv[i], nb = *A.nb;
-    uint32_t lo = 0, hi = nb;
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (A.kb[mid] < k) lo = mid + 1; else hi = mid; }
+    const uint32_t k = A.kv[i], nb = *A.nb, lo = lower_bound_u32(A.kb, nb, k);
     in = lo < nb && A.kb[lo] == k;
     if (in) bm = A.mb[lo];
     pos = i + lo;
@@ -129,19 +106,12 @@ __global__ __launch_bounds__(256) void region_merge_v_kernel(const MergeArgs A) 
 __global__ __launch_bounds__(256) void region_merge_b_kernel(const MergeArgs A) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= *A.nb) return;
-  const uint32_t k = A.kb[j];
-  uint32_t lo = 0, hi = A.nv;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (A.kv[mid] <= k) lo = mid + 1; else hi = mid; }
+  const uint32_t k = A.kb[j], lo = upper_bound_u32(A.kv, A.nv, k);
   const bool in_v = lo > 0 && A.kv[lo - 1u] == k;
   const bool keep = A.op == TDT_REGION_SET || !in_v;
   const uint32_t pos = lo + j;
   A.keep[pos] = keep ? 1u : 0u;
-  if (keep) A.slot[pos] = make_int4((int)region_compact3(k >> 2), (int)region_compact3(k >> 1), (int)region_compact3(k), (int)A.mb[j]);
-}
-
-__global__ __launch_bounds__(256) void region_gather_kernel(const int4 *slot, const uint32_t *excl, uint32_t n, int4 *out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n && excl[i + 1u] != excl[i]) out[excl[i]] = slot[i];
+  if (keep) A.slot[pos] = region_voxel(k, (int)A.mb[j]);
 }
 
 namespace {
@@ -195,7 +165,7 @@ void clip_shapes(const Request &R, int depth, std::vector<RegionShape> &out, uns
       r.lo[a] = (int32_t)lo; r.ext[a] = (uint32_t)e; n *= e;
     }
     if (n == 0) continue;                              // nothing of it in the grid
-    r.lane0 = (uint32_t)(*lanes < kBrushCap ? *lanes : 0);
+    r.lane0 = (uint32_t)(*lanes < kVoxelListCap ? *lanes : 0);
     *lanes += n;
     out.push_back(r);
   }
@@ -209,7 +179,7 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
   unsigned long long lanes = 0;
   if (!R.list) {
     clip_shapes(R, depth, shapes, &lanes);
-    if ((R.op == TDT_REGION_SET || R.op == TDT_REGION_FILL) && lanes > kBrushCap)
+    if ((R.op == TDT_REGION_SET || R.op == TDT_REGION_FILL) && lanes > kVoxelListCap)
       return fail(front, TDT_ERR_INVALID_VALUE, "the shapes enumerate " + std::to_string(lanes) + " candidate voxels (more than 2^26)");
   }
   hipStream_t st = ctx->stream;
@@ -263,12 +233,10 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
     if (!hist || !hscr || !flag || !fscr) return fail(front, TDT_ERR_HIP, kNoMemory);
     uint32_t *k = bk, *vv = bv;
     TDT_HIP(front, sort_pairs_u32(st, k, vv, bk_alt, bv_alt, b_raw, hist, hscr));
-    uint32_t *uk = k == bk ? bk_alt : bk, *uv = vv == bv ? bv_alt : bv;       // the pair the sort left free
-    hipLaunchKernelGGL(region_last_flags_kernel, dim3(blocks_of((size_t)b_raw + 1)), dim3(256), 0, st, (const uint32_t *)k, b_raw, flag);
+    kb = k == bk ? bk_alt : bk; mb = vv == bv ? bv_alt : bv; nb = b_count + 1;   // the pair the sort left free
+    voxlist_last_flags(st, k, b_raw, flag);
     TDT_HIP(front, exclusive_scan_u32(st, flag, flag, b_raw + 1u, fscr));
-    hipLaunchKernelGGL(region_unique_kernel, dim3(blocks_of(b_raw)), dim3(256), 0, st, (const uint32_t *)k, (const uint32_t *)vv, b_raw,
-                       (const uint32_t *)flag, uk, uv, b_count + 1);
-    kb = uk; mb = uv; nb = b_count + 1;
+    voxlist_unique(st, k, vv, b_raw, flag, kb, mb, nb);
   }
   // ---- merge ----
   const unsigned long long n_slots = (unsigned long long)nv + (kb ? b_raw : 0u);
@@ -288,53 +256,22 @@ int region_one(tdt_ctx *front, tdt_ctx *ctx, const Request &R, uint32_t *n_cells
     A.label = label; A.selected = selected;
     A.slot = slot; A.keep = keep;
     if (nv) {
-      if (kb) hipLaunchKernelGGL(region_vkeys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, kv);
+      if (kb) voxlist_keys(st, v, nv, kv);
       hipLaunchKernelGGL(region_merge_v_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, A);
     }
     if (kb && (R.op == TDT_REGION_SET || R.op == TDT_REGION_FILL))
       hipLaunchKernelGGL(region_merge_b_kernel, dim3(blocks_of(b_raw)), dim3(256), 0, st, A);
-    TDT_HIP(front, exclusive_scan_u32(st, keep, keep, (uint32_t)n_slots + 1u, kscr));
-    hipLaunchKernelGGL(region_gather_kernel, dim3(blocks_of(n_slots)), dim3(256), 0, st, (const int4 *)slot, (const uint32_t *)keep,
-                       (uint32_t)n_slots, res);
-    TDT_HIP(front, hipGetLastError());
-    TDT_HIP(front, hipMemcpyAsync(&n_res, keep + n_slots, sizeof n_res, hipMemcpyDeviceToHost, st));
-    TDT_HIP(front, hipStreamSynchronize(st));             // the merged count
+    if (int rc = scan_gather_count(front, st, slot, nullptr, keep, (uint32_t)n_slots, kscr, res, nullptr, &n_res)) return rc;   // the merged count
   }
   if (R.op == kOpIntersect) return list_to_host(front, st, res, n_res, sizeof(int4), "voxels", host_out, capacity, n_out);
   // ---- rebuild and install ----
-  tdt_buffer *built = nullptr;
-  uint32_t nc = 1;
-  if (n_res) {
-    const int rc = build_cells_from_device(ctx, (const int32_t *)res, n_res, depth, &built, &nc);
-    if (rc != TDT_OK) return ctx == front ? rc : fail(front, rc, tdt_last_error(ctx));
-  }
-  S.release();
-  *n_cells = nc;                                          // also on a misfit: the size the caller must grow the buffer to
-  return install_cells(front, ctx, built, nc);
+  return rebuild_install(front, ctx, res, n_res, depth, true, n_cells, [&] { S.release(); });
 }
 
-tdt_ctx *first_member(tdt_ctx *ctx) { return ctx->multi ? multi_first_member(ctx) : ctx; }
-
-// an edit of every replica; the checks fail on the first member, before anything is written, and the others hold the same bytes
+// an edit of every replica, a misfit reporting the size to grow to
 int region_edit(tdt_ctx *ctx, const Request &R, uint32_t *n_cells) {
   if (int rc = check_request(ctx, R)) return rc;
-  uint32_t nc = 0;
-  if (!ctx->multi) {
-    const int rc = region_one(ctx, ctx, R, &nc, nullptr, 0, nullptr);
-    if (n_cells && (rc == TDT_OK || nc)) *n_cells = nc;
-    return rc;
-  }
-  if (!ctx->ssbo[TDT_SLOT_CELLS] || !ctx->ssbo[TDT_SLOT_OCTREE_INTS])
-    return fail(ctx, TDT_ERR_INCOMPLETE, std::string("no buffer bound to shader-storage slot ") + (ctx->ssbo[TDT_SLOT_CELLS] ? "7" : "0"));
-  tdt_ctx *m0 = multi_first_member(ctx);
-  for (tdt_ctx *m : multi_members(ctx)) {
-    uint32_t k = 0;
-    const int rc = region_one(ctx, m, R, &k, nullptr, 0, nullptr);
-    if (m == m0) nc = k;
-    if (rc != TDT_OK) { if (n_cells && nc) *n_cells = nc; return rc; }
-  }
-  if (n_cells) *n_cells = nc;
-  return TDT_OK;
+  return edit_replicas(ctx, true, n_cells, [&](tdt_ctx *m, uint32_t *nc) { return region_one(ctx, m, R, nc, nullptr, 0, nullptr); });
 }
 
 }  // namespace

@@ -40,8 +40,6 @@
 
 namespace tdt {
 
-constexpr unsigned long long kSurfaceCap = TDT_REGION_BRUSH_CAP;
-
 struct SurfaceSegs { uint32_t at[7]; };                 // segment f = [at[f], at[f + 1]) of an array of at[6] items
 
 __device__ __forceinline__ int surface_seg_of(const SurfaceSegs &s, uint32_t j) {
@@ -55,11 +53,6 @@ __device__ __forceinline__ uint32_t surface_seg_start(const SurfaceSegs &s, uint
 #pragma unroll
   for (int t = 1; t < 6; t++) lo = j >= s.at[t] ? s.at[t] : lo;
   return lo;
-}
-
-__global__ __launch_bounds__(256) void surface_keys_kernel(const int4 *v, uint32_t n, uint32_t *k) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) { const int4 p = v[i]; k[i] = region_key(p.x, p.y, p.z); }
 }
 
 // mask[i]: bit f = face f of voxel i is exposed and the voxel is inside the union of the shapes; cnt[f * (n + 1) + i] = that bit,
@@ -222,8 +215,7 @@ int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch 
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = tree_voxels(front, ctx, 254u, S, &v, &nv, &depth)) return rc;
-  if (nv > kSurfaceCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(nv) + " voxels (more than 2^26)");
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
   if (nv == 0) return TDT_OK;
   // ---- probe: the faces, numbered direction by direction ----
   const size_t stride = (size_t)nv + 1, n_cnt = 6 * stride;                // < 2^32: nv <= 2^26
@@ -233,7 +225,7 @@ int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch 
   if (!keys || !mask || !cnt || !scr || !d_bounds) return fail(front, TDT_ERR_HIP, kNoMemory);
   const uint32_t n_shapes = (uint32_t)R.shapes.size();
   if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
-  hipLaunchKernelGGL(surface_keys_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, nv, keys);
+  voxlist_keys(st, v, nv, keys);
   hipLaunchKernelGGL(surface_probe_kernel, dim3(blocks_of(stride)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)keys, nv, depth,
                      (const RegionShape *)d_shapes, n_shapes, mask, cnt);
   TDT_HIP(front, exclusive_scan_u32(st, cnt, cnt, (uint32_t)n_cnt, scr));
@@ -244,7 +236,7 @@ int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch 
   if (int rc = P.read_bounds(cnt, idx, faces)) return rc;
   const uint32_t nf = faces.at[6];
   for (int f = 0; f < 6; f++)
-    if (faces.at[f + 1] - faces.at[f] > kSurfaceCap)
+    if (faces.at[f + 1] - faces.at[f] > kVoxelListCap)
       return fail(front, TDT_ERR_INVALID_VALUE, "direction " + std::to_string(f) + " has " + std::to_string(faces.at[f + 1] - faces.at[f]) +
                                                     " exposed faces (more than 2^26)");
   if (nf == 0) return TDT_OK;
@@ -303,7 +295,7 @@ int tdt_octree_extract_surface(tdt_ctx *ctx, const tdt_surface *opt, const tdt_r
   *n_quads = 0;
   Request R;
   if (int rc = make_request(ctx, opt, regions, n_regions, R)) return rc;
-  tdt_ctx *m = ctx->multi ? multi_first_member(ctx) : ctx;
+  tdt_ctx *m = first_member(ctx);
   TDT_HIP(ctx, hipSetDevice(m->device));
   DeviceScratch S;
   Drain drain{m->stream};                                // before S is freed

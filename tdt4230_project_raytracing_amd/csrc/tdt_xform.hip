@@ -173,7 +173,7 @@ int xform_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch &S,
   int4 *v = nullptr;
   uint32_t nv = 0;
   int depth = 0;
-  if (int rc = bitvol_tree_voxels(front, ctx, S, &v, &nv, &depth)) return rc;
+  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
   if (nv == 0) return TDT_OK;
   const long long N = 1ll << depth;
   // ---- the source box: bbox(V) & the shapes' bounding box (each shape clipped to the grid, the ones that leave it dropped;
@@ -250,8 +250,7 @@ int xform_list(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch &S,
   TDT_HIP(front, exclusive_scan_u32(st, flag, flag, (uint32_t)nb1, bscr));
   TDT_HIP(front, hipGetLastError());
   uint32_t n_active = 0;
-  TDT_HIP(front, hipMemcpyAsync(&n_active, flag + P.n_bricks, sizeof n_active, hipMemcpyDeviceToHost, st));
-  TDT_HIP(front, hipStreamSynchronize(st));                // the brick count
+  if (int rc = read_word(front, st, flag + P.n_bricks, &n_active)) return rc;   // the brick count
   front->xform_bricks[1] = n_active;
   if (n_active == 0) return TDT_OK;
   uint32_t *bk = S.get<uint32_t>(n_active), *bv = S.get<uint32_t>(n_active), *bk1 = S.get<uint32_t>(n_active), *bv1 = S.get<uint32_t>(n_active);

@@ -417,6 +417,26 @@ def used_or(scene):
     return int(scene.counts["cells"])
 
 
+@pytest.mark.parametrize("devices", [None, [0, 0]], ids=["single", "two-members"])
+def test_a_misfit_leaves_n_cells_and_the_bytes_alone(devices):
+    """Eight PARENT nodes that share one cell of eight different LEAFs: two cells whose canonical tree needs nine.  Compaction
+    writes *n_cells only once the tree is installed, on a single-device context and on every replica alike."""
+    cells = np.zeros((2, 8, 2), np.uint32)
+    cells[0, :] = [1, 1]
+    cells[1, :, 0], cells[1, :, 1] = np.arange(8), 2
+    ctx = rt.Context(0, devices=devices)
+    try:
+        vbos = bind_tree(ctx, cells.reshape(-1), 2, counter=2)
+        assert ctx.octree_census()["voxels"] == 64
+        nc = rt.ctypes.c_uint32(777)
+        assert rt.lib().tdt_octree_compact(ctx.h, rt.ctypes.byref(nc)) == rt.ERR_INVALID_VALUE
+        assert "(9 cells) does not fit in the cells buffer (2 cells)" in rt.lib().tdt_last_error(ctx.h).decode()
+        assert nc.value == 777
+        assert np.array_equal(vbos[0].read(np.uint32), cells.reshape(-1)) and int(vbos["counter"].read(np.uint32)[0]) == 2
+    finally:
+        ctx.close()
+
+
 def test_removing_every_voxel_compacts_to_one_cell():
     scene = host.Scene.config(1)
     used, depth = scene.counts["cells"], scene.max_depth

@@ -420,6 +420,31 @@ def test_errors_write_nothing():
         ctx.close()
 
 
+def test_two_member_failures_report_like_a_single_device():
+    """On a two-member context: the slot text before any member is touched, and a misfit on the first member reporting the cell
+    count it needs, nothing written on either replica."""
+    ctx = rt.Context(0, devices=[0, 0])
+    try:
+        ball = rt.sphere((8, 8, 8), 3)
+        with pytest.raises(rt.TdtError, match="no buffer bound to shader-storage slot 0") as e:
+            ctx.octree_edit_region(rt.REGION_SET, ball, 3)
+        assert e.value.code == rt.ERR_INCOMPLETE and e.value.n_cells == 0
+        root, counter = bind_cells(ctx, np.zeros(16, np.uint32), 1)
+        with pytest.raises(rt.TdtError, match="no buffer bound to shader-storage slot 7") as e:
+            ctx.octree_edit_region(rt.REGION_SET, ball, 3)
+        assert e.value.code == rt.ERR_INCOMPLETE and e.value.n_cells == 0
+        ints = rt.VertexBufferObject(ctx, np.array([4, 64, 1 << 10], np.int32))
+        ctx.bind_buffer_base(rt.SHADER_STORAGE_BUFFER, 7, ints)
+        need = len(built_cells(ctx, expected_region(np.zeros((0, 4), np.int32), rt.REGION_SET, [ball], 3, 4), 4)) // 16
+        assert need > 1
+        with pytest.raises(rt.TdtError, match="does not fit") as e:
+            ctx.octree_edit_region(rt.REGION_SET, ball, 3)
+        assert e.value.code == rt.ERR_INVALID_VALUE and e.value.n_cells == need
+        assert not root.read(np.uint32).any() and int(counter.read(np.uint32)[0]) == 12345
+    finally:
+        ctx.close()
+
+
 # ---- 6. ordering -----------------------------------------------------------------------------------------------------
 def test_edit_dispatched_just_before_is_included(oracle):
     scene = host.Scene.config(2)

@@ -51,7 +51,10 @@ def test_morph_kernels_have_no_scratch_and_no_spills():
     rows = kernel_resources.collect("tdt_morph.hip")
     names = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in rows}
     assert {"morph_probe_kernel", "morph_emit_kernel", "morph_unique_kernel", "morph_merge_list_kernel", "morph_merge_new_kernel",
-            "morph_gather_kernel", "morph_select_kernel", "morph_mask_result_kernel", "morph_mask_tree_kernel"} <= names
+            "morph_select_kernel", "morph_mask_result_kernel", "morph_mask_tree_kernel"} <= names
+    # the keys and gather kernels are the list layer's (resources: test_bitvol_api.py)
+    shared = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in kernel_resources.collect("tdt_voxlist.hip")}
+    assert {"voxlist_keys_kernel", "voxlist_gather_kernel"} <= shared and not {"morph_keys_kernel", "morph_gather_kernel"} & names
     assert sum("morph_probe_kernel<6>" in r["name"] for r in rows) == 1
     assert sum("morph_probe_kernel<26>" in r["name"] for r in rows) == 1
     for r in rows:

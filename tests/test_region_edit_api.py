@@ -101,7 +101,11 @@ def test_region_kernels_have_no_scratch_and_no_spills():
     import kernel_resources
     rows = [r for r in kernel_resources.collect("tdt_region.hip") if "region_" in r["name"]]
     names = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in rows}
-    assert {"region_brush_kernel", "region_merge_v_kernel", "region_merge_b_kernel", "region_gather_kernel"} <= names
+    assert {"region_brush_kernel", "region_merge_v_kernel", "region_merge_b_kernel"} <= names
+    # the keys, last-of-run unique and gather kernels are the list layer's (resources: test_bitvol_api.py)
+    shared = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in kernel_resources.collect("tdt_voxlist.hip")}
+    assert {"voxlist_keys_kernel", "voxlist_last_flags_kernel", "voxlist_unique_kernel", "voxlist_gather_kernel"} <= shared
+    assert not {"region_vkeys_kernel", "region_last_flags_kernel", "region_unique_kernel", "region_gather_kernel"} & names
     for r in rows:
         assert r["ScratchSize [bytes/lane]"] == 0, r["name"]
         assert r["SGPRs Spill"] == 0 and r["VGPRs Spill"] == 0, r["name"]

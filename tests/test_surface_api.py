@@ -58,8 +58,11 @@ def test_surface_kernels_have_no_scratch_and_no_spills():
     import kernel_resources
     rows = kernel_resources.collect("tdt_surface.hip")
     names = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in rows}
-    assert {"surface_keys_kernel", "surface_probe_kernel", "surface_bounds_kernel", "surface_emit_kernel", "surface_head_flags_kernel",
+    assert {"surface_probe_kernel", "surface_bounds_kernel", "surface_emit_kernel", "surface_head_flags_kernel",
             "surface_starts_kernel", "surface_runs_kernel", "surface_quads_kernel"} <= names
+    # the keys kernel is the list layer's (resources: test_bitvol_api.py)
+    shared = {re.match(r"tdt::(\w+)", r["name"]).group(1) for r in kernel_resources.collect("tdt_voxlist.hip")}
+    assert "voxlist_keys_kernel" in shared and "surface_keys_kernel" not in names
     for r in rows:
         assert r["ScratchSize [bytes/lane]"] == 0, r["name"]
         assert r["SGPRs Spill"] == 0 and r["VGPRs Spill"] == 0, r["name"]

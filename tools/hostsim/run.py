@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A bit-volume unit (csrc/tdt_fill.hip, tdt_distance.hip, tdt_xform.hip or tdt_geodesic.hip) and the layer under it
-(csrc/tdt_bitvol.hip, bitvol_device.hpp) — kernels and host code, unchanged — compiled for the CPU and run against a brute-force
+"""A bit-volume unit (csrc/tdt_fill.hip, tdt_distance.hip, tdt_xform.hip or tdt_geodesic.hip) and the layers under it
+(csrc/tdt_bitvol.hip, bitvol_device.hpp; the capped tree list of csrc/tdt_voxlist.hip) — kernels and host code, unchanged — compiled for the CPU and run against a brute-force
 model, under AddressSanitizer and UBSan.  No GPU, no HIP: hip/hip_runtime.h here stands in for the constructs the units use (a
 block is 256 real threads behind a pthread barrier, blocks run one after another, hipMalloc is malloc), device_scan.hpp for the
 scan, siblings.hpp for the pieces of the sibling units a unit calls (the slot check, the tree's voxel list, the sort, the edit
@@ -42,9 +42,10 @@ def main():
     unit = sys.argv[1]
     with tempfile.TemporaryDirectory() as tmp:
         # the units are compiled from copies next to the stand-in headers, so that their quoted includes find those first
-        srcs = [os.path.join(tmp, unit + "_unit.cpp"), os.path.join(tmp, "bitvol_unit.cpp"), os.path.join(tmp, unit + ".cpp")]
-        shutil.copy(os.path.join(CSRC, "tdt_" + unit + ".hip"), srcs[0])
-        shutil.copy(os.path.join(CSRC, "tdt_bitvol.hip"), srcs[1])
+        srcs = [os.path.join(tmp, unit + "_unit.cpp"), os.path.join(tmp, "bitvol_unit.cpp"), os.path.join(tmp, "voxlist_unit.cpp"),
+                os.path.join(tmp, unit + ".cpp")]
+        for src, name in zip(srcs, ("tdt_" + unit + ".hip", "tdt_bitvol.hip", "tdt_voxlist.hip")):
+            shutil.copy(os.path.join(CSRC, name), src)
         for f in ("region_device.hpp", "bitvol_device.hpp"):
             shutil.copy(os.path.join(CSRC, f), tmp)
         for f in ("device_scan.hpp", "siblings.hpp", unit + ".cpp"):
