@@ -111,13 +111,15 @@ class VertexArrayObject {
 // renderer/texture.rs:7-92
 class Texture {
  public:
-  static Texture new_2d(Context &ctx, int width, int height) {   // new_2d(TEXTURE0, 0, RGBA32F, RGBA, w, h) texture.rs:47-75
+  // new_2d(TEXTURE0, 0, RGBA32F, RGBA, w, h) texture.rs:47-75; bind = false (NEW): an image that is not the render target (a guide)
+  static Texture new_2d(Context &ctx, int width, int height, bool bind = true) {
     Texture t;
     t.ctx_ = &ctx; t.w_ = width; t.h_ = height;
     ctx.check(tdt_image_create_rgba32f(ctx.raw(), width, height, &t.img_));
-    t.bind();
+    if (bind) t.bind();
     return t;
   }
+  tdt_image *id() const { return img_; }
   void bind() const { ctx_->check(tdt_bind_image(ctx_->raw(), 0, img_)); }   // BindImageTexture(unit 0)
   int width() const { return w_; }
   int height() const { return h_; }
@@ -129,6 +131,15 @@ class Texture {
   }
   // NEW: the frame as the quad pass presents it (quad.frag:10), RGBA8, converted on the GPU
   void read_rgba8(bool top_down, uint8_t *dst) const { ctx_->check(tdt_image_read_rgba8(img_, top_down ? 1 : 0, dst)); }
+  // NEW: the edge-stopping a-trous filter, in place (tdt_image_denoise): `passes` 0..8 passes of step 1, 2, 4, .. that average only
+  // pixels whose guide texels (ComputeShader::dispatch_guide, an image of this size) carry the same surface key.  Asynchronous.
+  void denoise(const Texture &guide, int passes) const { ctx_->check(tdt_image_denoise(img_, guide.img_, passes, 0)); }
+  // NEW: a guide image's texels {kind, material, plane, t}
+  std::vector<tdt_guide_texel> read_guide() const {
+    std::vector<tdt_guide_texel> g((size_t)w_ * h_);
+    ctx_->check(tdt_image_read(img_, reinterpret_cast<float *>(g.data())));
+    return g;
+  }
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;
@@ -183,6 +194,11 @@ class ComputeShader {
     if (rays) rays->assign(xy.size() * 6, 0.0f);
     ctx_->check(tdt_pick_pixels(program.id(), xy.empty() ? nullptr : xy[0].data(), xy.size(), sample, rays ? rays->data() : nullptr, out.data()));
     return out;
+  }
+  // NEW: the first hit of every pixel on the device (tdt_dispatch_guide): texel (x, y) of `guide` receives the surface key and the
+  // depth of the primary ray of pixel (x, y), sample `sample`, of this program's camera; flags: TDT_GUIDE_ALL_MATERIALS.  Asynchronous.
+  void dispatch_guide(const Texture &guide, int sample = 0, uint32_t flags = 0) const {
+    ctx_->check(tdt_dispatch_guide(program.id(), guide.id(), sample, flags));
   }
  private:
   Context *ctx_ = nullptr;

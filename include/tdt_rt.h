@@ -282,6 +282,63 @@ int tdt_raycast_device(tdt_ctx *ctx, const void *rays_dev, size_t n, void *hits_
  * A TDT_PROGRAM_OCTREE_UPDATE program: TDT_ERR_INVALID_OPERATION. */
 int tdt_pick_pixels(tdt_compute *c, const int32_t *xy, size_t n, int sample, float *rays_out, tdt_ray_hit *out);
 
+/* ---- guide images and the denoiser -----------------------------------------------------------------------------------------
+ * A low-spp frame is the library's noisiest output; these two calls trade a little bias for much less variance between
+ * tdt_dispatch_accumulate and tdt_dispatch_resolve.  Every surface of a voxel scene is an axis-aligned face, so "same surface"
+ * is an exact predicate — same material, same face direction, same plane — and the filter built on it is specified bit for bit.
+ *
+ * tdt_dispatch_guide: for every texel (x, y) of `guide` — any RGBA32F image of the context, of any size, addressed like the
+ * trace's image (row 0 = bottom scan line); the camera uniforms define the rays, not the image — the primary ray of pixel (x, y)
+ * and sample `sample` >= 0 is traced exactly as tdt_pick_pixels traces it.  Asynchronous on the context's stream.  Reads slots
+ * 0, 6 and 7, and slot 1 unless TDT_GUIDE_ALL_MATERIALS is set; the bound image, the cost history, the hand-out order and the
+ * frame carry are left as they were.  The texel's 16 bytes become four 32-bit words of that pixel's tdt_ray_hit `hit`
+ * (struct tdt_guide_texel):
+ *   kind      0 = pass-through, otherwise 1 + face code, face code = 9 s(nx) + 3 s(ny) + s(nz) over hit.normal with s(v) = 0
+ *             for v < 0, 2 for v > 0, 1 otherwise (the normal may have more than one non-zero component)
+ *   material  hit.material (0 when the ray did not end on a leaf)
+ *   plane     hit.cell_min[a] + (hit.normal[a] > 0 ? hit.cell_size : 0.0f), one float add, a = the first of x, y, z whose normal
+ *             component is non-zero; +0.0 when kind = 0
+ *   t         hit.t: the depth image; not part of the key
+ * kind is 0 when status != TDT_RAY_HIT, or fresh_record == 0, or all three normal components are zero, or —
+ * TDT_GUIDE_ALL_MATERIALS clear — the material's entry in slot 1 (12 B per entry) does not lie inside the buffer or its first
+ * word, `type`, is not 0 (Lambertian).  Pass-through exists because sky is noise-free already and reflections and refractions are
+ * not smooth across a face: such pixels are not filtered.
+ *
+ * tdt_image_denoise: an a-trous wavelet filter over `img`, in place, asynchronous; B3 kernel k = {1/16, 1/4, 3/8, 1/4, 1/16};
+ * pass p = 0 .. passes - 1 uses step s = 2^p and reads the whole output of the pass before it; passes 0..8, 0 = no-op; flags 0.
+ * For pixel P = (x, y) of a pass, `in` being its input:
+ *   guide[P].kind == 0: all four channels are copied bit for bit.
+ *   otherwise: num = (0, 0, 0), den = 0; for j = -2..2 (outer), i = -2..2 (inner), Q = (x + i s, y + j s): the tap is SKIPPED
+ *   (not multiplied by zero) when Q lies outside the image or words 0, 1, 2 of guide[Q] differ from those of guide[P]; a kept
+ *   tap has w = k[j+2] * k[i+2] (exact in fp32), num.c = num.c + w * in[Q].c (a multiply, then an add: never fused), den = den + w;
+ *   after the taps out.c = num.c / den (IEEE divide) for c = r, g, b, and alpha is in[P]'s.  The centre tap always matches, so
+ *   den >= 9/64.
+ * That order is the contract: a numpy model of these lines gives the same bits (NaN and inf propagate as the arithmetic says).
+ * The filter does not care whether img holds running sums, means or a resolved frame; the intended use is accumulate, guide,
+ * denoise, resolve — filter linear sums, then take the square root.  The passes ping-pong through a grow-only scratch image the
+ * context owns and frees (one image; two for an odd number of three or more passes, so that the last pass lands in img; a single
+ * pass is copied back).
+ *
+ * Errors, nothing written: NULL handles, sample < 0, unknown guide flags, passes outside 0..8, non-zero denoise flags, img and guide
+ * of different sizes, the same image or sharing memory: TDT_ERR_INVALID_VALUE; tdt_dispatch_guide on a TDT_PROGRAM_OCTREE_UPDATE
+ * program, a program whose partition is not (0, 1) (tile buffers are not images), an image of another context:
+ * TDT_ERR_INVALID_OPERATION; slots 0, 6 or 7 unbound, or slot 1 unbound without TDT_GUIDE_ALL_MATERIALS: TDT_ERR_INCOMPLETE.  A
+ * multi-device context runs both calls on device_ids[0], where the assembled image lives, as the queries do. */
+#define TDT_GUIDE_ALL_MATERIALS 1u   /* key every hit, whatever its material: slot 1 is not read */
+typedef struct tdt_guide_texel {
+  uint32_t kind;          /* 0 = pass-through, otherwise 1 + face code */
+  uint32_t material;      /* hit.material */
+  float    plane;         /* the face's plane along its first normal axis */
+  float    t;             /* hit.t */
+} tdt_guide_texel;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_guide_texel) == 16, "tdt_guide_texel is one RGBA32F texel");
+#else
+_Static_assert(sizeof(tdt_guide_texel) == 16, "tdt_guide_texel is one RGBA32F texel");
+#endif
+int tdt_dispatch_guide(tdt_compute *c, tdt_image *guide, int sample, uint32_t flags);
+int tdt_image_denoise(tdt_image *img, const tdt_image *guide, int passes, uint32_t flags);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

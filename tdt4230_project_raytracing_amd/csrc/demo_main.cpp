@@ -13,12 +13,14 @@
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
-//            [--compact] [--config N] [--device N] [--out frame.pfm] [--png frame.png]
+//            [--compact] [--config N] [--device N] [--denoise N] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
 //   w a s d = translate Front / Left / Back / Rigth, u j = Up / Down, q e = turn_yaw(-/+ 1), r f = turn_pitch(-/+ 1),
 //   S / N = sprint / normal speed.  --png writes the frame as the quad pass would present it (main.rs:582-600).
+// --denoise N: the frame as accumulate, guide, N filter passes, resolve (ComputeShader::dispatch_guide, Texture::denoise) instead
+//   of the one dispatch: running sums averaged within each visible voxel face, before the square root.
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
@@ -101,7 +103,7 @@ int main(int argc, char **argv) {
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
-  int config = -1;
+  int config = -1, denoise = 0;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -118,6 +120,7 @@ int main(int argc, char **argv) {
     else if (a == "--click") { const std::string v = next(); if (v != "left" && v != "right") { std::fprintf(stderr, "--click left|right\n"); return 2; } place = v == "left"; }
     else if (a == "--material") { material = std::atoi(next()); material_given = true; }
     else if (a == "--compact") compact = true;
+    else if (a == "--denoise") { denoise = std::atoi(next()); if (denoise < 0 || denoise > 8) { std::fprintf(stderr, "--denoise 0..8\n"); return 2; } }
     else if (a == "--brush") {
       char kind[16] = {0};
       if (std::sscanf(next(), "%15[a-z]:%d", kind, &brush_size) != 2 || brush_size < 0 || (std::strcmp(kind, "sphere") && std::strcmp(kind, "box"))) {
@@ -468,7 +471,16 @@ int main(int argc, char **argv) {
     }
     // main.rs:578-580
     octree.vao.bind();
-    raytrace_program.dispatch_compute(camera.render_texture.width() + 1, camera.render_texture.height() + 1, camera.render_texture.depth());
+    const int dw = camera.render_texture.width() + 1, dh = camera.render_texture.height() + 1, dd = camera.render_texture.depth();
+    if (denoise > 0) {                                                                   // NEW: sums, first hits, filter, then the square root
+      const Texture guide = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
+      ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, 0, spp, nullptr));
+      raytrace_program.dispatch_guide(guide);
+      camera.render_texture.denoise(guide, denoise);
+      ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, spp));
+    } else {
+      raytrace_program.dispatch_compute(dw, dh, dd);
+    }
     VertexArrayObject::unbind();
     const std::vector<float> px = camera.render_texture.read();
     unsigned long long h = 1469598103934665603ull;                                        // FNV-1a of the frame's bits

@@ -7,7 +7,8 @@
 // tdt_bitvol.hip: the dense bit volume that tdt_fill.hip, tdt_distance.hip, tdt_xform.hip and tdt_geodesic.hip stand on, from
 // the tree's list to the result's (its templates over a unit's own kernels: bitvol_device.hpp); tdt_xform.hip: affine
 // transforms of selections; tdt_geodesic.hip: geodesic distance; tdt_voxlist.hip: the Morton-sorted voxel list the list-based units
-// share: the capped tree list, keys, last-of-run unique, scan-gather-count).  The host helpers around a call that every editing unit
+// share: the capped tree list, keys, last-of-run unique, scan-gather-count); tdt_denoise.hip: first-hit guide images and the
+// edge-stopping filter over them.  The host helpers around a call that every editing unit
 // repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
@@ -66,6 +67,7 @@ struct tdt_ctx {
   tdt::Multi *multi = nullptr;             // non-null: this is a multi-device context (tdt_ctx_create_multi); see tdt_multi.hip
   tdt::EditScratch *edit = nullptr;        // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
   void *query = nullptr; size_t query_bytes = 0;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
+  void *denoise = nullptr; size_t denoise_bytes = 0;   // ping-pong images of tdt_image_denoise (tdt_denoise.hip), grow-only
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
@@ -313,5 +315,12 @@ int bitvol_emit_list(tdt_ctx *front, hipStream_t st, uint32_t *k, uint32_t *v, u
 
 // ---- tdt_query.hip ----
 void query_scratch_destroy(tdt_ctx *ctx);
+// the kernel arguments a query needs: slots 0, 6, 7 of the member context m (unbound: TDT_ERR_INCOMPLETE); errors are reported on `front`
+int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P);
+// the camera uniforms of a program into P (what primary_ray reads)
+void query_camera(const tdt_compute *cam, TraceParams &P);
+
+// ---- tdt_denoise.hip ----
+void denoise_scratch_destroy(tdt_ctx *ctx);
 
 }  // namespace tdt

@@ -3,14 +3,13 @@
 // One query ray per lane runs OctreeHit (rc:397-450) as the trace kernel's general build runs it for a fresh invocation
 // (zeroed Carry): root slab test, restart-from-root loop, the literal treeLookup (the float formula: right for every
 // cell_count), the padded empty-cell exit and the i > 0 leaf slab test with its fall-back to the call site's old
-// temporaries.  A plain gather kernel: no persistent blocks, no LDS node table, no jump tables, no bricks — node reads go
-// straight to the cells buffer through a raw buffer resource whose range check is the reference's robust access.
+// temporaries.  The traversal itself is query_first_hit (query_device.hpp), which the guide kernel (tdt_denoise.hip) runs too.
 #include <cstring>
 #include <new>
 #include <string>
 
 #include "tdt_internal.hpp"
-#include "trace_device.hpp"
+#include "query_device.hpp"
 
 namespace tdt {
 
@@ -31,11 +30,7 @@ __global__ __launch_bounds__(kQueryBlock) void raycast_kernel(const TraceParams 
   __syncthreads();
   const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
   if (i >= n) return;
-  NodeSource ns;
-  ns.lds = s_escape; ns.lds_nodes = 0u; ns.lds_cells = 0u;
-  ns.grid = nullptr; ns.grid_ok = false; ns.grid_band = 2.0f; ns.full = nullptr; ns.grid32 = nullptr; ns.bricks = nullptr;
-  ns.thr = nullptr; ns.thr_f0max = 0.0f;
-  ns.cells = __builtin_amdgcn_make_buffer_rsrc((void *)P.cells, 0, (int)((P.cells_dwords >> 1) << 3), 0x00020000);
+  const NodeSource ns = query_node_source(P, s_escape);
 
   Ray r;
   if (PICK) {
@@ -49,86 +44,14 @@ __global__ __launch_bounds__(kQueryBlock) void raycast_kernel(const TraceParams 
     r = {a[0], a[1], a[2], a[3], a[4], a[5]};
   }
 
-  // OctreeHit prologue rc:399-408: the root call site (t_min = 0.0003, t_max = +inf)
-  const float inf = __builtin_inff();
-  float ix, iy, iz;
-  q_rcp3(r.dx, r.dy, r.dz, ix, iy, iz);
-  const float lx = (P.min_x + -r.ox) * ix, ly = (P.min_y + -r.oy) * iy, lz = (P.min_z + -r.oz) * iz;
-  const float ux = ((P.min_x + P.scale) + -r.ox) * ix, uy = ((P.min_y + P.scale) + -r.oy) * iy, uz = ((P.min_z + P.scale) + -r.oz) * iz;
-  const float mnx = hw_min(lx, ux), mny = hw_min(ly, uy), mnz = hw_min(lz, uz);
-  const float mxx = hw_max(lx, ux), mxy = hw_max(ly, uy), mxz = hw_max(lz, uz);
-  const float root_enter = hw_max(hw_max(hw_max(mnx, 0.0003f), mny), mnz);
-  const float root_exit = hw_min(hw_min(hw_min(mxx, inf), mxy), mxz);
-  const bool root_hit = root_exit >= root_enter;
-  HitTmp root = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, false};
-  float root_t = 0.f, t_octree_max = inf;
-  if (root_hit) {
-    cube_hit_record(r, root_enter, P.min_x, P.min_y, P.min_z, P.scale, root);
-    root_t = root_enter;
-    t_octree_max = root_exit;
-  }
-
-  // the loop rc:410-447
-  float t_stride = root_t, inv_pow_depth = 0.5f;
-  int it = 0, lookups = 0, status = TDT_RAY_MISS;
-  uint32_t material = 0u;
-  HitTmp rec = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, false};
-  float t_rec = 0.f, cmin_x = 0.f, cmin_y = 0.f, cmin_z = 0.f, csize = 0.f;
-  bool fresh = false;
-  Counters cnt = {};
-  for (;;) {
-    if (!(it < P.max_iter && t_stride < t_octree_max)) {
-      status = (t_stride < t_octree_max) ? TDT_RAY_ITER_LIMIT : TDT_RAY_MISS;
-      break;
-    }
-    const float adv = f_max(0.0001f * (inv_pow_depth + 0.1f), 0.000001f);
-    const float tt = t_stride + adv;
-    const float wx = tt * r.dx + r.ox, wy = tt * r.dy + r.oy, wz = tt * r.dz + r.oz;
-    const float px = (wx + -P.min_x) * P.inv_scale, py = (wy + -P.min_y) * P.inv_scale, pz = (wz + -P.min_z) * P.inv_scale;
-    const float ex = f_fract(px) + -px, ey = f_fract(py) + -py, ez = f_fract(pz) + -pz;
-    if ((__builtin_fabsf(ez) + __builtin_fabsf(ey)) != -__builtin_fabsf(ex)) break;    // rc:417: not in the octree -> false
-    lookups++;
-    const float ipd_in = inv_pow_depth;
-    float gx, gy, gz; uint32_t value;
-    const bool leaf = tree_lookup<false>(P, ns, px, py, pz, inv_pow_depth, gx, gy, gz, value, cnt);
-    const float bx = gx * P.scale + P.min_x, by = gy * P.scale + P.min_y, bz = gz * P.scale + P.min_z;
-    const float cs0 = P.scale * inv_pow_depth;
-    if (leaf) {                                      // rc:421-436
-      status = TDT_RAY_HIT; material = value;
-      cmin_x = bx; cmin_y = by; cmin_z = bz; csize = cs0;
-      if (it > 0) {
-        float t_enter, t_exit;
-        cube_slabs(r, ix, iy, iz, bx, by, bz, cs0, t_stride, t_octree_max, t_enter, t_exit);
-        if (!(t_exit < t_enter)) { cube_hit_record(r, t_enter, bx, by, bz, cs0, rec); t_rec = t_enter; fresh = true; }
-      } else {
-        rec = root; t_rec = root_t; fresh = root_hit;
-      }
-      break;
-    }
-    // rc:438-446: the empty cell, padded
-    float t_enter, t_exit;
-    cube_slabs(r, ix, iy, iz, bx + -0.00001f, by + -0.00001f, bz + -0.00001f, cs0 + 0.00002f, t_stride, t_octree_max, t_enter, t_exit);
-    const float ts_new = !(t_exit < t_enter) ? t_exit : t_octree_max;
-    // a step that leaves (t_stride, inv_pow_depth) as it found them repeats itself up to max_iter (the loop body is a function of
-    // those two and the ray): the shader ends at the iteration limit with every remaining iteration reaching treeLookup
-    if (__float_as_uint(ts_new) == __float_as_uint(t_stride) && __float_as_uint(inv_pow_depth) == __float_as_uint(ipd_in)) {
-      lookups = P.max_iter;
-      status = TDT_RAY_ITER_LIMIT;
-      break;
-    }
-    t_stride = ts_new;
-    it++;
-  }
-
+  const QueryRecord q = query_first_hit(P, ns, r);
   QueryOut o;
-  o.q[0] = make_uint4((uint32_t)status, material, __float_as_uint(t_rec), (uint32_t)lookups);
-  o.q[1] = make_uint4(__float_as_uint(rec.px), __float_as_uint(rec.py), __float_as_uint(rec.pz), __float_as_uint(rec.nx));
-  o.q[2] = make_uint4(__float_as_uint(rec.ny), __float_as_uint(rec.nz), rec.ff ? 1u : 0u, fresh ? 1u : 0u);
-  o.q[3] = make_uint4(__float_as_uint(cmin_x), __float_as_uint(cmin_y), __float_as_uint(cmin_z), __float_as_uint(csize));
+  o.q[0] = make_uint4((uint32_t)q.status, q.material, __float_as_uint(q.t), (uint32_t)q.lookups);
+  o.q[1] = make_uint4(__float_as_uint(q.rec.px), __float_as_uint(q.rec.py), __float_as_uint(q.rec.pz), __float_as_uint(q.rec.nx));
+  o.q[2] = make_uint4(__float_as_uint(q.rec.ny), __float_as_uint(q.rec.nz), q.rec.ff ? 1u : 0u, q.fresh ? 1u : 0u);
+  o.q[3] = make_uint4(__float_as_uint(q.cmin_x), __float_as_uint(q.cmin_y), __float_as_uint(q.cmin_z), __float_as_uint(q.csize));
   hits[i] = o;
 }
-
-namespace {
 
 // the kernel arguments a query needs: slots 0, 6, 7 of the member context; errors are reported on `front`
 int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P) {
@@ -143,6 +66,17 @@ int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P) {
   P.cells = (const uint32_t *)cells->dev; P.cells_dwords = (uint32_t)(cells->bytes >> 2);
   return TDT_OK;
 }
+
+// the camera uniforms of a program (primary_ray reads them)
+void query_camera(const tdt_compute *cam, TraceParams &P) {
+  P.image_width = cam->image_width; P.image_height = cam->image_height;
+  for (int i = 0; i < 3; i++) {
+    P.hor[i] = cam->horizontal[i]; P.ver[i] = cam->vertical[i]; P.llc[i] = cam->lower_left_corner[i]; P.org[i] = cam->origin[i];
+  }
+  P.samples_per_pixel = cam->samples_per_pixel; P.max_bounce = cam->max_bounce;
+}
+
+namespace {
 
 // grow-only staging on the member context
 int query_scratch(tdt_ctx *front, tdt_ctx *m, size_t bytes, void **out) {
@@ -228,11 +162,7 @@ int tdt_pick_pixels(tdt_compute *c, const int32_t *xy, size_t n, int sample, flo
   TraceParams P;
   if (int rc = tdt::query_params(ctx, m, P)) return rc;
   if (n > (~size_t(0)) / 128) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "too many rays");
-  P.image_width = cam->image_width; P.image_height = cam->image_height;
-  for (int i = 0; i < 3; i++) {
-    P.hor[i] = cam->horizontal[i]; P.ver[i] = cam->vertical[i]; P.llc[i] = cam->lower_left_corner[i]; P.org[i] = cam->origin[i];
-  }
-  P.samples_per_pixel = cam->samples_per_pixel; P.max_bounce = cam->max_bounce;
+  tdt::query_camera(cam, P);
   TDT_HIP(ctx, hipSetDevice(m->device));
   // staging: hits (16-byte aligned at the start), then the pixel pairs, then the rays
   const size_t hit_bytes = n * sizeof(tdt_ray_hit), xy_bytes = n * 8, ray_bytes = rays_out ? n * 24 : 0;

@@ -2163,6 +2163,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   delete ctx->trace;
   tdt::edit_scratch_destroy(ctx);
   tdt::query_scratch_destroy(ctx);
+  tdt::denoise_scratch_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -38,6 +38,12 @@ def hits_from_bytes(b):
     return np.ascontiguousarray(b, np.uint8).reshape(-1, 64).view(RAY_HIT_DTYPE).reshape(-1)
 
 
+# guide images and the denoiser (include/tdt_rt.h): the flag and struct tdt_guide_texel, field for field
+GUIDE_ALL_MATERIALS = 1
+GUIDE_TEXEL_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("plane", "<f4"), ("t", "<f4")])
+assert GUIDE_TEXEL_DTYPE.itemsize == 16
+
+
 # region edits (include/tdt_rt.h): shapes, ops, and struct tdt_region
 SHAPE_BOX, SHAPE_SPHERE = 0, 1
 REGION_SET, REGION_FILL, REGION_PAINT, REGION_CLEAR = 0, 1, 2, 3
@@ -297,6 +303,8 @@ SYMBOLS = [
     ("tdt_raycast", _I, [_P, _P, _S, _P]),
     ("tdt_raycast_device", _I, [_P, _P, _S, _P]),
     ("tdt_pick_pixels", _I, [_P, _P, _S, _I, _P, _P]),
+    ("tdt_dispatch_guide", _I, [_P, _P, _I, ctypes.c_uint32]),
+    ("tdt_image_denoise", _I, [_P, _P, _I, ctypes.c_uint32]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -1012,6 +1020,16 @@ class Texture:
         self.ctx.check(lib().tdt_image_read_rgba8(self.h, 1 if top_down else 0, img.ctypes.data))
         return img
 
+    def denoise(self, guide, passes):
+        """tdt_image_denoise: `passes` (0..8) a-trous passes of step 1, 2, 4, .. over this image, in place, averaging only pixels
+        whose texels of `guide` (a Texture of this size that ComputeShader.dispatch_guide filled) carry the same surface key
+        (kind, material, plane); kind-0 pixels pass through.  Asynchronous."""
+        self.ctx.check(lib().tdt_image_denoise(self.h, guide.h, int(passes), 0))
+
+    def read_guide(self):
+        """The texels of a guide image as an (H, W) array of GUIDE_TEXEL_DTYPE (kind, material, plane, t)."""
+        return self.read().view(GUIDE_TEXEL_DTYPE).reshape(self._h, self._w)
+
 
 class Program:
     """Uniform-by-name setters of program.rs:35-83 (the program object itself is the kernel)."""
@@ -1056,6 +1074,12 @@ class ComputeShader:
         self.ctx.check(lib().tdt_pick_pixels(self.h, p.ctypes.data, p.shape[0], int(sample),
                                              rays.ctypes.data if return_rays else None, out.ctypes.data))
         return (out, rays) if return_rays else out
+
+    def dispatch_guide(self, texture, sample=0, all_materials=False):
+        """tdt_dispatch_guide: texel (x, y) of `texture` (any Texture of the context, usually an unbound one) receives the surface
+        key and depth of what the primary ray of pixel (x, y), sample `sample`, of this program's camera hits first — what pick
+        returns for it, four words of it (Texture.read_guide).  Only Lambertian hits are keyed unless all_materials.  Asynchronous."""
+        self.ctx.check(lib().tdt_dispatch_guide(self.h, texture.h, int(sample), GUIDE_ALL_MATERIALS if all_materials else 0))
 
     # --- extensions (no reference counterpart) ---
     def set_partition(self, rank, world):
@@ -1216,6 +1240,7 @@ class Renderer:
             self.texture = Texture.wrap_device(self.ctx, image_ptr, w, rows)
         else:
             self.texture = Texture.new_2d(self.ctx, w, rows)
+        self.guide = None                      # render(denoise=N) creates it on first use
 
     def dispatch(self, width=None, height=None):
         """main.rs:579: dispatch_compute(texture.width() + 1, texture.height() + 1, 1)."""
@@ -1223,7 +1248,20 @@ class Renderer:
         h = self.camera.image_height + 1 if height is None else height
         self.shader.dispatch_compute(w, h, 1)
 
-    def render(self, width=None, height=None):
+    def render(self, width=None, height=None, denoise=0):
+        """The frame.  denoise = N > 0: the same samples as running sums (dispatch_accumulate), the first-hit guide of sample 0,
+        N filter passes over the sums, then the resolve — the square root is taken of the filtered sums."""
+        if denoise > 0:
+            w = self.camera.image_width + 1 if width is None else width
+            h = self.camera.image_height + 1 if height is None else height
+            spp = self.camera.samples_per_pixel
+            if self.guide is None:
+                self.guide = Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False)
+            self.shader.dispatch_accumulate(w, h, 1, 0, spp)
+            self.shader.dispatch_guide(self.guide)
+            self.texture.denoise(self.guide, denoise)
+            self.shader.dispatch_resolve(w, h, 1, spp)
+            return self.texture.read()
         self.dispatch(width, height)
         return self.texture.read()
 
