@@ -108,6 +108,8 @@ class VertexArrayObject {
   static void unbind() {}
 };
 
+class ComputeShader;
+
 // renderer/texture.rs:7-92
 class Texture {
  public:
@@ -140,6 +142,15 @@ class Texture {
     ctx_->check(tdt_image_read(img_, reinterpret_cast<float *>(g.data())));
     return g;
   }
+  // NEW: every byte to zero (tdt_image_clear): before accumulating a sample range that does not start at sample 0; a
+  // multi-device context's image is refused
+  void clear() const { ctx_->check(tdt_image_clear(img_)); }
+  // NEW: temporal reprojection (tdt_image_reproject) with this texture as the frame's running sums of `spp` samples: hist_out
+  // receives the sums plus, where the earlier frame (its view, guide and history: all three or none) saw the same surface point, at
+  // most max_samples of that frame's history; mean_out (may be this texture, or null) receives rgb / sample count.  `guide` is what
+  // shader.dispatch_guide(guide, sample) wrote under the shader's current camera.  Asynchronous.  (Defined below ComputeShader.)
+  void reproject(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view, const Texture *prev_guide,
+                 const Texture *prev_hist, float max_samples, const Texture &hist_out, const Texture *mean_out = nullptr) const;
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;
@@ -200,10 +211,23 @@ class ComputeShader {
   void dispatch_guide(const Texture &guide, int sample = 0, uint32_t flags = 0) const {
     ctx_->check(tdt_dispatch_guide(program.id(), guide.id(), sample, flags));
   }
+  // NEW: a snapshot of this program's camera uniforms (tdt_compute_view): what a later frame reprojects into
+  tdt_view view() const {
+    tdt_view v;
+    ctx_->check(tdt_compute_view(program.id(), &v));
+    return v;
+  }
  private:
   Context *ctx_ = nullptr;
   int group_size_[3] = {0, 0, 0};
 };
+
+inline void Texture::reproject(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view,
+                               const Texture *prev_guide, const Texture *prev_hist, float max_samples, const Texture &hist_out,
+                               const Texture *mean_out) const {
+  ctx_->check(tdt_image_reproject(shader.program.id(), sample, guide.img_, img_, spp, prev_view, prev_guide ? prev_guide->img_ : nullptr,
+                                  prev_hist ? prev_hist->img_ : nullptr, max_samples, hist_out.img_, mean_out ? mean_out->img_ : nullptr, 0));
+}
 
 // renderer/octree.rs:10-183
 class Octree {

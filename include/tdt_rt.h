@@ -339,6 +339,75 @@ _Static_assert(sizeof(tdt_guide_texel) == 16, "tdt_guide_texel is one RGBA32F te
 int tdt_dispatch_guide(tdt_compute *c, tdt_image *guide, int sample, uint32_t flags);
 int tdt_image_denoise(tdt_image *img, const tdt_image *guide, int passes, uint32_t flags);
 
+/* ---- temporal reprojection ------------------------------------------------------------------------------------------------
+ * The filter above reduces variance within a frame; this call carries samples from one frame of a moving camera to the next.
+ * It can be exact here: a ray from the old eye through a world point W on the plane of an axis-aligned face meets that plane only
+ * at W, so if the old frame's pixel under W carries the same guide key (kind, material, plane), it saw W up to the pixel's
+ * footprint.  History is validated by that bit-exact comparison and nothing else: no depth or normal tolerance.  The guide keys
+ * only Lambertian hits by default, whose radiance does not depend on the view.
+ *
+ * A HISTORY IMAGE is an RGBA32F image whose rgb are running sums of radiance samples and whose alpha is the number of samples
+ * behind them, as a float.  tdt_view is a snapshot of the camera uniforms primary_ray reads; tdt_compute_view fills one from the
+ * program's current uniforms (a multi-device program: its first member's).
+ *
+ * tdt_image_reproject, asynchronous on the context's stream, one lane per pixel, reads no scene buffer:
+ *   guide       what tdt_dispatch_guide(c, guide, sample, ..) wrote under c's CURRENT camera (the caller keeps them consistent)
+ *   sums        this frame's running sums of `spp` samples as tdt_dispatch_accumulate leaves them; alpha is ignored
+ *   prev_view, prev_guide, prev_hist   the view, guide and history of an earlier frame; all three NULL for a first frame.  The two
+ *               images have one size, which may differ from the current one; prev_view defines the mapping (its image_width /
+ *               image_height scale the jitter) independently of the images' sizes
+ *   hist_out    receives this frame's history; mean_out (may be NULL) receives rgb = hist_out.rgb / hist_out.a, alpha = 1.
+ *               mean_out may be `sums` itself (a lane reads only its own pixel of sums); it may not be any other argument.
+ * Per call, on the host, in double from the fp32 fields of prev_view, every product and every add / subtract rounded on its own:
+ *   a = horizontal, b = vertical, c = lower_left_corner - origin; Ru = b x c, Rv = c x a, Rw = a x b, each component as
+ *   p = x*y; q = z*w; p - q; det = (c.z Rw.z + c.y Rw.y) + c.x Rw.x.  det not finite or 0: TDT_ERR_INVALID_VALUE.  det < 0: all three
+ *   rows are negated.  The nine numbers are then rounded to fp32.
+ * Per pixel P = (x, y), in fp32, each operation rounded, never fused:
+ *   g = guide[P]; r = the primary ray of (x, y, sample) under c's camera (the bits of tdt_pick_pixels' rays_out).
+ *   Without history, or with g.kind == 0: hist_out[P] = (sums.rgb, (float)spp).
+ *   Otherwise W.k = r.o.k + g.t * r.d.k; D.k = W.k - prev.origin.k; nu = (Ru.z D.z + Ru.y D.y) + Ru.x D.x, nv and nw likewise with
+ *   Rv and Rw; fx = (nu / nw) * (float)(prev.image_width - 1); fy = (nv / nw) * (float)(prev.image_height - 1).
+ *   The history is FOUND iff nw > 0, and fx >= 0 && fx < (float)prev_w && fy >= 0 && fy < (float)prev_h (prev_w, prev_h: the size
+ *   of the prev images; NaN fails), and with Q = ((int)fx, (int)fy) words 0, 1, 2 of prev_guide[Q] equal those of g, and
+ *   hn = prev_hist[Q].a satisfies hn > 0.  prev_hist[Q] is read only after the key matched.
+ *   Found: h = prev_hist[Q]; if hn > max_samples: s = max_samples / hn, h.rgb = h.rgb * s, hn = max_samples;
+ *   hist_out[P] = (sums.rgb + h.rgb, (float)spp + hn).  Not found: as without history.
+ * max_samples caps the history's length: once it is reached, what enters is an exponential moving average.
+ * The intended frame k: accumulate [k spp, (k+1) spp) into the bound image, guide with sample = k spp, reproject with mean_out =
+ * the bound image, optionally tdt_image_denoise, tdt_dispatch_resolve(.., total_spp = 1) (the divide by 1 is exact); the history
+ * and guide images ping-pong between frames.  A range that does not start at sample 0 is ADDED to what the bound image holds, which
+ * after a frame is the resolved picture: tdt_image_clear (all bytes of the image to zero, asynchronous on the context's stream; a
+ * NULL image: TDT_ERR_INVALID_VALUE) comes before the accumulate of every frame but the first.  An image of a multi-device
+ * context: TDT_ERR_INVALID_OPERATION, nothing written (there a bound image's running sums live in the members' tile buffers, out
+ * of this handle's reach; the frame above is a single-device one).
+ *
+ * tdt_debug_reproject_counts (synchronises): of the context's last tdt_image_reproject that returned TDT_OK (a call that fails
+ * leaves the counts of the call before it), [0] keyed pixels (kind != 0), [1] found, [2] rejected by key or hn, [3] rejected by nw
+ * or off-screen; [1] + [2] + [3] = [0] when history was given, else they are 0.  Before any call, and after one on an image of no
+ * pixels, all four are 0.
+ *
+ * Errors, nothing written: NULL c, guide, sums or hist_out; prev_* neither all NULL nor all non-NULL; sample < 0; spp < 1; flags
+ * != 0; max_samples not >= 1 (NaN included); guide, sums, hist_out and mean_out not of one size; prev_guide and prev_hist of
+ * different sizes, or wider or taller than 2^24 (past which (float)prev_w is no longer exact); a view with image_width < 2 or
+ * image_height < 2, or a degenerate determinant; any two images sharing memory except mean_out == sums: TDT_ERR_INVALID_VALUE.
+ * A TDT_PROGRAM_OCTREE_UPDATE program, a partition other than (0, 1), an image of another context: TDT_ERR_INVALID_OPERATION.
+ * A multi-device context runs on device_ids[0]. */
+typedef struct tdt_view {
+  float   origin[3], lower_left_corner[3], horizontal[3], vertical[3];
+  int32_t image_width, image_height;
+} tdt_view;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_view) == 56, "tdt_view is 56 bytes");
+#else
+_Static_assert(sizeof(tdt_view) == 56, "tdt_view is 56 bytes");
+#endif
+int tdt_compute_view(const tdt_compute *c, tdt_view *out);
+int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp,
+                        const tdt_view *prev_view, const tdt_image *prev_guide, const tdt_image *prev_hist,
+                        float max_samples, tdt_image *hist_out, tdt_image *mean_out, uint32_t flags);
+int tdt_debug_reproject_counts(tdt_ctx *ctx, uint64_t out[4]);
+int tdt_image_clear(tdt_image *img);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

@@ -13,7 +13,7 @@
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
-//            [--compact] [--config N] [--device N] [--denoise N] [--out frame.pfm] [--png frame.png]
+//            [--compact] [--config N] [--device N] [--denoise N] [--temporal N [--turn DEG]] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -21,6 +21,11 @@
 //   S / N = sprint / normal speed.  --png writes the frame as the quad pass would present it (main.rs:582-600).
 // --denoise N: the frame as accumulate, guide, N filter passes, resolve (ComputeShader::dispatch_guide, Texture::denoise) instead
 //   of the one dispatch: running sums averaged within each visible voxel face, before the square root.
+// --temporal N [--turn DEG]: N frames instead of one, the camera yawing DEG degrees (default 1) before every frame but the first
+//   (turn_yaw takes units of 2 * turn_rate radians; DEG is converted with the camera's turn_rate, that of --settings included),
+//   each frame's spp samples joined by the history of the frame before wherever that frame saw the same surface point
+//   (ComputeShader::view, Texture::reproject; at most 64 samples of history); the last frame is the one written.  Combines with
+//   --denoise, which then filters each frame's means.  Prints the last frame's found / rejected pixel counts.
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
@@ -103,7 +108,8 @@ int main(int argc, char **argv) {
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
-  int config = -1, denoise = 0;
+  int config = -1, denoise = 0, temporal = 0;
+  float turn = 1.0f;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -121,6 +127,8 @@ int main(int argc, char **argv) {
     else if (a == "--material") { material = std::atoi(next()); material_given = true; }
     else if (a == "--compact") compact = true;
     else if (a == "--denoise") { denoise = std::atoi(next()); if (denoise < 0 || denoise > 8) { std::fprintf(stderr, "--denoise 0..8\n"); return 2; } }
+    else if (a == "--temporal") { temporal = std::atoi(next()); if (temporal < 1) { std::fprintf(stderr, "--temporal N, N >= 1\n"); return 2; } }
+    else if (a == "--turn") turn = (float)std::atof(next());
     else if (a == "--brush") {
       char kind[16] = {0};
       if (std::sscanf(next(), "%15[a-z]:%d", kind, &brush_size) != 2 || brush_size < 0 || (std::strcmp(kind, "sphere") && std::strcmp(kind, "box"))) {
@@ -472,7 +480,30 @@ int main(int argc, char **argv) {
     // main.rs:578-580
     octree.vao.bind();
     const int dw = camera.render_texture.width() + 1, dh = camera.render_texture.height() + 1, dd = camera.render_texture.depth();
-    if (denoise > 0) {                                                                   // NEW: sums, first hits, filter, then the square root
+    if (temporal > 0) {                                                                  // NEW: a turn of `temporal` frames with history
+      const int tw = camera.render_texture.width(), th = camera.render_texture.height();
+      const Texture hist[2] = {Texture::new_2d(ctx, tw, th, false), Texture::new_2d(ctx, tw, th, false)};
+      const Texture guides[2] = {Texture::new_2d(ctx, tw, th, false), Texture::new_2d(ctx, tw, th, false)};
+      const tdt_compute *const prog = raytrace_program.program.id();
+      tdt_view prev_view = {};
+      // turn_yaw(angle) rotates by 2 * angle * turn_rate radians (camera.rs:56-62), so DEG degrees are this many of its units
+      const float turn_units = turn * 0.017453292519943295f / (2.0f * camera.settings().turn_rate);
+      for (int k = 0; k < temporal; k++) {
+        const int cur = k & 1, old = cur ^ 1;
+        if (k) { camera.turn_yaw(raytrace_program.program, turn_units); camera.render_texture.clear(); }
+        ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, k * spp, spp, nullptr));
+        raytrace_program.dispatch_guide(guides[cur], k * spp);
+        camera.render_texture.reproject(raytrace_program, k * spp, guides[cur], spp, k ? &prev_view : nullptr, k ? &guides[old] : nullptr,
+                                        k ? &hist[old] : nullptr, 64.0f, hist[cur], &camera.render_texture);
+        if (denoise > 0) camera.render_texture.denoise(guides[cur], denoise);
+        ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, 1));
+        ctx.check(tdt_compute_view(prog, &prev_view));
+      }
+      uint64_t counts[4];
+      ctx.check(tdt_debug_reproject_counts(ctx.raw(), counts));
+      std::printf("temporal frames %d keyed %llu found %llu rejected-key %llu rejected-screen %llu\n", temporal, (unsigned long long)counts[0],
+                  (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
+    } else if (denoise > 0) {                                                            // NEW: sums, first hits, filter, then the square root
       const Texture guide = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
       ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, 0, spp, nullptr));
       raytrace_program.dispatch_guide(guide);

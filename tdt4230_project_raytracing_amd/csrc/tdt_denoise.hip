@@ -144,9 +144,6 @@ __global__ __launch_bounds__(256) void denoise_gather_kernel(const float4 *__res
 
 namespace {
 
-// the image a call works on: a multi-device handle stands for the assembled frame on the first device
-const tdt_image *device_image(const tdt_image *img) { return img->ctx->multi ? img->full : img; }
-
 int denoise_scratch(tdt_ctx *front, tdt_ctx *m, size_t bytes, void **out) {
   if (m->denoise_bytes < bytes) {
     TDT_HIP(front, hipStreamSynchronize(m->stream));            // (passes queued earlier may still use the old one)

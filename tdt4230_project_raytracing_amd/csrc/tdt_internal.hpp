@@ -8,8 +8,8 @@
 // the tree's list to the result's (its templates over a unit's own kernels: bitvol_device.hpp); tdt_xform.hip: affine
 // transforms of selections; tdt_geodesic.hip: geodesic distance; tdt_voxlist.hip: the Morton-sorted voxel list the list-based units
 // share: the capped tree list, keys, last-of-run unique, scan-gather-count); tdt_denoise.hip: first-hit guide images and the
-// edge-stopping filter over them.  The host helpers around a call that every editing unit
-// repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
+// edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides.  The host helpers
+// around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,6 +68,7 @@ struct tdt_ctx {
   tdt::EditScratch *edit = nullptr;        // scratch of the parallel voxel-edit path (tdt_edit.hip), allocated on first use
   void *query = nullptr; size_t query_bytes = 0;   // staging of the host-memory ray queries (tdt_query.hip), grow-only
   void *denoise = nullptr; size_t denoise_bytes = 0;   // ping-pong images of tdt_image_denoise (tdt_denoise.hip), grow-only
+  unsigned long long *reproject_counts = nullptr;      // tdt_debug_reproject_counts: four device words of the last tdt_image_reproject (tdt_reproject.hip)
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
@@ -322,5 +323,10 @@ void query_camera(const tdt_compute *cam, TraceParams &P);
 
 // ---- tdt_denoise.hip ----
 void denoise_scratch_destroy(tdt_ctx *ctx);
+// the image a call works on: a multi-device handle stands for the assembled frame on the first device
+inline const tdt_image *device_image(const tdt_image *img) { return img->ctx->multi ? img->full : img; }
+
+// ---- tdt_reproject.hip ----
+void reproject_counts_destroy(tdt_ctx *ctx);
 
 }  // namespace tdt

@@ -44,6 +44,15 @@ GUIDE_TEXEL_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("plane", "<
 assert GUIDE_TEXEL_DTYPE.itemsize == 16
 
 
+class VIEW(ctypes.Structure):
+    """struct tdt_view: a snapshot of the camera uniforms primary_ray reads (temporal reprojection maps into it)."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("lower_left_corner", ctypes.c_float * 3), ("horizontal", ctypes.c_float * 3),
+                ("vertical", ctypes.c_float * 3), ("image_width", ctypes.c_int32), ("image_height", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(VIEW) == 56
+
+
 # region edits (include/tdt_rt.h): shapes, ops, and struct tdt_region
 SHAPE_BOX, SHAPE_SPHERE = 0, 1
 REGION_SET, REGION_FILL, REGION_PAINT, REGION_CLEAR = 0, 1, 2, 3
@@ -305,6 +314,10 @@ SYMBOLS = [
     ("tdt_pick_pixels", _I, [_P, _P, _S, _I, _P, _P]),
     ("tdt_dispatch_guide", _I, [_P, _P, _I, ctypes.c_uint32]),
     ("tdt_image_denoise", _I, [_P, _P, _I, ctypes.c_uint32]),
+    ("tdt_compute_view", _I, [_P, ctypes.POINTER(VIEW)]),
+    ("tdt_image_reproject", _I, [_P, _I, _P, _P, _I, ctypes.POINTER(VIEW), _P, _P, _F, _P, _P, ctypes.c_uint32]),
+    ("tdt_debug_reproject_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tdt_image_clear", _I, [_P]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -890,6 +903,13 @@ class Context:
         """tdt_debug_geodesic_passes: the relaxation passes of the last geodesic call that changed the volume."""
         return int(lib().tdt_debug_geodesic_passes(self.h))
 
+    def reproject_counts(self):
+        """tdt_debug_reproject_counts: (keyed, found, rejected by key or sample count, rejected behind or off-screen) of the last
+        Texture.reproject (blocks)."""
+        c = (ctypes.c_uint64 * 4)()
+        self.check(lib().tdt_debug_reproject_counts(self.h, c))
+        return tuple(int(v) for v in c)
+
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
         return int(lib().tdt_debug_fill_passes(self.h))
@@ -1030,6 +1050,23 @@ class Texture:
         """The texels of a guide image as an (H, W) array of GUIDE_TEXEL_DTYPE (kind, material, plane, t)."""
         return self.read().view(GUIDE_TEXEL_DTYPE).reshape(self._h, self._w)
 
+    def clear(self):
+        """tdt_image_clear: every byte of the image to zero (before accumulating a sample range that does not start at 0).  A
+        multi-device context's image is refused: there the running sums live in the members' tile buffers."""
+        self.ctx.check(lib().tdt_image_clear(self.h))
+
+    def reproject(self, shader, sample, guide, spp, prev=None, max_samples=64.0, hist_out=None, mean_out=None):
+        """tdt_image_reproject with this texture as `sums` (running sums of `spp` samples): hist_out receives the sums plus, where an
+        earlier frame saw the same surface point, that frame's history; prev = (VIEW, guide Texture, history Texture) of the earlier
+        frame or None for a first frame; `guide` is what shader.dispatch_guide(guide, sample) wrote under the current camera.
+        mean_out (may be this texture) receives history rgb / history alpha.  Asynchronous."""
+        if hist_out is None:
+            raise ValueError("reproject needs a history texture to write (hist_out)")
+        view, pg, ph = prev if prev is not None else (None, None, None)
+        self.ctx.check(lib().tdt_image_reproject(shader.h, int(sample), guide.h, self.h, int(spp), ctypes.byref(view) if view is not None else None,
+                                                 pg.h if pg is not None else None, ph.h if ph is not None else None, float(max_samples),
+                                                 hist_out.h, mean_out.h if mean_out is not None else None, 0))
+
 
 class Program:
     """Uniform-by-name setters of program.rs:35-83 (the program object itself is the kernel)."""
@@ -1080,6 +1117,12 @@ class ComputeShader:
         key and depth of what the primary ray of pixel (x, y), sample `sample`, of this program's camera hits first — what pick
         returns for it, four words of it (Texture.read_guide).  Only Lambertian hits are keyed unless all_materials.  Asynchronous."""
         self.ctx.check(lib().tdt_dispatch_guide(self.h, texture.h, int(sample), GUIDE_ALL_MATERIALS if all_materials else 0))
+
+    def view(self):
+        """tdt_compute_view: a VIEW snapshot of this program's current camera uniforms."""
+        v = VIEW()
+        self.ctx.check(lib().tdt_compute_view(self.h, ctypes.byref(v)))
+        return v
 
     # --- extensions (no reference counterpart) ---
     def set_partition(self, rank, world):
@@ -1220,6 +1263,12 @@ def upload_scene(ctx, scene):
     return vbos
 
 
+# Renderer.render_temporal's sample indices stay below this.  primary_ray hashes fract(K * (x + (float)sample)) with K = 0.02062:
+# up to 2^20 the float spacing of that product (2^-9) is far below K, so consecutive samples still get different jitter; near
+# 2^24 they would coincide, and k * spp as a C int would overflow later still.
+TEMPORAL_SAMPLE_PERIOD = 1 << 20
+
+
 class Renderer:
     """Convenience wrapper used by tests, smoke() and bench.py: a context with one scene, one
     camera and one image, i.e. the state main.rs has built when it reaches its render loop."""
@@ -1241,6 +1290,7 @@ class Renderer:
         else:
             self.texture = Texture.new_2d(self.ctx, w, rows)
         self.guide = None                      # render(denoise=N) creates it on first use
+        self.temporal = None                   # render_temporal's state, created on first use
 
     def dispatch(self, width=None, height=None):
         """main.rs:579: dispatch_compute(texture.width() + 1, texture.height() + 1, 1)."""
@@ -1263,6 +1313,47 @@ class Renderer:
             self.shader.dispatch_resolve(w, h, 1, spp)
             return self.texture.read()
         self.dispatch(width, height)
+        return self.texture.read()
+
+    def render_temporal(self, width=None, height=None, cam=None, denoise=0, max_samples=64.0, reset=False):
+        """One frame of an interactive sequence, with the samples of earlier frames reprojected into it (Texture.reproject).  Frame k
+        traces samples [k spp, (k+1) spp) of the camera's samples_per_pixel, takes the guide of sample k spp, adds the history of the
+        frame before wherever that frame saw the same surface point (at most max_samples of it), filters the means with `denoise`
+        passes and resolves them.  cam, when given, becomes the renderer's camera (the camera moved); reset drops the history and
+        starts again at frame 0 — after a scene edit, whose lighting change nothing here detects.  The renderer owns the frame
+        counter, the two history and the two guide textures and the previous view.  The sample index wraps to 0 every
+        TEMPORAL_SAMPLE_PERIOD // spp frames (the history is kept): a session of any length stays inside the range in which the
+        sampler tells samples apart.  Returns the resolved frame.  A single-device
+        renderer whose image is the whole frame only: on several devices the running sums live in per-device tile buffers."""
+        if self.ctx.device_count() != 1 or self.texture.width() != self.camera.image_width or self.texture.height() != self.camera.image_height:
+            raise ValueError("render_temporal needs a single-device renderer that owns the whole image")
+        if cam is not None:
+            if (cam.image_width, cam.image_height) != (self.camera.image_width, self.camera.image_height):
+                raise ValueError("render_temporal keeps one image size: the new camera's differs")
+            self.camera = cam
+            initial_uniforms(cam, self.shader.program)
+        w = self.camera.image_width + 1 if width is None else width
+        h = self.camera.image_height + 1 if height is None else height
+        spp = self.camera.samples_per_pixel
+        t = self.temporal
+        if t is None:
+            new = lambda: Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False)  # noqa: E731
+            t = self.temporal = {"frame": 0, "view": None, "hist": (new(), new()), "guide": (new(), new())}
+        if reset:
+            t["frame"], t["view"] = 0, None
+        k = t["frame"]
+        cur, old = k & 1, (k & 1) ^ 1
+        sample = (k % max(1, TEMPORAL_SAMPLE_PERIOD // spp)) * spp
+        if sample:
+            self.texture.clear()               # (a range that starts past sample 0 is added to what the image holds)
+        self.shader.dispatch_accumulate(w, h, 1, sample, spp)
+        self.shader.dispatch_guide(t["guide"][cur], sample=sample)
+        prev = (t["view"], t["guide"][old], t["hist"][old]) if t["view"] is not None else None
+        self.texture.reproject(self.shader, sample, t["guide"][cur], spp, prev, max_samples, hist_out=t["hist"][cur], mean_out=self.texture)
+        if denoise > 0:
+            self.texture.denoise(t["guide"][cur], denoise)
+        self.shader.dispatch_resolve(w, h, 1, 1)
+        t["view"], t["frame"] = self.shader.view(), k + 1
         return self.texture.read()
 
     def pick(self, xy, sample=0, return_rays=False):
