@@ -151,6 +151,22 @@ class Texture {
   // shader.dispatch_guide(guide, sample) wrote under the shader's current camera.  Asynchronous.  (Defined below ComputeShader.)
   void reproject(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view, const Texture *prev_guide,
                  const Texture *prev_hist, float max_samples, const Texture &hist_out, const Texture *mean_out = nullptr) const;
+  // NEW: the variance of the luminance of rgb into alpha (tdt_image_variance): 0 for kind-0 pixels, from `moments` (what
+  // reproject_moments wrote, or null) where a pixel has at least min_frames frames behind it, from its 7x7 same-key neighbourhood
+  // elsewhere.  Asynchronous.
+  void variance(const Texture &guide, const Texture *moments = nullptr, float min_frames = 4.0f) const {
+    ctx_->check(tdt_image_variance(img_, guide.img_, moments ? moments->img_ : nullptr, min_frames, 0));
+  }
+  // NEW: denoise's passes with a luminance edge-stopping weight scaled by the variance in alpha (tdt_image_denoise_variance):
+  // max(lim - d^2, 0), lim = sigma^2 * (3x3 prefiltered variance of the centre) + floor.  Asynchronous.
+  void denoise_variance(const Texture &guide, int passes, float sigma, float floor = 0.0f) const {
+    ctx_->check(tdt_image_denoise_variance(img_, guide.img_, passes, sigma, floor, 0));
+  }
+  // NEW: reproject, and moments_out receives the luminance moments (m1, m2, frames, 0) joined with prev_moments' wherever the
+  // history was found (tdt_image_reproject_moments); prev_moments comes and goes with the other prev_*.  (Defined below ComputeShader.)
+  void reproject_moments(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view,
+                         const Texture *prev_guide, const Texture *prev_hist, const Texture *prev_moments, float max_samples,
+                         const Texture &hist_out, const Texture &moments_out, const Texture *mean_out = nullptr) const;
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;
@@ -227,6 +243,14 @@ inline void Texture::reproject(const ComputeShader &shader, int sample, const Te
                                const Texture *mean_out) const {
   ctx_->check(tdt_image_reproject(shader.program.id(), sample, guide.img_, img_, spp, prev_view, prev_guide ? prev_guide->img_ : nullptr,
                                   prev_hist ? prev_hist->img_ : nullptr, max_samples, hist_out.img_, mean_out ? mean_out->img_ : nullptr, 0));
+}
+
+inline void Texture::reproject_moments(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view,
+                                       const Texture *prev_guide, const Texture *prev_hist, const Texture *prev_moments, float max_samples,
+                                       const Texture &hist_out, const Texture &moments_out, const Texture *mean_out) const {
+  ctx_->check(tdt_image_reproject_moments(shader.program.id(), sample, guide.img_, img_, spp, prev_view, prev_guide ? prev_guide->img_ : nullptr,
+                                          prev_hist ? prev_hist->img_ : nullptr, prev_moments ? prev_moments->img_ : nullptr, max_samples,
+                                          hist_out.img_, moments_out.img_, mean_out ? mean_out->img_ : nullptr, 0));
 }
 
 // renderer/octree.rs:10-183

@@ -408,6 +408,65 @@ int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, cons
 int tdt_debug_reproject_counts(tdt_ctx *ctx, uint64_t out[4]);
 int tdt_image_clear(tdt_image *img);
 
+/* ---- luminance variance and the variance-guided filter --------------------------------------------------------------------
+ * tdt_image_denoise stops at surface edges and nowhere else: inside a face every same-key neighbour counts in full, however
+ * different its radiance.  These three calls add what tells a lighting edge from noise: a per-pixel estimate of the variance of
+ * the luminance, and a filter whose second edge-stopping weight is scaled by it.  The variance lives in the image's ALPHA channel,
+ * which neither tdt_image_denoise nor the resolve uses (tdt_dispatch_resolve overwrites it with 1), so a tap is still one texel.
+ * Throughout lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b; all arithmetic is fp32, each operation rounded on its own,
+ * never fused; "same key" and "inside the image" are tdt_image_denoise's, and a tap that fails them is SKIPPED, not weighted by
+ * zero.  A numpy model of these lines gives the same bits.
+ *
+ * tdt_image_variance, asynchronous on the context's stream: writes img[P].a for every pixel P = (x, y) and nothing else (the alpha
+ * word alone is stored, and rgb alone is loaded); moments may be NULL.
+ *   guide[P].kind == 0: a = +0.0f.
+ *   Temporal estimate, when moments != NULL and n = moments[P].z satisfies n >= min_frames (NaN fails): mu = m.x / n; e2 = m.y / n;
+ *   v = e2 - mu * mu; v = v > 0 ? v : 0 (a NaN gives 0); a = v / n — the variance of the mean of n frames, which is what img holds
+ *   in the temporal frame.
+ *   Spatial estimate otherwise: K = 0, s1 = 0, s2 = 0; for j = -3..3 (outer), i = -3..3 (inner), Q = (x + i, y + j) inside the image
+ *   with the same key: l = lum(img[Q].rgb); K = K + 1.0f; s1 = s1 + l; s2 = s2 + l * l.  Then mu = s1 / K; v = s2 / K - mu * mu;
+ *   v = v > 0 ? v : 0; a = v.  The centre always counts, so K >= 1; with K == 1 the variance is 0.
+ *
+ * tdt_image_denoise_variance: tdt_image_denoise's a-trous frame — the B3 kernel k, step s = 2^p in pass p, passes 0..8 (0 = no-op),
+ * the same scratch images, the last pass lands in img — with a luminance weight.  Once, on the host: s2 = sigma * sigma.
+ * For pixel P of a pass, `in` being its input:
+ *   guide[P].kind == 0: all four channels are copied bit for bit.
+ *   otherwise lP = lum(in[P].rgb), and the prefiltered variance, always at distance 1 whatever the step, with g = {1/4, 1/2, 1/4}:
+ *   gnum = 0, gden = 0; for j = -1..1 (outer), i = -1..1 (inner), Q = (x + i, y + j) inside the image with the same key:
+ *   wg = g[j+1] * g[i+1]; gnum = gnum + wg * in[Q].a; gden = gden + wg.  gv = gnum / gden; lim = s2 * gv + floor.
+ *   If !(lim > 0 && lim < INFINITY): all four channels of in[P] are copied bit for bit — a pixel whose variance is unknown or
+ *   zero is left alone.
+ *   Otherwise num = (0, 0, 0), den = 0, vnum = 0; for j = -2..2 (outer), i = -2..2 (inner), Q = (x + i s, y + j s): skipped when Q
+ *   lies outside the image or its key differs; d = lum(in[Q].rgb) - lP; d2 = d * d; skipped unless d2 < lim (a comparison: NaN
+ *   fails); w = (k[j+2] * k[i+2]) * (lim - d2); num.c = num.c + w * in[Q].c for c = r, g, b; den = den + w;
+ *   vnum = vnum + (w * w) * in[Q].a.  After the taps out.c = num.c / den; out.a = vnum / (den * den).
+ * The luminance weight is max(lim - d2, 0), compactly supported; its normalising 1 / lim is common to all taps and cancels.  NaN and
+ * infinities propagate as these lines say: a NaN centre keeps no tap, den = 0, and the output is NaN.
+ *
+ * A MOMENTS IMAGE is an RGBA32F image whose texels are (m1, m2, n, 0): the sums over frames of the frame's luminance and of its
+ * square, and the number of frames.  tdt_image_reproject_moments is tdt_image_reproject — hist_out, mean_out, the four counts, the
+ * FOUND predicate and Q are exactly that call's — and also writes moments_out.  Once, on the host: mf = max_samples / (float)spp.
+ * Per pixel: l = lum(sums.rgb / (float)spp), three IEEE divides, then lum.
+ *   Not found, no history, or kind == 0: moments_out[P] = (l, l * l, 1, 0).
+ *   Found: hm = prev_moments[Q], read only after the key matched and hn > 0.  If !(hm.z > 0): as not found.  If hm.z > mf:
+ *   sc = mf / hm.z; hm.x = hm.x * sc; hm.y = hm.y * sc; hm.z = mf.  moments_out[P] = (l + hm.x, l * l + hm.y, 1.0f + hm.z, 0).
+ * prev_moments is NULL exactly when the other prev_* are, and has their size.
+ * The intended frames: accumulate, guide, tdt_image_variance (spatial), tdt_image_denoise_variance, resolve; and, temporal,
+ * clear, accumulate, guide, tdt_image_reproject_moments with mean_out = the bound image, tdt_image_variance with moments_out,
+ * tdt_image_denoise_variance, resolve with total_spp = 1; the moments images ping-pong like the histories.
+ *
+ * Errors, nothing written: NULL handles (moments of tdt_image_variance and mean_out excepted); images not of one size; any two
+ * images sharing memory except mean_out == sums; passes outside 0..8; flags != 0; sigma not > 0 or not finite; floor not >= 0 or not
+ * finite; min_frames not >= 1 (NaN included); whatever tdt_image_reproject refuses: TDT_ERR_INVALID_VALUE.  An image of another
+ * context; for tdt_image_reproject_moments a TDT_PROGRAM_OCTREE_UPDATE program or a partition other than (0, 1):
+ * TDT_ERR_INVALID_OPERATION.  A multi-device context runs all three on device_ids[0]. */
+int tdt_image_variance(tdt_image *img, const tdt_image *guide, const tdt_image *moments, float min_frames, uint32_t flags);
+int tdt_image_denoise_variance(tdt_image *img, const tdt_image *guide, int passes, float sigma, float floor, uint32_t flags);
+int tdt_image_reproject_moments(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp,
+                                const tdt_view *prev_view, const tdt_image *prev_guide, const tdt_image *prev_hist,
+                                const tdt_image *prev_moments, float max_samples, tdt_image *hist_out, tdt_image *moments_out,
+                                tdt_image *mean_out, uint32_t flags);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

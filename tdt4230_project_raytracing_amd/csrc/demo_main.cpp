@@ -13,7 +13,7 @@
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
-//            [--compact] [--config N] [--device N] [--denoise N] [--temporal N [--turn DEG]] [--out frame.pfm] [--png frame.png]
+//            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -21,6 +21,9 @@
 //   S / N = sprint / normal speed.  --png writes the frame as the quad pass would present it (main.rs:582-600).
 // --denoise N: the frame as accumulate, guide, N filter passes, resolve (ComputeShader::dispatch_guide, Texture::denoise) instead
 //   of the one dispatch: running sums averaged within each visible voxel face, before the square root.
+// --variance SIGMA (with --denoise N): the N passes are the variance-guided ones (Texture::variance, Texture::denoise_variance): the
+//   variance of each pixel's luminance, from its 7x7 same-key neighbourhood or, with --temporal, from the moments of the frames
+//   behind it (Texture::reproject_moments) where there are at least 4, scales a second, luminance edge-stopping weight.
 // --temporal N [--turn DEG]: N frames instead of one, the camera yawing DEG degrees (default 1) before every frame but the first
 //   (turn_yaw takes units of 2 * turn_rate radians; DEG is converted with the camera's turn_rate, that of --settings included),
 //   each frame's spp samples joined by the history of the frame before wherever that frame saw the same surface point
@@ -109,7 +112,7 @@ int main(int argc, char **argv) {
   long long pad_cells = 0;
   std::vector<int32_t> box;
   int config = -1, denoise = 0, temporal = 0;
-  float turn = 1.0f;
+  float turn = 1.0f, variance = 0.0f;                                                    // variance 0: the key-only filter
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -127,6 +130,7 @@ int main(int argc, char **argv) {
     else if (a == "--material") { material = std::atoi(next()); material_given = true; }
     else if (a == "--compact") compact = true;
     else if (a == "--denoise") { denoise = std::atoi(next()); if (denoise < 0 || denoise > 8) { std::fprintf(stderr, "--denoise 0..8\n"); return 2; } }
+    else if (a == "--variance") { variance = (float)std::atof(next()); if (!(variance > 0.0f) || !(variance < 1e30f)) { std::fprintf(stderr, "--variance SIGMA, SIGMA > 0\n"); return 2; } }
     else if (a == "--temporal") { temporal = std::atoi(next()); if (temporal < 1) { std::fprintf(stderr, "--temporal N, N >= 1\n"); return 2; } }
     else if (a == "--turn") turn = (float)std::atof(next());
     else if (a == "--brush") {
@@ -207,6 +211,7 @@ int main(int argc, char **argv) {
     else if (a == "--config") config = std::atoi(next());
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
+  if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
   if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
   try {
     Context ctx(device);
@@ -484,6 +489,8 @@ int main(int argc, char **argv) {
       const int tw = camera.render_texture.width(), th = camera.render_texture.height();
       const Texture hist[2] = {Texture::new_2d(ctx, tw, th, false), Texture::new_2d(ctx, tw, th, false)};
       const Texture guides[2] = {Texture::new_2d(ctx, tw, th, false), Texture::new_2d(ctx, tw, th, false)};
+      std::vector<Texture> moments;                                                      // (two more images, only with --variance)
+      if (variance > 0.0f) for (int i = 0; i < 2; i++) moments.push_back(Texture::new_2d(ctx, tw, th, false));
       const tdt_compute *const prog = raytrace_program.program.id();
       tdt_view prev_view = {};
       // turn_yaw(angle) rotates by 2 * angle * turn_rate radians (camera.rs:56-62), so DEG degrees are this many of its units
@@ -493,9 +500,17 @@ int main(int argc, char **argv) {
         if (k) { camera.turn_yaw(raytrace_program.program, turn_units); camera.render_texture.clear(); }
         ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, k * spp, spp, nullptr));
         raytrace_program.dispatch_guide(guides[cur], k * spp);
-        camera.render_texture.reproject(raytrace_program, k * spp, guides[cur], spp, k ? &prev_view : nullptr, k ? &guides[old] : nullptr,
-                                        k ? &hist[old] : nullptr, 64.0f, hist[cur], &camera.render_texture);
-        if (denoise > 0) camera.render_texture.denoise(guides[cur], denoise);
+        if (variance > 0.0f) {
+          camera.render_texture.reproject_moments(raytrace_program, k * spp, guides[cur], spp, k ? &prev_view : nullptr, k ? &guides[old] : nullptr,
+                                                  k ? &hist[old] : nullptr, k ? &moments[old] : nullptr, 64.0f, hist[cur], moments[cur],
+                                                  &camera.render_texture);
+          camera.render_texture.variance(guides[cur], &moments[cur]);
+          camera.render_texture.denoise_variance(guides[cur], denoise, variance);
+        } else {
+          camera.render_texture.reproject(raytrace_program, k * spp, guides[cur], spp, k ? &prev_view : nullptr, k ? &guides[old] : nullptr,
+                                          k ? &hist[old] : nullptr, 64.0f, hist[cur], &camera.render_texture);
+          if (denoise > 0) camera.render_texture.denoise(guides[cur], denoise);
+        }
         ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, 1));
         ctx.check(tdt_compute_view(prog, &prev_view));
       }
@@ -507,7 +522,12 @@ int main(int argc, char **argv) {
       const Texture guide = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
       ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, 0, spp, nullptr));
       raytrace_program.dispatch_guide(guide);
-      camera.render_texture.denoise(guide, denoise);
+      if (variance > 0.0f) {
+        camera.render_texture.variance(guide);
+        camera.render_texture.denoise_variance(guide, denoise, variance);
+      } else {
+        camera.render_texture.denoise(guide, denoise);
+      }
       ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, spp));
     } else {
       raytrace_program.dispatch_compute(dw, dh, dd);

@@ -1,0 +1,109 @@
+// The device side both reprojection kernels share (tdt_reproject.hip: reproject_kernel; tdt_variance.hip:
+// reproject_moments_kernel): the per-call arguments and the one body, so that Q and the FOUND predicate exist once.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "trace_params.h"
+#include "trace_device.hpp"
+#include "denoise_device.hpp"
+
+namespace tdt {
+
+constexpr uint32_t kReprojectTile = 16;              // as the guide kernel's tile
+
+struct ReprojectArgs {
+  float ru[3], rv[3], rw[3];                         // rows of det * inverse(a | b | c) of the earlier view, det > 0
+  float org[3];                                      // its origin
+  float sx, sy;                                      // (float)(image_width - 1), (float)(image_height - 1) of the earlier view
+  float fpw, fph;                                    // (float) sizes of the earlier images
+  int pw;                                            // their row length
+  int has_prev;
+  float fspp, max_samples;
+};
+
+// The one body of both kernels.  MOMENTS adds the moments image (tdt_image_reproject_moments): the frame's luminance and its
+// square join the moments of the texel the history came from; everything else, Q and the FOUND predicate included, is this code.
+template <bool MOMENTS>
+TDT_DEV void reproject_body(const TraceParams &P, int sample, const ReprojectArgs &A, const uint4 *__restrict__ guide, const float4 *sums,
+                            const uint4 *__restrict__ prev_guide, const float4 *__restrict__ prev_hist, float4 *__restrict__ hist_out,
+                            float4 *mean_out, int w, int h, uint32_t tiles_x, unsigned long long *__restrict__ counts,
+                            const float4 *__restrict__ prev_moments, float4 *__restrict__ moments_out, float mf) {
+  __shared__ uint32_t s_count[4];
+  if (threadIdx.x < 4) s_count[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int x = (int)(tx * kReprojectTile + (threadIdx.x & (kReprojectTile - 1))), y = (int)(ty * kReprojectTile + threadIdx.x / kReprojectTile);
+  // what became of this lane's pixel: 0 = outside the image or not keyed, 1 = found, 2 = rejected by key or hn, 3 = by nw or off-screen
+  uint32_t fate = 0u;
+  bool keyed = false;
+  if (x < w && y < h) {
+    const size_t p = (size_t)y * (size_t)w + (size_t)x;
+    const uint4 g = guide[p];
+    const float4 s = sums[p];
+    float4 o = make_float4(s.x, s.y, s.z, A.fspp);
+    float4 mo = make_float4(0.f, 0.f, 1.0f, 0.f);
+    if (MOMENTS) {
+      const float l = lum(s.x / A.fspp, s.y / A.fspp, s.z / A.fspp);
+      mo.x = l; mo.y = l * l;
+    }
+    keyed = g.x != 0u;
+    if (keyed && A.has_prev) {
+      const Ray r = primary_ray(P, x, y, sample);
+      const float t = __uint_as_float(g.w);
+      const float dx = (r.ox + t * r.dx) - A.org[0], dy = (r.oy + t * r.dy) - A.org[1], dz = (r.oz + t * r.dz) - A.org[2];
+      const float nu = (A.ru[2] * dz + A.ru[1] * dy) + A.ru[0] * dx;
+      const float nv = (A.rv[2] * dz + A.rv[1] * dy) + A.rv[0] * dx;
+      const float nw = (A.rw[2] * dz + A.rw[1] * dy) + A.rw[0] * dx;
+      const float fx = (nu / nw) * A.sx, fy = (nv / nw) * A.sy;
+      fate = 3u;
+      if (nw > 0.f && fx >= 0.f && fx < A.fpw && fy >= 0.f && fy < A.fph) {
+        const size_t q = (size_t)(int)fy * (size_t)A.pw + (size_t)(int)fx;
+        const uint4 k = prev_guide[q];
+        fate = 2u;
+        if (k.x == g.x && k.y == g.y && k.z == g.z) {
+          float4 hq = prev_hist[q];
+          if (hq.w > 0.f) {
+            fate = 1u;
+            if (hq.w > A.max_samples) {
+              const float sc = A.max_samples / hq.w;
+              hq.x = hq.x * sc; hq.y = hq.y * sc; hq.z = hq.z * sc; hq.w = A.max_samples;
+            }
+            o = make_float4(s.x + hq.x, s.y + hq.y, s.z + hq.z, A.fspp + hq.w);
+            if (MOMENTS) {
+              float4 hm = prev_moments[q];
+              if (hm.z > 0.f) {
+                if (hm.z > mf) {
+                  const float sc = mf / hm.z;
+                  hm.x = hm.x * sc; hm.y = hm.y * sc; hm.z = mf;
+                }
+                mo = make_float4(mo.x + hm.x, mo.y + hm.y, 1.0f + hm.z, 0.f);
+              }
+            }
+          }
+        }
+      }
+    }
+    hist_out[p] = o;
+    if (MOMENTS) moments_out[p] = mo;
+    if (mean_out) mean_out[p] = make_float4(o.x / o.w, o.y / o.w, o.z / o.w, 1.0f);
+  }
+  // the block's counts: one LDS add per wave and counter, then one global add per counter
+  const unsigned long long m0 = __ballot(keyed), m1 = __ballot(fate == 1u), m2 = __ballot(fate == 2u), m3 = __ballot(fate == 3u);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (m0) atomicAdd(&s_count[0], (uint32_t)__popcll(m0));
+    if (m1) atomicAdd(&s_count[1], (uint32_t)__popcll(m1));
+    if (m2) atomicAdd(&s_count[2], (uint32_t)__popcll(m2));
+    if (m3) atomicAdd(&s_count[3], (uint32_t)__popcll(m3));
+  }
+  __syncthreads();
+  if (threadIdx.x < 4 && s_count[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_count[threadIdx.x]);
+}
+
+// tdt_variance.hip: launches reproject_moments_kernel, the MOMENTS form of the body (the arguments of reproject_kernel, then the earlier
+// frame's moments or null, the moments image to write, and mf = max_samples / (float)spp)
+void reproject_moments_launch(dim3 grid, hipStream_t stream, const TraceParams &P, int sample, const ReprojectArgs &A, const uint4 *guide,
+                              const float4 *sums, const uint4 *prev_guide, const float4 *prev_hist, float4 *hist_out, float4 *mean_out, int w, int h,
+                              uint32_t tiles_x, unsigned long long *counts, const float4 *prev_moments, float4 *moments_out, float mf);
+
+}  // namespace tdt

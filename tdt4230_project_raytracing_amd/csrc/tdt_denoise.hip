@@ -13,6 +13,7 @@
 
 #include "tdt_internal.hpp"
 #include "query_device.hpp"
+#include "denoise_device.hpp"
 
 namespace tdt {
 
@@ -48,14 +49,7 @@ __global__ __launch_bounds__(256) void guide_kernel(const TraceParams P, int sam
   guide[(size_t)y * (size_t)gw + (size_t)x] = make_uint4(kind, q.material, plane, __float_as_uint(q.t));
 }
 
-// ---- the filter ----
-constexpr int kTileW = 32, kTileH = 8;               // pixels of a block, one per lane
-constexpr int kMaxPasses = 8;
-
-// words 0, 1, 2 of a guide texel; w = 1 marks a texel inside the image (outside: all four zero, which matches no centre)
-TDT_DEV uint4 key_of(const uint4 g) { return make_uint4(g.x, g.y, g.z, 1u); }
-TDT_DEV bool same_key(const uint4 a, const uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
-
+// ---- the filter (tile, key_of, same_key, tile_origin: denoise_device.hpp, shared with tdt_variance.hip) ----
 struct Sums { float r, g, b, den; };
 // one kept tap: w = k[j] * k[i] (exact), unfused multiply, then add (the build's parity flags)
 TDT_DEV void add_tap(Sums &s, int j, int i, const float4 c) {
@@ -65,11 +59,6 @@ TDT_DEV void add_tap(Sums &s, int j, int i, const float4 c) {
   s.den = s.den + w;
 }
 TDT_DEV float4 finish(const Sums &s, const float4 centre) { return make_float4(s.r / s.den, s.g / s.den, s.b / s.den, centre.w); }
-
-TDT_DEV void tile_origin(uint32_t tiles_x, int &x0, int &y0) {
-  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  x0 = (int)tx * kTileW; y0 = (int)ty * kTileH;
-}
 
 // steps 1 and 2: the tile and its halo of 2 * S texels through LDS
 template <int S>
@@ -158,6 +147,22 @@ int denoise_scratch(tdt_ctx *front, tdt_ctx *m, size_t bytes, void **out) {
 
 }  // namespace
 
+int denoise_sequence(tdt_ctx *front, tdt_ctx *m, float *img, int w, int h, int passes, float **seq) {
+  // The result must end in img.  An even number of passes alternates img -> S1 -> img; an odd number of three or more opens with
+  // img -> S1 -> S2 -> img, which leaves an even rest; one pass alone goes to S1 and is copied back (a pass cannot run in place).
+  const size_t bytes = (size_t)w * (size_t)h * 16;
+  const bool three = (passes & 1) && passes >= 3;
+  void *scratch = nullptr;
+  if (int rc = denoise_scratch(front, m, three ? 2 * bytes : bytes, &scratch)) return rc;
+  float *const I = img, *const S1 = (float *)scratch, *const S2 = (float *)((char *)scratch + bytes);
+  int n = 0, rest = passes;
+  seq[n++] = I;
+  if (three) { seq[n++] = S1; seq[n++] = S2; seq[n++] = I; rest -= 3; }
+  for (; rest >= 2; rest -= 2) { seq[n++] = S1; seq[n++] = I; }
+  if (rest) seq[n++] = S1;
+  return TDT_OK;
+}
+
 void denoise_scratch_destroy(tdt_ctx *ctx) {
   if (ctx->denoise) (void)hipFree(ctx->denoise);
   ctx->denoise = nullptr; ctx->denoise_bytes = 0;
@@ -218,23 +223,14 @@ int tdt_image_denoise(tdt_image *img, const tdt_image *guide, int passes, uint32
   if (tiles_x * tiles_y > 0x7FFFFFFFull) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "image too large");
   tdt_ctx *m = tdt::first_member(ctx);
   TDT_HIP(ctx, hipSetDevice(m->device));
-  // The result must end in img.  An even number of passes alternates img -> S1 -> img; an odd number of three or more opens with
-  // img -> S1 -> S2 -> img, which leaves an even rest; one pass alone goes to S1 and is copied back (a pass cannot run in place).
+  float *seq[tdt::kMaxPasses + 1];
+  if (int rc = tdt::denoise_sequence(ctx, m, a->dev, a->w, a->h, passes, seq)) return rc;
+  float *const I = seq[0];
   const size_t bytes = (size_t)a->w * (size_t)a->h * 16;
-  const bool three = (passes & 1) && passes >= 3;
-  void *scratch = nullptr;
-  if (int rc = tdt::denoise_scratch(ctx, m, three ? 2 * bytes : bytes, &scratch)) return rc;
-  float4 *const I = (float4 *)a->dev, *const S1 = (float4 *)scratch, *const S2 = (float4 *)((char *)scratch + bytes);
-  float4 *seq[tdt::kMaxPasses + 1];
-  int n = 0, rest = passes;
-  seq[n++] = I;
-  if (three) { seq[n++] = S1; seq[n++] = S2; seq[n++] = I; rest -= 3; }
-  for (; rest >= 2; rest -= 2) { seq[n++] = S1; seq[n++] = I; }
-  if (rest) seq[n++] = S1;
   const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
   for (int p = 0; p < passes; p++) {
-    const float4 *src = seq[p];
-    float4 *dst = seq[p + 1];
+    const float4 *src = (const float4 *)seq[p];
+    float4 *dst = (float4 *)seq[p + 1];
     if (p == 0) hipLaunchKernelGGL(tdt::denoise_tile_kernel<1>, grid, block, 0, m->stream, src, (const uint4 *)g->dev, dst, a->w, a->h, (uint32_t)tiles_x);
     else if (p == 1) hipLaunchKernelGGL(tdt::denoise_tile_kernel<2>, grid, block, 0, m->stream, src, (const uint4 *)g->dev, dst, a->w, a->h, (uint32_t)tiles_x);
     else hipLaunchKernelGGL(tdt::denoise_gather_kernel, grid, block, 0, m->stream, src, (const uint4 *)g->dev, dst, a->w, a->h, 1 << p, (uint32_t)tiles_x);

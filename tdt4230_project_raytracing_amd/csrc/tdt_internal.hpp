@@ -8,7 +8,8 @@
 // the tree's list to the result's (its templates over a unit's own kernels: bitvol_device.hpp); tdt_xform.hip: affine
 // transforms of selections; tdt_geodesic.hip: geodesic distance; tdt_voxlist.hip: the Morton-sorted voxel list the list-based units
 // share: the capped tree list, keys, last-of-run unique, scan-gather-count); tdt_denoise.hip: first-hit guide images and the
-// edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides.  The host helpers
+// edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides; tdt_variance.hip: the
+// variance of the luminance and the filter it guides.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
@@ -323,10 +324,19 @@ void query_camera(const tdt_compute *cam, TraceParams &P);
 
 // ---- tdt_denoise.hip ----
 void denoise_scratch_destroy(tdt_ctx *ctx);
+// the images passes 0 .. passes - 1 (1..8) of an in-place filter over img (w x h RGBA32F on member m) read and write: pass p goes
+// seq[p] -> seq[p + 1], seq[0] = img, the others the context's grow-only scratch; seq holds passes + 1 entries.  Ends in img
+// unless passes == 1 (the caller copies seq[1] back).  tdt_variance.hip's filter runs through the same sequence.
+int denoise_sequence(tdt_ctx *front, tdt_ctx *m, float *img, int w, int h, int passes, float **seq);
 // the image a call works on: a multi-device handle stands for the assembled frame on the first device
 inline const tdt_image *device_image(const tdt_image *img) { return img->ctx->multi ? img->full : img; }
 
 // ---- tdt_reproject.hip ----
 void reproject_counts_destroy(tdt_ctx *ctx);
+// do two images share memory?
+inline bool overlap(const tdt_image *a, const tdt_image *b) {
+  const float *ea = a->dev + (size_t)a->w * (size_t)a->h * 4, *eb = b->dev + (size_t)b->w * (size_t)b->h * 4;
+  return a->dev < eb && b->dev < ea;
+}
 
 }  // namespace tdt

@@ -1,11 +1,13 @@
-// Temporal reprojection (include/tdt_rt.h, tdt_compute_view / tdt_image_reproject / tdt_debug_reproject_counts).
+// Temporal reprojection (include/tdt_rt.h, tdt_compute_view / tdt_image_reproject / tdt_image_reproject_moments /
+// tdt_debug_reproject_counts).
 //
 // One lane per pixel of the current frame: the world point its guide texel stands for (primary ray origin + t * direction) is
 // projected into an earlier frame's view, and that frame's history texel is added to this frame's sums when its guide texel carries
 // the same key.  Voxel faces are axis-aligned planes, so an equal key (kind, material, plane) means "the old pixel saw this face
 // at this point" with no tolerance.  The projection is three dot products with the rows of the inverse of (horizontal, vertical,
 // lower_left_corner - origin) scaled by its determinant (the host computes them once per call, in double), and two divides.
-// The arithmetic and its order are the header's, so a numpy model gives the same bits.
+// The arithmetic and its order are the header's, so a numpy model gives the same bits.  The kernel's body is reproject_device.hpp's,
+// which the moments form (tdt_image_reproject_moments: this file's host code, tdt_variance.hip's kernel) instantiates as well.
 //
 // The kernel is a gather bound by memory: 32 B read and 16 or 32 B written per pixel at home, and up to 32 B gathered from the old
 // frame.  A block covers a 16x16 tile, so that the old frame's texels its lanes ask for lie close together too.
@@ -15,79 +17,17 @@
 #include "tdt_internal.hpp"
 #include "trace_params.h"
 #include "trace_device.hpp"
+#include "reproject_device.hpp"
 
 namespace tdt {
 
-constexpr uint32_t kReprojectTile = 16;              // as the guide kernel's tile
 constexpr int kMaxPrevSide = 1 << 24;                // (float)side is exact up to here: fx < (float)prev_w then bounds (int)fx
-
-struct ReprojectArgs {
-  float ru[3], rv[3], rw[3];                         // rows of det * inverse(a | b | c) of the earlier view, det > 0
-  float org[3];                                      // its origin
-  float sx, sy;                                      // (float)(image_width - 1), (float)(image_height - 1) of the earlier view
-  float fpw, fph;                                    // (float) sizes of the earlier images
-  int pw;                                            // their row length
-  int has_prev;
-  float fspp, max_samples;
-};
 
 __global__ __launch_bounds__(256) void reproject_kernel(const TraceParams P, int sample, const ReprojectArgs A, const uint4 *__restrict__ guide,
                                                         const float4 *sums, const uint4 *__restrict__ prev_guide,
                                                         const float4 *__restrict__ prev_hist, float4 *__restrict__ hist_out, float4 *mean_out,
                                                         int w, int h, uint32_t tiles_x, unsigned long long *__restrict__ counts) {
-  __shared__ uint32_t s_count[4];
-  if (threadIdx.x < 4) s_count[threadIdx.x] = 0u;
-  __syncthreads();
-  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int x = (int)(tx * kReprojectTile + (threadIdx.x & (kReprojectTile - 1))), y = (int)(ty * kReprojectTile + threadIdx.x / kReprojectTile);
-  // what became of this lane's pixel: 0 = outside the image or not keyed, 1 = found, 2 = rejected by key or hn, 3 = by nw or off-screen
-  uint32_t fate = 0u;
-  bool keyed = false;
-  if (x < w && y < h) {
-    const size_t p = (size_t)y * (size_t)w + (size_t)x;
-    const uint4 g = guide[p];
-    const float4 s = sums[p];
-    float4 o = make_float4(s.x, s.y, s.z, A.fspp);
-    keyed = g.x != 0u;
-    if (keyed && A.has_prev) {
-      const Ray r = primary_ray(P, x, y, sample);
-      const float t = __uint_as_float(g.w);
-      const float dx = (r.ox + t * r.dx) - A.org[0], dy = (r.oy + t * r.dy) - A.org[1], dz = (r.oz + t * r.dz) - A.org[2];
-      const float nu = (A.ru[2] * dz + A.ru[1] * dy) + A.ru[0] * dx;
-      const float nv = (A.rv[2] * dz + A.rv[1] * dy) + A.rv[0] * dx;
-      const float nw = (A.rw[2] * dz + A.rw[1] * dy) + A.rw[0] * dx;
-      const float fx = (nu / nw) * A.sx, fy = (nv / nw) * A.sy;
-      fate = 3u;
-      if (nw > 0.f && fx >= 0.f && fx < A.fpw && fy >= 0.f && fy < A.fph) {
-        const size_t q = (size_t)(int)fy * (size_t)A.pw + (size_t)(int)fx;
-        const uint4 k = prev_guide[q];
-        fate = 2u;
-        if (k.x == g.x && k.y == g.y && k.z == g.z) {
-          float4 hq = prev_hist[q];
-          if (hq.w > 0.f) {
-            fate = 1u;
-            if (hq.w > A.max_samples) {
-              const float sc = A.max_samples / hq.w;
-              hq.x = hq.x * sc; hq.y = hq.y * sc; hq.z = hq.z * sc; hq.w = A.max_samples;
-            }
-            o = make_float4(s.x + hq.x, s.y + hq.y, s.z + hq.z, A.fspp + hq.w);
-          }
-        }
-      }
-    }
-    hist_out[p] = o;
-    if (mean_out) mean_out[p] = make_float4(o.x / o.w, o.y / o.w, o.z / o.w, 1.0f);
-  }
-  // the block's counts: one LDS add per wave and counter, then one global add per counter
-  const unsigned long long m0 = __ballot(keyed), m1 = __ballot(fate == 1u), m2 = __ballot(fate == 2u), m3 = __ballot(fate == 3u);
-  if ((threadIdx.x & 63u) == 0u) {
-    if (m0) atomicAdd(&s_count[0], (uint32_t)__popcll(m0));
-    if (m1) atomicAdd(&s_count[1], (uint32_t)__popcll(m1));
-    if (m2) atomicAdd(&s_count[2], (uint32_t)__popcll(m2));
-    if (m3) atomicAdd(&s_count[3], (uint32_t)__popcll(m3));
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && s_count[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_count[threadIdx.x]);
+  reproject_body<false>(P, sample, A, guide, sums, prev_guide, prev_hist, hist_out, mean_out, w, h, tiles_x, counts, nullptr, nullptr, 0.f);
 }
 
 namespace {
@@ -120,11 +60,6 @@ bool view_rows(const tdt_view &v, ReprojectArgs &A) {
   return true;
 }
 
-bool overlap(const tdt_image *a, const tdt_image *b) {
-  const float *ea = a->dev + (size_t)a->w * (size_t)a->h * 4, *eb = b->dev + (size_t)b->w * (size_t)b->h * 4;
-  return a->dev < eb && b->dev < ea;
-}
-
 }  // namespace
 
 void reproject_counts_destroy(tdt_ctx *ctx) {
@@ -151,17 +86,21 @@ int tdt_compute_view(const tdt_compute *c, tdt_view *out) {
   return TDT_OK;
 }
 
-int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp, const tdt_view *prev_view,
-                        const tdt_image *prev_guide, const tdt_image *prev_hist, float max_samples, tdt_image *hist_out, tdt_image *mean_out,
-                        uint32_t flags) {
+// both reprojection calls; with_moments: prev_moments comes and goes with the other prev_*, moments_out is required
+static int reproject_run(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp, const tdt_view *prev_view,
+                         const tdt_image *prev_guide, const tdt_image *prev_hist, const tdt_image *prev_moments, float max_samples,
+                         tdt_image *hist_out, tdt_image *moments_out, tdt_image *mean_out, uint32_t flags, bool with_moments) {
   if (!c) return TDT_ERR_INVALID_VALUE;
   tdt_ctx *ctx = c->ctx;
   if (!guide || !sums || !hist_out) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "null guide, sums or history image");
-  const bool has_prev = prev_view || prev_guide || prev_hist;
-  if (has_prev && !(prev_view && prev_guide && prev_hist))
-    return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier frame's view, guide and history come together or not at all");
+  if (with_moments && !moments_out) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "null moments image");
+  const bool has_prev = prev_view || prev_guide || prev_hist || prev_moments;
+  if (has_prev && !(prev_view && prev_guide && prev_hist && (prev_moments || !with_moments)))
+    return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, with_moments ? "the earlier frame's view, guide, history and moments come together or not at all"
+                                                              : "the earlier frame's view, guide and history come together or not at all");
   if (c->kind != TDT_PROGRAM_RAYTRACER) return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "reprojection needs a raytracer program (its camera)");
-  const tdt_image *handles[6] = {guide, sums, hist_out, mean_out, prev_guide, prev_hist};
+  constexpr int N = 8;
+  const tdt_image *handles[N] = {guide, sums, hist_out, mean_out, prev_guide, prev_hist, prev_moments, moments_out};
   for (const tdt_image *i : handles)
     if (i && i->ctx != ctx) return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "an image belongs to another context");
   if (c->part_rank != 0 || c->part_world != 1)
@@ -170,13 +109,14 @@ int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, cons
   if (spp < 1) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "spp must be at least 1");
   if (flags != 0) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "flags must be 0");
   if (!(max_samples >= 1.0f)) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "max_samples must be at least 1");
-  const tdt_image *im[6];
-  for (int i = 0; i < 6; i++) im[i] = handles[i] ? tdt::device_image(handles[i]) : nullptr;
-  const tdt_image *g = im[0], *s = im[1], *ho = im[2], *mo = im[3], *pg = im[4], *ph = im[5];
-  if (s->w != g->w || s->h != g->h || ho->w != g->w || ho->h != g->h || (mo && (mo->w != g->w || mo->h != g->h)))
-    return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "guide, sums, history and mean differ in size");
-  for (int i = 0; i < 6; i++)
-    for (int j = i + 1; j < 6; j++) {
+  const tdt_image *im[N];
+  for (int i = 0; i < N; i++) im[i] = handles[i] ? tdt::device_image(handles[i]) : nullptr;
+  const tdt_image *g = im[0], *s = im[1], *ho = im[2], *mo = im[3], *pg = im[4], *ph = im[5], *pm = im[6], *mm = im[7];
+  if (s->w != g->w || s->h != g->h || ho->w != g->w || ho->h != g->h || (mo && (mo->w != g->w || mo->h != g->h)) ||
+      (mm && (mm->w != g->w || mm->h != g->h)))
+    return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, with_moments ? "guide, sums, history, moments and mean differ in size" : "guide, sums, history and mean differ in size");
+  for (int i = 0; i < N; i++)
+    for (int j = i + 1; j < N; j++) {
       if (!im[i] || !im[j]) continue;
       if (i == 1 && j == 3 && im[i]->dev == im[j]->dev) continue;        // mean_out == sums: in place
       if (im[i] == im[j] || tdt::overlap(im[i], im[j])) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "two of the images are one (or share memory)");
@@ -184,6 +124,7 @@ int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, cons
   tdt::ReprojectArgs A = {};
   if (has_prev) {
     if (pg->w != ph->w || pg->h != ph->h) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier guide and history differ in size");
+    if (pm && (pm->w != pg->w || pm->h != pg->h)) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier guide and moments differ in size");
     if (pg->w > tdt::kMaxPrevSide || pg->h > tdt::kMaxPrevSide) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier images are too large");
     if (prev_view->image_width < 2 || prev_view->image_height < 2)
       return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier view's image_width and image_height must be at least 2");
@@ -207,11 +148,32 @@ int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, cons
   }
   TDT_HIP(ctx, hipMemsetAsync(m->reproject_counts, 0, 4 * sizeof(unsigned long long), m->stream));
   if (tiles_x * tiles_y == 0) return TDT_OK;                             // (an empty image: the counts of this call are zero)
-  hipLaunchKernelGGL(tdt::reproject_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, m->stream, P, sample, A, (const uint4 *)g->dev,
-                     (const float4 *)s->dev, has_prev ? (const uint4 *)pg->dev : nullptr, has_prev ? (const float4 *)ph->dev : nullptr,
-                     (float4 *)ho->dev, mo ? (float4 *)mo->dev : nullptr, g->w, g->h, (uint32_t)tiles_x, m->reproject_counts);
+  const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
+  const uint4 *PG = has_prev ? (const uint4 *)pg->dev : nullptr;
+  const float4 *PH = has_prev ? (const float4 *)ph->dev : nullptr;
+  float4 *MO = mo ? (float4 *)mo->dev : nullptr;
+  if (with_moments)                                                      // (that kernel is tdt_variance.hip's, over the same body)
+    tdt::reproject_moments_launch(grid, m->stream, P, sample, A, (const uint4 *)g->dev, (const float4 *)s->dev, PG, PH, (float4 *)ho->dev, MO, g->w,
+                                  g->h, (uint32_t)tiles_x, m->reproject_counts, has_prev ? (const float4 *)pm->dev : nullptr, (float4 *)mm->dev,
+                                  max_samples / (float)spp);
+  else
+    hipLaunchKernelGGL(tdt::reproject_kernel, grid, block, 0, m->stream, P, sample, A, (const uint4 *)g->dev, (const float4 *)s->dev, PG, PH,
+                       (float4 *)ho->dev, MO, g->w, g->h, (uint32_t)tiles_x, m->reproject_counts);
   TDT_HIP(ctx, hipGetLastError());
   return TDT_OK;
+}
+
+int tdt_image_reproject(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp, const tdt_view *prev_view,
+                        const tdt_image *prev_guide, const tdt_image *prev_hist, float max_samples, tdt_image *hist_out, tdt_image *mean_out,
+                        uint32_t flags) {
+  return reproject_run(c, sample, guide, sums, spp, prev_view, prev_guide, prev_hist, nullptr, max_samples, hist_out, nullptr, mean_out, flags, false);
+}
+
+int tdt_image_reproject_moments(tdt_compute *c, int sample, const tdt_image *guide, const tdt_image *sums, int spp, const tdt_view *prev_view,
+                                const tdt_image *prev_guide, const tdt_image *prev_hist, const tdt_image *prev_moments, float max_samples,
+                                tdt_image *hist_out, tdt_image *moments_out, tdt_image *mean_out, uint32_t flags) {
+  return reproject_run(c, sample, guide, sums, spp, prev_view, prev_guide, prev_hist, prev_moments, max_samples, hist_out, moments_out, mean_out,
+                       flags, true);
 }
 
 int tdt_image_clear(tdt_image *img) {

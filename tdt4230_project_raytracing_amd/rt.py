@@ -318,6 +318,9 @@ SYMBOLS = [
     ("tdt_image_reproject", _I, [_P, _I, _P, _P, _I, ctypes.POINTER(VIEW), _P, _P, _F, _P, _P, ctypes.c_uint32]),
     ("tdt_debug_reproject_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_image_clear", _I, [_P]),
+    ("tdt_image_variance", _I, [_P, _P, _P, _F, ctypes.c_uint32]),
+    ("tdt_image_denoise_variance", _I, [_P, _P, _I, _F, _F, ctypes.c_uint32]),
+    ("tdt_image_reproject_moments", _I, [_P, _I, _P, _P, _I, ctypes.POINTER(VIEW), _P, _P, _P, _F, _P, _P, _P, ctypes.c_uint32]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -1067,6 +1070,30 @@ class Texture:
                                                  pg.h if pg is not None else None, ph.h if ph is not None else None, float(max_samples),
                                                  hist_out.h, mean_out.h if mean_out is not None else None, 0))
 
+    def variance(self, guide, moments=None, min_frames=4.0):
+        """tdt_image_variance: this image's alpha becomes the variance of the luminance of its rgb — 0 for kind-0 pixels, from the
+        temporal moments (a Texture that reproject_moments wrote) where a pixel has at least min_frames frames behind it, from
+        its 7x7 same-key neighbourhood elsewhere.  rgb is left as it is.  Asynchronous."""
+        self.ctx.check(lib().tdt_image_variance(self.h, guide.h, moments.h if moments is not None else None, float(min_frames), 0))
+
+    def denoise_variance(self, guide, passes, sigma, floor=0.0):
+        """tdt_image_denoise_variance: denoise's passes with a second edge-stopping weight max(lim - d^2, 0) on the difference d of
+        luminance, lim = sigma^2 * (the centre's 3x3 prefiltered variance, read from alpha) + floor; alpha carries the variance of
+        the filtered pixel on.  Pixels of kind 0, and those whose lim is not positive and finite, are copied.  Asynchronous."""
+        self.ctx.check(lib().tdt_image_denoise_variance(self.h, guide.h, int(passes), float(sigma), float(floor), 0))
+
+    def reproject_moments(self, shader, sample, guide, spp, prev=None, max_samples=64.0, hist_out=None, moments_out=None, mean_out=None):
+        """tdt_image_reproject_moments: reproject, and moments_out receives (sum of the frames' luminances, sum of their squares,
+        frame count, 0) joined with the earlier frame's moments wherever its history was found; prev = (VIEW, guide Texture, history
+        Texture, moments Texture) of the earlier frame or None for a first frame.  Asynchronous."""
+        if hist_out is None or moments_out is None:
+            raise ValueError("reproject_moments needs a history and a moments texture to write (hist_out, moments_out)")
+        view, pg, ph, pm = prev if prev is not None else (None, None, None, None)
+        self.ctx.check(lib().tdt_image_reproject_moments(shader.h, int(sample), guide.h, self.h, int(spp),
+                                                         ctypes.byref(view) if view is not None else None, pg.h if pg is not None else None,
+                                                         ph.h if ph is not None else None, pm.h if pm is not None else None, float(max_samples),
+                                                         hist_out.h, moments_out.h, mean_out.h if mean_out is not None else None, 0))
+
 
 class Program:
     """Uniform-by-name setters of program.rs:35-83 (the program object itself is the kernel)."""
@@ -1267,6 +1294,8 @@ def upload_scene(ctx, scene):
 # up to 2^20 the float spacing of that product (2^-9) is far below K, so consecutive samples still get different jitter; near
 # 2^24 they would coincide, and k * spp as a C int would overflow later still.
 TEMPORAL_SAMPLE_PERIOD = 1 << 20
+# The sigma of Texture.denoise_variance that DESIGN.md's quality table recommends: renderer.variance = VARIANCE_SIGMA.
+VARIANCE_SIGMA = 4.0
 
 
 class Renderer:
@@ -1291,6 +1320,10 @@ class Renderer:
             self.texture = Texture.new_2d(self.ctx, w, rows)
         self.guide = None                      # render(denoise=N) creates it on first use
         self.temporal = None                   # render_temporal's state, created on first use
+        # sigma of the variance-guided filter that render(denoise=N) and render_temporal(denoise=N) run instead of the key-only one;
+        # None: the key-only filter, exactly the calls made before the variance unit existed.  VARIANCE_SIGMA is the measured default.
+        self.variance = None
+        self.variance_min_frames = 4.0         # render_temporal: frames behind a pixel from which its temporal variance is trusted
 
     def dispatch(self, width=None, height=None):
         """main.rs:579: dispatch_compute(texture.width() + 1, texture.height() + 1, 1)."""
@@ -1300,7 +1333,9 @@ class Renderer:
 
     def render(self, width=None, height=None, denoise=0):
         """The frame.  denoise = N > 0: the same samples as running sums (dispatch_accumulate), the first-hit guide of sample 0,
-        N filter passes over the sums, then the resolve — the square root is taken of the filtered sums."""
+        N filter passes over the sums, then the resolve — the square root is taken of the filtered sums.  With self.variance =
+        SIGMA the passes are the variance-guided ones (Texture.variance's spatial estimate, then Texture.denoise_variance with that
+        sigma); None, the default: the key-only filter."""
         if denoise > 0:
             w = self.camera.image_width + 1 if width is None else width
             h = self.camera.image_height + 1 if height is None else height
@@ -1309,7 +1344,11 @@ class Renderer:
                 self.guide = Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False)
             self.shader.dispatch_accumulate(w, h, 1, 0, spp)
             self.shader.dispatch_guide(self.guide)
-            self.texture.denoise(self.guide, denoise)
+            if self.variance is None:
+                self.texture.denoise(self.guide, denoise)
+            else:
+                self.texture.variance(self.guide)
+                self.texture.denoise_variance(self.guide, denoise, self.variance)
             self.shader.dispatch_resolve(w, h, 1, spp)
             return self.texture.read()
         self.dispatch(width, height)
@@ -1323,7 +1362,10 @@ class Renderer:
         starts again at frame 0 — after a scene edit, whose lighting change nothing here detects.  The renderer owns the frame
         counter, the two history and the two guide textures and the previous view.  The sample index wraps to 0 every
         TEMPORAL_SAMPLE_PERIOD // spp frames (the history is kept): a session of any length stays inside the range in which the
-        sampler tells samples apart.  Returns the resolved frame.  A single-device
+        sampler tells samples apart.  With self.variance = SIGMA and denoise > 0 the frames also carry luminance moments
+        (Texture.reproject_moments; two more textures, created when first asked for), Texture.variance takes the temporal estimate
+        where a pixel has enough frames and the spatial one elsewhere, and the passes are Texture.denoise_variance's; asked for in
+        the middle of a sequence, the moments start at that frame.  Returns the resolved frame.  A single-device
         renderer whose image is the whole frame only: on several devices the running sums live in per-device tile buffers."""
         if self.ctx.device_count() != 1 or self.texture.width() != self.camera.image_width or self.texture.height() != self.camera.image_height:
             raise ValueError("render_temporal needs a single-device renderer that owns the whole image")
@@ -1349,9 +1391,23 @@ class Renderer:
         self.shader.dispatch_accumulate(w, h, 1, sample, spp)
         self.shader.dispatch_guide(t["guide"][cur], sample=sample)
         prev = (t["view"], t["guide"][old], t["hist"][old]) if t["view"] is not None else None
-        self.texture.reproject(self.shader, sample, t["guide"][cur], spp, prev, max_samples, hist_out=t["hist"][cur], mean_out=self.texture)
-        if denoise > 0:
-            self.texture.denoise(t["guide"][cur], denoise)
+        if self.variance is not None and denoise > 0:
+            if "moments" not in t:
+                t["moments"] = (Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False),
+                                Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False))
+                t["moments_live"] = False
+            if not t["moments_live"]:
+                t["moments"][old].clear()              # (the frame before wrote none: frame count 0, nothing behind this one)
+            self.texture.reproject_moments(self.shader, sample, t["guide"][cur], spp, prev + (t["moments"][old],) if prev is not None else None,
+                                           max_samples, hist_out=t["hist"][cur], moments_out=t["moments"][cur], mean_out=self.texture)
+            self.texture.variance(t["guide"][cur], t["moments"][cur], self.variance_min_frames)
+            self.texture.denoise_variance(t["guide"][cur], denoise, self.variance)
+            t["moments_live"] = True
+        else:
+            t["moments_live"] = False                  # (a frame without moments breaks their sequence)
+            self.texture.reproject(self.shader, sample, t["guide"][cur], spp, prev, max_samples, hist_out=t["hist"][cur], mean_out=self.texture)
+            if denoise > 0:
+                self.texture.denoise(t["guide"][cur], denoise)
         self.shader.dispatch_resolve(w, h, 1, 1)
         t["view"], t["frame"] = self.shader.view(), k + 1
         return self.texture.read()
