@@ -1,5 +1,5 @@
-// The device side both reprojection kernels share (tdt_reproject.hip: reproject_kernel; tdt_variance.hip:
-// reproject_moments_kernel): the per-call arguments and the one body, so that Q and the FOUND predicate exist once.
+// The device side both reprojection kernels of tdt_reproject.hip share (reproject_kernel, reproject_moments_kernel): the per-call
+// arguments and the one body, so that Q and the FOUND predicate exist once.  The block's tile is denoise_device.hpp's 16x16.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -9,8 +9,6 @@
 #include "denoise_device.hpp"
 
 namespace tdt {
-
-constexpr uint32_t kReprojectTile = 16;              // as the guide kernel's tile
 
 struct ReprojectArgs {
   float ru[3], rv[3], rw[3];                         // rows of det * inverse(a | b | c) of the earlier view, det > 0
@@ -32,8 +30,8 @@ TDT_DEV void reproject_body(const TraceParams &P, int sample, const ReprojectArg
   __shared__ uint32_t s_count[4];
   if (threadIdx.x < 4) s_count[threadIdx.x] = 0u;
   __syncthreads();
-  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int x = (int)(tx * kReprojectTile + (threadIdx.x & (kReprojectTile - 1))), y = (int)(ty * kReprojectTile + threadIdx.x / kReprojectTile);
+  int x, y;
+  ray_tile_pixel(tiles_x, x, y);
   // what became of this lane's pixel: 0 = outside the image or not keyed, 1 = found, 2 = rejected by key or hn, 3 = by nw or off-screen
   uint32_t fate = 0u;
   bool keyed = false;
@@ -99,11 +97,5 @@ TDT_DEV void reproject_body(const TraceParams &P, int sample, const ReprojectArg
   __syncthreads();
   if (threadIdx.x < 4 && s_count[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_count[threadIdx.x]);
 }
-
-// tdt_variance.hip: launches reproject_moments_kernel, the MOMENTS form of the body (the arguments of reproject_kernel, then the earlier
-// frame's moments or null, the moments image to write, and mf = max_samples / (float)spp)
-void reproject_moments_launch(dim3 grid, hipStream_t stream, const TraceParams &P, int sample, const ReprojectArgs &A, const uint4 *guide,
-                              const float4 *sums, const uint4 *prev_guide, const float4 *prev_hist, float4 *hist_out, float4 *mean_out, int w, int h,
-                              uint32_t tiles_x, unsigned long long *counts, const float4 *prev_moments, float4 *moments_out, float mf);
 
 }  // namespace tdt

@@ -9,14 +9,16 @@
 // transforms of selections; tdt_geodesic.hip: geodesic distance; tdt_voxlist.hip: the Morton-sorted voxel list the list-based units
 // share: the capped tree list, keys, last-of-run unique, scan-gather-count); tdt_denoise.hip: first-hit guide images and the
 // edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides; tdt_variance.hip: the
-// variance of the luminance and the filter it guides.  The host helpers
-// around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source.
+// variance of the luminance and the filter it guides (what these three share on the device: denoise_device.hpp).  The host helpers
+// around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
+// and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "tdt_rt.h"
@@ -322,21 +324,75 @@ int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P);
 // the camera uniforms of a program into P (what primary_ray reads)
 void query_camera(const tdt_compute *cam, TraceParams &P);
 
-// ---- tdt_denoise.hip ----
+// ---- tdt_denoise.hip, and the host frame of an image call that it, tdt_variance.hip and tdt_reproject.hip share ----
+constexpr int kMaxPasses = 8;
 void denoise_scratch_destroy(tdt_ctx *ctx);
+void reproject_counts_destroy(tdt_ctx *ctx);           // (tdt_reproject.hip)
 // the images passes 0 .. passes - 1 (1..8) of an in-place filter over img (w x h RGBA32F on member m) read and write: pass p goes
 // seq[p] -> seq[p + 1], seq[0] = img, the others the context's grow-only scratch; seq holds passes + 1 entries.  Ends in img
-// unless passes == 1 (the caller copies seq[1] back).  tdt_variance.hip's filter runs through the same sequence.
+// unless passes == 1 (run_passes copies seq[1] back).
 int denoise_sequence(tdt_ctx *front, tdt_ctx *m, float *img, int w, int h, int passes, float **seq);
 // the image a call works on: a multi-device handle stands for the assembled frame on the first device
 inline const tdt_image *device_image(const tdt_image *img) { return img->ctx->multi ? img->full : img; }
-
-// ---- tdt_reproject.hip ----
-void reproject_counts_destroy(tdt_ctx *ctx);
+// the program whose camera a call reads: a multi-device program's first member's
+inline const tdt_compute *camera_program(const tdt_compute *c) { return c->replicas.empty() ? c : c->replicas[0]; }
 // do two images share memory?
 inline bool overlap(const tdt_image *a, const tdt_image *b) {
   const float *ea = a->dev + (size_t)a->w * (size_t)a->h * 4, *eb = b->dev + (size_t)b->w * (size_t)b->h * 4;
   return a->dev < eb && b->dev < ea;
+}
+// one block per tw x th tile of a w x h image: the grid and its row length
+inline int image_grid(tdt_ctx *ctx, int w, int h, int tw, int th, const char *too_large, dim3 &grid, uint32_t &tiles_x) {
+  const unsigned long long nx = ((unsigned long long)w + tw - 1) / tw, ny = ((unsigned long long)h + th - 1) / th;
+  if (nx * ny > 0x7FFFFFFFull) return fail(ctx, TDT_ERR_INVALID_VALUE, too_large);
+  grid = dim3((unsigned)(nx * ny)); tiles_x = (uint32_t)nx;
+  return TDT_OK;
+}
+// The handles of an image call (null: not given), in two steps, because an entry point checks its other arguments in between.
+// First: every one belongs to ctx.
+inline int images_of_context(tdt_ctx *ctx, const tdt_image *const *handles, int n, const char *another_context) {
+  for (int i = 0; i < n; i++)
+    if (handles[i] && handles[i]->ctx != ctx) return fail(ctx, TDT_ERR_INVALID_OPERATION, another_context);
+  return TDT_OK;
+}
+// Then: im[i] = the device image of each; the first n_sized have the size of the first, and no two of the n are one image or
+// share memory — but for handles in_place_i < in_place_j at one address (tdt_image_reproject's mean_out == sums; -1: none).
+inline int images_fit(tdt_ctx *ctx, const tdt_image *const *handles, int n, int n_sized, const tdt_image **im, const char *differ_in_size,
+                      const char *share_memory, int in_place_i = -1, int in_place_j = -1) {
+  for (int i = 0; i < n; i++) im[i] = handles[i] ? device_image(handles[i]) : nullptr;
+  for (int i = 1; i < n_sized; i++)
+    if (im[i] && (im[i]->w != im[0]->w || im[i]->h != im[0]->h)) return fail(ctx, TDT_ERR_INVALID_VALUE, differ_in_size);
+  for (int i = 0; i < n; i++)
+    for (int j = i + 1; j < n; j++) {
+      if (!im[i] || !im[j]) continue;
+      if (i == in_place_i && j == in_place_j && im[i]->dev == im[j]->dev) continue;
+      if (im[i] == im[j] || overlap(im[i], im[j])) return fail(ctx, TDT_ERR_INVALID_VALUE, share_memory);
+    }
+  return TDT_OK;
+}
+// Passes 1..8 of an in-place filter over the image a, on the context's first member: the grid of tw x th tiles, the scratch
+// sequence, pass p (step 2^p) as launch(tile_step<1>{}) / launch(tile_step<2>{}) / launch(tile_step<0>{}) — the two LDS-tile
+// kernels, then the gather — with (step, grid, stream, src, dst, tiles_x), and the copy back when the sequence ends in the scratch.
+template <int S> using tile_step = std::integral_constant<int, S>;
+template <class Launch> int run_passes(tdt_ctx *ctx, const tdt_image *a, int passes, int tw, int th, Launch launch) {
+  dim3 grid;
+  uint32_t tiles_x;
+  if (int rc = image_grid(ctx, a->w, a->h, tw, th, "image too large", grid, tiles_x)) return rc;
+  tdt_ctx *m = first_member(ctx);
+  TDT_HIP(ctx, hipSetDevice(m->device));
+  float *seq[kMaxPasses + 1];
+  if (int rc = denoise_sequence(ctx, m, a->dev, a->w, a->h, passes, seq)) return rc;
+  for (int p = 0; p < passes; p++) {
+    const float *src = seq[p];
+    float *dst = seq[p + 1];
+    if (p == 0) launch(tile_step<1>{}, 1, grid, m->stream, src, dst, tiles_x);
+    else if (p == 1) launch(tile_step<2>{}, 2, grid, m->stream, src, dst, tiles_x);
+    else launch(tile_step<0>{}, 1 << p, grid, m->stream, src, dst, tiles_x);
+  }
+  TDT_HIP(ctx, hipGetLastError());
+  if (seq[passes] != seq[0])
+    TDT_HIP(ctx, hipMemcpyAsync(seq[0], seq[passes], (size_t)a->w * (size_t)a->h * 16, hipMemcpyDeviceToDevice, m->stream));
+  return TDT_OK;
 }
 
 }  // namespace tdt

@@ -157,7 +157,7 @@ int tdt_pick_pixels(tdt_compute *c, const int32_t *xy, size_t n, int sample, flo
   if (sample < 0) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "negative sample index");
   for (size_t i = 0; i < 2 * n; i++)
     if (xy[i] < 0) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "negative pixel coordinate");
-  const tdt_compute *cam = c->replicas.empty() ? c : c->replicas[0];     // (a multi-device program: its first member's camera)
+  const tdt_compute *cam = tdt::camera_program(c);
   tdt_ctx *m = cam->ctx;
   TraceParams P;
   if (int rc = tdt::query_params(ctx, m, P)) return rc;

@@ -6,11 +6,13 @@
 // the same key.  Voxel faces are axis-aligned planes, so an equal key (kind, material, plane) means "the old pixel saw this face
 // at this point" with no tolerance.  The projection is three dot products with the rows of the inverse of (horizontal, vertical,
 // lower_left_corner - origin) scaled by its determinant (the host computes them once per call, in double), and two divides.
-// The arithmetic and its order are the header's, so a numpy model gives the same bits.  The kernel's body is reproject_device.hpp's,
-// which the moments form (tdt_image_reproject_moments: this file's host code, tdt_variance.hip's kernel) instantiates as well.
+// The arithmetic and its order are the header's, so a numpy model gives the same bits.  Both kernels, reproject_kernel and the
+// moments form that feeds tdt_image_variance its temporal moments, instantiate the one body of reproject_device.hpp; the host
+// frame around them (handles, grid, camera program) is tdt_internal.hpp's, shared with tdt_denoise.hip and tdt_variance.hip.
 //
 // The kernel is a gather bound by memory: 32 B read and 16 or 32 B written per pixel at home, and up to 32 B gathered from the old
-// frame.  A block covers a 16x16 tile, so that the old frame's texels its lanes ask for lie close together too.
+// frame.  A block covers the guide kernel's 16x16 tile (denoise_device.hpp), so that the old frame's texels its lanes ask for lie
+// close together too.
 #include <cmath>
 #include <string>
 
@@ -28,6 +30,17 @@ __global__ __launch_bounds__(256) void reproject_kernel(const TraceParams P, int
                                                         const float4 *__restrict__ prev_hist, float4 *__restrict__ hist_out, float4 *mean_out,
                                                         int w, int h, uint32_t tiles_x, unsigned long long *__restrict__ counts) {
   reproject_body<false>(P, sample, A, guide, sums, prev_guide, prev_hist, hist_out, mean_out, w, h, tiles_x, counts, nullptr, nullptr, 0.f);
+}
+
+// the moments form (tdt_image_reproject_moments): the arguments above, then the earlier frame's moments or null, the moments image
+// to write, and mf = max_samples / (float)spp
+__global__ __launch_bounds__(256) void reproject_moments_kernel(const TraceParams P, int sample, const ReprojectArgs A,
+                                                                const uint4 *__restrict__ guide, const float4 *sums,
+                                                                const uint4 *__restrict__ prev_guide, const float4 *__restrict__ prev_hist,
+                                                                float4 *__restrict__ hist_out, float4 *mean_out, int w, int h, uint32_t tiles_x,
+                                                                unsigned long long *__restrict__ counts,
+                                                                const float4 *__restrict__ prev_moments, float4 *__restrict__ moments_out, float mf) {
+  reproject_body<true>(P, sample, A, guide, sums, prev_guide, prev_hist, hist_out, mean_out, w, h, tiles_x, counts, prev_moments, moments_out, mf);
 }
 
 namespace {
@@ -76,9 +89,8 @@ int tdt_compute_view(const tdt_compute *c, tdt_view *out) {
   tdt_ctx *ctx = c->ctx;
   if (!out) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "null view");
   if (c->kind != TDT_PROGRAM_RAYTRACER) return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "a view needs a raytracer program (its camera)");
-  const tdt_compute *cam = c->replicas.empty() ? c : c->replicas[0];     // (a multi-device program: its first member's camera)
   TraceParams P;
-  tdt::query_camera(cam, P);                                             // the one place that reads a program's camera
+  tdt::query_camera(tdt::camera_program(c), P);                          // the one place that reads a program's camera
   for (int i = 0; i < 3; i++) {
     out->origin[i] = P.org[i]; out->lower_left_corner[i] = P.llc[i]; out->horizontal[i] = P.hor[i]; out->vertical[i] = P.ver[i];
   }
@@ -99,28 +111,20 @@ static int reproject_run(tdt_compute *c, int sample, const tdt_image *guide, con
     return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, with_moments ? "the earlier frame's view, guide, history and moments come together or not at all"
                                                               : "the earlier frame's view, guide and history come together or not at all");
   if (c->kind != TDT_PROGRAM_RAYTRACER) return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "reprojection needs a raytracer program (its camera)");
-  constexpr int N = 8;
-  const tdt_image *handles[N] = {guide, sums, hist_out, mean_out, prev_guide, prev_hist, prev_moments, moments_out};
-  for (const tdt_image *i : handles)
-    if (i && i->ctx != ctx) return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "an image belongs to another context");
+  constexpr int N = 8, SIZED = 5;                                        // (the first five share the guide's size; mean_out may be sums)
+  const tdt_image *handles[N] = {guide, sums, hist_out, mean_out, moments_out, prev_guide, prev_hist, prev_moments}, *im[N];
+  if (int rc = tdt::images_of_context(ctx, handles, N, "an image belongs to another context")) return rc;
   if (c->part_rank != 0 || c->part_world != 1)
     return tdt::fail(ctx, TDT_ERR_INVALID_OPERATION, "reprojection works on images, not tile buffers: the program's partition must be (0, 1)");
   if (sample < 0) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "negative sample index");
   if (spp < 1) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "spp must be at least 1");
   if (flags != 0) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "flags must be 0");
   if (!(max_samples >= 1.0f)) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "max_samples must be at least 1");
-  const tdt_image *im[N];
-  for (int i = 0; i < N; i++) im[i] = handles[i] ? tdt::device_image(handles[i]) : nullptr;
-  const tdt_image *g = im[0], *s = im[1], *ho = im[2], *mo = im[3], *pg = im[4], *ph = im[5], *pm = im[6], *mm = im[7];
-  if (s->w != g->w || s->h != g->h || ho->w != g->w || ho->h != g->h || (mo && (mo->w != g->w || mo->h != g->h)) ||
-      (mm && (mm->w != g->w || mm->h != g->h)))
-    return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, with_moments ? "guide, sums, history, moments and mean differ in size" : "guide, sums, history and mean differ in size");
-  for (int i = 0; i < N; i++)
-    for (int j = i + 1; j < N; j++) {
-      if (!im[i] || !im[j]) continue;
-      if (i == 1 && j == 3 && im[i]->dev == im[j]->dev) continue;        // mean_out == sums: in place
-      if (im[i] == im[j] || tdt::overlap(im[i], im[j])) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "two of the images are one (or share memory)");
-    }
+  if (int rc = tdt::images_fit(ctx, handles, N, SIZED, im, with_moments ? "guide, sums, history, moments and mean differ in size"
+                                                                        : "guide, sums, history and mean differ in size",
+                               "two of the images are one (or share memory)", 1, 3))
+    return rc;
+  const tdt_image *g = im[0], *s = im[1], *ho = im[2], *mo = im[3], *mm = im[4], *pg = im[5], *ph = im[6], *pm = im[7];
   tdt::ReprojectArgs A = {};
   if (has_prev) {
     if (pg->w != ph->w || pg->h != ph->h) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier guide and history differ in size");
@@ -134,10 +138,10 @@ static int reproject_run(tdt_compute *c, int sample, const tdt_image *guide, con
     A.has_prev = 1;
   }
   A.fspp = (float)spp; A.max_samples = max_samples;
-  const unsigned long long tiles_x = ((unsigned long long)g->w + tdt::kReprojectTile - 1) / tdt::kReprojectTile,
-                           tiles_y = ((unsigned long long)g->h + tdt::kReprojectTile - 1) / tdt::kReprojectTile;
-  if (tiles_x * tiles_y > 0x7FFFFFFFull) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "image too large");
-  const tdt_compute *cam = c->replicas.empty() ? c : c->replicas[0];     // (a multi-device program: its first member's camera)
+  dim3 grid;
+  uint32_t tiles_x;
+  if (int rc = tdt::image_grid(ctx, g->w, g->h, tdt::kRayTile, tdt::kRayTile, "image too large", grid, tiles_x)) return rc;
+  const tdt_compute *cam = tdt::camera_program(c);
   tdt_ctx *m = cam->ctx;
   TraceParams P = {};
   tdt::query_camera(cam, P);
@@ -147,18 +151,15 @@ static int reproject_run(tdt_compute *c, int sample, const tdt_image *guide, con
     if (e != hipSuccess) { m->reproject_counts = nullptr; return tdt::hip_fail(ctx, e, "hipMalloc (reprojection counts)"); }
   }
   TDT_HIP(ctx, hipMemsetAsync(m->reproject_counts, 0, 4 * sizeof(unsigned long long), m->stream));
-  if (tiles_x * tiles_y == 0) return TDT_OK;                             // (an empty image: the counts of this call are zero)
-  const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
-  const uint4 *PG = has_prev ? (const uint4 *)pg->dev : nullptr;
-  const float4 *PH = has_prev ? (const float4 *)ph->dev : nullptr;
-  float4 *MO = mo ? (float4 *)mo->dev : nullptr;
-  if (with_moments)                                                      // (that kernel is tdt_variance.hip's, over the same body)
-    tdt::reproject_moments_launch(grid, m->stream, P, sample, A, (const uint4 *)g->dev, (const float4 *)s->dev, PG, PH, (float4 *)ho->dev, MO, g->w,
-                                  g->h, (uint32_t)tiles_x, m->reproject_counts, has_prev ? (const float4 *)pm->dev : nullptr, (float4 *)mm->dev,
-                                  max_samples / (float)spp);
+  const uint4 *G = (const uint4 *)g->dev, *PG = has_prev ? (const uint4 *)pg->dev : nullptr;
+  const float4 *S = (const float4 *)s->dev, *PH = has_prev ? (const float4 *)ph->dev : nullptr;
+  float4 *HO = (float4 *)ho->dev, *MO = mo ? (float4 *)mo->dev : nullptr;
+  if (with_moments)
+    hipLaunchKernelGGL(tdt::reproject_moments_kernel, grid, dim3(256), 0, m->stream, P, sample, A, G, S, PG, PH, HO, MO, g->w, g->h, tiles_x,
+                       m->reproject_counts, has_prev ? (const float4 *)pm->dev : nullptr, (float4 *)mm->dev, max_samples / (float)spp);
   else
-    hipLaunchKernelGGL(tdt::reproject_kernel, grid, block, 0, m->stream, P, sample, A, (const uint4 *)g->dev, (const float4 *)s->dev, PG, PH,
-                       (float4 *)ho->dev, MO, g->w, g->h, (uint32_t)tiles_x, m->reproject_counts);
+    hipLaunchKernelGGL(tdt::reproject_kernel, grid, dim3(256), 0, m->stream, P, sample, A, G, S, PG, PH, HO, MO, g->w, g->h, tiles_x,
+                       m->reproject_counts);
   TDT_HIP(ctx, hipGetLastError());
   return TDT_OK;
 }

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import denoise_model as model
+from image_util import INSIDE_TURNED, PASSES, SIZES, _all_pixels, _bits, _raises, _wrapped
 from tdt4230_project_raytracing_amd import host, rt
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,6 @@ pytestmark = pytest.mark.gpu
 W, H = 64, 48
 OUTSIDE = ((0.0, 0.2, 0.9), 0.0, -8.0, 90.0)         # (origin, yaw, pitch, fov), as tests/test_gpu_raycast.py poses its cameras
 INSIDE = ((0.0, -0.1, -0.3), 0.0, 0.0, 90.0)
-INSIDE_TURNED = ((0.1, 0.05, -0.6), 135.0, 10.0, 70.0)
 COVER = (64, 64)                                     # a dispatch whose 32x32 work-groups cover all of 64x48
 
 
@@ -32,14 +32,6 @@ def _scene(name):
     if name == "config1":
         return host.Scene.config(1)
     return host.Scene.generate(host.SCENE_TERRAIN, 8, 1 << 20, 100, 0x9A1C4)      # the depth-8 terrain of test_gpu_raycast._scenes
-
-
-def _all_pixels(w, h):
-    return np.stack(np.meshgrid(np.arange(w), np.arange(h)), -1).reshape(-1, 2).astype(np.int32)     # row-major: y outer, x inner
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- guide equals pick -----------------------------------------------------------------------------------------------------
@@ -83,11 +75,7 @@ def test_guide_is_pick_in_four_words(name):
     assert flagged
 
 
-# ---- filter equals model ---------------------------------------------------------------------------------------------------
-SIZES = [(1, 1), (2, 2), (5, 5), (33, 17), (64, 48), (257, 19), (19, 257)]      # wider and taller than any tile
-PASSES = [1, 2, 3, 5, 8]
-
-
+# ---- filter equals model (at image_util's SIZES and PASSES) ------------------------------------------------------------------
 def make_case(w, h, seed):
     """(img (h, w, 4) float32, guide (h, w) GUIDE_DTYPE): random patches of 3-5 keys — two of them differ from the first only by
     one ulp of `plane`, or only in `material` —, single-texel islands with keys of their own, kind-0 holes; colours random with
@@ -126,14 +114,6 @@ def make_case(w, h, seed):
     img[(special >= 0.06) & (special < 0.064)] = np.float32(np.inf if seed % 2 else -np.inf)      # (rare: they spread with every pass)
     img[(special >= 0.064) & (special < 0.068)] = np.float32(np.nan)
     return img, guide
-
-
-def _wrapped(ctx, a):
-    """A host array as a torch tensor on the GPU, wrapped (not bound) as a texture of its height and width."""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.float32).reshape(a.shape[0], a.shape[1], 4).copy()).to("cuda:0")
-    torch.cuda.synchronize()
-    return t, rt.Texture.wrap_device(ctx, t.data_ptr(), a.shape[1], a.shape[0], bind=False)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -221,12 +201,6 @@ def test_multi_device_context_runs_on_the_first_device():
 
 
 # ---- errors ----------------------------------------------------------------------------------------------------------------
-def _raises(code, fn, *args, **kw):
-    with pytest.raises(rt.TdtError) as e:
-        fn(*args, **kw)
-    assert e.value.code == code, e.value
-
-
 def test_errors_write_nothing():
     L = rt.lib()
     scene = host.Scene.config(1)

@@ -17,6 +17,7 @@ import pytest
 
 import denoise_model
 import reproject_model as model
+from image_util import INSIDE_TURNED, _all_pixels, _bits, _wrapped
 from tdt4230_project_raytracing_amd import host, rt
 
 pytestmark = pytest.mark.gpu
@@ -46,14 +47,6 @@ def _cover(w, h):
     return -(-w // 32) * 32, -(-h // 32) * 32
 
 
-def _all_pixels(w, h):
-    return np.stack(np.meshgrid(np.arange(w), np.arange(h)), -1).reshape(-1, 2).astype(np.int32)     # row-major: y outer, x inner
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _same(got, want, what):
     diff = _bits(got) != _bits(want)
     assert not diff.any(), (what, int(diff.sum()), np.argwhere(diff)[:4].tolist())
@@ -67,7 +60,6 @@ def _same(got, want, what):
 # on different faces, and the identical pose finds 16 % of its keyed pixels again (29 of 187 from (0, 0.2, 0.9), measured) — that is
 # what nearest-texel history gives on sub-pixel geometry, and DESIGN.md says so.  Its pairs here therefore look at the block of
 # voxels in the octant x, y < 0, z < -0.5 from 0.05 away through a 3 degree lens, where a voxel is about twenty pixels wide.
-INSIDE_TURNED = ((0.1, 0.05, -0.6), 135.0, 10.0, 70.0)
 CLOSE_UP = ((-0.2503, -0.2497, -0.45), 0.0, 0.0, 3.0)
 PAIRS = {
     "config1": {
@@ -229,14 +221,6 @@ def make_case(w, h, pw, ph, seed, cap):
     prev_hist = colours(pw, ph)
     prev_hist[..., 3] = counts[rng.integers(0, len(counts), (ph, pw))]
     return {"guide": guide_of(w, h), "sums": colours(w, h), "prev_guide": guide_of(pw, ph), "prev_hist": prev_hist}
-
-
-def _wrapped(ctx, a):
-    """A host array as a torch tensor on the GPU, wrapped (not bound) as a texture of its height and width."""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.float32).reshape(a.shape[0], a.shape[1], 4).copy()).to("cuda:0")
-    torch.cuda.synchronize()
-    return t, rt.Texture.wrap_device(ctx, t.data_ptr(), a.shape[1], a.shape[0], bind=False)
 
 
 HAND_CUR = ((0.05, 0.1, 0.2), 20.0, -5.0, 80.0)

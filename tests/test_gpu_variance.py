@@ -10,17 +10,15 @@ import pytest
 import denoise_model
 import reproject_model
 import variance_model as model
+from image_util import INSIDE_TURNED, PASSES, SIZES, _all_pixels, _bits, _raises, _wrapped  # noqa: F401
 from test_gpu_denoise import make_case
-from test_gpu_reproject import PAIRS, SPP, _all_pixels, _bits, _cam, _cover, _same, _units, _wrapped, gpu_frame, renderers  # noqa: F401
+from test_gpu_reproject import PAIRS, SPP, _cam, _cover, _same, _units, gpu_frame, renderers  # noqa: F401
 from tdt4230_project_raytracing_amd import host, rt
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 W, H = 64, 48
-INSIDE_TURNED = ((0.1, 0.05, -0.6), 135.0, 10.0, 70.0)
-SIZES = [(1, 1), (2, 2), (5, 5), (33, 17), (64, 48), (257, 19), (19, 257)]      # narrower than the 7x7 window .. wider and taller than any tile
-PASSES = [1, 2, 3, 5, 8]
 SIGMA = 2.0
 
 
@@ -291,12 +289,6 @@ def test_multi_device_context_runs_on_the_first_device():
 
 
 # ---- errors ----------------------------------------------------------------------------------------------------------------
-def _raises(code, fn, *args, **kw):
-    with pytest.raises(rt.TdtError) as e:
-        fn(*args, **kw)
-    assert e.value.code == code, e.value
-
-
 def test_errors_write_nothing():
     L = rt.lib()
     scene = host.Scene.config(1)

@@ -69,7 +69,7 @@ def test_kernels_have_no_scratch_and_no_spills():
     rows = kernel_resources.collect("tdt_variance.hip")
     names = sorted(re.match(r"tdt::(\w+(?:<\d+>)?)", r["name"]).group(1) for r in rows)
     assert names == ["denoise_variance_gather_kernel", "denoise_variance_tile_kernel<1>", "denoise_variance_tile_kernel<2>",
-                     "reproject_moments_kernel", "variance_kernel"]
+                     "variance_kernel"]                            # (reproject_moments_kernel: tests/test_reproject_api.py)
     for r in rows:
         assert r["ScratchSize [bytes/lane]"] == 0, r["name"]
         assert r["SGPRs Spill"] == 0 and r["VGPRs Spill"] == 0, r["name"]
@@ -80,8 +80,6 @@ def test_kernels_have_no_scratch_and_no_spills():
             assert lds == (32 + 8) * (8 + 8) * 36 < 24 * 1024          # a halo of 4: 640 texels
         elif "variance_kernel" in r["name"] and "denoise" not in r["name"]:
             assert lds == (32 + 6) * (8 + 6) * 20                      # a halo of 3: key + luminance
-        elif "reproject_moments_kernel" in r["name"]:
-            assert lds == 16                                          # the block's four counters, as reproject_kernel
         else:
             assert lds == 0
     from tdt4230_project_raytracing_amd import build
@@ -89,19 +87,48 @@ def test_kernels_have_no_scratch_and_no_spills():
     assert "denoise_device.hpp" in build.DEVICE_HEADERS and "reproject_device.hpp" in build.DEVICE_HEADERS
 
 
+# what is matched is the DEFINITION (its characteristic line), not the name: a copy under another name is found too
+ONE_DEFINITION = {
+    "the B3 table": (r"\{0\.0625f, 0\.25f, 0\.375f, 0\.25f, 0\.0625f\}", "denoise_device.hpp"),
+    "the prefilter table": (r"\{0\.25f, 0\.5f, 0\.25f\}", "denoise_device.hpp"),
+    "the variance-guided weight's cut": (r"\bd2 < lim\)", "denoise_device.hpp"),
+    "the usable limit": (r"lim > 0\.f && lim < INFINITY", "denoise_device.hpp"),
+    "the staging loop's bounds test": (r"gx >= 0 && gx < w && gy >= 0 && gy < h", "denoise_device.hpp"),
+    "the 16x16 tile's pixel": (r"threadIdx\.x & \(k\w+ - 1\)\)\)[;,] y = ", "denoise_device.hpp"),
+    "the 32x8 tile's origin": (r"x0 = \(int\)tx \* kTileW", "denoise_device.hpp"),
+    "the too-large refusal": (r"> 0x7FFFFFFFull\) return (tdt::)?fail\(", "tdt_internal.hpp"),
+    "the first-member camera": (r"replicas\.empty\(\) \? c : c->replicas\[0\]", "tdt_internal.hpp"),
+    "the N-handle overlap loop": (r"== \w+\[j\] \|\| (tdt::)?overlap\(", "tdt_internal.hpp"),
+    "the reprojection's history read": (r"prev_guide\[q\]", "reproject_device.hpp"),
+    "the scratch sequence": (r"\bint denoise_sequence\([^;]*\{", "tdt_denoise.hip"),
+    "the scratch sequence's caller": (r"(?<!int )\bdenoise_sequence\(", "tdt_internal.hpp"),
+}
+
+
 def test_units_share_their_device_code():
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("tdt_denoise.hip", "tdt_variance.hip", "tdt_reproject.hip", "denoise_device.hpp",
-                                                            "reproject_device.hpp")}
-    for fn in ("key_of", "same_key", "tile_origin", "lum"):
+    files = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp", ".h", ".cpp"))]
+    text = {f: open(os.path.join(CSRC, f)).read() for f in files}
+    for what, (pattern, owner) in ONE_DEFINITION.items():
+        found = {f: len(re.findall(pattern, t)) for f, t in text.items() if re.search(pattern, t)}
+        assert found == {owner: 1}, (what, found)
+    for fn in ("key_of", "same_key", "tile_origin", "ray_tile_pixel", "lum", "stage_tile", "add_tap", "add_prefilter_tap", "finish", "usable",
+               "filter_tile", "filter_gather"):
         defined = [f for f, t in text.items() if re.search(r"TDT_DEV\s+\w+\s+" + fn + r"\(", t)]
         assert defined == ["denoise_device.hpp"], (fn, defined)
-    for unit in ("tdt_denoise.hip", "tdt_variance.hip"):
-        assert '#include "denoise_device.hpp"' in text[unit] and "tile_origin(tiles_x, x0, y0)" in text[unit] and "same_key(" in text[unit], unit
-        assert "denoise_sequence(" in text[unit], unit                # one scratch sequence
-    assert len(re.findall(r"\bint denoise_sequence\(", text["tdt_denoise.hip"])) == 1 and "hipMalloc" not in text["tdt_variance.hip"]
-    # one projection, one FOUND predicate: the body both reprojection kernels instantiate
-    assert text["reproject_device.hpp"].count("prev_guide[q]") == 1 and "prev_guide[q]" not in text["tdt_reproject.hip"] + text["tdt_variance.hip"]
-    assert "reproject_body<false>(" in text["tdt_reproject.hip"] and "reproject_body<true>(" in text["tdt_variance.hip"]
+    # the four filter kernels are instantiations of the tile and the gather body; all three staged kernels go through the one staging loop
+    assert "filter_tile<S, false>(" in text["tdt_denoise.hip"] and "filter_gather<false>(" in text["tdt_denoise.hip"]
+    assert "filter_tile<S, true>(" in text["tdt_variance.hip"] and "filter_gather<true>(" in text["tdt_variance.hip"]
+    assert "stage_tile<kVarRadius>(" in text["tdt_variance.hip"] and text["denoise_device.hpp"].count("stage_tile<2 * S>(") == 1
+    # one pass loop: an entry point hands run_passes its launcher (the tile kernel or the gather) and launches nothing else itself
+    for unit, entry in (("tdt_denoise.hip", "tdt_image_denoise"), ("tdt_variance.hip", "tdt_image_denoise_variance")):
+        body = re.search(r"\nint " + entry + r"\(.*?\n\}\n", text[unit], re.S).group(0)
+        before, handed = body.split("return tdt::run_passes(")
+        assert "hipLaunchKernelGGL" not in before and handed.count("hipLaunchKernelGGL") == 2, entry
+        assert not re.search(r"\bfor \(|hipGetLastError|hipMemcpy|hipSetDevice", body), entry
+    assert "hipMalloc" not in text["tdt_variance.hip"]
+    # both reprojection kernels live with the host code that launches them
+    assert "reproject_body<false>(" in text["tdt_reproject.hip"] and "reproject_body<true>(" in text["tdt_reproject.hip"]
+    assert "reproject_device.hpp" not in text["tdt_variance.hip"] and "reproject_body" not in text["tdt_variance.hip"] and not any("reproject_moments_launch" in t for t in text.values())
 
 
 def test_renderer_hpp_compiles_with_the_new_members(tmp_path):
