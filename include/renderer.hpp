@@ -167,6 +167,12 @@ class Texture {
   void reproject_moments(const ComputeShader &shader, int sample, const Texture &guide, int spp, const tdt_view *prev_view,
                          const Texture *prev_guide, const Texture *prev_hist, const Texture *prev_moments, float max_samples,
                          const Texture &hist_out, const Texture &moments_out, const Texture *mean_out = nullptr) const;
+  // NEW: guide-keyed upsampling into this texture (tdt_image_upsample): `src`, sums traced at reduced resolution, spread over this
+  // image's pixels, each taking only texels whose key in src_guide (of src's size) equals its own in dst_guide (of this size):
+  // validated bilinear, else the mean of the same-key texels of the 4x4 ring, else the nearest texel.  Asynchronous.
+  void upsample(const Texture &dst_guide, const Texture &src, const Texture &src_guide) const {
+    ctx_->check(tdt_image_upsample(img_, dst_guide.img_, src.img_, src_guide.img_, 0));
+  }
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;

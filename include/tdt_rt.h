@@ -467,6 +467,52 @@ int tdt_image_reproject_moments(tdt_compute *c, int sample, const tdt_image *gui
                                 const tdt_image *prev_moments, float max_samples, tdt_image *hist_out, tdt_image *moments_out,
                                 tdt_image *mean_out, uint32_t flags);
 
+/* ---- guide-keyed upsampling ------------------------------------------------------------------------------------------------
+ * A first-hit guide costs a tenth of a low-spp trace, so the geometry of a frame is nearly free at full resolution and only its
+ * radiance is expensive.  tdt_image_upsample spreads sums traced at reduced resolution — an ordinary tdt_dispatch_accumulate under
+ * a camera whose image_width / image_height are smaller, into an image of that size — over a full-resolution image, and the
+ * guide key (kind, material, plane) of the two resolutions keeps radiance from crossing a face edge: exact, no depth or normal
+ * tolerance.  The result is a sums image that tdt_image_denoise, tdt_image_variance, tdt_image_reproject and tdt_dispatch_resolve
+ * take unchanged.
+ *
+ * tdt_image_upsample, asynchronous on the context's stream, one lane per pixel of dst, reads no scene buffer and no camera:
+ *   dst, dst_guide   W x H: the image to write and what tdt_dispatch_guide wrote under the full-resolution camera
+ *   src, src_guide   w x h, 1 <= w <= W, 1 <= h <= H, every side <= 32768: the low-resolution sums and the guide of the SAME
+ *                    sample under the low-resolution camera (the same frustum; the caller keeps them consistent).  W / w need
+ *                    not be an integer, nor equal H / h.
+ * "Same key" is tdt_image_denoise's: words 0, 1, 2 of two guide texels are equal.  A kind-0 texel is treated like any other:
+ * sky interpolates among sky, a pass-through hit among pass-through hits of its material.
+ * The mapping, in exact integers, per axis.  primary_ray samples pixel x at (x + jitter) / (image_width - 1), so pixel x of the full
+ * frame lies at x (w - 1) / (W - 1) of the low one.  W == 1: i0 = 0, fx = 0.  Otherwise n = x (w - 1); i0 = n / (W - 1) (the integer
+ * floor); r = n % (W - 1); fx = (float)r / (float)(W - 1) (an IEEE divide).  i1 = min(i0 + 1, w - 1).  The nearest texel `in` is i0
+ * when 2 r < W - 1, else i1.  Likewise for y with H, h: j0, j1, fy, jn.
+ * Per pixel P = (x, y), g = dst_guide[P], all in fp32, each operation rounded on its own, never fused:
+ *   Stage 1, validated bilinear.  num = (0, 0, 0, 0), den = 0; wx = {1.0f - fx, fx}, wy = {1.0f - fy, fy}; for the taps
+ *   Q = (i0, j0), (i1, j0), (i0, j1), (i1, j1) in that order: wt = wy * wx; the tap is SKIPPED unless wt > 0 (so a zero-weight tap
+ *   never contributes, which covers the clamped i1 == i0) and skipped when the key of src_guide[Q] differs from g's; src[Q] is
+ *   read only after the key matched.  A kept tap: num.c = num.c + wt * src[Q].c for c = r, g, b, a, then den = den + wt.
+ *   If den > 0: dst[P].c = num.c / den (IEEE divide): class 1.
+ *   Stage 2, the ring, only if den == 0 (num is still zero).  K = 0; for j = j0 - 1 .. j0 + 2 (outer), i = i0 - 1 .. i0 + 2 (inner),
+ *   Q = (i, j) inside src with the same key: num.c = num.c + src[Q].c, then K = K + 1.0f.  If K > 0: dst[P].c = num.c / K: class 2.
+ *   Stage 3, a hole: no texel of the 4x4 neighbourhood saw this surface.  dst[P] = src[(in, jn)] bit for bit: class 3.
+ * All four channels are interpolated alike, so alpha carries whatever the caller keeps there (a variance, a sample count); running
+ * sums of `spp` samples come out as running sums of `spp` samples.  Stage 1 starts from +0, so with equal sizes and equal guides
+ * the call returns src bit for bit except that -0 comes back as +0 (and a NaN as the NaN the divide by 1 gives).  That order is
+ * the contract: a numpy model of these lines gives the same bits.
+ * A hole is what sub-pixel geometry gives: where a low-resolution texel covers several faces, most full-resolution pixels find
+ * their face in none of the sixteen texels around them, and the call degrades to nearest-texel magnification there.
+ *
+ * tdt_debug_upsample_counts (synchronises): of the context's last tdt_image_upsample that returned TDT_OK (a call that fails leaves
+ * the counts of the call before it), [0] pixels of dst, [1], [2], [3] the pixels of class 1, 2, 3; [1] + [2] + [3] = [0].  Before
+ * any call all four are 0.
+ *
+ * Errors, nothing written: a NULL handle; flags != 0; dst and dst_guide of different sizes; src and src_guide of different sizes;
+ * src wider or taller than dst; a side above 32768 (x (w - 1) then fits 32 bits); any two of the four images the same or sharing
+ * memory: TDT_ERR_INVALID_VALUE.  An image of another context: TDT_ERR_INVALID_OPERATION.  A multi-device context runs the call on
+ * device_ids[0], as tdt_image_denoise does. */
+int tdt_image_upsample(tdt_image *dst, const tdt_image *dst_guide, const tdt_image *src, const tdt_image *src_guide, uint32_t flags);
+int tdt_debug_upsample_counts(tdt_ctx *ctx, uint64_t out[4]);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

@@ -13,7 +13,8 @@
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
-//            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--out frame.pfm] [--png frame.png]
+//            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--upsample S]
+//            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
 // --move replays key presses through the camera controller (main.rs:506-546), one 1/60 s frame each:
@@ -29,6 +30,10 @@
 //   each frame's spp samples joined by the history of the frame before wherever that frame saw the same surface point
 //   (ComputeShader::view, Texture::reproject; at most 64 samples of history); the last frame is the one written.  Combines with
 //   --denoise, which then filters each frame's means.  Prints the last frame's found / rejected pixel counts.
+// --upsample S: the frame's radiance traced at 1 / S of the resolution (S >= 1): accumulate and guide under the camera with
+//   image_width = ceil(W / S), image_height = ceil(H / S) into images of that size, the full-resolution guide, Texture::upsample into
+//   the render texture, then --denoise N [--variance SIGMA] over it as above, and the resolve.  Prints the bilinear / ring / hole
+//   pixel counts.  Not with --temporal.
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
@@ -111,7 +116,7 @@ int main(int argc, char **argv) {
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
-  int config = -1, denoise = 0, temporal = 0;
+  int config = -1, denoise = 0, temporal = 0, upsample = 0;
   float turn = 1.0f, variance = 0.0f;                                                    // variance 0: the key-only filter
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -133,6 +138,7 @@ int main(int argc, char **argv) {
     else if (a == "--variance") { variance = (float)std::atof(next()); if (!(variance > 0.0f) || !(variance < 1e30f)) { std::fprintf(stderr, "--variance SIGMA, SIGMA > 0\n"); return 2; } }
     else if (a == "--temporal") { temporal = std::atoi(next()); if (temporal < 1) { std::fprintf(stderr, "--temporal N, N >= 1\n"); return 2; } }
     else if (a == "--turn") turn = (float)std::atof(next());
+    else if (a == "--upsample") { upsample = std::atoi(next()); if (upsample < 1) { std::fprintf(stderr, "--upsample S, S >= 1\n"); return 2; } }
     else if (a == "--brush") {
       char kind[16] = {0};
       if (std::sscanf(next(), "%15[a-z]:%d", kind, &brush_size) != 2 || brush_size < 0 || (std::strcmp(kind, "sphere") && std::strcmp(kind, "box"))) {
@@ -212,6 +218,7 @@ int main(int argc, char **argv) {
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
+  if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
   if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
   try {
     Context ctx(device);
@@ -517,6 +524,30 @@ int main(int argc, char **argv) {
       uint64_t counts[4];
       ctx.check(tdt_debug_reproject_counts(ctx.raw(), counts));
       std::printf("temporal frames %d keyed %llu found %llu rejected-key %llu rejected-screen %llu\n", temporal, (unsigned long long)counts[0],
+                  (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
+    } else if (upsample > 0) {                                                           // NEW: radiance at 1 / upsample of the resolution
+      const int tw = camera.render_texture.width(), th = camera.render_texture.height();
+      const int lw = (tw + upsample - 1) / upsample, lh = (th + upsample - 1) / upsample;
+      const Texture guide = Texture::new_2d(ctx, tw, th, false), low = Texture::new_2d(ctx, lw, lh, false), low_guide = Texture::new_2d(ctx, lw, lh, false);
+      const Program &prog = raytrace_program.program;
+      prog.set_i32("camera.image_width", lw); prog.set_i32("camera.image_height", lh);
+      low.bind();
+      ctx.check(tdt_dispatch_accumulate(prog.id(), (lw + 31) / 32 * 32, (lh + 31) / 32 * 32, dd, 0, spp, nullptr));   // (all of the low image)
+      raytrace_program.dispatch_guide(low_guide);
+      prog.set_i32("camera.image_width", tw); prog.set_i32("camera.image_height", th);
+      camera.render_texture.bind();
+      raytrace_program.dispatch_guide(guide);
+      camera.render_texture.upsample(guide, low, low_guide);
+      if (variance > 0.0f) {
+        camera.render_texture.variance(guide);
+        camera.render_texture.denoise_variance(guide, denoise, variance);
+      } else if (denoise > 0) {
+        camera.render_texture.denoise(guide, denoise);
+      }
+      ctx.check(tdt_dispatch_resolve(prog.id(), dw, dh, dd, spp));
+      uint64_t counts[4];
+      ctx.check(tdt_debug_upsample_counts(ctx.raw(), counts));
+      std::printf("upsample %d from %dx%d pixels %llu bilinear %llu ring %llu holes %llu\n", upsample, lw, lh, (unsigned long long)counts[0],
                   (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
     } else if (denoise > 0) {                                                            // NEW: sums, first hits, filter, then the square root
       const Texture guide = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);

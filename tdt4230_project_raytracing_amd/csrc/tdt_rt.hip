@@ -2165,6 +2165,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   tdt::query_scratch_destroy(ctx);
   tdt::denoise_scratch_destroy(ctx);
   tdt::reproject_counts_destroy(ctx);
+  tdt::upsample_counts_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -321,6 +321,8 @@ SYMBOLS = [
     ("tdt_image_variance", _I, [_P, _P, _P, _F, ctypes.c_uint32]),
     ("tdt_image_denoise_variance", _I, [_P, _P, _I, _F, _F, ctypes.c_uint32]),
     ("tdt_image_reproject_moments", _I, [_P, _I, _P, _P, _I, ctypes.POINTER(VIEW), _P, _P, _P, _F, _P, _P, _P, ctypes.c_uint32]),
+    ("tdt_image_upsample", _I, [_P, _P, _P, _P, ctypes.c_uint32]),
+    ("tdt_debug_upsample_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -913,6 +915,12 @@ class Context:
         self.check(lib().tdt_debug_reproject_counts(self.h, c))
         return tuple(int(v) for v in c)
 
+    def upsample_counts(self):
+        """tdt_debug_upsample_counts: (pixels, validated bilinear, ring, holes) of the last Texture.upsample (blocks)."""
+        c = (ctypes.c_uint64 * 4)()
+        self.check(lib().tdt_debug_upsample_counts(self.h, c))
+        return tuple(int(v) for v in c)
+
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
         return int(lib().tdt_debug_fill_passes(self.h))
@@ -1093,6 +1101,12 @@ class Texture:
                                                          ctypes.byref(view) if view is not None else None, pg.h if pg is not None else None,
                                                          ph.h if ph is not None else None, pm.h if pm is not None else None, float(max_samples),
                                                          hist_out.h, moments_out.h, mean_out.h if mean_out is not None else None, 0))
+
+    def upsample(self, dst_guide, src, src_guide):
+        """tdt_image_upsample into this texture: `src` (sums traced at reduced resolution) spread over this image's pixels, each
+        taking only texels whose key in `src_guide` equals its own in `dst_guide` (a Texture of this size; src_guide of src's):
+        validated bilinear, else the mean of the same-key texels of the 4x4 ring, else the nearest texel.  Asynchronous."""
+        self.ctx.check(lib().tdt_image_upsample(self.h, dst_guide.h, src.h, src_guide.h, 0))
 
 
 class Program:
@@ -1320,6 +1334,7 @@ class Renderer:
             self.texture = Texture.new_2d(self.ctx, w, rows)
         self.guide = None                      # render(denoise=N) creates it on first use
         self.temporal = None                   # render_temporal's state, created on first use
+        self.low = None                        # render_upsampled's low-resolution (sums, guide) textures, created on first use
         # sigma of the variance-guided filter that render(denoise=N) and render_temporal(denoise=N) run instead of the key-only one;
         # None: the key-only filter, exactly the calls made before the variance unit existed.  VARIANCE_SIGMA is the measured default.
         self.variance = None
@@ -1410,6 +1425,51 @@ class Renderer:
                 self.texture.denoise(t["guide"][cur], denoise)
         self.shader.dispatch_resolve(w, h, 1, 1)
         t["view"], t["frame"] = self.shader.view(), k + 1
+        return self.texture.read()
+
+    def render_upsampled(self, scale=2, denoise=0, width=None, height=None):
+        """The frame with its radiance traced at 1 / scale of the resolution (Texture.upsample).  The low camera is the renderer's
+        with only image_width = ceil(W / scale) and image_height = ceil(H / scale) changed — the same frustum.  The frame: under
+        the low uniforms, with a low texture bound, accumulate [0, spp) over the whole low image and take the low guide of sample 0;
+        under the full uniforms the full guide of sample 0; upsample into the renderer's texture; `denoise` > 0: the filter calls
+        render(denoise=N) makes (self.variance decides which); bind the renderer's texture and resolve with spp.  width / height are
+        the resolve's dispatch, as render's.  scale=1 goes through the same calls.  The low texture and the two guides are created
+        on first use.  A single-device renderer whose image is the whole frame only; whether it returns or raises, the uniforms and
+        the binding are the full-resolution ones afterwards.  Returns the resolved frame."""
+        if isinstance(scale, bool) or not isinstance(scale, int) or scale < 1:
+            raise ValueError("render_upsampled: scale must be an int >= 1")
+        W, H = self.camera.image_width, self.camera.image_height
+        if self.ctx.device_count() != 1 or self.texture.width() != W or self.texture.height() != H:
+            raise ValueError("render_upsampled needs a single-device renderer that owns the whole image")
+        w = W + 1 if width is None else width
+        h = H + 1 if height is None else height
+        spp = self.camera.samples_per_pixel
+        lw, lh = -(-W // scale), -(-H // scale)
+        if self.guide is None:
+            self.guide = Texture.new_2d(self.ctx, W, H, bind=False)
+        if self.low is None or (self.low[0].width(), self.low[0].height()) != (lw, lh):
+            self.low = (Texture.new_2d(self.ctx, lw, lh, bind=False), Texture.new_2d(self.ctx, lw, lh, bind=False))
+        low, low_guide = self.low
+        program = self.shader.program
+        try:
+            program.set_i32("camera.image_width", lw)
+            program.set_i32("camera.image_height", lh)
+            low.bind()
+            self.shader.dispatch_accumulate(-(-lw // 32) * 32, -(-lh // 32) * 32, 1, 0, spp)    # (work-groups over all of the low image)
+            self.shader.dispatch_guide(low_guide)
+        finally:
+            program.set_i32("camera.image_width", W)
+            program.set_i32("camera.image_height", H)
+            self.texture.bind()
+        self.shader.dispatch_guide(self.guide)
+        self.texture.upsample(self.guide, low, low_guide)
+        if denoise > 0:
+            if self.variance is None:
+                self.texture.denoise(self.guide, denoise)
+            else:
+                self.texture.variance(self.guide)
+                self.texture.denoise_variance(self.guide, denoise, self.variance)
+        self.shader.dispatch_resolve(w, h, 1, spp)
         return self.texture.read()
 
     def pick(self, xy, sample=0, return_rays=False):
