@@ -173,6 +173,14 @@ class Texture {
   void upsample(const Texture &dst_guide, const Texture &src, const Texture &src_guide) const {
     ctx_->check(tdt_image_upsample(img_, dst_guide.img_, src.img_, src_guide.img_, 0));
   }
+  // NEW: the sampling controller (tdt_image_adapt) with this texture as the running sums: after a batch of spp_count samples for
+  // the live pixels of state_in, state_out receives their updated (L, m2, n, w), w negated where the pixel stops.  guide may be
+  // null.  state_out is the mask of the next ComputeShader::dispatch_accumulate_masked.  Asynchronous.
+  void adapt(const Texture *guide, const Texture &state_in, const Texture &state_out, int spp_count, const tdt_adapt &a) const {
+    ctx_->check(tdt_image_adapt(img_, guide ? guide->img_ : nullptr, state_in.img_, state_out.img_, spp_count, &a, 0));
+  }
+  // NEW: running sums to means by the sample counts of `state`, alpha = the variance of the mean luminance (tdt_image_adapt_mean)
+  void adapt_mean(const Texture &state) const { ctx_->check(tdt_image_adapt_mean(img_, state.img_, 0)); }
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;
@@ -232,6 +240,11 @@ class ComputeShader {
   // depth of the primary ray of pixel (x, y), sample `sample`, of this program's camera; flags: TDT_GUIDE_ALL_MATERIALS.  Asynchronous.
   void dispatch_guide(const Texture &guide, int sample = 0, uint32_t flags = 0) const {
     ctx_->check(tdt_dispatch_guide(program.id(), guide.id(), sample, flags));
+  }
+  // NEW: tdt_dispatch_accumulate for the covered pixels whose texel of `mask` has w >= 0 (tdt_dispatch_accumulate_masked); every
+  // other pixel keeps its texel and its carry.  A Texture::adapt state image is such a mask.
+  void dispatch_accumulate_masked(int width, int height, int depth, int spp_begin, int spp_count, void *carry, const Texture &mask) const {
+    ctx_->check(tdt_dispatch_accumulate_masked(program.id(), width, height, depth, spp_begin, spp_count, carry, mask.id()));
   }
   // NEW: a snapshot of this program's camera uniforms (tdt_compute_view): what a later frame reprojects into
   tdt_view view() const {

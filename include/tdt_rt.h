@@ -178,6 +178,19 @@ int tdt_assemble_tiles(tdt_compute *c, const void *gathered, int world, int tile
  * device memory; NULL = start from / discard the initial state). */
 int tdt_dispatch_accumulate(tdt_compute *c, int width, int height, int depth, int spp_begin, int spp_count,
                             void *carry_device_ptr);
+/* tdt_dispatch_accumulate restricted to the covered pixels whose texel of `mask` is LIVE.  mask is an RGBA32F image of the bound
+ * image's size; pixel P is live when mask[P].w >= 0.0f: +0 and -0 are live, negative values and NaN are not.  A live pixel gets
+ * exactly the bits tdt_dispatch_accumulate would give it from the same prior state (image texel and carry); a pixel that is not
+ * live keeps its image texel and its 64 bytes of carry byte for byte.  With no live pixel the call traces nothing and returns
+ * TDT_OK.  The done flags are one more producer for the hand-out order's filter (the miss pre-pass is the other), so the trace
+ * kernels are the ones every other dispatch runs.  A partition set with tdt_set_partition works on a full-size image: only owned
+ * groups are traced.  The call may change the cost history, i.e. the schedule of later frames, never a pixel of them.  The state
+ * image of tdt_image_adapt is such a mask.
+ * Errors, nothing traced: a NULL mask, a negative range, an unaligned carry, a mask whose size differs from the bound image's:
+ * TDT_ERR_INVALID_VALUE.  A multi-device context; a bound tile buffer (the full image must be bound); a mask of another context;
+ * a mask that is the bound image or shares memory with it: TDT_ERR_INVALID_OPERATION. */
+int tdt_dispatch_accumulate_masked(tdt_compute *c, int width, int height, int depth, int spp_begin, int spp_count,
+                                   void *carry_device_ptr, const tdt_image *mask);
 /* image = clamp(sqrt(sum / total_spp), 0, 1), alpha = 1: raytracer.comp:249-251 — EVERY covered pixel of the bound image, whatever its
  * alpha (a pixel no pass wrote resolves from the zeros or whatever the caller put there).  (Inside tdt_dispatch_compute, and only for a
  * frame whose miss pre-pass ran, the library's own resolve leaves the pixels that pass finished — alpha 1 — alone.) */
@@ -512,6 +525,68 @@ int tdt_image_reproject_moments(tdt_compute *c, int sample, const tdt_image *gui
  * device_ids[0], as tdt_image_denoise does. */
 int tdt_image_upsample(tdt_image *dst, const tdt_image *dst_guide, const tdt_image *src, const tdt_image *src_guide, uint32_t flags);
 int tdt_debug_upsample_counts(tdt_ctx *ctx, uint64_t out[4]);
+
+/* ---- adaptive sampling: the sampling controller ------------------------------------------------------------------------------
+ * tdt_dispatch_accumulate_masked traces a batch of samples for the live pixels of a mask; these calls decide, after each batch,
+ * which pixels stay live.  The decision is the classic batch-means test: the variance of the means of the batches a pixel has
+ * received estimates the error of its running mean, and the pixel stops when that error is below a fraction of its brightness.
+ *
+ * A STATE IMAGE is an RGBA32F image whose texels are (L, m2, n, w): L the luminance of the running sums at the last update, m2 the
+ * sum of the squared batch luminances, n the number of batches, |w| the number of samples behind the pixel.  A pixel HAS STOPPED
+ * when !(w >= 0.0f): w < 0, or a NaN.  That is exactly "not live" in tdt_dispatch_accumulate_masked, so a state image is a mask,
+ * and a cleared image (tdt_image_clear) is "every pixel live, nothing traced".  Throughout lum(c) = (0.2126f * c.r + 0.7152f * c.g)
+ * + 0.0722f * c.b; all arithmetic is fp32, each operation rounded on its own, never fused.  A numpy model of these lines gives the
+ * same bits, with one exception: where a line computes a NaN, the result is a NaN whose sign and payload are not specified (a
+ * texel that is copied keeps its bits, NaN or not).
+ *
+ * tdt_image_adapt, asynchronous on the context's stream, after a batch of k = spp_count samples was added to `sums` for the live
+ * pixels of state_in.  Once, on the host: kf = (float)k, lo = (float)a->min_samples, hi = (float)a->max_samples.  Per pixel P with
+ * st = state_in[P]:
+ *   P has stopped: state_out[P] = st bit for bit, and P PASSES.
+ *   Otherwise the update: Lc = lum(sums[P].rgb); lb = (Lc - st.L) / kf; m2' = st.m2 + lb * lb; n' = st.n + 1.0f; s' = st.w + kf;
+ *   mean = Lc / s'; v = m2' / n' - mean * mean; var = v < 0 ? 0 : v (a NaN stays a NaN); err2 = var / n';
+ *   mx = mean > a->floor ? mean : a->floor (a NaN mean gives floor); thr = a->tolerance * mx; thr2 = thr * thr.
+ *   P is CAPPED when s' >= hi, and then PASSES.  Otherwise P passes when s' >= lo && n' >= 2.0f && err2 <= thr2: comparisons, which
+ *   a NaN fails, so a pixel whose sums are not finite runs to the cap.
+ *   The stop.  guide == NULL: P stops when it passes.  With a guide (what tdt_dispatch_guide wrote for sample 0 of the frame): a
+ *   capped P stops; any other P stops when it passes AND every texel Q of its 3x3 neighbourhood that lies inside the image and has
+ *   the same key (tdt_image_denoise's: words 0, 1, 2 of the two guide texels are equal; a kind-0 texel is treated like any other)
+ *   passes, Q's test being evaluated from state_in and sums as above, never from state_out.  So a pixel whose few batches happened
+ *   to agree does not stop next to pixels of its own face that are still noisy; neighbours that stopped earlier or are capped do
+ *   not hold it back.
+ *   state_out[P] = (Lc, m2', n', stopped ? -s' : s').
+ * state_in and state_out are distinct images that ping-pong, as the history images of tdt_image_reproject do.  Batch-mean variance
+ * needs two batches: nothing stops before its second update unless it is capped.
+ *
+ * tdt_debug_adapt_counts (synchronises): of the context's last tdt_image_adapt that returned TDT_OK, [0] the pixels that had not
+ * stopped in state_in, [1] those of them stopped by the tolerance, [2] stopped by the cap, [3] still live;
+ * [1] + [2] + [3] = [0].  Before any call all four are 0.
+ *
+ * tdt_image_adapt_mean, asynchronous: img holds the running sums the state describes.  Per pixel, aw = |state[P].w|.  aw == 0:
+ * nothing is written.  Otherwise img[P].c = img[P].c / aw for c = r, g, b (IEEE divides), and img[P].a = the variance of the mean
+ * luminance: n >= 2.0f (NaN fails): mean = L / aw; v = m2 / n - mean * mean; v = v > 0 ? v : 0 (a NaN gives 0); a = v / n; else
+ * a = +0.0f.  The result is the kind of image tdt_image_reproject's mean_out is: tdt_image_denoise, tdt_image_denoise_variance (the
+ * alpha is its variance) and tdt_dispatch_resolve with total_spp = 1 take it unchanged.
+ *
+ * The intended frame: clear the bound image and a state image; then repeat { tdt_dispatch_accumulate_masked(begin, k, carry,
+ * state); tdt_image_adapt(image, guide, state, other state, k, ..); swap the states; begin += k } until count [3] is 0; then
+ * tdt_image_adapt_mean, the filter, the resolve.  Masks only shrink, so every pixel holds a prefix [0, n_P) of the sample
+ * sequence and begin is the same for all live pixels.  Reading the counts is a host synchronisation per round.
+ *
+ * Errors, nothing written: a NULL handle (guide excepted) or a NULL a; flags != 0; spp_count outside 1..2^24; tolerance or floor
+ * negative or not finite; min_samples outside 0..2^24; max_samples outside 1..2^24; images not of one size; any two of the images
+ * the same or sharing memory: TDT_ERR_INVALID_VALUE.  An image of another context; a multi-device context:
+ * TDT_ERR_INVALID_OPERATION. */
+typedef struct tdt_adapt {
+  float   tolerance;           /* relative error of the mean luminance at which a pixel stops */
+  float   floor;               /* the brightness below which the error is measured against `floor` itself */
+  int32_t min_samples;         /* no pixel stops by the tolerance with fewer samples */
+  int32_t max_samples;         /* the cap: a pixel with this many samples stops */
+} tdt_adapt;
+int tdt_image_adapt(const tdt_image *sums, const tdt_image *guide /* may be NULL */, const tdt_image *state_in, tdt_image *state_out,
+                    int spp_count, const tdt_adapt *a, uint32_t flags);
+int tdt_debug_adapt_counts(tdt_ctx *ctx, uint64_t out[4]);
+int tdt_image_adapt_mean(tdt_image *img, const tdt_image *state, uint32_t flags);
 
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing

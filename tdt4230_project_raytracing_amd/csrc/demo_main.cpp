@@ -14,6 +14,7 @@
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--upsample S]
+//            [--adaptive TOL [--batch K]]
 //            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -34,6 +35,11 @@
 //   image_width = ceil(W / S), image_height = ceil(H / S) into images of that size, the full-resolution guide, Texture::upsample into
 //   the render texture, then --denoise N [--variance SIGMA] over it as above, and the resolve.  Prints the bilinear / ring / hole
 //   pixel counts.  Not with --temporal.
+// --adaptive TOL [--batch K]: the frame's samples in batches of K (default 2) for the pixels that are still noisy
+//   (ComputeShader::dispatch_accumulate_masked, Texture::adapt with the guide of sample 0): a pixel stops when the error of its mean
+//   luminance is below TOL of it in its whole same-key 3x3 neighbourhood, at the latest with spp samples; then Texture::adapt_mean,
+//   --denoise N [--variance SIGMA] over the means (the variance is the batch means' own), and the resolve.  Prints the rounds and
+//   the mean samples per pixel.  Not with --temporal or --upsample.
 // --pick X,Y [--click left|right] [--material N]: the click handler aimed at pixel (X, Y) of the frame's camera (texture
 //   coordinates, row 0 at the bottom; sample 0): prints what the pick hit and, on a hit, places (left, the default) or removes
 //   (right) a voxel of material N (default 1) through Octree::update_vbo before the frame is rendered.
@@ -116,7 +122,8 @@ int main(int argc, char **argv) {
   std::vector<int32_t> mask;
   long long pad_cells = 0;
   std::vector<int32_t> box;
-  int config = -1, denoise = 0, temporal = 0, upsample = 0;
+  int config = -1, denoise = 0, temporal = 0, upsample = 0, batch = 2;
+  float adaptive = -1.0f;
   float turn = 1.0f, variance = 0.0f;                                                    // variance 0: the key-only filter
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -138,6 +145,8 @@ int main(int argc, char **argv) {
     else if (a == "--variance") { variance = (float)std::atof(next()); if (!(variance > 0.0f) || !(variance < 1e30f)) { std::fprintf(stderr, "--variance SIGMA, SIGMA > 0\n"); return 2; } }
     else if (a == "--temporal") { temporal = std::atoi(next()); if (temporal < 1) { std::fprintf(stderr, "--temporal N, N >= 1\n"); return 2; } }
     else if (a == "--turn") turn = (float)std::atof(next());
+    else if (a == "--adaptive") { adaptive = (float)std::atof(next()); if (!(adaptive >= 0.0f) || !(adaptive < 1e30f)) { std::fprintf(stderr, "--adaptive TOL, TOL >= 0\n"); return 2; } }
+    else if (a == "--batch") { batch = std::atoi(next()); if (batch < 1) { std::fprintf(stderr, "--batch K, K >= 1\n"); return 2; } }
     else if (a == "--upsample") { upsample = std::atoi(next()); if (upsample < 1) { std::fprintf(stderr, "--upsample S, S >= 1\n"); return 2; } }
     else if (a == "--brush") {
       char kind[16] = {0};
@@ -218,6 +227,7 @@ int main(int argc, char **argv) {
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
+  if (adaptive >= 0.0f && (temporal > 0 || upsample > 0)) { std::fprintf(stderr, "--adaptive does not combine with --temporal or --upsample\n"); return 2; }
   if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
   if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
   try {
@@ -549,6 +559,29 @@ int main(int argc, char **argv) {
       ctx.check(tdt_debug_upsample_counts(ctx.raw(), counts));
       std::printf("upsample %d from %dx%d pixels %llu bilinear %llu ring %llu holes %llu\n", upsample, lw, lh, (unsigned long long)counts[0],
                   (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
+    } else if (adaptive >= 0.0f) {                                                       // NEW: batches of samples for the pixels that are still noisy
+      const int tw = camera.render_texture.width(), th = camera.render_texture.height();
+      const Texture guide = Texture::new_2d(ctx, tw, th, false), carry = Texture::new_2d(ctx, 4 * tw, th, false);   // (carry: 16 floats per pixel)
+      const Texture states[2] = {Texture::new_2d(ctx, tw, th, false), Texture::new_2d(ctx, tw, th, false)};
+      const tdt_adapt limits = {adaptive, 0.05f, 4, spp};                                // the cap is the camera's samples per pixel
+      camera.render_texture.clear();
+      uint64_t counts[4] = {0, 0, 0, 0}, samples = 0;
+      int cur = 0, rounds = 0;
+      for (int begin = 0;; begin += batch) {
+        raytrace_program.dispatch_accumulate_masked(dw, dh, dd, begin, batch, tdt_image_device_ptr(carry.id()), states[cur]);
+        if (begin == 0) raytrace_program.dispatch_guide(guide);
+        camera.render_texture.adapt(&guide, states[cur], states[cur ^ 1], batch, limits);
+        cur ^= 1; rounds++;
+        ctx.check(tdt_debug_adapt_counts(ctx.raw(), counts));
+        samples += counts[0] * (uint64_t)batch;
+        if (counts[3] == 0) break;
+      }
+      camera.render_texture.adapt_mean(states[cur]);
+      if (variance > 0.0f) camera.render_texture.denoise_variance(guide, denoise, variance);    // (alpha: the batch-mean variance adapt_mean left)
+      else if (denoise > 0) camera.render_texture.denoise(guide, denoise);
+      ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, 1));
+      std::printf("adaptive %g batch %d rounds %d mean spp %.3f of %d\n", (double)adaptive, batch, rounds,
+                  (double)samples / ((double)tw * (double)th), spp);
     } else if (denoise > 0) {                                                            // NEW: sums, first hits, filter, then the square root
       const Texture guide = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
       ctx.check(tdt_dispatch_accumulate(raytrace_program.program.id(), dw, dh, dd, 0, spp, nullptr));

@@ -10,7 +10,8 @@
 // share: the capped tree list, keys, last-of-run unique, scan-gather-count); tdt_denoise.hip: first-hit guide images and the
 // edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides; tdt_variance.hip: the
 // variance of the luminance and the filter it guides (what these three share on the device: denoise_device.hpp); tdt_upsample.hip:
-// guide-keyed upsampling of a frame traced at reduced resolution.  The host helpers
+// guide-keyed upsampling of a frame traced at reduced resolution; tdt_adaptive.hip: the sampling controller that turns per-pixel
+// variance into the masks of tdt_dispatch_accumulate_masked.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
@@ -74,6 +75,7 @@ struct tdt_ctx {
   void *denoise = nullptr; size_t denoise_bytes = 0;   // ping-pong images of tdt_image_denoise (tdt_denoise.hip), grow-only
   unsigned long long *reproject_counts = nullptr;      // tdt_debug_reproject_counts: four device words of the last tdt_image_reproject (tdt_reproject.hip)
   unsigned long long *upsample_counts = nullptr;       // tdt_debug_upsample_counts: the device word block of the last tdt_image_upsample (tdt_upsample.hip)
+  unsigned long long *adapt_counts = nullptr;          // tdt_debug_adapt_counts: the device word block of the last tdt_image_adapt (tdt_adaptive.hip)
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
@@ -326,11 +328,13 @@ int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P);
 // the camera uniforms of a program into P (what primary_ray reads)
 void query_camera(const tdt_compute *cam, TraceParams &P);
 
-// ---- tdt_denoise.hip, and the host frame of an image call that it, tdt_variance.hip, tdt_reproject.hip and tdt_upsample.hip share ----
+// ---- tdt_denoise.hip, and the host frame of an image call that it, tdt_variance.hip, tdt_reproject.hip, tdt_upsample.hip and
+// tdt_adaptive.hip share ----
 constexpr int kMaxPasses = 8;
 void denoise_scratch_destroy(tdt_ctx *ctx);
 void reproject_counts_destroy(tdt_ctx *ctx);           // (tdt_reproject.hip)
 void upsample_counts_destroy(tdt_ctx *ctx);            // (tdt_upsample.hip)
+void adapt_counts_destroy(tdt_ctx *ctx);               // (tdt_adaptive.hip)
 // the images passes 0 .. passes - 1 (1..8) of an in-place filter over img (w x h RGBA32F on member m) read and write: pass p goes
 // seq[p] -> seq[p + 1], seq[0] = img, the others the context's grow-only scratch; seq holds passes + 1 entries.  Ends in img
 // unless passes == 1 (run_passes copies seq[1] back).

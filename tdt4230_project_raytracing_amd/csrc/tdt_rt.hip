@@ -821,6 +821,19 @@ __global__ __launch_bounds__(256) void miss_prepass_kernel(const TraceParams P, 
   done[slot] = (!covered || all_miss) ? 1u : 0u;      // (slots outside the covered image have nothing to trace either)
 }
 
+// Masked accumulate (tdt_dispatch_accumulate_masked): the other producer of done flags.  One lane per queue slot, addressed as the
+// resolve addresses its pixels; a slot is handed out when its pixel is covered and its mask texel is live (mask.w >= 0: +0 and -0
+// are, negatives and NaN are not).  The mask has the bound image's size and the image is no tile buffer (the entry point checks
+// both), so a covered pixel's texel exists.  The trace kernel touches image and carry of the slots it is handed only.
+__global__ __launch_bounds__(256) void mask_slots_kernel(const TraceParams P, const float4 *__restrict__ mask, uint8_t *__restrict__ done) {
+  int x, y; size_t pix;
+  const bool covered = pixel_of_thread(P, x, y, pix);
+  const size_t slot = (size_t)(blockIdx.x >> 2) * 1024u + (size_t)((blockIdx.x & 3) * 256 + threadIdx.x);
+  bool live = false;
+  if (covered) live = mask[pix].w >= 0.0f;
+  done[slot] = (!covered || !live) ? 1u : 0u;
+}
+
 // The hand-out order without the slots the pre-pass finished: a stable compaction in two passes over chunks of kFilterChunk entries
 // (per-chunk counts; then every block sums the counts before its chunk and writes).  order == nullptr: image order (the identity).
 constexpr uint32_t kFilterChunk = 4096;
@@ -1674,6 +1687,7 @@ struct LaunchRequest {
   bool probe = false;                                  // the probe launch of a two-phase frame (kernel name only)
   bool prepass_ran = false;                            // the frame's miss pre-pass ran: its done slots are left out (tdt_dispatch_resolve on its own: false, every pixel is resolved)
   unsigned long long *counts_out = nullptr;            // instrumented dispatch: where its eight totals go
+  const float *mask = nullptr;                         // masked accumulate: the mask image's texels (mask_slots_kernel); null: every covered pixel
 };
 
 int bind_params(const tdt_compute *c, int width, int height, const LaunchRequest &rq, TraceParams &P, Cover &k, Tiles &t) {
@@ -1738,6 +1752,16 @@ int launch_miss_prepass(tdt_ctx *ctx, TraceState &S, int owned, const TraceParam
   TDT_HIP(ctx, S.grow(S.miss.capacity, (uint32_t)owned, {{S.miss.slot_done, n}, {S.miss.slot_live, n},
                                                          {S.miss.filter_counts, (n + tdt::kFilterChunk - 1) / tdt::kFilterChunk + 1}}));
   hipLaunchKernelGGL(tdt::miss_prepass_kernel, dim3((unsigned)owned * 4u), dim3(256), 0, ctx->stream, P, S.miss.slot_done);
+  TDT_HIP(ctx, hipGetLastError());
+  return TDT_OK;
+}
+
+// the done flags of a masked accumulate (see mask_slots_kernel); grows the arrays the miss pre-pass shares, as that pass does
+int launch_mask_slots(tdt_ctx *ctx, TraceState &S, int owned, const TraceParams &P, const float *mask) {
+  const size_t n = (size_t)owned * 1024;
+  TDT_HIP(ctx, S.grow(S.miss.capacity, (uint32_t)owned, {{S.miss.slot_done, n}, {S.miss.slot_live, n},
+                                                         {S.miss.filter_counts, (n + tdt::kFilterChunk - 1) / tdt::kFilterChunk + 1}}));
+  hipLaunchKernelGGL(tdt::mask_slots_kernel, dim3((unsigned)owned * 4u), dim3(256), 0, ctx->stream, P, reinterpret_cast<const float4 *>(mask), S.miss.slot_done);
   TDT_HIP(ctx, hipGetLastError());
   return TDT_OK;
 }
@@ -2091,7 +2115,9 @@ int launch(tdt_compute *c, int width, int height, int depth, const LaunchRequest
       if (int rc = plan_order(ctx, S, sig, rq, t.owned, (uint32_t)ctx->num_cus * (uint32_t)(build.per_cu * build.block), h)) return rc;
       P.slot_order = h.slot_order; P.plan = h.plan; P.slot_cost = h.slot_cost;
     }
-    if (rq.prepass_ran && !rq.counts_out)
+    if (rq.mask)                       // (never in a frame whose pre-pass ran: the two share S.miss, and each writes every flag it filters by)
+      if (int rc = launch_mask_slots(ctx, S, t.owned, P, rq.mask)) return rc;
+    if ((rq.prepass_ran || rq.mask) && !rq.counts_out)
       if (int rc = filter_done(ctx, S.miss, t.owned, P.slot_order)) return rc;
     if (int rc = launch_trace(ctx, S, rq, f, build, t.owned, P)) return rc;
   }
@@ -2166,6 +2192,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   tdt::denoise_scratch_destroy(ctx);
   tdt::reproject_counts_destroy(ctx);
   tdt::upsample_counts_destroy(ctx);
+  tdt::adapt_counts_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -2530,6 +2557,27 @@ int tdt_dispatch_accumulate(tdt_compute *c, int width, int height, int depth, in
   if (carry && ((uintptr_t)carry & 15) != 0) return fail(c->ctx, TDT_ERR_INVALID_VALUE, "carry memory must be 16-byte aligned");
   LaunchRequest rq;
   rq.kind = LaunchRequest::kAccumulate; rq.spp_begin = spp_begin; rq.spp_count = spp_count; rq.carry = carry;
+  return launch(c, width, height, depth, rq);
+}
+
+int tdt_dispatch_accumulate_masked(tdt_compute *c, int width, int height, int depth, int spp_begin, int spp_count, void *carry,
+                                   const tdt_image *mask) {
+  if (!c) return TDT_ERR_INVALID_VALUE;
+  tdt_ctx *ctx = c->ctx;
+  if (!mask) return fail(ctx, TDT_ERR_INVALID_VALUE, "null mask image");
+  if (c->kind != TDT_PROGRAM_RAYTRACER) return fail(ctx, TDT_ERR_INVALID_OPERATION, "not the raytracer program");
+  if (spp_begin < 0 || spp_count < 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "negative sample range");
+  if (ctx->multi) return fail(ctx, TDT_ERR_INVALID_OPERATION, "a masked accumulate is a single-device call (the mask lives on one device)");
+  if (mask->ctx != ctx) return fail(ctx, TDT_ERR_INVALID_OPERATION, "the mask image belongs to another context");
+  if (carry && ((uintptr_t)carry & 15) != 0) return fail(ctx, TDT_ERR_INVALID_VALUE, "carry memory must be 16-byte aligned");
+  const tdt_image *img = ctx->image0;
+  if (!img) return fail(ctx, TDT_ERR_INCOMPLETE, "no image bound to unit 0");
+  if (img->w != c->image_width || img->h != c->image_height)
+    return fail(ctx, TDT_ERR_INVALID_OPERATION, "a masked accumulate needs the full camera.image_width x image_height image bound, not a tile buffer");
+  if (mask->w != img->w || mask->h != img->h) return fail(ctx, TDT_ERR_INVALID_VALUE, "the mask and the bound image differ in size");
+  if (mask == img || tdt::overlap(mask, img)) return fail(ctx, TDT_ERR_INVALID_OPERATION, "the mask is the bound image (or shares its memory)");
+  LaunchRequest rq;
+  rq.kind = LaunchRequest::kAccumulate; rq.spp_begin = spp_begin; rq.spp_count = spp_count; rq.carry = carry; rq.mask = mask->dev;
   return launch(c, width, height, depth, rq);
 }
 

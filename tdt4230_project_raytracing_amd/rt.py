@@ -250,6 +250,14 @@ def _mesh(vertices, triangles, materials, material):
     return mesh, (v, t, m)
 
 
+class Adapt(ctypes.Structure):
+    """struct tdt_adapt: the relative error of the mean luminance at which a pixel stops, the brightness floor that error is
+    measured against, and the fewest / most samples a pixel receives."""
+    _fields_ = [("tolerance", ctypes.c_float), ("floor", ctypes.c_float), ("min_samples", ctypes.c_int32), ("max_samples", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Adapt) == 16
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -285,6 +293,7 @@ SYMBOLS = [
     ("tdt_dispatch_compute", _I, [_P, _I, _I, _I]),
     ("tdt_set_partition", _I, [_P, _I, _I]),
     ("tdt_dispatch_accumulate", _I, [_P, _I, _I, _I, _I, _I, _P]),
+    ("tdt_dispatch_accumulate_masked", _I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     ("tdt_dispatch_resolve", _I, [_P, _I, _I, _I, _I]),
     ("tdt_covered_pixels", ctypes.c_int64, [_P, _I, _I, _I]),
     ("tdt_owned_tiles", _I, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -323,6 +332,9 @@ SYMBOLS = [
     ("tdt_image_reproject_moments", _I, [_P, _I, _P, _P, _I, ctypes.POINTER(VIEW), _P, _P, _P, _F, _P, _P, _P, ctypes.c_uint32]),
     ("tdt_image_upsample", _I, [_P, _P, _P, _P, ctypes.c_uint32]),
     ("tdt_debug_upsample_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tdt_image_adapt", _I, [_P, _P, _P, _P, _I, ctypes.POINTER(Adapt), ctypes.c_uint32]),
+    ("tdt_debug_adapt_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tdt_image_adapt_mean", _I, [_P, _P, ctypes.c_uint32]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -921,6 +933,13 @@ class Context:
         self.check(lib().tdt_debug_upsample_counts(self.h, c))
         return tuple(int(v) for v in c)
 
+    def adapt_counts(self):
+        """tdt_debug_adapt_counts: (live before, stopped by the tolerance, stopped by the cap, still live) of the last Texture.adapt
+        (blocks)."""
+        c = (ctypes.c_uint64 * 4)()
+        self.check(lib().tdt_debug_adapt_counts(self.h, c))
+        return tuple(int(v) for v in c)
+
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
         return int(lib().tdt_debug_fill_passes(self.h))
@@ -1108,6 +1127,24 @@ class Texture:
         validated bilinear, else the mean of the same-key texels of the 4x4 ring, else the nearest texel.  Asynchronous."""
         self.ctx.check(lib().tdt_image_upsample(self.h, dst_guide.h, src.h, src_guide.h, 0))
 
+    def adapt(self, guide, state_in, state_out, spp_count, tolerance, floor=0.0, min_samples=0, max_samples=1 << 24):
+        """tdt_image_adapt with this texture as `sums`: after a batch of spp_count samples for the live pixels of state_in,
+        state_out receives every live pixel's updated (L, m2, n, w) with w negated where the pixel stops — the error of its mean
+        luminance is below tolerance * max(mean, floor), with a guide (may be None) in its whole same-key 3x3 neighbourhood, or it
+        has max_samples.  state_out is the next ComputeShader.dispatch_accumulate_masked's mask.  Asynchronous."""
+        a = Adapt(float(tolerance), float(floor), int(min_samples), int(max_samples))
+        self.ctx.check(lib().tdt_image_adapt(self.h, guide.h if guide is not None else None, state_in.h, state_out.h, int(spp_count),
+                                             ctypes.byref(a), 0))
+
+    def adapt_mean(self, state):
+        """tdt_image_adapt_mean: this texture's running sums become means, rgb / the sample count |w| of `state`, and alpha the
+        variance of the mean luminance; pixels without samples are left alone.  Asynchronous."""
+        self.ctx.check(lib().tdt_image_adapt_mean(self.h, state.h, 0))
+
+    def device_ptr(self):
+        """tdt_image_device_ptr: the address of the texels in device memory."""
+        return int(lib().tdt_image_device_ptr(self.h) or 0)
+
 
 class Program:
     """Uniform-by-name setters of program.rs:35-83 (the program object itself is the kernel)."""
@@ -1172,6 +1209,12 @@ class ComputeShader:
     def dispatch_accumulate(self, width, height, depth, spp_begin, spp_count, carry_ptr=None):
         self.ctx.check(lib().tdt_dispatch_accumulate(self.h, width, height, depth, spp_begin, spp_count,
                                                      ctypes.c_void_p(carry_ptr) if carry_ptr else None))
+
+    def dispatch_accumulate_masked(self, width, height, depth, spp_begin, spp_count, carry_ptr, mask):
+        """tdt_dispatch_accumulate_masked: dispatch_accumulate for the covered pixels whose texel of `mask` (a Texture of the bound
+        image's size) has w >= 0; every other pixel keeps its texel and its carry.  A Texture.adapt state image is such a mask."""
+        self.ctx.check(lib().tdt_dispatch_accumulate_masked(self.h, width, height, depth, spp_begin, spp_count,
+                                                            ctypes.c_void_p(carry_ptr) if carry_ptr else None, mask.h))
 
     def dispatch_resolve(self, width, height, depth, total_spp):
         self.ctx.check(lib().tdt_dispatch_resolve(self.h, width, height, depth, total_spp))
@@ -1335,6 +1378,8 @@ class Renderer:
         self.guide = None                      # render(denoise=N) creates it on first use
         self.temporal = None                   # render_temporal's state, created on first use
         self.low = None                        # render_upsampled's low-resolution (sums, guide) textures, created on first use
+        self.adaptive = None                   # render_adaptive's two state textures and its carry, created on first use
+        self.adaptive_floor = 0.05             # render_adaptive: the brightness below which the error is measured against this value
         # sigma of the variance-guided filter that render(denoise=N) and render_temporal(denoise=N) run instead of the key-only one;
         # None: the key-only filter, exactly the calls made before the variance unit existed.  VARIANCE_SIGMA is the measured default.
         self.variance = None
@@ -1470,6 +1515,58 @@ class Renderer:
                 self.texture.variance(self.guide)
                 self.texture.denoise_variance(self.guide, denoise, self.variance)
         self.shader.dispatch_resolve(w, h, 1, spp)
+        return self.texture.read()
+
+    def render_adaptive(self, tolerance, batch=2, min_samples=4, max_samples=None, denoise=0):
+        """The frame with its samples spent where the image is still noisy (ComputeShader.dispatch_accumulate_masked, Texture.adapt).
+        Clear the texture, one state texture and the carry; then rounds of `batch` samples for the pixels still live, each followed
+        by Texture.adapt (with the guide of sample 0, taken once) and a read of its counts, until nothing is live — at the latest
+        when every live pixel has max_samples (None: the camera's samples_per_pixel).  Then Texture.adapt_mean, `denoise` > 0: the
+        filter calls render(denoise=N) makes (self.variance decides which; the variance-guided filter reads the batch-mean variance
+        adapt_mean left in alpha), and the resolve with total_spp = 1.  Every pixel ends with a prefix [0, n) of the sample
+        sequence, n a multiple of batch; self.adaptive["samples"]() reads the last call's per-pixel sample counts, ["rounds"] its rounds.  A
+        single-device renderer whose image is the whole frame only.  Returns the resolved frame."""
+        W, H = self.camera.image_width, self.camera.image_height
+        if self.ctx.device_count() != 1 or self.texture.width() != W or self.texture.height() != H:
+            raise ValueError("render_adaptive needs a single-device renderer that owns the whole image")
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise ValueError("render_adaptive: batch must be an int >= 1")
+        cap = self.camera.samples_per_pixel if max_samples is None else max_samples
+        if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
+            raise ValueError("render_adaptive: max_samples must be an int >= 1")
+        w, h = W + 1, H + 1
+        if self.guide is None:
+            self.guide = Texture.new_2d(self.ctx, W, H, bind=False)
+        if self.adaptive is None:
+            new = lambda cols: Texture.new_2d(self.ctx, cols, H, bind=False)  # noqa: E731
+            self.adaptive = {"state": (new(W), new(W)), "carry": new(4 * W)}      # (the carry: 16 floats per pixel = four texels)
+        t = self.adaptive
+        cur, other = t["state"]
+        self.texture.clear()
+        cur.clear()
+        t["carry"].clear()
+        carry = t["carry"].device_ptr()
+        begin, rounds = 0, 0
+        while True:
+            self.shader.dispatch_accumulate_masked(w, h, 1, begin, batch, carry, cur)
+            if rounds == 0:
+                self.shader.dispatch_guide(self.guide)
+            self.texture.adapt(self.guide, cur, other, batch, tolerance, self.adaptive_floor, min_samples, cap)
+            cur, other = other, cur
+            begin += batch
+            rounds += 1
+            if self.ctx.adapt_counts()[3] == 0:
+                break
+        t["state"] = (cur, other)
+        t["rounds"] = rounds
+        t["samples"] = lambda: np.abs(cur.read()[..., 3]).astype(np.int64)
+        self.texture.adapt_mean(cur)
+        if denoise > 0:
+            if self.variance is None:
+                self.texture.denoise(self.guide, denoise)
+            else:
+                self.texture.denoise_variance(self.guide, denoise, self.variance)
+        self.shader.dispatch_resolve(w, h, 1, 1)
         return self.texture.read()
 
     def pick(self, xy, sample=0, return_rays=False):
