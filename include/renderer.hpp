@@ -181,6 +181,21 @@ class Texture {
   }
   // NEW: running sums to means by the sample counts of `state`, alpha = the variance of the mean luminance (tdt_image_adapt_mean)
   void adapt_mean(const Texture &state) const { ctx_->check(tdt_image_adapt_mean(img_, state.img_, 0)); }
+  // NEW: a voxel list {x, y, z, m} (4 ints each, m ignored) drawn over this texture, in place (tdt_image_overlay): the pixels whose
+  // voxel in `ids` (ComputeShader::dispatch_voxel_ids, an image of this size) is in the list are blended with style.fill, those
+  // within style.edge_width pixels of the selection's border with style.edge.  First hit only.  The passes are queued.
+  void overlay(const Texture &ids, const std::vector<int32_t> &voxels_xyzm, const tdt_overlay &style) const {
+    ctx_->check(tdt_image_overlay(img_, ids.img_, voxels_xyzm.empty() ? nullptr : voxels_xyzm.data(), voxels_xyzm.size() / 4, &style));
+  }
+  // NEW: the distinct voxels {x, y, z, material + 1} visible in this voxel-id image inside rect = {x0, y0, x1, y1} (inclusive,
+  // clipped; null: the whole image), in Morton order (tdt_image_extract_voxels): the brush of Octree::edit_voxels
+  std::vector<int32_t> extract_voxels(const int32_t *rect = nullptr) const {
+    size_t n = 0;
+    ctx_->check(tdt_image_extract_voxels(img_, rect, nullptr, 0, &n));
+    std::vector<int32_t> v(n * 4);
+    if (n) ctx_->check(tdt_image_extract_voxels(img_, rect, v.data(), n, &n));
+    return v;
+  }
  private:
   Context *ctx_ = nullptr;
   tdt_image *img_ = nullptr;
@@ -240,6 +255,11 @@ class ComputeShader {
   // depth of the primary ray of pixel (x, y), sample `sample`, of this program's camera; flags: TDT_GUIDE_ALL_MATERIALS.  Asynchronous.
   void dispatch_guide(const Texture &guide, int sample = 0, uint32_t flags = 0) const {
     ctx_->check(tdt_dispatch_guide(program.id(), guide.id(), sample, flags));
+  }
+  // NEW: the voxel a click on every pixel would act on (tdt_dispatch_voxel_ids): texel (x, y) of `ids` receives tdt_pick_grid_voxel
+  // of that pixel's pick as a tdt_voxel_id_texel; place = 0 the voxel behind the face, 1 the empty cell in front.  Asynchronous.
+  void dispatch_voxel_ids(const Texture &ids, int place = 0, int sample = 0) const {
+    ctx_->check(tdt_dispatch_voxel_ids(program.id(), ids.id(), place, sample));
   }
   // NEW: tdt_dispatch_accumulate for the covered pixels whose texel of `mask` has w >= 0 (tdt_dispatch_accumulate_masked); every
   // other pixel keeps its texel and its carry.  A Texture::adapt state image is such a mask.

@@ -588,6 +588,93 @@ int tdt_image_adapt(const tdt_image *sums, const tdt_image *guide /* may be NULL
 int tdt_debug_adapt_counts(tdt_ctx *ctx, uint64_t out[4]);
 int tdt_image_adapt_mean(tdt_image *img, const tdt_image *state, uint32_t flags);
 
+/* ---- screen-space selection: voxel-id images, overlays, marquee ---------------------------------------------------------------
+ * The editing calls below produce Morton-sorted voxel lists, the image calls above work on RGBA32F images keyed by each pixel's
+ * first hit; these calls join the two.  The one primitive is a VOXEL-ID IMAGE: per pixel, the grid voxel a click on that pixel
+ * would act on.  Membership of that voxel in a list gives an overlay (a tdt_octree_extract_* preview drawn into a frame), the
+ * distinct ids of a rectangle give a marquee selection (the brush of tdt_octree_edit_voxels).  The id image depends on camera
+ * and tree only: a brush that is dragged re-runs only the overlay.  First hit only: occluded voxels of a list are not shown, and
+ * with place == 1 only empty cells adjacent to a visible face have a pixel.
+ *
+ * tdt_dispatch_voxel_ids: for every texel (x, y) of `ids` — any RGBA32F image of the context, of any size; the camera uniforms
+ * define the rays, not the image — the primary ray of pixel (x, y) and sample `sample` >= 0 is traced exactly as
+ * tdt_dispatch_guide traces it: one lane per texel, 16x16 ray tiles.  Asynchronous on the context's stream.  Reads slots 0, 6 and
+ * 7 only; the bound image, the cost history, the hand-out order and the frame carry are left as they were.  The texel receives the
+ * voxel tdt_pick_grid_voxel(hit, floats, ints, place) returns for that pixel's tdt_pick_pixels record `hit`, computed in fp64 on the
+ * device.  For each axis a: q = ((double)point[a] - (double)min[a]) / (double)scale + side * (double)normal[a] * half, where
+ * half = 0.5 / 2^depth, side is +1 for place == 1 (the empty cell in front of the face) and -1 for place == 0 (the voxel behind
+ * it); k[a] = floor(q * 2^depth).  The voxel is valid when 0 <= k[a] < 2^depth on all three axes.  Products by +-1 and by powers
+ * of two are exact, so the only roundings are the subtraction, the divide and the add, each a correctly rounded fp64 operation.
+ * tdt_pick_grid_voxel (tdt_host.h) stays the single statement of this arithmetic that tests compare against.  The texel's 16 bytes
+ * (struct tdt_voxel_id_texel):
+ *   state     1 when status == TDT_RAY_HIT, fresh_record != 0 and the voxel is valid, otherwise 0: exactly when tdt_pick_grid_voxel
+ *             succeeds
+ *   key       the voxel's Morton key, spread3(x) << 2 | spread3(y) << 1 | spread3(z) in tdt_octree_extract's order; 0 when
+ *             state == 0
+ *   material  hit.material, as the guide's word
+ *   t         the bits of hit.t, as the guide's word
+ * Errors, nothing written: NULL handles, sample < 0, place not 0 or 1: TDT_ERR_INVALID_VALUE; a TDT_PROGRAM_OCTREE_UPDATE program,
+ * a partition other than (0, 1), an image of another context: TDT_ERR_INVALID_OPERATION; slots 0, 6 or 7 unbound:
+ * TDT_ERR_INCOMPLETE; max_depth outside 1..10 (the key must fit 30 bits) or a scale that is not positive and finite:
+ * TDT_ERR_INVALID_VALUE.  A multi-device context runs on device_ids[0].
+ *
+ * tdt_image_overlay: tints, in place over `img`, the pixels whose voxel is in a list.  `ids` has img's size and shares no memory
+ * with it.  voxels_xyzm is a host array of n x {x, y, z, m} as tdt_octree_edit_voxels takes it with TDT_REGION_CLEAR: m is
+ * ignored, the order is arbitrary, duplicates are allowed, voxels with a coordinate outside [0, 1024) are dropped.  n == 0: the
+ * list is empty and img is unchanged, bit for bit.  The list is uploaded before the call returns (one synchronisation of the
+ * stream; the host array may be freed on return); keys, sort, unique and the pass itself are queued.  For pixel P:
+ *   member(P): ids[P].state == 1 and ids[P].key is in the list.
+ *   edge(P): member(P), edge_width >= 1, and some Q != P inside the image with max(|dx|, |dy|) <= edge_width satisfies one of:
+ *   !member(Q); TDT_OVERLAY_VOXEL_EDGES is set, and ids[Q].state != 1 or ids[Q].key != ids[P].key.  Pixels outside the image
+ *   are not consulted.
+ *   A non-member pixel keeps all four channels bit for bit.  A member pixel takes col = edge(P) ? style->edge : style->fill and
+ *   a = col[3]; out.c = (in.c * (1.0f - a)) + (col.c * a) for c = r, g, b: one subtract, two multiplies and one add, each rounded
+ *   on its own (NaN and inf propagate as the arithmetic says); alpha is in's.
+ * The intended use is on a resolved frame.  A numpy model of these lines gives the same bits, with one exception: where a line
+ * computes a NaN (inf * 0 with a = 1, inf - inf, an operation on a NaN), the result is a NaN whose sign and payload are not
+ * specified (IEEE 754 leaves them open); a channel that is copied keeps its bits, NaN or not.
+ *
+ * tdt_debug_overlay_counts (synchronises): of the context's last tdt_image_overlay that returned TDT_OK (a call that fails leaves
+ * the counts of the call before it), [0] pixels, [1] state == 1 pixels, [2] member pixels, [3] edge pixels.  Before any call all
+ * four are 0.
+ *
+ * Errors, nothing written: NULL img, ids or style, a NULL list with n > 0, edge_width outside 0..4, unknown flags, n above the
+ * voxel-list cap (TDT_REGION_BRUSH_CAP), img and ids of different sizes, the same image or sharing memory: TDT_ERR_INVALID_VALUE;
+ * an image of another context: TDT_ERR_INVALID_OPERATION.  A multi-device context runs on device_ids[0].
+ *
+ * tdt_image_extract_voxels: the distinct voxels of the state == 1 texels inside rect = {x0, y0, x1, y1}, inclusive, clipped to
+ * the image; NULL means the whole image; an empty rect after clipping, or x0 > x1 (or y0 > y1), gives 0 voxels.  The output is
+ * {x, y, z, material + 1}, Morton-sorted, by tdt_octree_extract's rules: voxels_xyzm == NULL: only the count; capacity < the
+ * count: TDT_ERR_INVALID_VALUE, *n_voxels still set, nothing written.  Where several texels carry one key with different
+ * materials (possible only for place == 1 ids), the last texel in row-major order wins: the stable sort and last-of-run rule of
+ * tdt_octree_build_cells.  A selected texel with material >= 254, or a rect of more than TDT_REGION_BRUSH_CAP texels:
+ * TDT_ERR_INVALID_VALUE, nothing written.  NULL ids or n_voxels: TDT_ERR_INVALID_VALUE.  Synchronous.  The result is the brush of
+ * tdt_octree_edit_voxels: marquee paint or clear is extract followed by edit. */
+#define TDT_OVERLAY_VOXEL_EDGES 1u   /* outline every voxel of the selection, not only the selection's silhouette */
+typedef struct tdt_voxel_id_texel {
+  uint32_t state;         /* 1 = tdt_pick_grid_voxel succeeds for this pixel, else 0 */
+  uint32_t key;           /* the voxel's Morton key; 0 when state == 0 */
+  uint32_t material;      /* hit.material */
+  uint32_t t;             /* the bits of hit.t */
+} tdt_voxel_id_texel;
+typedef struct tdt_overlay {
+  float    fill[4];       /* r, g, b, a for member pixels */
+  float    edge[4];       /* r, g, b, a for edge pixels */
+  int32_t  edge_width;    /* 0..4 pixels; 0 = no outline */
+  uint32_t flags;         /* TDT_OVERLAY_VOXEL_EDGES */
+} tdt_overlay;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_voxel_id_texel) == 16, "tdt_voxel_id_texel is one RGBA32F texel");
+static_assert(sizeof(tdt_overlay) == 40, "tdt_overlay is 40 bytes");
+#else
+_Static_assert(sizeof(tdt_voxel_id_texel) == 16, "tdt_voxel_id_texel is one RGBA32F texel");
+_Static_assert(sizeof(tdt_overlay) == 40, "tdt_overlay is 40 bytes");
+#endif
+int tdt_dispatch_voxel_ids(tdt_compute *c, tdt_image *ids, int place, int sample);
+int tdt_image_overlay(tdt_image *img, const tdt_image *ids, const int32_t *voxels_xyzm, size_t n, const tdt_overlay *style);
+int tdt_debug_overlay_counts(tdt_ctx *ctx, uint64_t out[4]);
+int tdt_image_extract_voxels(const tdt_image *ids, const int32_t rect[4], int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

@@ -14,7 +14,7 @@
 //            [--fill-enclosed [--conn 6|26] [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--upsample S]
-//            [--adaptive TOL [--batch K]]
+//            [--adaptive TOL [--batch K]] [--preview] [--select-rect X0,Y0,X1,Y1 [--op ..] [--material K]]
 //            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -57,6 +57,14 @@
 //   voxels of its material only with --match-material) or through the air (empty: from the voxel in front of it), by face steps
 //   (6, the default), face / edge / corner steps of cost 1 (26) or the chamfer weights 3 / 4 / 5 (345), inside the --mask box
 //   only — is applied with `op` in material K (solid: default the voxel's own).  Prints the pick and the new cell count.
+// --preview: with --box, --pick --brush or --pick --flood, the edit is not applied: the tree's voxels it would touch are
+//   extracted (tdt_octree_extract_region / tdt_octree_extract_connected) and drawn over the finished frame
+//   (ComputeShader::dispatch_voxel_ids with place 0, sample 0; Texture::overlay: fill 1, .6, 0, .35, edge 1, .6, 0, 1 of width 1).
+//   First hit only: voxels that something hides are not shown.  Prints the list's size and the overlay's pixel counts.
+// --select-rect X0,Y0,X1,Y1 [--op set|fill|paint|clear] [--material K]: marquee edit: the distinct voxels visible inside the pixel
+//   rectangle (inclusive, row 0 at the bottom; Texture::extract_voxels of the voxel ids of sample 0: for set / fill the empty
+//   cells in front of the visible faces, for paint / clear the voxels behind them) get `op` in material K
+//   (Octree::edit_voxels), after the picks, before --morph.  Prints the list's size and the new cell count.
 // --components [--connect 6|26] [--match any|material]: prints the component count and the largest component's size.
 // --morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]: voxel morphology (Octree::morph) of R steps with
 //   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
@@ -125,6 +133,8 @@ int main(int argc, char **argv) {
   int config = -1, denoise = 0, temporal = 0, upsample = 0, batch = 2;
   float adaptive = -1.0f;
   float turn = 1.0f, variance = 0.0f;                                                    // variance 0: the key-only filter
+  bool preview = false;
+  std::vector<int32_t> select_rect;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -224,12 +234,17 @@ int main(int argc, char **argv) {
     else if (a == "--no-merge") export_merge = false;
     else if (a == "--any-material") export_by_material = false;
     else if (a == "--config") config = std::atoi(next());
+    else if (a == "--preview") preview = true;
+    else if (a == "--select-rect") { int32_t v[4]; if (std::sscanf(next(), "%d,%d,%d,%d", v, v + 1, v + 2, v + 3) != 4) { std::fprintf(stderr, "--select-rect X0,Y0,X1,Y1\n"); return 2; } select_rect.assign(v, v + 4); }
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
   if (adaptive >= 0.0f && (temporal > 0 || upsample > 0)) { std::fprintf(stderr, "--adaptive does not combine with --temporal or --upsample\n"); return 2; }
   if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
   if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
+  const bool preview_box = !box.empty() && mesh_path.empty(), preview_pick = pick_x >= 0 && reach_cost < 0 && (flood_op >= 0 || brush_shape >= 0);
+  if (preview && preview_box == preview_pick) { std::fprintf(stderr, "--preview needs one of --box, --pick with --brush, --pick with --flood\n"); return 2; }
+  if (preview && (temporal > 0 || !select_rect.empty())) { std::fprintf(stderr, "--preview does not combine with --temporal or --select-rect\n"); return 2; }
   try {
     Context ctx(device);
     // main.rs:156-160
@@ -304,6 +319,14 @@ int main(int argc, char **argv) {
     // main.rs:455-468
     Octree octree = Octree::new_(min_point, scale, ints[0], ints[2], (int)counts[0], ints[1]);
     octree.init_global_buffers(ctx);
+    std::vector<int32_t> preview_list;                                                     // --preview: the selection, drawn over the frame
+    auto region_voxels = [&](const tdt_region &r) {                                        // the tree's voxels inside r (tdt_octree_extract_region)
+      size_t n = 0;
+      ctx.check(tdt_octree_extract_region(ctx.raw(), &r, 1, nullptr, 0, &n));
+      std::vector<int32_t> v(n * 4);
+      if (n) ctx.check(tdt_octree_extract_region(ctx.raw(), &r, 1, v.data(), n, &n));
+      return v;
+    };
     if (!edit.empty()) {                                                                  // main.rs:555-569, one click
       std::vector<float> delta(500, 0.0f);
       std::copy(edit.begin(), edit.end(), delta.begin());
@@ -342,9 +365,33 @@ int main(int argc, char **argv) {
       tdt_region r{};
       r.shape = TDT_SHAPE_BOX;
       for (int a = 0; a < 3; a++) { r.a[a] = box[a]; r.b[a] = box[3 + a]; }
-      std::printf("box cells %u\n", octree.edit_region(ctx, op, {r}, material));
+      if (preview) { preview_list = region_voxels(r); std::printf("preview box voxels %zu\n", preview_list.size() / 4); }
+      else std::printf("box cells %u\n", octree.edit_region(ctx, op, {r}, material));
     }
-    if (pick_x >= 0 && reach_cost >= 0) {                                                // a reach click at the pixel
+    if (preview && preview_pick) {                                                       // NEW: the click's selection, not applied
+      const tdt_ray_hit h = raytrace_program.pick({{{pick_x, pick_y}}}, 0)[0];
+      const float floats[7] = {min_point[0], min_point[1], min_point[2], 0.0f, scale, 1.0f / scale, 1.0f / (float)ints[2]};
+      const int side = flood_op < 0 && (op == TDT_REGION_SET || op == TDT_REGION_FILL) ? 1 : 0;   // (as Octree::brush / Octree::flood aim)
+      int32_t c[3];
+      const bool hit = tdt_pick_grid_voxel(&h, floats, ints, side, c) == 0;
+      if (hit && flood_op >= 0) {
+        tdt_select sel{};
+        sel.connectivity = connect; sel.match = match; sel.min_voxels = 0; sel.max_voxels = 0xFFFFFFFFu;
+        size_t n = 0;
+        ctx.check(tdt_octree_extract_connected(ctx.raw(), &sel, c, 1, nullptr, 0, nullptr, 0, &n));
+        preview_list.resize(n * 4);
+        if (n) ctx.check(tdt_octree_extract_connected(ctx.raw(), &sel, c, 1, nullptr, 0, preview_list.data(), n, &n));
+      } else if (hit) {
+        tdt_region r{};
+        r.shape = brush_shape;
+        for (int a = 0; a < 3; a++) r.a[a] = c[a];
+        if (brush_shape == TDT_SHAPE_SPHERE) r.b[0] = brush_size;
+        else for (int a = 0; a < 3; a++) { r.a[a] = c[a] - brush_size; r.b[a] = c[a] + brush_size; }
+        preview_list = region_voxels(r);
+      }
+      std::printf("pick %d,%d status %d material %u fresh %d preview %s voxels %zu\n", pick_x, pick_y, h.status, h.material, h.fresh_record,
+                  flood_op >= 0 ? "flood" : "brush", preview_list.size() / 4);
+    } else if (pick_x >= 0 && reach_cost >= 0) {                                              // a reach click at the pixel
       tdt_ray_hit h;
       uint32_t cells = 0;
       tdt_geodesic g{};
@@ -388,6 +435,15 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
                   h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
+    }
+    if (!select_rect.empty()) {                                                           // NEW: marquee: `op` over what the rectangle shows
+      const Texture ids = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
+      raytrace_program.dispatch_voxel_ids(ids, op == TDT_REGION_SET || op == TDT_REGION_FILL ? 1 : 0, 0);
+      std::vector<int32_t> list = ids.extract_voxels(select_rect.data());
+      if (op != TDT_REGION_CLEAR) for (size_t i = 3; i < list.size(); i += 4) list[i] = material + 1;
+      static const char *op_names[4] = {"set", "fill", "paint", "clear"};
+      std::printf("select-rect %d,%d,%d,%d op %s voxels %zu cells %u\n", select_rect[0], select_rect[1], select_rect[2], select_rect[3], op_names[op],
+                  list.size() / 4, octree.edit_voxels(ctx, op, list));
     }
     if (morph_op >= 0) {
       tdt_morph m{};
@@ -595,6 +651,16 @@ int main(int argc, char **argv) {
       ctx.check(tdt_dispatch_resolve(raytrace_program.program.id(), dw, dh, dd, spp));
     } else {
       raytrace_program.dispatch_compute(dw, dh, dd);
+    }
+    if (preview) {                                                                       // NEW: the selection over the resolved frame
+      const Texture ids = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);
+      raytrace_program.dispatch_voxel_ids(ids, 0, 0);
+      const tdt_overlay style = {{1.0f, 0.6f, 0.0f, 0.35f}, {1.0f, 0.6f, 0.0f, 1.0f}, 1, 0u};
+      camera.render_texture.overlay(ids, preview_list, style);
+      uint64_t counts[4];
+      ctx.check(tdt_debug_overlay_counts(ctx.raw(), counts));
+      std::printf("preview voxels %zu pixels %llu with-voxel %llu member %llu edge %llu\n", preview_list.size() / 4, (unsigned long long)counts[0],
+                  (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
     }
     VertexArrayObject::unbind();
     const std::vector<float> px = camera.render_texture.read();

@@ -11,7 +11,8 @@
 // edge-stopping filter over them; tdt_reproject.hip: temporal reprojection of samples through those guides; tdt_variance.hip: the
 // variance of the luminance and the filter it guides (what these three share on the device: denoise_device.hpp); tdt_upsample.hip:
 // guide-keyed upsampling of a frame traced at reduced resolution; tdt_adaptive.hip: the sampling controller that turns per-pixel
-// variance into the masks of tdt_dispatch_accumulate_masked.  The host helpers
+// variance into the masks of tdt_dispatch_accumulate_masked; tdt_select.hip: screen-space selection, where the two halves meet:
+// voxel-id images, overlays of a voxel list and the voxels of a rectangle.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
@@ -76,6 +77,8 @@ struct tdt_ctx {
   unsigned long long *reproject_counts = nullptr;      // tdt_debug_reproject_counts: four device words of the last tdt_image_reproject (tdt_reproject.hip)
   unsigned long long *upsample_counts = nullptr;       // tdt_debug_upsample_counts: the device word block of the last tdt_image_upsample (tdt_upsample.hip)
   unsigned long long *adapt_counts = nullptr;          // tdt_debug_adapt_counts: the device word block of the last tdt_image_adapt (tdt_adaptive.hip)
+  unsigned long long *overlay_counts = nullptr;        // tdt_debug_overlay_counts: the device word block of the last tdt_image_overlay (tdt_select.hip)
+  void *select = nullptr; size_t select_bytes = 0;     // the list of tdt_image_overlay in device memory (tdt_select.hip), grow-only
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
@@ -335,6 +338,7 @@ void denoise_scratch_destroy(tdt_ctx *ctx);
 void reproject_counts_destroy(tdt_ctx *ctx);           // (tdt_reproject.hip)
 void upsample_counts_destroy(tdt_ctx *ctx);            // (tdt_upsample.hip)
 void adapt_counts_destroy(tdt_ctx *ctx);               // (tdt_adaptive.hip)
+void select_scratch_destroy(tdt_ctx *ctx);             // (tdt_select.hip: the overlay's list and its counts)
 // the images passes 0 .. passes - 1 (1..8) of an in-place filter over img (w x h RGBA32F on member m) read and write: pass p goes
 // seq[p] -> seq[p + 1], seq[0] = img, the others the context's grow-only scratch; seq holds passes + 1 entries.  Ends in img
 // unless passes == 1 (run_passes copies seq[1] back).

@@ -2193,6 +2193,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
   tdt::reproject_counts_destroy(ctx);
   tdt::upsample_counts_destroy(ctx);
   tdt::adapt_counts_destroy(ctx);
+  tdt::select_scratch_destroy(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

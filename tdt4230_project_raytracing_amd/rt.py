@@ -258,6 +258,36 @@ class Adapt(ctypes.Structure):
 
 assert ctypes.sizeof(Adapt) == 16
 
+OVERLAY_VOXEL_EDGES = 1
+VOXEL_ID_TEXEL_DTYPE = np.dtype([("state", "<u4"), ("key", "<u4"), ("material", "<u4"), ("t", "<u4")])
+assert VOXEL_ID_TEXEL_DTYPE.itemsize == 16
+
+
+class Overlay(ctypes.Structure):
+    """struct tdt_overlay: the colours (r, g, b, a) of member and of edge pixels, the outline's width in pixels (0..4, 0 = none)
+    and the flags (OVERLAY_VOXEL_EDGES: outline every voxel, not only the selection's silhouette)."""
+    _fields_ = [("fill", ctypes.c_float * 4), ("edge", ctypes.c_float * 4), ("edge_width", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(Overlay) == 40
+
+
+def _overlay(fill, edge, edge_width, voxel_edges):
+    """The Overlay of Texture.overlay's arguments, refused here where they are not what the struct can carry."""
+    fill = tuple(float(v) for v in fill)
+    edge = fill if edge is None else tuple(float(v) for v in edge)
+    if len(fill) != 4 or len(edge) != 4:
+        raise ValueError("overlay: fill and edge are (r, g, b, a)")
+    if isinstance(edge_width, bool) or not isinstance(edge_width, (int, np.integer)) or not 0 <= edge_width <= 4:
+        raise ValueError("overlay: edge_width must be an int 0..4")
+    return Overlay((ctypes.c_float * 4)(*fill), (ctypes.c_float * 4)(*edge), int(edge_width), OVERLAY_VOXEL_EDGES if voxel_edges else 0)
+
+
+def _place(place):
+    if isinstance(place, bool) or place not in (0, 1):
+        raise ValueError("place must be 1 (the empty cell in front of the face) or 0 (the voxel behind it)")
+    return int(place)
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -335,6 +365,10 @@ SYMBOLS = [
     ("tdt_image_adapt", _I, [_P, _P, _P, _P, _I, ctypes.POINTER(Adapt), ctypes.c_uint32]),
     ("tdt_debug_adapt_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_image_adapt_mean", _I, [_P, _P, ctypes.c_uint32]),
+    ("tdt_dispatch_voxel_ids", _I, [_P, _P, _I, _I]),
+    ("tdt_image_overlay", _I, [_P, _P, _P, _S, ctypes.POINTER(Overlay)]),
+    ("tdt_debug_overlay_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tdt_image_extract_voxels", _I, [_P, ctypes.POINTER(ctypes.c_int32), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -940,6 +974,12 @@ class Context:
         self.check(lib().tdt_debug_adapt_counts(self.h, c))
         return tuple(int(v) for v in c)
 
+    def overlay_counts(self):
+        """tdt_debug_overlay_counts: (pixels, pixels with a voxel, member pixels, edge pixels) of the last Texture.overlay (blocks)."""
+        c = (ctypes.c_uint64 * 4)()
+        self.check(lib().tdt_debug_overlay_counts(self.h, c))
+        return tuple(int(v) for v in c)
+
     def fill_passes(self):
         """tdt_debug_fill_passes: the flood passes of the last enclosed-space call that changed the volume."""
         return int(lib().tdt_debug_fill_passes(self.h))
@@ -1141,6 +1181,35 @@ class Texture:
         variance of the mean luminance; pixels without samples are left alone.  Asynchronous."""
         self.ctx.check(lib().tdt_image_adapt_mean(self.h, state.h, 0))
 
+    def read_voxel_ids(self):
+        """The texels of a voxel-id image as an (H, W) array of VOXEL_ID_TEXEL_DTYPE (state, key, material, t: the bits of hit.t)."""
+        return self.read().view(VOXEL_ID_TEXEL_DTYPE).reshape(self._h, self._w)
+
+    def overlay(self, ids, voxels, fill, edge=None, edge_width=1, voxel_edges=False):
+        """tdt_image_overlay over this texture, in place: the pixels whose voxel in `ids` (a Texture of this size that
+        ComputeShader.dispatch_voxel_ids filled) is in `voxels` — an (n, 4) int32 list {x, y, z, m}, m ignored, any order — are
+        blended with fill = (r, g, b, a), those within edge_width pixels of the selection's border (voxel_edges: of their
+        voxel's) with edge (None: fill).  The passes are queued; `voxels` may be dropped on return."""
+        style = _overlay(fill, edge, edge_width, voxel_edges)
+        v = np.ascontiguousarray(np.asarray(voxels, np.int32).reshape(-1, 4))
+        self.ctx.check(lib().tdt_image_overlay(self.h, ids.h, v.ctypes.data if len(v) else None, len(v), ctypes.byref(style)))
+
+    def extract_voxels(self, rect=None):
+        """tdt_image_extract_voxels of this voxel-id image: the distinct voxels visible inside rect = (x0, y0, x1, y1), inclusive
+        and clipped to the image (None: all of it), as an (n, 4) int32 array {x, y, z, material + 1}, Morton-sorted: the brush of
+        Context.octree_edit_voxels.  Blocks."""
+        r = None
+        if rect is not None:
+            if len(rect) != 4:
+                raise ValueError("extract_voxels: rect is (x0, y0, x1, y1)")
+            r = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+        n = ctypes.c_size_t(0)
+        self.ctx.check(lib().tdt_image_extract_voxels(self.h, r, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            self.ctx.check(lib().tdt_image_extract_voxels(self.h, r, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
     def device_ptr(self):
         """tdt_image_device_ptr: the address of the texels in device memory."""
         return int(lib().tdt_image_device_ptr(self.h) or 0)
@@ -1195,6 +1264,13 @@ class ComputeShader:
         key and depth of what the primary ray of pixel (x, y), sample `sample`, of this program's camera hits first — what pick
         returns for it, four words of it (Texture.read_guide).  Only Lambertian hits are keyed unless all_materials.  Asynchronous."""
         self.ctx.check(lib().tdt_dispatch_guide(self.h, texture.h, int(sample), GUIDE_ALL_MATERIALS if all_materials else 0))
+
+    def dispatch_voxel_ids(self, texture, place=0, sample=0):
+        """tdt_dispatch_voxel_ids: texel (x, y) of `texture` (any Texture of the context, usually an unbound one) receives the grid
+        voxel a click on pixel (x, y) would act on — host.pick_grid_voxel of what pick returns for it: place=0 the voxel behind
+        the face, place=1 the empty cell in front of it — as (state, Morton key, material, t) (Texture.read_voxel_ids).
+        Asynchronous."""
+        self.ctx.check(lib().tdt_dispatch_voxel_ids(self.h, texture.h, _place(place), int(sample)))
 
     def view(self):
         """tdt_compute_view: a VIEW snapshot of this program's current camera uniforms."""
@@ -1379,7 +1455,8 @@ class Renderer:
         self.temporal = None                   # render_temporal's state, created on first use
         self.low = None                        # render_upsampled's low-resolution (sums, guide) textures, created on first use
         self.adaptive = None                   # render_adaptive's two state textures and its carry, created on first use
-        self.adaptive_floor = 0.05             # render_adaptive: the brightness below which the error is measured against this value
+        self.ids = None                        # render_overlay's and select_rect's voxel-id texture, created on first use
+        self.adaptive_floor = 0.05            # render_adaptive: the brightness below which the error is measured against this value
         # sigma of the variance-guided filter that render(denoise=N) and render_temporal(denoise=N) run instead of the key-only one;
         # None: the key-only filter, exactly the calls made before the variance unit existed.  VARIANCE_SIGMA is the measured default.
         self.variance = None
@@ -1568,6 +1645,46 @@ class Renderer:
                 self.texture.denoise_variance(self.guide, denoise, self.variance)
         self.shader.dispatch_resolve(w, h, 1, 1)
         return self.texture.read()
+
+    def _ids_texture(self):
+        """The voxel-id texture of render_overlay and select_rect, of the renderer's texture's size, created on first use."""
+        if self.ids is None:
+            self.ids = Texture.new_2d(self.ctx, self.texture.width(), self.texture.height(), bind=False)
+        return self.ids
+
+    def render_overlay(self, voxels, place=0, fill=(1, .6, 0, .35), edge=(1, .6, 0, 1), edge_width=1, voxel_edges=False, width=None,
+                       height=None, denoise=0):
+        """The frame with a voxel list drawn over it — the preview of an edit that has not been applied: render(width, height,
+        denoise), the voxel ids of sample 0 (ComputeShader.dispatch_voxel_ids with `place`), Texture.overlay of `voxels` over the
+        resolved frame.  First hit only: voxels of the list that something hides are not shown.  Returns (frame, ids), ids being
+        Texture.read_voxel_ids() of the frame's id image; while camera and tree stay as they are, another list needs only
+        render + self.texture.overlay(self.ids, ..).  A renderer whose image is the whole frame only."""
+        style = _overlay(fill, edge, edge_width, voxel_edges)
+        place = _place(place)
+        v = np.ascontiguousarray(np.asarray(voxels, np.int32).reshape(-1, 4))
+        if self.texture.width() != self.camera.image_width or self.texture.height() != self.camera.image_height:
+            raise ValueError("render_overlay needs a renderer that owns the whole image")
+        self.render(width, height, denoise)
+        ids = self._ids_texture()
+        self.shader.dispatch_voxel_ids(ids, place, 0)
+        self.texture.overlay(ids, v, style.fill[:], style.edge[:], style.edge_width, voxel_edges)
+        return self.texture.read(), ids.read_voxel_ids()
+
+    def select_rect(self, rect, place=0, sample=0):
+        """Marquee selection: the distinct voxels visible inside rect = (x0, y0, x1, y1) (inclusive pixel coordinates, row 0 at
+        the bottom, clipped to the image) — for every pixel the voxel a click there would act on (`place`, `sample` as
+        ComputeShader.dispatch_voxel_ids takes them) — as an (n, 4) int32 list {x, y, z, material + 1}, Morton-sorted: what
+        Context.octree_edit_voxels takes.  A renderer whose image is the whole frame only."""
+        if rect is None or len(rect) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in rect):
+            raise ValueError("select_rect: rect is four ints (x0, y0, x1, y1)")
+        place = _place(place)
+        if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or sample < 0:
+            raise ValueError("select_rect: sample must be an int >= 0")
+        if self.texture.width() != self.camera.image_width or self.texture.height() != self.camera.image_height:
+            raise ValueError("select_rect needs a renderer that owns the whole image")
+        ids = self._ids_texture()
+        self.shader.dispatch_voxel_ids(ids, place, int(sample))
+        return ids.extract_voxels(rect)
 
     def pick(self, xy, sample=0, return_rays=False):
         """ComputeShader.pick with this renderer's camera: what is under each pixel."""
