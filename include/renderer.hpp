@@ -428,6 +428,28 @@ class Octree {
                                         regions.empty() ? nullptr : regions.data(), regions.size(), material, &n));
     return n;
   }
+  // NEW: through-selection (tdt_octree_extract_screen): every voxel of the bound tree whose centre (TDT_SCREEN_WINDOW: all eight
+  // corners) projects, in `view`, into sel's rectangle, the polygon (x, y pairs; TDT_SCREEN_POLYGON) or the mask image
+  // (TDT_SCREEN_MASK), hidden or not, as {x, y, z, material + 1} in Morton order: the brush of edit_voxels
+  std::vector<int32_t> extract_screen(const Context &ctx, const tdt_view &view, const tdt_screen_select &sel,
+                                      const std::vector<int32_t> &polygon_xy = {}, const Texture *mask = nullptr) const {
+    size_t n = 0;
+    const int32_t *p = polygon_xy.empty() ? nullptr : polygon_xy.data();
+    tdt_image *m = mask ? mask->id() : nullptr;
+    ctx.check(tdt_octree_extract_screen(ctx.raw(), &view, &sel, p, polygon_xy.size() / 2, m, nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_screen(ctx.raw(), &view, &sel, p, polygon_xy.size() / 2, m, v.data(), n, &n));
+    return v;
+  }
+  // NEW: op (TDT_REGION_PAINT with `material` / TDT_REGION_CLEAR) over that selection, the list never leaving the device
+  // (tdt_octree_edit_screen); the bound tree rebuilt in place; returns the number of cells
+  uint32_t edit_screen(const Context &ctx, int op, const tdt_view &view, const tdt_screen_select &sel, const std::vector<int32_t> &polygon_xy,
+                       const Texture *mask, int32_t material) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_screen(ctx.raw(), op, &view, &sel, polygon_xy.empty() ? nullptr : polygon_xy.data(), polygon_xy.size() / 2,
+                                     mask ? mask->id() : nullptr, material, &n));
+    return n;
+  }
   // NEW: a flood click, the paint bucket / delete-object tool: pick pixel (x, y) of the raytracer's camera (sample 0) and on a
   // hit apply `op` to the components `sel` selects that hold the grid voxel behind the face (tdt_pick_grid_voxel, place 0).
   // Returns whether an edit ran; *hit receives the pick, *n_cells the size.

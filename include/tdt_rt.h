@@ -675,6 +675,79 @@ int tdt_image_overlay(tdt_image *img, const tdt_image *ids, const int32_t *voxel
 int tdt_debug_overlay_counts(tdt_ctx *ctx, uint64_t out[4]);
 int tdt_image_extract_voxels(const tdt_image *ids, const int32_t rect[4], int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
 
+/* ---- through-selection ----------------------------------------------------------------------------------------------------
+ * The other marquee of an editor: "select everything inside this lasso", "delete all glass behind this rectangle".  Screen-space
+ * selection above is first hit only; this is a test per voxel, not per pixel: every voxel of the tree's list V is projected into a
+ * view and selected when it lands inside a screen shape, whether something hides it or not.  No occlusion test (that is
+ * tdt_image_extract_voxels), no hierarchical culling (the call walks the whole tree, as every list-based unit does), and only the
+ * centre or all eight corners are tested: a "crossing" marquee, a voxel that merely touches the shape, is not built.
+ *
+ * World points.  For voxel k at depth d = max_depth, min and scale come from slot 6, read as tdt_pick_grid_voxel reads them
+ * (floats[0..2], floats[4]).  The centre is u[a] = (2 k[a] + 1) * 2^-(d+1); a corner is (k[a] + c) * 2^-d with c in {0, 1}; both are
+ * exact in fp32.  w[a] = (u[a] * scale) + min[a]: two rounded fp32 operations, never fused.
+ * Projection.  It is exactly tdt_image_reproject's Q, one function on the device: D = w - view.origin; Ru, Rv, Rw from the view as
+ * that call computes them per call; nu = (Ru.z D.z + Ru.y D.y) + Ru.x D.x, nv and nw likewise with Rv and Rw;
+ * fx = (nu / nw) * (float)(image_width - 1); fy = (nv / nw) * (float)(image_height - 1).  Every operation is rounded, none fused.
+ * A point is in front and on screen when nw > 0 && fx >= 0 && fx < (float)image_width && fy >= 0 && fy < (float)image_height; its
+ * pixel is (px, py) = ((int)fx, (int)fy).  Only comparisons consume fx and fy, so a NaN (a point at the eye) simply fails.
+ * Shape tests on (px, py):
+ *   TDT_SCREEN_RECT     x0 <= px <= x1 && y0 <= py <= y1 with rect = {x0, y0, x1, y1}, inclusive, as tdt_image_extract_voxels'
+ *                       rect; x0 > x1 or y0 > y1 selects nothing.
+ *   TDT_SCREEN_POLYGON  polygon_xy holds n_vertices (3..256) pairs x, y, each |coordinate| <= 2^20.  The even-odd rule at the
+ *                       pixel centre, in integers on doubled coordinates: P = (2px+1, 2py+1), A = 2a, B = 2b for each edge a -> b,
+ *                       closing the last vertex to the first.  An edge counts when (Ay > Py) != (By > Py) and P is strictly left
+ *                       of its crossing: in int64, s = (Px-Ax)*(By-Ay) - (Bx-Ax)*(Py-Ay), and the edge counts when
+ *                       (By > Ay) ? s < 0 : s > 0.  Py is odd and vertex rows are even, so no vertex lies on the scan line.  The
+ *                       pixel is inside when the count is odd.  The polygon (x0,y0), (x1+1,y0), (x1+1,y1+1), (x0,y1+1) is the
+ *                       RECT x0..x1, y0..y1.
+ *   TDT_SCREEN_MASK     mask is an RGBA32F image of the context of exactly image_width x image_height; the pixel is inside when
+ *                       mask[py][px].x > 0.0f (NaN and -0 are outside).
+ * Selection.  Without TDT_SCREEN_WINDOW the tested point is the centre.  With it all eight corners must pass the front / screen
+ * test and the shape test, and the centre is not tested: the voxel lies entirely inside a convex shape.  Then
+ * material < 0 || voxel material == material.  Then min_distance*min_distance <= dd && dd <= max_distance*max_distance with
+ * dd = (D.z*D.z + D.y*D.y) + D.x*D.x of the centre; both squares are rounded fp32 products.  An unused polygon_xy or mask is ignored.
+ * As with a pick, the selection is not always what one sees: a voxel whose centre projects onto the border between two pixels falls
+ * on the side the fp32 arithmetic above puts it, and a voxel hidden behind others is selected like a visible one.
+ *
+ * tdt_octree_extract_screen follows tdt_octree_extract_region's rules: the selected voxels as {x, y, z, material + 1},
+ * Morton-sorted; voxels_xyzm == NULL only counts; capacity < the count: TDT_ERR_INVALID_VALUE with *n_voxels set.  Synchronous.  A
+ * multi-device context answers from device_ids[0].
+ * tdt_octree_edit_screen: op TDT_REGION_PAINT (every selected voxel gets `material`, 0..253) or TDT_REGION_CLEAR (removed); the
+ * selection is a subset of V, so SET would equal PAINT and FILL would be empty: both are TDT_ERR_INVALID_VALUE.  The list never
+ * leaves the device; the tree is left canonical, as for every region edit, on every replica.  Synchronous.
+ * tdt_debug_screen_counts (synchronises): of the context's last of these two calls that returned TDT_OK (a failing call leaves
+ * them unchanged), [0] voxels of V, [1] voxels whose tested points are all in front and on screen, [2] of those, the voxels
+ * inside the shape, [3] voxels selected, after material and distance.  Before any call all four are 0.
+ *
+ * Errors, nothing written and nothing queued: NULL ctx, view, sel or n_voxels; a shape outside the enum; unknown flag bits; a
+ * filter material outside -1..253 (edit: `material` outside 0..253, an op other than PAINT / CLEAR); a distance that is NaN or
+ * negative, or min_distance > max_distance; POLYGON with NULL vertices, a count outside 3..256 or a coordinate beyond +-2^20; MASK
+ * with a NULL image or an image of another size; image_width or image_height < 2 or above 2^24 (past which (float)image_width is
+ * no longer exact); a degenerate view (tdt_image_reproject's determinant); max_depth outside 1..10; a scale that is not positive
+ * and finite; |V| above 2^26 (TDT_REGION_BRUSH_CAP): TDT_ERR_INVALID_VALUE.  A mask of another context, or a MASK edit on a
+ * multi-device context (the mask lives on device_ids[0] only; RECT and POLYGON edit every replica): TDT_ERR_INVALID_OPERATION.
+ * Slots 0, 6 or 7 unbound: TDT_ERR_INCOMPLETE. */
+enum { TDT_SCREEN_RECT = 0, TDT_SCREEN_POLYGON = 1, TDT_SCREEN_MASK = 2 };
+#define TDT_SCREEN_WINDOW 1u          /* all eight corners of the voxel must pass, not its centre */
+#define TDT_SCREEN_MAX_VERTICES 256
+typedef struct tdt_screen_select {
+  int32_t  shape;                     /* TDT_SCREEN_* */
+  int32_t  rect[4];                   /* x0, y0, x1, y1 inclusive, as tdt_image_extract_voxels' rect (RECT only) */
+  uint32_t flags;
+  int32_t  material;                  /* -1: any; 0..253: only voxels of this material */
+  float    min_distance, max_distance;/* 0 and +inf: no limit */
+} tdt_screen_select;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_screen_select) == 36, "tdt_screen_select is 36 bytes");
+#else
+_Static_assert(sizeof(tdt_screen_select) == 36, "tdt_screen_select is 36 bytes");
+#endif
+int tdt_octree_extract_screen(tdt_ctx *ctx, const tdt_view *view, const tdt_screen_select *sel, const int32_t *polygon_xy,
+                              size_t n_vertices, const tdt_image *mask, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+int tdt_octree_edit_screen(tdt_ctx *ctx, int op, const tdt_view *view, const tdt_screen_select *sel, const int32_t *polygon_xy,
+                           size_t n_vertices, const tdt_image *mask, int32_t material, uint32_t *n_cells);
+int tdt_debug_screen_counts(tdt_ctx *ctx, uint64_t out[4]);
+
 /* ---- voxel extraction and compaction ----------------------------------------------------------------------------------
  * The steps octree_update.comp lists as TODOs (octree_update.comp:86-94: removing cells that become empty, removing
  * hierarchies when nodes empty) as explicit operations; edits themselves keep the reference's allocate-only semantics.

@@ -15,6 +15,8 @@
 //            [--export-mesh FILE.ply [--no-merge] [--any-material] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--compact] [--config N] [--device N] [--denoise N [--variance SIGMA]] [--temporal N [--turn DEG]] [--upsample S]
 //            [--adaptive TOL [--batch K]] [--preview] [--select-rect X0,Y0,X1,Y1 [--op ..] [--material K]]
+//            [--select-through X0,Y0,X1,Y1 | --lasso X,Y;X,Y;... [--window] [--only-material K] [--max-distance D]
+//             [--op paint|clear --material K] [--preview]]
 //            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -65,6 +67,12 @@
 //   rectangle (inclusive, row 0 at the bottom; Texture::extract_voxels of the voxel ids of sample 0: for set / fill the empty
 //   cells in front of the visible faces, for paint / clear the voxels behind them) get `op` in material K
 //   (Octree::edit_voxels), after the picks, before --morph.  Prints the list's size and the new cell count.
+// --select-through X0,Y0,X1,Y1 | --lasso X,Y;X,Y;... [--window] [--only-material K] [--max-distance D] [--op paint|clear --material K]
+//   [--preview]: the marquee that selects through the model (Octree::extract_screen / edit_screen): every voxel whose centre
+//   (--window: all eight of whose corners) projects into the pixel rectangle (inclusive) or the lasso polygon (3..256 vertices,
+//   even-odd rule) under the frame's camera, hidden or not, of material K only (--only-material) and no farther than D from the
+//   eye (--max-distance).  With --op paint|clear the edit is applied (paint in --material K), after --select-rect and before
+//   --morph; without --op, --preview draws the list over the frame.  Prints the list's size and the call's four counts.
 // --components [--connect 6|26] [--match any|material]: prints the component count and the largest component's size.
 // --morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]: voxel morphology (Octree::morph) of R steps with
 //   the 6- (default) or 26-neighbourhood, new voxels inheriting their material, the outside of the grid empty; --mask limits the
@@ -98,6 +106,7 @@
 //   rendered; prints the census (Octree::census) before and after.
 // --config N: the synthetic scene N of libtdthost (tdt_scene_config) instead of main.rs's scene literal, with its own octree
 //   parameters (slots 6 / 7) and cell count.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -135,6 +144,10 @@ int main(int argc, char **argv) {
   float turn = 1.0f, variance = 0.0f;                                                    // variance 0: the key-only filter
   bool preview = false;
   std::vector<int32_t> select_rect;
+  std::vector<int32_t> through_rect, lasso;                                              // --select-through / --lasso
+  bool through_window = false, op_given = false;
+  int only_material = -1;
+  float max_distance = INFINITY;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -168,6 +181,7 @@ int main(int argc, char **argv) {
     else if (a == "--box") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--box x0,y0,z0,x1,y1,z1\n"); return 2; } box.assign(v, v + 6); }
     else if (a == "--op") {
       const std::string v = next();
+      op_given = true;
       if (v == "set") op = TDT_REGION_SET; else if (v == "fill") op = TDT_REGION_FILL; else if (v == "paint") op = TDT_REGION_PAINT;
       else if (v == "clear") op = TDT_REGION_CLEAR; else { std::fprintf(stderr, "--op set|fill|paint|clear\n"); return 2; }
     }
@@ -236,14 +250,30 @@ int main(int argc, char **argv) {
     else if (a == "--config") config = std::atoi(next());
     else if (a == "--preview") preview = true;
     else if (a == "--select-rect") { int32_t v[4]; if (std::sscanf(next(), "%d,%d,%d,%d", v, v + 1, v + 2, v + 3) != 4) { std::fprintf(stderr, "--select-rect X0,Y0,X1,Y1\n"); return 2; } select_rect.assign(v, v + 4); }
+    else if (a == "--select-through") { int32_t v[4]; if (std::sscanf(next(), "%d,%d,%d,%d", v, v + 1, v + 2, v + 3) != 4) { std::fprintf(stderr, "--select-through X0,Y0,X1,Y1\n"); return 2; } through_rect.assign(v, v + 4); }
+    else if (a == "--lasso") {
+      const char *t = next();
+      int x, y, used;
+      while (std::sscanf(t, "%d,%d%n", &x, &y, &used) == 2) { lasso.push_back(x); lasso.push_back(y); t += used; if (*t == ';') t++; else break; }
+      if (*t || lasso.size() < 6 || lasso.size() > 2 * TDT_SCREEN_MAX_VERTICES) { std::fprintf(stderr, "--lasso X,Y;X,Y;... (3..256 vertices)\n"); return 2; }
+    }
+    else if (a == "--window") through_window = true;
+    else if (a == "--only-material") { only_material = std::atoi(next()); if (only_material < 0 || only_material > 253) { std::fprintf(stderr, "--only-material 0..253\n"); return 2; } }
+    else if (a == "--max-distance") { max_distance = (float)std::atof(next()); if (!(max_distance >= 0.0f)) { std::fprintf(stderr, "--max-distance D, D >= 0\n"); return 2; } }
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
+  const bool through = !through_rect.empty() || !lasso.empty();
+  if (!through_rect.empty() && !lasso.empty()) { std::fprintf(stderr, "--select-through and --lasso do not combine\n"); return 2; }
+  if (!through && (through_window || only_material >= 0 || max_distance != INFINITY)) { std::fprintf(stderr, "--window, --only-material and --max-distance need --select-through or --lasso\n"); return 2; }
+  if (through && op_given && op != TDT_REGION_PAINT && op != TDT_REGION_CLEAR) { std::fprintf(stderr, "--select-through / --lasso take --op paint|clear\n"); return 2; }
+  if (through && op_given && preview) { std::fprintf(stderr, "--select-through / --lasso: --preview shows the list, --op applies it; not both\n"); return 2; }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
   if (adaptive >= 0.0f && (temporal > 0 || upsample > 0)) { std::fprintf(stderr, "--adaptive does not combine with --temporal or --upsample\n"); return 2; }
   if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
   if (solid && mesh_path.empty()) { std::fprintf(stderr, "--solid needs --mesh FILE.ply\n"); return 2; }
   const bool preview_box = !box.empty() && mesh_path.empty(), preview_pick = pick_x >= 0 && reach_cost < 0 && (flood_op >= 0 || brush_shape >= 0);
-  if (preview && preview_box == preview_pick) { std::fprintf(stderr, "--preview needs one of --box, --pick with --brush, --pick with --flood\n"); return 2; }
+  if (preview && !through && preview_box == preview_pick) { std::fprintf(stderr, "--preview needs one of --box, --pick with --brush, --pick with --flood\n"); return 2; }
+  if (preview && through && (preview_box || preview_pick)) { std::fprintf(stderr, "--preview shows one selection: --select-through / --lasso or --box / --pick\n"); return 2; }
   if (preview && (temporal > 0 || !select_rect.empty())) { std::fprintf(stderr, "--preview does not combine with --temporal or --select-rect\n"); return 2; }
   try {
     Context ctx(device);
@@ -444,6 +474,27 @@ int main(int argc, char **argv) {
       static const char *op_names[4] = {"set", "fill", "paint", "clear"};
       std::printf("select-rect %d,%d,%d,%d op %s voxels %zu cells %u\n", select_rect[0], select_rect[1], select_rect[2], select_rect[3], op_names[op],
                   list.size() / 4, octree.edit_voxels(ctx, op, list));
+    }
+    if (through) {                                                                        // NEW: the marquee that selects through the model
+      tdt_screen_select q{};
+      q.shape = lasso.empty() ? TDT_SCREEN_RECT : TDT_SCREEN_POLYGON;
+      for (int a = 0; a < 4 && lasso.empty(); a++) q.rect[a] = through_rect[a];
+      q.flags = through_window ? TDT_SCREEN_WINDOW : 0u; q.material = only_material; q.min_distance = 0.0f; q.max_distance = max_distance;
+      const tdt_view view = raytrace_program.view();
+      uint64_t counts[4];
+      if (op_given) {
+        static const char *op_names[4] = {"set", "fill", "paint", "clear"};
+        const uint32_t cells = octree.edit_screen(ctx, op, view, q, lasso, nullptr, material);
+        ctx.check(tdt_debug_screen_counts(ctx.raw(), counts));
+        std::printf("select-through op %s voxels %llu on-screen %llu in-shape %llu selected %llu cells %u\n", op_names[op], (unsigned long long)counts[0],
+                    (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3], cells);
+      } else {
+        const std::vector<int32_t> list = octree.extract_screen(ctx, view, q, lasso);
+        ctx.check(tdt_debug_screen_counts(ctx.raw(), counts));
+        std::printf("select-through voxels %llu on-screen %llu in-shape %llu selected %llu list %zu\n", (unsigned long long)counts[0],
+                    (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3], list.size() / 4);
+        if (preview) preview_list = list;
+      }
     }
     if (morph_op >= 0) {
       tdt_morph m{};

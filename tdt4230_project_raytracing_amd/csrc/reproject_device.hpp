@@ -1,19 +1,29 @@
 // The device side both reprojection kernels of tdt_reproject.hip share (reproject_kernel, reproject_moments_kernel): the per-call
-// arguments and the one body, so that Q and the FOUND predicate exist once.  The block's tile is denoise_device.hpp's 16x16.
+// arguments and the one body, so that Q (view_project, which tdt_screen.hip calls too) and the FOUND predicate exist once.  The
+// block's tile is denoise_device.hpp's 16x16.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "tdt_internal.hpp"
 #include "trace_params.h"
 #include "trace_device.hpp"
 #include "denoise_device.hpp"
 
 namespace tdt {
 
+// Q, the projection of the header (tdt_image_reproject; tdt_screen.hip maps voxels through it too): d = the world point minus the
+// view's origin; nw and the pixel coordinates (fx, fy) before the cast.  Every operation rounded, none fused; a caller only compares
+// fx and fy (a NaN fails) before it casts them.
+TDT_DEV void view_project(const ViewRows &V, float dx, float dy, float dz, float &nw, float &fx, float &fy) {
+  const float nu = (V.ru[2] * dz + V.ru[1] * dy) + V.ru[0] * dx;
+  const float nv = (V.rv[2] * dz + V.rv[1] * dy) + V.rv[0] * dx;
+  nw = (V.rw[2] * dz + V.rw[1] * dy) + V.rw[0] * dx;
+  fx = (nu / nw) * V.sx; fy = (nv / nw) * V.sy;
+}
+
 struct ReprojectArgs {
-  float ru[3], rv[3], rw[3];                         // rows of det * inverse(a | b | c) of the earlier view, det > 0
-  float org[3];                                      // its origin
-  float sx, sy;                                      // (float)(image_width - 1), (float)(image_height - 1) of the earlier view
+  ViewRows view;                                     // the earlier view (tdt_internal.hpp, view_rows)
   float fpw, fph;                                    // (float) sizes of the earlier images
   int pw;                                            // their row length
   int has_prev;
@@ -49,11 +59,9 @@ TDT_DEV void reproject_body(const TraceParams &P, int sample, const ReprojectArg
     if (keyed && A.has_prev) {
       const Ray r = primary_ray(P, x, y, sample);
       const float t = __uint_as_float(g.w);
-      const float dx = (r.ox + t * r.dx) - A.org[0], dy = (r.oy + t * r.dy) - A.org[1], dz = (r.oz + t * r.dz) - A.org[2];
-      const float nu = (A.ru[2] * dz + A.ru[1] * dy) + A.ru[0] * dx;
-      const float nv = (A.rv[2] * dz + A.rv[1] * dy) + A.rv[0] * dx;
-      const float nw = (A.rw[2] * dz + A.rw[1] * dy) + A.rw[0] * dx;
-      const float fx = (nu / nw) * A.sx, fy = (nv / nw) * A.sy;
+      const float dx = (r.ox + t * r.dx) - A.view.org[0], dy = (r.oy + t * r.dy) - A.view.org[1], dz = (r.oz + t * r.dz) - A.view.org[2];
+      float nw, fx, fy;
+      view_project(A.view, dx, dy, dz, nw, fx, fy);
       fate = 3u;
       if (nw > 0.f && fx >= 0.f && fx < A.fpw && fy >= 0.f && fy < A.fph) {
         const size_t q = (size_t)(int)fy * (size_t)A.pw + (size_t)(int)fx;

@@ -12,7 +12,8 @@
 // variance of the luminance and the filter it guides (what these three share on the device: denoise_device.hpp); tdt_upsample.hip:
 // guide-keyed upsampling of a frame traced at reduced resolution; tdt_adaptive.hip: the sampling controller that turns per-pixel
 // variance into the masks of tdt_dispatch_accumulate_masked; tdt_select.hip: screen-space selection, where the two halves meet:
-// voxel-id images, overlays of a voxel list and the voxels of a rectangle.  The host helpers
+// voxel-id images, overlays of a voxel list and the voxels of a rectangle; tdt_screen.hip: through-selection, the tree's voxels
+// projected into a view and tested against a rectangle, a polygon or a mask.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
@@ -79,6 +80,7 @@ struct tdt_ctx {
   unsigned long long *adapt_counts = nullptr;          // tdt_debug_adapt_counts: the device word block of the last tdt_image_adapt (tdt_adaptive.hip)
   unsigned long long *overlay_counts = nullptr;        // tdt_debug_overlay_counts: the device word block of the last tdt_image_overlay (tdt_select.hip)
   void *select = nullptr; size_t select_bytes = 0;     // the list of tdt_image_overlay in device memory (tdt_select.hip), grow-only
+  uint64_t screen_counts[4] = {0, 0, 0, 0};            // tdt_debug_screen_counts: of the last through-selection that returned TDT_OK (tdt_screen.hip)
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
@@ -249,6 +251,8 @@ constexpr unsigned long long kVoxelListCap = TDT_REGION_BRUSH_CAP;   // voxels o
 // tree_voxels with the leaf limit of the editing units (254), held to kVoxelListCap (checked on the expanded list: 16 B per voxel
 // of the tree before it can fail)
 int tree_voxels_capped(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth);
+// the cap alone, for a unit that is handed the tree's list (a VoxelSelect): n > kVoxelListCap is TDT_ERR_INVALID_VALUE
+int voxlist_within_cap(tdt_ctx *front, uint32_t n);
 // k[i] = the Morton key of voxel i, n > 0
 void voxlist_keys(hipStream_t st, const int4 *v, uint32_t n, uint32_t *k);
 // behind a stable sort of n > 0 pairs by key: flag[i] = i is the LAST of its run of equal keys and not the all-ones key, over n + 1
@@ -330,6 +334,15 @@ void query_scratch_destroy(tdt_ctx *ctx);
 int query_params(tdt_ctx *front, tdt_ctx *m, TraceParams &P);
 // the camera uniforms of a program into P (what primary_ray reads)
 void query_camera(const tdt_compute *cam, TraceParams &P);
+
+// ---- tdt_reproject.hip: a view as the device projects into it (reproject_device.hpp, view_project) ----
+struct ViewRows {
+  float ru[3], rv[3], rw[3];                         // rows of det * inverse(a | b | c) of the view, det > 0
+  float org[3];                                      // its origin
+  float sx, sy;                                      // (float)(image_width - 1), (float)(image_height - 1)
+};
+// the header's per-call arithmetic (tdt_image_reproject) from a view's fp32 fields; false: the determinant is zero or not finite
+bool view_rows(const tdt_view &v, ViewRows &R);
 
 // ---- tdt_denoise.hip, and the host frame of an image call that it, tdt_variance.hip, tdt_reproject.hip, tdt_upsample.hip and
 // tdt_adaptive.hip share ----

@@ -43,11 +43,9 @@ __global__ __launch_bounds__(256) void reproject_moments_kernel(const TraceParam
   reproject_body<true>(P, sample, A, guide, sums, prev_guide, prev_hist, hist_out, mean_out, w, h, tiles_x, counts, prev_moments, moments_out, mf);
 }
 
-namespace {
-
 // Ru, Rv, Rw of the header from a view's fp32 fields, in double, one rounding per operation (the build does not contract), then
-// rounded to fp32; false: the determinant is zero or not finite
-bool view_rows(const tdt_view &v, ReprojectArgs &A) {
+// rounded to fp32, with the origin and (float)(image_width - 1), (float)(image_height - 1); false: the determinant is zero or not finite
+bool view_rows(const tdt_view &v, ViewRows &A) {
   double a[3], b[3], c[3];
   for (int i = 0; i < 3; i++) {
     a[i] = (double)v.horizontal[i]; b[i] = (double)v.vertical[i];
@@ -70,10 +68,9 @@ bool view_rows(const tdt_view &v, ReprojectArgs &A) {
     A.ru[i] = (float)(sign * ru[i]); A.rv[i] = (float)(sign * rv[i]); A.rw[i] = (float)(sign * rw[i]);
     A.org[i] = v.origin[i];
   }
+  A.sx = (float)(v.image_width - 1); A.sy = (float)(v.image_height - 1);
   return true;
 }
-
-}  // namespace
 
 void reproject_counts_destroy(tdt_ctx *ctx) {
   if (ctx->reproject_counts) (void)hipFree(ctx->reproject_counts);
@@ -132,8 +129,7 @@ static int reproject_run(tdt_compute *c, int sample, const tdt_image *guide, con
     if (pg->w > tdt::kMaxPrevSide || pg->h > tdt::kMaxPrevSide) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier images are too large");
     if (prev_view->image_width < 2 || prev_view->image_height < 2)
       return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier view's image_width and image_height must be at least 2");
-    if (!tdt::view_rows(*prev_view, A)) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier view is degenerate (determinant zero or not finite)");
-    A.sx = (float)(prev_view->image_width - 1); A.sy = (float)(prev_view->image_height - 1);
+    if (!tdt::view_rows(*prev_view, A.view)) return tdt::fail(ctx, TDT_ERR_INVALID_VALUE, "the earlier view is degenerate (determinant zero or not finite)");
     A.fpw = (float)pg->w; A.fph = (float)pg->h; A.pw = pg->w;
     A.has_prev = 1;
   }

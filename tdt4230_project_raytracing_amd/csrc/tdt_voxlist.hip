@@ -38,10 +38,14 @@ __global__ __launch_bounds__(256) void voxlist_gather_kernel(const int4 *v, cons
   if (ok) ok[excl[i]] = k[i];
 }
 
+int voxlist_within_cap(tdt_ctx *front, uint32_t n) {
+  if (n > kVoxelListCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(n) + " voxels (more than 2^26)");
+  return TDT_OK;
+}
+
 int tree_voxels_capped(tdt_ctx *front, tdt_ctx *ctx, DeviceScratch &S, int4 **out, uint32_t *n, int *depth) {
   if (int rc = tree_voxels(front, ctx, 254u, S, out, n, depth)) return rc;
-  if (*n > kVoxelListCap) return fail(front, TDT_ERR_INVALID_VALUE, "the tree holds " + std::to_string(*n) + " voxels (more than 2^26)");
-  return TDT_OK;
+  return voxlist_within_cap(front, *n);
 }
 
 void voxlist_keys(hipStream_t st, const int4 *v, uint32_t n, uint32_t *k) {

@@ -288,6 +288,58 @@ def _place(place):
         raise ValueError("place must be 1 (the empty cell in front of the face) or 0 (the voxel behind it)")
     return int(place)
 
+
+# through-selection (include/tdt_rt.h): shapes, the flag and struct tdt_screen_select
+SCREEN_RECT, SCREEN_POLYGON, SCREEN_MASK = 0, 1, 2
+SCREEN_WINDOW = 1
+SCREEN_MAX_VERTICES = 256
+
+
+class ScreenSelect(ctypes.Structure):
+    """struct tdt_screen_select: the shape (SCREEN_*), rect = (x0, y0, x1, y1) inclusive (SCREEN_RECT only), the flags
+    (SCREEN_WINDOW: all eight corners of a voxel must pass, not its centre), the material filter (-1: any) and the distance range
+    from the view's origin (0 and inf: no limit)."""
+    _fields_ = [("shape", ctypes.c_int32), ("rect", ctypes.c_int32 * 4), ("flags", ctypes.c_uint32), ("material", ctypes.c_int32),
+                ("min_distance", ctypes.c_float), ("max_distance", ctypes.c_float)]
+
+
+assert ctypes.sizeof(ScreenSelect) == 36
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _screen_select(rect, polygon, mask, window, material, min_distance, max_distance):
+    """(ScreenSelect, polygon as a contiguous (n, 2) int32 array or None, mask) of the arguments every through-selection call takes,
+    refused here where they are not what the C ABI can carry."""
+    if sum(a is not None for a in (rect, polygon, mask)) != 1:
+        raise ValueError("through-selection takes exactly one of rect, polygon and mask")
+    if not isinstance(window, (bool, np.bool_)):
+        raise ValueError("window must be a bool")
+    if material is not None and (not _is_int(material) or not 0 <= material <= 253):
+        raise ValueError("material must be None (any) or an int 0..253")
+    lo, hi = float(min_distance), float(max_distance)
+    if not (0.0 <= lo <= hi):
+        raise ValueError("the distances must be 0 <= min_distance <= max_distance")
+    sel = ScreenSelect(SCREEN_RECT, (ctypes.c_int32 * 4)(), SCREEN_WINDOW if window else 0, -1 if material is None else int(material), lo, hi)
+    pts = None
+    if rect is not None:
+        if len(rect) != 4 or not all(_is_int(v) and abs(v) < 2**31 for v in rect):
+            raise ValueError("rect is four ints (x0, y0, x1, y1)")
+        sel.rect = (ctypes.c_int32 * 4)(*[int(v) for v in rect])
+    elif polygon is not None:
+        p = np.asarray(polygon)
+        if p.ndim != 2 or p.shape[1] != 2 or not 3 <= len(p) <= SCREEN_MAX_VERTICES or p.dtype.kind not in "iu" or np.abs(p.astype(np.int64)).max() > 1 << 20:
+            raise ValueError("polygon is 3..256 integer vertices (x, y), each coordinate within +-2^20")
+        sel.shape = SCREEN_POLYGON
+        pts = np.ascontiguousarray(p, np.int32)
+    else:
+        if not isinstance(mask, Texture):
+            raise ValueError("mask is a Texture of the view's size")
+        sel.shape = SCREEN_MASK
+    return sel, pts, mask
+
 # every symbol include/tdt_rt.h declares: (name, restype, argtypes)
 _P, _I, _U, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
 _PP = ctypes.POINTER(ctypes.c_void_p)
@@ -369,6 +421,10 @@ SYMBOLS = [
     ("tdt_image_overlay", _I, [_P, _P, _P, _S, ctypes.POINTER(Overlay)]),
     ("tdt_debug_overlay_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_image_extract_voxels", _I, [_P, ctypes.POINTER(ctypes.c_int32), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_extract_screen", _I, [_P, ctypes.POINTER(VIEW), ctypes.POINTER(ScreenSelect), _P, _S, _P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_screen", _I, [_P, _I, ctypes.POINTER(VIEW), ctypes.POINTER(ScreenSelect), _P, _S, _P, ctypes.c_int32,
+                                    ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_debug_screen_counts", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tdt_octree_census", _I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     ("tdt_octree_extract", _I, [_P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_compact", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -978,6 +1034,47 @@ class Context:
         """tdt_debug_overlay_counts: (pixels, pixels with a voxel, member pixels, edge pixels) of the last Texture.overlay (blocks)."""
         c = (ctypes.c_uint64 * 4)()
         self.check(lib().tdt_debug_overlay_counts(self.h, c))
+        return tuple(int(v) for v in c)
+
+    def octree_extract_screen(self, view, rect=None, polygon=None, mask=None, window=False, material=None, min_distance=0.0,
+                              max_distance=float("inf")):
+        """tdt_octree_extract_screen: through-selection.  Every voxel of the bound tree whose centre (window: all eight of whose
+        corners) projects, in `view` (a VIEW: ComputeShader.view()), into the screen shape — exactly one of rect = (x0, y0, x1, y1)
+        inclusive, polygon = 3..256 integer vertices (even-odd rule at the pixel centre) and mask = a Texture of the view's size
+        (inside where its red channel is > 0) — hidden or not, filtered by material (None: any) and by its centre's distance from
+        the view's origin: (n, 4) int32 {x, y, z, material + 1}, Morton-sorted.  One walk: the output is sized by the tree's voxel
+        count, an upper bound of the selection.  Blocks."""
+        if not isinstance(view, VIEW):
+            raise ValueError("view is a VIEW (ComputeShader.view())")
+        sel, pts, mask = _screen_select(rect, polygon, mask, window, material, min_distance, max_distance)
+        out = np.empty((self._voxel_count(), 4), np.int32)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_extract_screen(self.h, ctypes.byref(view), ctypes.byref(sel), pts.ctypes.data if pts is not None else None,
+                                                   len(pts) if pts is not None else 0, mask.h if mask is not None else None,
+                                                   out.ctypes.data if len(out) else None, len(out), ctypes.byref(n)))
+        return out[: n.value].copy()
+
+    def octree_edit_screen(self, op, view, rect=None, polygon=None, mask=None, window=False, material=None, min_distance=0.0,
+                           max_distance=float("inf"), paint_material=0):
+        """tdt_octree_edit_screen: op REGION_PAINT (with paint_material 0..253) or REGION_CLEAR over what octree_extract_screen
+        would return for the same arguments; the list never leaves the device.  Rebuilds the bound tree in place on every replica
+        (a mask: single-device contexts only) and returns the canonical tree's cell count."""
+        if not isinstance(view, VIEW):
+            raise ValueError("view is a VIEW (ComputeShader.view())")
+        sel, pts, mask = _screen_select(rect, polygon, mask, window, material, min_distance, max_distance)
+        if not _is_int(paint_material) or not 0 <= paint_material <= 253:
+            raise ValueError("paint_material must be an int 0..253")
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_screen(self.h, int(op), ctypes.byref(view), ctypes.byref(sel),
+                                                      pts.ctypes.data if pts is not None else None, len(pts) if pts is not None else 0,
+                                                      mask.h if mask is not None else None, int(paint_material), ctypes.byref(n)), n)
+        return int(n.value)
+
+    def screen_counts(self):
+        """tdt_debug_screen_counts: (voxels of the tree, those whose tested points are all in front and on screen, of those the
+        voxels inside the shape, voxels selected after the filters) of the last octree_extract_screen / octree_edit_screen (blocks)."""
+        c = (ctypes.c_uint64 * 4)()
+        self.check(lib().tdt_debug_screen_counts(self.h, c))
         return tuple(int(v) for v in c)
 
     def fill_passes(self):
@@ -1685,6 +1782,18 @@ class Renderer:
         ids = self._ids_texture()
         self.shader.dispatch_voxel_ids(ids, place, int(sample))
         return ids.extract_voxels(rect)
+
+    def select_through(self, rect=None, polygon=None, mask=None, **filters):
+        """The marquee that selects through the model: every voxel of the scene that projects, under the renderer's current
+        camera (ComputeShader.view), into rect = (x0, y0, x1, y1), the lasso `polygon` or the Texture `mask` — hidden or not, unlike
+        select_rect — with Context.octree_extract_screen's filters (window, material, min_distance, max_distance), as an (n, 4)
+        int32 list {x, y, z, material + 1}, Morton-sorted: what Context.octree_edit_voxels and render_overlay take."""
+        unknown = set(filters) - {"window", "material", "min_distance", "max_distance"}
+        if unknown:
+            raise ValueError("select_through: unknown filter " + ", ".join(sorted(unknown)))
+        _screen_select(rect, polygon, mask, filters.get("window", False), filters.get("material"), filters.get("min_distance", 0.0),
+                       filters.get("max_distance", float("inf")))
+        return self.ctx.octree_extract_screen(self.shader.view(), rect=rect, polygon=polygon, mask=mask, **filters)
 
     def pick(self, xy, sample=0, return_rays=False):
         """ComputeShader.pick with this renderer's camera: what is under each pixel."""
