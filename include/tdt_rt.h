@@ -1287,7 +1287,13 @@ int tdt_debug_pixel_log(tdt_ctx *ctx, uint32_t *out, size_t n_u32);
  * from the position and what the level walk over the packed node table ends on.
  * Mode 18, on the same bound tree: the table in its plane form (entries that carry three byte offsets into a per-block table of
  * padded slab planes).  For every position the six planes fetched through the entry's offsets must equal, bit for bit, the planes
- * the arithmetic form computes from the 16-bit entry, the bound octree corner and scale. */
+ * the arithmetic form computes from the 16-bit entry, the bound octree corner and scale.
+ * Mode 19, on the same bound tree: the lanes in a band that the five-wave whole-depth builds serve from the table instead of the
+ * level walk.  For every integer n of 2^max_depth x, every float x in [0, 1) whose 2^max_depth x lies within the band (2^-11) of n
+ * (n = 0: the first and last 32 floats of every binade) and every finest-level (y, z): where the classification does not leave the
+ * lane to the walk, what a step reads through the table entry of the resolved position must equal, bit for bit, what the level walk
+ * over the packed node table ends on (slab planes, cell size, LEAF or not, a LEAF's value).  The outcome counts follow the mismatches
+ * in tdt_debug_counters: [1] lanes resolved to position n, [2] to n - 2^j, [3] lanes left to the walk. */
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches);
 /* A cell_count that is not a power of two (the reference's own: 100000, main.rs:459) takes treeLookup's x index
  * (raytracer.comp:376-378) through two per-cell thresholds on the level's coordinate instead of the float formula (csrc/

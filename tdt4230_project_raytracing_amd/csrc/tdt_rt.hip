@@ -126,7 +126,9 @@ enum : int { STAT_TRAV_PASS = 0, STAT_TRAV_LANES, STAT_INSIDE_LANES, STAT_ALIVE_
              STAT_NEWRAY_PASS, STAT_NEWRAY_LANES, STAT_GATE_WAIT_LANES, STAT_DRAINED_TRAV_PASS, STAT_DRAINED_EVENT_PASS, STAT_LOOP_PASS, STAT_WAVE_TICKS, STAT_WAVES,
              STAT_T_FIRST, STAT_T_LAST,
              STAT_FALLBACK_PASS = 32, STAT_FALLBACK_LANES,      // whole-depth builds: traversal passes that took the level walk (a lane in a band), and the lanes in a band
-             STAT_COUNT = 34 };
+             STAT_BAND_PASS, STAT_BAND_LANES,                   // five-wave whole-depth builds: traversal passes with a lane in a band, and those lanes
+             STAT_RESOLVED_LANES,                               // ... and the lanes in a band of the passes that went on with the table load (band_resolve_x)
+             STAT_COUNT = 37 };
 #ifdef TDT_STATS
 TDT_DEV void stat_add(uint32_t *row, int i, unsigned long long mask) {      // mask: the lanes (of those executing this) that are live in the region
   const unsigned long long m = __ballot(1);
@@ -226,6 +228,13 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
   ns.grid_band = FULL ? Grid<5>::kBand : (ns.grid_ok ? (TABLE && kUseGrid ? __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)s_band)) : Grid<GL>::kBand) : 2.0f);
   ns.thr = s_thr; ns.thr_f0max = P.thr_f0max;
   ns.full = P.full_grid;
+  if constexpr (kCold && kBandResolve) {
+    // the parent-index table's address as a value of its own (asm: not re-derived from the table's base inside the loop): only the unlikely
+    // block of a wave with a lane in a band reads it, and the whole-depth table's base keeps the scalar pair the all-safe path loads through
+    uintptr_t pa = (uintptr_t)P.full_grid + kFullParentOffset;
+    asm volatile("" : "+s"(pa));
+    ns.parents = reinterpret_cast<const uint16_t *>(pa);
+  }
   if constexpr (kPlanes) ns.planes = s_planes;
   ns.grid32 = s_grid32; ns.bricks = P.bricks;
   if (BRICK) {
@@ -965,12 +974,16 @@ __global__ __launch_bounds__(256) void selftest_index_kernel(float inv_cell_coun
 // (none can for depth <= 6: six significand bits; checked, not argued).
 template <int BITS>
 __global__ __launch_bounds__(256) void build_full_grid_kernel(const uint32_t *__restrict__ cells, uint32_t cells_dwords, int depth,
-                                                             typename FullEntry<BITS>::Type *__restrict__ grid, uint32_t *__restrict__ bad) {
+                                                             typename FullEntry<BITS>::Type *__restrict__ grid, uint32_t *__restrict__ bad,
+                                                             uint16_t *__restrict__ parents) {
   const uint32_t e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (1u << (3 * depth))) return;
   const uint32_t xg = e >> (2 * depth), yg = (e >> depth) & ((1u << depth) - 1u), zg = e & ((1u << depth) - 1u);
   uint32_t v = 0, code = 1u, m = 0;
   bool ok = true;
+  // parents (or none): the parent-index table (full_parent_index), each level-L position written by the thread of its lowest finest position
+  const uint32_t low = __builtin_ctz((xg | yg | zg) | (1u << depth));      // this thread stands for its position at levels depth - low ..
+  if (parents && low == (uint32_t)depth) parents[0] = 0;
   for (int l = 1; l <= depth && code == 1u; l++) {
     const int sh = depth - l;
     const uint32_t idx = ((2u * v + ((xg >> sh) & 1u)) << 2) + (((yg >> sh) & 1u) << 1) + ((zg >> sh) & 1u);
@@ -979,7 +992,11 @@ __global__ __launch_bounds__(256) void build_full_grid_kernel(const uint32_t *__
     code = (type == 0u) ? 0u : (type == 2u ? 2u : 1u);
     v = value; m = (uint32_t)l;
     if (code == 1u && l < depth && v >= grid_v_bound(l)) ok = false;
+    if (parents && l < depth && (uint32_t)sh <= low) parents[full_parent_index((uint32_t)l, xg >> sh, yg >> sh, zg >> sh)] = (uint16_t)(code == 1u ? v : 0u);
   }
+  if (parents)                                        // levels the descent did not reach: 0 (never decisive, see band_classify)
+    for (int l = (int)m + 1; l < depth; l++)
+      if ((uint32_t)(depth - l) <= low) parents[full_parent_index((uint32_t)l, xg >> (depth - l), yg >> (depth - l), zg >> (depth - l))] = 0;
   uint32_t enc = (((uint32_t)depth - m) << 2) | code;  // depth - levels: what the lookup shifts the digits by, and the exponent of the cell size above 2^-depth (a PARENT: 0)
   if (code == 2u) { enc |= v << 5; ok = ok && v < 2048u; }
   if (!full_entry_encode<BITS>(enc & 0xFFFFu, depth, xg, yg, zg, grid[e])) ok = false;
@@ -1057,6 +1074,101 @@ __global__ __launch_bounds__(256) void selftest_plane_table_kernel(const FullGri
   }
   for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor((long long)bad, o, 64);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
+}
+
+// tdt_selftest 19: the lanes in a band that the five-wave builds serve from the table (band_classify, band_resolve_x).  Block row n:
+// the integer the band lies around, 0 .. 2^DEPTH; its threads: every finest-level (Yi, Zi); each runs over every float fx0 in [0, 1)
+// with |2^DEPTH fx0 - n| <= the band, by bit pattern outward from n 2^-DEPTH on both sides.  (n = 0: the band is every float up to
+// 2^-(11 + DEPTH), 9e8 of them and all of one class — position 0; it takes the first and last 32 floats of every binade, denormals
+// included.)  Where the classification keeps the lane off the walk, what the step reads through the table entry of the resolved position
+// must be, bit for bit, what the level walk over the packed node image ends on and computes: the slab planes (the block's plane table
+// against slab_planes on the walk's digits), the cell size, LEAF or not, a LEAF's value.  out[0] mismatches, out[1] lanes resolved to n,
+// out[2] to n - 2^j (an odd n from below: n - 1), out[3] lanes left to the walk.
+template <int DEPTH, bool UNIT>
+__global__ __launch_bounds__(256) void selftest_band_resolve_kernel(const FullGridEntry *__restrict__ grid, const uint16_t *__restrict__ parents,
+                                                                   const uint16_t *__restrict__ packed, uint32_t lds_nodes, float scale,
+                                                                   float min_x, float min_y, float min_z, unsigned long long *out) {
+  __shared__ __attribute__((aligned(8))) float2 s_planes[PlaneTable::kEntries];
+  build_plane_table<DEPTH, UNIT>(s_planes, scale, min_x, min_y, min_z);
+  __syncthreads();
+  const uint32_t n = blockIdx.y, e = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long bad = 0, to_n = 0, to_low = 0, to_walk = 0;
+  if (e < (1u << (2 * DEPTH))) {
+    const uint32_t Yi = e >> DEPTH, Zi = e & ((1u << DEPTH) - 1u);
+    const float band = Grid<5>::kBand, two_d = (float)(1 << DEPTH), centre = (float)n / two_d;      // (exact)
+    auto check = [&](float fx0) __attribute__((always_inline)) {      // (inlined at its four call sites: the counters stay in registers, no scratch)
+      const float tg = fx0 * two_d, rn = __builtin_rintf(tg);
+      const int kind = band_classify(tg, rn);
+      // (every counter is added to by value: a choice between counters is an indexed variable, in scratch)
+      to_walk += kind == BAND_WALK ? 1u : 0u;
+      if (kind == BAND_WALK) return;
+      const uint32_t xg = kind == BAND_PARENT ? band_resolve_x<DEPTH>(parents, fx0, (uint32_t)rn, Yi, Zi) : (uint32_t)tg;
+      to_n += xg == (uint32_t)rn ? 1u : 0u; to_low += xg == (uint32_t)rn ? 0u : 1u;
+      uint32_t wrong = xg >= (1u << DEPTH) ? 1u : 0u;
+      if (!wrong) {
+      // the walk (tree_lookup_pow2's levels over the staged nodes)
+      uint32_t v = 0, code = 1u, qx = 1u;
+      float fx = fx0;
+      for (int l = 1; l <= DEPTH && code == 1u; l++) {
+        const int sh = DEPTH - l;
+        const float fv = (float)v;
+        const float q = (fv + fx) - fv;
+        const bool a = q > 0.5f, b = (q == 1.0f);
+        const uint32_t ix = (v + v + (uint32_t)a) + (uint32_t)b;
+        qx = qx + qx + ((a && !b) ? 1u : 0u);
+        const uint32_t idx = ((ix << 2) + (((Yi >> sh) & 1u) << 1) + ((Zi >> sh) & 1u)) & 0x1FFFFFFFu;
+        const uint32_t nd = idx < lds_nodes ? packed[idx] : 0u;               // past the staged nodes: the all-EMPTY sentinel cell
+        v = nd >> 2; code = nd & 3u;
+        fx = f_fract_nonneg(fx0 * __uint_as_float((uint32_t)(127 + l) << 23));
+      }
+      const int m = 31 - __builtin_clz(qx);
+      qx ^= 1u << m;
+      const float ipd = __uint_as_float((uint32_t)(127 - m) << 23);
+      const int sh = DEPTH - m;
+      const bool leaf = code == 2u;
+      const float2 wx = slab_planes<UNIT>((float)qx * ipd, ipd, leaf, scale, min_x), wy = slab_planes<UNIT>((float)(Yi >> sh) * ipd, ipd, leaf, scale, min_y),
+                   wz = slab_planes<UNIT>((float)(Zi >> sh) * ipd, ipd, leaf, scale, min_z);
+      // the step, through the entry of the resolved position
+      const FullGridEntry g = grid[(xg << (2 * DEPTH)) | (Yi << DEPTH) | Zi];
+      float ai; uint32_t av; bool al; float2 tx, ty, tz;
+      if constexpr (kFullEntryForm == kFullPlanes) {
+        CellPlanes cp;
+        al = full_entry_planes<DEPTH>(g, s_planes, cp, ai, av);
+        tx = make_float2(cp.lox, cp.hix); ty = make_float2(cp.loy, cp.hiy); tz = make_float2(cp.loz, cp.hiz);
+      } else {
+        float gx, gy, gz;
+        al = full_entry_decode<kFullEntryForm, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, ai, av);
+        tx = slab_planes<UNIT>(gx, ai, al, scale, min_x); ty = slab_planes<UNIT>(gy, ai, al, scale, min_y); tz = slab_planes<UNIT>(gz, ai, al, scale, min_z);
+      }
+      auto ne = [](float a, float b) { return __float_as_uint(a) != __float_as_uint(b); };
+      if (ne(tx.x, wx.x) || ne(tx.y, wx.y) || ne(ty.x, wy.x) || ne(ty.y, wy.y) || ne(tz.x, wz.x) || ne(tz.y, wz.y) || ne(ai, ipd) || al != leaf || (leaf && av != v)) wrong = 1u;
+      }
+      bad += wrong;
+    };
+    if (n == 0u) {
+      const uint32_t top = __float_as_uint(band / two_d);                      // the last float of the band: 2^-(11 + DEPTH)
+      for (uint32_t ex = 0; ex <= (top >> 23); ex++)
+        for (uint32_t k = 0; k < 64u; k++) {
+          const uint32_t bits = (ex << 23) | (k < 32u ? k : 0x7FFFFFu - (k - 32u));
+          if (bits != 0u && bits <= top) check(__uint_as_float(bits));         // (+0 is the tie: the walk's)
+        }
+    } else {
+      const uint32_t c = __float_as_uint(centre);
+      if (n < (1u << DEPTH)) {
+        check(centre);                                                          // the tie
+        for (uint32_t bits = c + 1u; __uint_as_float(bits) * two_d - (float)n <= band; bits++) check(__uint_as_float(bits));
+      }
+      for (uint32_t bits = c - 1u; (float)n - __uint_as_float(bits) * two_d <= band; bits--) check(__uint_as_float(bits));
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    bad += __shfl_xor((long long)bad, o, 64); to_n += __shfl_xor((long long)to_n, o, 64);
+    to_low += __shfl_xor((long long)to_low, o, 64); to_walk += __shfl_xor((long long)to_walk, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (bad) atomicAdd(&out[0], bad);
+    atomicAdd(&out[1], to_n); atomicAdd(&out[2], to_low); atomicAdd(&out[3], to_walk);
+  }
 }
 
 // The bricks of BRICK builds (see tree_lookup_pow2): one block per level-5 position e = x5 << 10 | y5 << 5 | z5.  Every thread walks
@@ -1988,10 +2100,14 @@ int prepare_full_grid(tdt_ctx *ctx, TraceState &S, TreeForm &f, TraceParams &P) 
   const TraceState::TableKey key{cb, cb->version, P.max_depth};
   if (!(T.full_key == key)) {
     const size_t entries = (size_t)1 << (3 * P.max_depth);
-    if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + 2));      // 8^6 entries and the `bad` word behind them
+    // 8^6 entries, the `bad` word behind them, and the parent-index table at kFullParentOffset (band_resolve_x)
+    constexpr size_t kParentEntries = (tdt::kFullParentEntries * sizeof(uint16_t) + sizeof(FullGridEntry) - 1) / sizeof(FullGridEntry);
+    static_assert(tdt::kFullParentOffset == (((size_t)1 << 18) + 2) * sizeof(FullGridEntry), "the parent-index table starts behind the `bad` word");
+    if (!T.full_grid) TDT_HIP(ctx, S.alloc(T.full_grid, ((size_t)1 << 18) + 2 + kParentEntries));
     uint32_t *bad = reinterpret_cast<uint32_t *>(T.full_grid + ((size_t)1 << 18));
     TDT_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad);
+    hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P.cells, P.cells_dwords, P.max_depth, T.full_grid, bad,
+                       reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(T.full_grid) + tdt::kFullParentOffset));
     TDT_HIP(ctx, hipGetLastError());
     uint32_t flag = 1;
     TDT_HIP(ctx, hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
@@ -2745,7 +2861,9 @@ int tdt_debug_wave_ends(tdt_ctx *ctx, uint64_t *out, int n) {
 /* Exhaustive self-test of the kernels' short correctly-rounded rcp / sqrt / rsq forms against the
  * IEEE expressions on all 2^32 inputs; *mismatches must come back 0 (which: 0 rcp, 1 sqrt, 2 rsq). */
 // tdt_selftest 17 (selftest_full_grid_kernel) and 18 (selftest_plane_table_kernel: the table in its plane form, whatever form the
-// product was built with) on the cells buffer bound to ctx: the tree must be one the whole-depth table serves
+// product was built with) on the cells buffer bound to ctx: the tree must be one the whole-depth table serves.  19
+// (selftest_band_resolve_kernel): the product's table and the parent-index table built beside it; the three outcome counts go to
+// ctx->counters[1..3] (tdt_debug_counters), behind the mismatches in [0]
 static int selftest_full_grid(tdt_ctx *front, int which, uint64_t *mismatches) {
   tdt_ctx *ctx = front->multi ? tdt::multi_first_member(front) : front;
   TDT_HIP(front, hipSetDevice(ctx->device));
@@ -2761,22 +2879,23 @@ static int selftest_full_grid(tdt_ctx *front, int which, uint64_t *mismatches) {
   const uint32_t staged = buf_nodes < tdt::kLdsCells * 8u ? (buf_nodes & ~7u) : tdt::kLdsCells * 8u;
   const size_t entries = (size_t)1 << (3 * P.max_depth);
   tdt::DeviceScratch mem;
-  FullGridEntry *grid = which == 17 ? mem.get<FullGridEntry>(entries) : nullptr;
+  FullGridEntry *grid = which != 18 ? mem.get<FullGridEntry>(entries) : nullptr;
+  uint16_t *parents = which == 19 ? mem.get<uint16_t>(tdt::kFullParentEntries) : nullptr;
   FullGridEntry64 *grid_planes = which == 18 ? mem.get<FullGridEntry64>(entries) : nullptr;
   uint16_t *grid16 = mem.get<uint16_t>(entries), *packed = mem.get<uint16_t>((size_t)tdt::kLdsCells * 8);
-  unsigned long long *words = mem.get<unsigned long long>(4);                // mismatches; bad (two builds); scan results
-  if ((!grid && !grid_planes) || !grid16 || !packed || !words) return tdt::hip_fail(front, hipErrorOutOfMemory, "tdt_selftest 17");
+  unsigned long long *words = mem.get<unsigned long long>(8);                // mismatches; bad (two builds); scan results; mode 19: mismatches and its three counts
+  if ((!grid && !grid_planes) || (which == 19 && !parents) || !grid16 || !packed || !words) return tdt::hip_fail(front, hipErrorOutOfMemory, "tdt_selftest 17");
   uint32_t *bad = reinterpret_cast<uint32_t *>(words + 1), *scan = reinterpret_cast<uint32_t *>(words + 2);
-  TDT_HIP(front, hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  TDT_HIP(front, hipMemsetAsync(words, 0, 8 * sizeof(unsigned long long), ctx->stream));
   if (staged) hipLaunchKernelGGL(tdt::pack_cells_kernel, dim3((staged + 255) / 256), dim3(256), 0, ctx->stream, cells, cells_dwords, packed, staged);
   if (buf_nodes) {
     unsigned nb = (buf_nodes + 255) / 256; if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(tdt::scan_cells_kernel, dim3(nb), dim3(256), 0, ctx->stream, cells, buf_nodes, scan);
   }
   const dim3 blocks((unsigned)((entries + 255) / 256));
-  if (which == 17) hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid, bad);
-  else hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullPlanes>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid_planes, bad);
-  hipLaunchKernelGGL(tdt::build_full_grid_kernel<16>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid16, bad + 1);
+  if (which != 18) hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullEntryForm>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid, bad, parents);
+  else hipLaunchKernelGGL(tdt::build_full_grid_kernel<tdt::kFullPlanes>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid_planes, bad, (uint16_t *)nullptr);
+  hipLaunchKernelGGL(tdt::build_full_grid_kernel<16>, blocks, dim3(256), 0, ctx->stream, cells, cells_dwords, P.max_depth, grid16, bad + 1, (uint16_t *)nullptr);
   TDT_HIP(front, hipGetLastError());
   uint32_t res[4] = {0, 0, 0, 0}, flags[2] = {1, 1};
   TDT_HIP(front, hipMemcpyAsync(res, scan, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
@@ -2786,23 +2905,33 @@ static int selftest_full_grid(tdt_ctx *front, int which, uint64_t *mismatches) {
   const bool served = buf_nodes > 0 && res[2] <= staged && res[1] <= tdt::kPackedMaxValue && res[0] < (1u << 22) && flags[0] == 0 && flags[1] == 0;
   if (!served) return tdt::fail(front, TDT_ERR_INVALID_OPERATION, "tdt_selftest 17: the bound tree is not one the whole-depth table serves");
   const uint32_t lds_nodes = (res[2] + 7u) & ~7u;                            // the live cells alone are staged (classify_tree)
+  // the step's own choice between the UNIT and the multiplying build (launch_trace)
+  const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f;
   if (which == 17) hipLaunchKernelGGL(tdt::selftest_full_grid_kernel, blocks, dim3(256), 0, ctx->stream, P.max_depth, grid, grid16, packed, lds_nodes, words);
-  else {
-    // the step's own choice between the UNIT and the multiplying build (launch_trace)
-    const bool unit = P.scale == 1.0f && P.inv_scale == 1.0f && P.min_x != 0.0f && P.min_y != 0.0f && P.min_z != 0.0f;
+  else if (which == 19) {
+    auto kernel = P.max_depth == 5 ? (unit ? tdt::selftest_band_resolve_kernel<5, true> : tdt::selftest_band_resolve_kernel<5, false>)
+                                   : (unit ? tdt::selftest_band_resolve_kernel<6, true> : tdt::selftest_band_resolve_kernel<6, false>);
+    const unsigned side = 1u << P.max_depth;
+    hipLaunchKernelGGL(kernel, dim3((side * side + 255u) / 256u, side + 1u), dim3(256), 0, ctx->stream, grid, parents, packed, lds_nodes,
+                       P.scale, P.min_x, P.min_y, P.min_z, words + 4);
+  } else {
     auto kernel = P.max_depth == 5 ? (unit ? tdt::selftest_plane_table_kernel<5, true> : tdt::selftest_plane_table_kernel<5, false>)
                                    : (unit ? tdt::selftest_plane_table_kernel<6, true> : tdt::selftest_plane_table_kernel<6, false>);
     hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, ctx->stream, grid_planes, grid16, P.scale, P.min_x, P.min_y, P.min_z, words);
   }
   TDT_HIP(front, hipGetLastError());
-  TDT_HIP(front, hipMemcpyAsync(mismatches, words, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (which == 19) {
+    if (!front->counters) TDT_HIP(front, hipMalloc((void **)&front->counters, (32 + 16384 + 256) * sizeof(unsigned long long)));
+    TDT_HIP(front, hipMemcpyAsync(front->counters, words + 4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  TDT_HIP(front, hipMemcpyAsync(mismatches, which == 19 ? words + 4 : words, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   TDT_HIP(front, hipStreamSynchronize(ctx->stream));
   return TDT_OK;
 }
 
 int tdt_selftest(tdt_ctx *ctx, int which, uint64_t *mismatches) {
-  if (!ctx || !mismatches || which < 0 || which > 18) return TDT_ERR_INVALID_VALUE;
-  if (which == 17 || which == 18) return selftest_full_grid(ctx, which, mismatches);
+  if (!ctx || !mismatches || which < 0 || which > 19) return TDT_ERR_INVALID_VALUE;
+  if (which >= 17 && which <= 19) return selftest_full_grid(ctx, which, mismatches);
   TDT_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->counters) TDT_HIP(ctx, hipMalloc((void **)&ctx->counters, (32 + 16384 + 256) * sizeof(unsigned long long)));
   TDT_HIP(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));

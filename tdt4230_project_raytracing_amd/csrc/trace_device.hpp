@@ -196,6 +196,7 @@ struct NodeSource {
   const void *grid;                                   // top-level jump table (Grid<GL>::Entry[], see build_top_grid), or unusable when !grid_ok
   bool grid_ok; float grid_band;                      // grid_band = kGridBand, or 2 when the table is unusable
   const FullGridEntry *full;                          // FULL builds: the whole-depth table in global memory (see tree_lookup_pow2)
+  const uint16_t *parents;                            // five-wave FULL builds: the parent-index table behind it (see band_resolve_x)
   const float2 *planes; float vmin_x, vmin_y, vmin_z; // FULL builds, plane form: the block's plane table (LDS, see PlaneTable) and the octree's corner it was filled with
   const uint32_t *grid32; const void *bricks;         // BRICK builds: the 5-level table with brick headers (LDS) and the bricks (global memory, 16-bit entries)
   const float2 *thr; float thr_f0max;                 // FORM_TABLE builds: (F1, F2) per cell (LDS) and the scene-wide bound on F0, see x_thresholds
@@ -689,6 +690,44 @@ TDT_DEV bool full_entry_planes(const FullGridEntry64 &g, const float2 *planes, C
   value = (g.w0 >> 5) & 0x7FFu;
   return (g.w0 & 3u) == 2u;
 }
+// The parent-index table behind the whole-depth table (same allocation, same key): for L = 0 .. depth - 1 and every level-L position
+// (x, y, z), the cell index the plain-digit descent holds after L levels (0 where it ended earlier), 16 bits each (below grid_v_bound),
+// level L at entry (8^L - 1) / 7.  It serves the lanes in a band of the five-wave builds (band_resolve_x).  8^6 entries of the whole-depth
+// table and its `bad` word come first.
+constexpr uint32_t kFullParentOffset = ((1u << 18) + 2u) * (uint32_t)sizeof(FullGridEntry);   // bytes from the whole-depth table's base
+constexpr uint32_t kFullParentEntries = ((1u << 18) - 1u) / 7u;                               // depth 6: 37 449
+// ((8^L - 1) / 7 = 1 + 8 + ... + 8^(L-1): the octal number 111111 less its last 6 - L digits)
+TDT_DEV uint32_t full_parent_index(uint32_t L, uint32_t x, uint32_t y, uint32_t z) { return (kFullParentEntries >> (18u - 3u * L)) + ((x << (2u * L)) | (y << L) | z); }
+// A lane in a band (tg = 2^D c_x within 2^-11 of the integer n = rint(tg); Yi, Zi as the table lookup has them) without the level walk.
+// j = trailing zeros of n, lc = D - j the critical level: above it every level's coordinate is at least 2^-6 from 1/2 and 1 and, with cell
+// indices below grid_v_bound, takes the plain digit, which n - 1 and n share.
+//   tg > n, n > 0: at lc f = 1/2 + eps, so a = q > 0.5 is the plain digit 1 or, when v + f rounds down to v + 1/2, 0; below lc f is
+//                  tiny: all-zero digits.  The descent is the plain one of n (a = 1) or of n - 2^j (a = 0): both are table entries, and one
+//                  cell when the descent ended above lc.  a needs the cell index after lc - 1 levels: one load from the parent table.
+//   tg > n, n = 0: no critical level, plain digits, position 0.           tg < n, n odd: lc = D, f = 1/2 - eps, a = 0: position n - 1.
+//   tg < n, n even, and tg == n: kept by the walk (below lc f is just under 1, where q == 1 moves to the next cell of the array).
+// BAND_WALK: this lane needs the walk; BAND_PARENT: position from the parent's index (band_resolve_x); BAND_FLOOR: position floor(tg).
+// Checked for every float in every band x every (Yi, Zi) against the walk: tdt_selftest 19.
+#ifdef TDT_NO_BAND_RESOLVE
+constexpr bool kBandResolve = false;                  // (A/B control: every wave with a lane in a band walks)
+#else
+constexpr bool kBandResolve = true;
+#endif
+enum : int { BAND_FLOOR = 0, BAND_PARENT = 1, BAND_WALK = 2 };
+TDT_DEV int band_classify(float tg, float rn) {
+  const uint32_t n = (uint32_t)rn;
+  if (tg > rn) return n != 0u ? BAND_PARENT : BAND_FLOOR;
+  return (tg < rn && (n & 1u) != 0u) ? BAND_FLOOR : BAND_WALK;
+}
+template <int DEPTH>
+TDT_DEV uint32_t band_resolve_x(const uint16_t *parents, float fx0, uint32_t n, uint32_t Yi, uint32_t Zi) {
+  const uint32_t j = (uint32_t)__builtin_ctz(n), L = (uint32_t)DEPTH - 1u - j, s = j + 1u;            // L = lc - 1 levels above the critical one
+  const uint32_t v = parents[full_parent_index(L, n >> s, Yi >> s, Zi >> s)];
+  const float f = f_fract_nonneg(fx0 * __uint_as_float((127u + L) << 23));      // the walk's coordinate of level lc: fract(c 2^(lc-1))
+  const float fv = (float)v;
+  const float q = (fv + f) - fv;
+  return q > 0.5f ? n : n - (1u << j);
+}
 // UNIT and cp: the plane form of the FULL builds (cp != nullptr there and nowhere else) — *cp gets the cell's planes, from the table or,
 // behind the walk, from slab_planes; gx, gy, gz are then not written
 // GLOBAL: no LDS node table (ns.lds is not read): every level of the walk reads the cells from global memory, range-checked
@@ -714,10 +753,10 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
   constexpr int kGridLevels = FULL ? DEPTH : kTableLevels;            // levels the jump covers (BRICK builds: never continue after their jump)
   if constexpr (FULL && !COUNT) {
     const float tg = fx0 * (float)(1 << DEPTH);       // exact
-    const bool safe = __builtin_fabsf(tg - __builtin_rintf(tg)) > ns.grid_band;
-    if (__builtin_expect(__ballot(!safe) == 0ull, 1)) {
-      // the whole lookup: levels visited, the cell's digits and what it holds (see build_full_grid_kernel)
-      const uint32_t xg = (uint32_t)tg;
+    const float rn = __builtin_rintf(tg);
+    const bool safe = __builtin_fabsf(tg - rn) > ns.grid_band;
+    // the whole lookup: levels visited, the cell's digits and what it holds (see build_full_grid_kernel)
+    auto table = [&](uint32_t xg) -> bool {
       // (64 bits: one 8-byte load.  The byte offset — below 2 MB at depth 6 — formed in 32 bits beside the table's scalar base: no 64-bit add)
       constexpr int kEntryShift = sizeof(FullGridEntry) == 8 ? 3 : (sizeof(FullGridEntry) == 4 ? 2 : 1);
       static_assert(sizeof(FullGridEntry) == (1u << kEntryShift) && 3 * DEPTH + kEntryShift < 32, "the table's byte offset in 32 bits");
@@ -726,6 +765,31 @@ TDT_DEV bool tree_lookup_pow2(const TraceParams &P, const NodeSource &ns, float 
       const FullGridEntry g = *reinterpret_cast<const FullGridEntry *>(reinterpret_cast<const char *>(ns.full) + off);
       if constexpr (PLANES) return full_entry_planes<DEPTH>(g, ns.planes, *cp, inv_pow_depth, value);
       else return full_entry_decode<kFullEntryBits, DEPTH>(g, xg, Yi, Zi, gx, gy, gz, inv_pow_depth, value);
+    };
+    if constexpr (kBandResolve && GLOBAL) {
+      uint32_t xg = (uint32_t)tg;
+      const unsigned long long in_band = __ballot(!safe);
+      bool walk = false;                              // (wave-uniform)
+      if (__builtin_expect(in_band != 0ull, 0)) {
+        // a lane in a band: unless one of them is of the kind only the walk serves, each takes the table entry of the position the walk
+        // would end at (band_classify), and the wave joins the table's one load after all
+        const int kind = safe ? BAND_FLOOR : band_classify(tg, rn);
+        const unsigned long long walks = __ballot(kind == BAND_WALK);
+#ifdef TDT_STATS
+        if ((threadIdx.x & 63) == (uint32_t)__builtin_ctzll(__ballot(1))) {
+          ns.stat_fallback[2] += 1u; ns.stat_fallback[3] += (uint32_t)__popcll(in_band);
+          if (walks == 0ull) ns.stat_fallback[4] += (uint32_t)__popcll(in_band);
+        }
+#endif
+        walk = true;
+        if (walks == 0ull) {
+          if (kind == BAND_PARENT) xg = band_resolve_x<DEPTH>(ns.parents, fx0, (uint32_t)rn, Yi, Zi);
+          walk = false;
+        }
+      }
+      if (!walk) return table(xg);
+    } else {
+      if (__builtin_expect(__ballot(!safe) == 0ull, 1)) return table((uint32_t)tg);
     }
 #ifdef TDT_STATS
     {                                                 // the wave takes the level walk: one pass, and the lanes in a band that sent it there

@@ -1087,10 +1087,17 @@ class Context:
 
     def selftest(self, which):
         """Mismatches of the short rcp (0) / sqrt (1) / rsq (2) forms vs IEEE over all 2^32 inputs; the other modes: include/tdt_rt.h
-        (17: the whole-depth table of the bound cells buffer, every position; 18: its plane form, planes through the offsets vs arithmetic)."""
+        (17: the whole-depth table of the bound cells buffer, every position; 18: its plane form, planes through the offsets vs arithmetic;
+        19: the lanes in a band served from the table, every float of every band; its outcome counts: selftest_band_counts)."""
         n = ctypes.c_uint64(0)
         self.check(lib().tdt_selftest(self.h, which, ctypes.byref(n)))
         return n.value
+
+    def selftest_band_counts(self):
+        """After selftest(19): lanes resolved to position n, to n - 2^j, and left to the level walk."""
+        c = (ctypes.c_uint64 * 32)()
+        self.check(lib().tdt_debug_counters(self.h, c))
+        return {"to_n": int(c[1]), "to_lower": int(c[2]), "to_walk": int(c[3])}
 
     def last_variant(self):
         """The build of the trace kernel the last trace launch ran: dict(form, depth, resident, full, brick, unit) and its launch
@@ -1103,7 +1110,7 @@ class Context:
     STAT_NAMES = ("trav_pass", "trav_lanes", "inside_lanes", "alive_lanes", "event_pass", "event_lanes", "hit_pass", "hit_lanes", "lamb_pass", "lamb_lanes",
                   "metal_pass", "metal_lanes", "diel_pass", "diel_lanes", "end_pass", "end_lanes", "pixel_end_pass", "pixel_end_lanes", "fetch_pass", "fetch_lanes",
                   "primary_pass", "primary_lanes", "newray_pass", "newray_lanes", "gate_wait_lanes", "drained_trav_pass", "drained_event_pass", "loop_pass",
-                  "wave_ticks", "waves", "t_first", "t_last", "fallback_pass", "fallback_lanes")
+                  "wave_ticks", "waves", "t_first", "t_last", "fallback_pass", "fallback_lanes", "band_pass", "band_lanes", "resolved_lanes")
 
     def stats(self, reset=True):
         """Pass / lane statistics of the product trace kernels since the last reset (a -DTDT_STATS build of the library only)."""
