@@ -500,6 +500,33 @@ class Octree {
     if (n) ctx.check(tdt_octree_distance_field(ctx.raw(), lo, hi, max_d2, border, f.data(), nearest ? nearest->data() : nullptr, n, &n));
     return f;
   }
+  // NEW: the smooth brush (tdt_octree_smooth): s.iterations steps of the ball-density threshold filter with the ball of squared
+  // radius s.radius2, inside the union of `mask` (none: everywhere); the bound tree rebuilt in place; returns the number of cells
+  uint32_t smooth(const Context &ctx, const tdt_smooth &s, const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_smooth(ctx.raw(), &s, mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: what smooth would leave, as voxels {x, y, z, material + 1} in Morton order, the tree untouched (tdt_octree_extract_smooth)
+  std::vector<int32_t> extract_smooth(const Context &ctx, const tdt_smooth &s, const std::vector<tdt_region> &mask = {}) const {
+    size_t n = 0;
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    ctx.check(tdt_octree_extract_smooth(ctx.raw(), &s, r, mask.size(), nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_smooth(ctx.raw(), &s, r, mask.size(), v.data(), n, &n));
+    return v;
+  }
+  // NEW: how many voxels of the tree the ball of squared radius radius2 around each voxel of the inclusive box lo..hi holds
+  // (tdt_octree_density_field), x fastest; `support` (optional) receives the number of ball points inside the grid per voxel
+  std::vector<int32_t> density_field(const Context &ctx, const int32_t lo[3], const int32_t hi[3], int32_t radius2,
+                                     std::vector<int32_t> *support = nullptr) const {
+    size_t n = 0;
+    ctx.check(tdt_octree_density_field(ctx.raw(), lo, hi, radius2, nullptr, nullptr, 0, &n));
+    std::vector<int32_t> d(n);
+    if (support) support->assign(n, 0);
+    if (n) ctx.check(tdt_octree_density_field(ctx.raw(), lo, hi, radius2, d.data(), support ? support->data() : nullptr, n, &n));
+    return d;
+  }
   // NEW: move, turn, mirror, rotate or scale a selection (tdt_octree_transform): x is the destination -> source map (the
   // tdt_xform_* builders of tdt_host.h make one from a forward transform); the voxels of the tree inside the union of `mask`
   // (none: all of it) are resampled through it and applied with op (TDT_REGION_*) as a voxel list that never leaves the device.

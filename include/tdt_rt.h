@@ -1125,6 +1125,70 @@ int tdt_octree_extract_morph_round(tdt_ctx *ctx, const tdt_round *r, const tdt_r
 int tdt_octree_distance_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, int32_t border, int32_t *field,
                               int32_t *nearest_xyz, size_t capacity, size_t *n_voxels);
 
+/* ---- voxel smoothing ---------------------------------------------------------------------------------------------------------
+ * The smooth brush: the density of the object around every voxel, thresholded; and the raw density as a field.  N = 2^max_depth,
+ * G = [0, N)^3, V = what tdt_octree_extract returns, B(r2) = { d in Z^3 : |d|^2 <= r2 } as in the round unit, r2 = `radius2` in
+ * 1..225 here, so R (the smallest integer with R * R >= r2) <= 15, every x-chord of the ball is at most 31 voxels wide, and |B|
+ * (tdt_ball_size) is odd.  For a set S and a voxel q of G:
+ *   DENSITY  d(q, S) = |{ p in q + B : p in S }|.  Points outside G are never in S; nothing wraps around the grid.
+ *   SUPPORT  n(q) = |B| with `border` = 0: the outside of the grid counts as empty space.  n(q) = |(q + B) & G| with `border` = 1:
+ *     the outside of the grid is left out of the vote, so an object cut by a grid face is not rounded off there.
+ *   THRESHOLD TEST  T(q, S): `threshold` = 0 (majority): 2 d > n.  `threshold` in 1..65536, a Q16 fraction of the support:
+ *     65536 d >= threshold * n, exact in 32-bit unsigned arithmetic because d <= |B(225)| < 2^15.  Either way T implies d >= 1.
+ *   ONE STEP  F(S) by `mode`: TDT_SMOOTH_BOTH: the voxels of G with T.  TDT_SMOOTH_ADD: S plus those with T (fills dents only).
+ *     TDT_SMOOTH_REMOVE: those of S with T (shaves bumps only).
+ *   MATERIALS  A voxel of S that survives keeps its material.  A new voxel q gets `material` when that is >= 0, otherwise the
+ *     material of its NEAREST voxel of S by the round unit's rule: among the p in S at the least |p - q|^2 the one with the
+ *     lowest x, then y, then z.  Such a p lies inside q + B because d >= 1.  It is taken on the set BEFORE the step.
+ *   MASK  With n_regions > 0, M = the union of the shapes by the exact integer test of region edits, a step is
+ *     (F(S) & M) + (S \ M); densities are always taken on the whole current set.
+ *   RESULT  S_0 = V, S_(k + 1) = one step applied to S_k; the result is S_iterations, `iterations` in 1..16.  (A step that
+ *     changes nothing ends the loop: every later one would change nothing either.)
+ * Identities: threshold 1, BOTH, border 0 is tdt_octree_morph_round's DILATE at the same radius2, inherited materials included;
+ * threshold 65536, BOTH is its ERODE with the same border; ADD gives a superset of V, REMOVE a subset of V with V's materials;
+ * with border 0 and threshold 0 a step never leaves bbox(S) (for q outside the box along an axis, mirroring d in that axis maps
+ * the ball points that can be occupied injectively onto points that cannot, so 2 d <= |B| - |{d_axis = 0}| < |B|).
+ * tdt_octree_smooth rewrites the bound cells buffer in place into tdt_octree_build_cells(result, max_depth) by
+ * tdt_octree_compact's install rule, on every replica of a multi-device context; a failure leaves all of them unchanged.
+ * *n_cells is written after the install, and on a misfit before the refusal: the size the buffer must grow to.  The list never
+ * leaves the device between iterations or before the install.  tdt_octree_extract_smooth returns the same result as a
+ * Morton-sorted list by tdt_octree_extract's rules from device_ids[0] (voxels_xyzm == NULL only counts; capacity below the count:
+ * TDT_ERR_INVALID_VALUE with the count set); the tree, its counter and its versions are untouched.
+ * tdt_octree_density_field follows tdt_octree_distance_field in every convention — the inclusive box inside G holding <= 2^26
+ * voxels, density[((z - lo z) * ey + (y - lo y)) * ex + (x - lo x)], density == NULL only setting *n_voxels without walking the
+ * tree, capacity below the count: TDT_ERR_INVALID_VALUE with the count set, a multi-device context answering from device_ids[0],
+ * an empty tree being valid (all zeros): density[i] = d(q, V), and support (optional) [i] = |(q + B) & G|, the n(q) of border 1.
+ * tdt_ball_size is |B(radius2)| for 1..4096 and -1 otherwise, in host arithmetic.
+ * Limit, checked on the host before any volume is allocated: the DOMAIN — bbox(V) grown by iterations * R on every side and
+ * clipped to G, or the field's box grown by R — holds <= TDT_SMOOTH_DOMAIN_CAP voxels.  With border 0 and a threshold of 0 or
+ * above 32768 the growth is 0, by the last identity.  Over the domain the unit keeps two bit volumes and a count per 32 voxels;
+ * |V| and every list stay within 2^26 voxels (TDT_REGION_BRUSH_CAP).
+ * Errors, nothing written: a NULL struct or pointer, radius2 outside 1..225, iterations outside 1..16, threshold outside
+ * 0..65536, a bad mode, material outside -1..253, border outside 0..1, a bad shape, NULL regions with a count above 0, a bad
+ * box, a LEAF value >= 254, a limit exceeded: TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound: TDT_ERR_INCOMPLETE.  Ordered after
+ * work queued on the context's stream; synchronous. */
+#define TDT_SMOOTH_DOMAIN_CAP (1u << 28)
+enum { TDT_SMOOTH_BOTH = 0, TDT_SMOOTH_ADD = 1, TDT_SMOOTH_REMOVE = 2 };
+typedef struct tdt_smooth {
+  int32_t radius2;             /* the squared radius of the ball, 1..225 */
+  int32_t iterations;          /* steps, 1..16 */
+  int32_t threshold;           /* 0: majority; 1..65536: Q16 fraction of the support */
+  int32_t mode;                /* TDT_SMOOTH_* */
+  int32_t material;            /* -1: a new voxel inherits its nearest voxel's; 0..253: every new voxel gets this LEAF value */
+  int32_t border;              /* 0 = outside the grid is empty space, 1 = outside the grid is left out of the vote */
+} tdt_smooth;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_smooth) == 24, "tdt_smooth is 24 bytes");
+#else
+_Static_assert(sizeof(tdt_smooth) == 24, "tdt_smooth is 24 bytes");
+#endif
+int32_t tdt_ball_size(int32_t radius2);
+int tdt_octree_smooth(tdt_ctx *ctx, const tdt_smooth *s, const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+int tdt_octree_extract_smooth(tdt_ctx *ctx, const tdt_smooth *s, const tdt_region *regions, size_t n_regions, int32_t *voxels_xyzm,
+                              size_t capacity, size_t *n_voxels);
+int tdt_octree_density_field(tdt_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t radius2, int32_t *density, int32_t *support,
+                             size_t capacity, size_t *n_voxels);
+
 /* ---- affine transforms of voxel selections -------------------------------------------------------------------------------
  * Move, turn, mirror, rotate and scale a selection by resampling.  N = 2^max_depth, G = [0, N)^3, V = what tdt_octree_extract
  * returns, S = the voxels of V inside the mask: all of V with n_regions == 0, otherwise those inside the union of the regions

@@ -8,6 +8,7 @@
 //            [--reach COST [--steps 6|26|345] [--medium solid|empty] [--match-material] [--op ..] [--material K] [--mask ..]]
 //            [--morph dilate|erode|open|close|shell:R [--conn 6|26] [--mask x0,y0,z0,x1,y1,z1]] [--cells N]
 //            [--morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]]
+//            [--smooth R2[:ITER] [--threshold Q16] [--smooth-mode both|add|remove] [--material K] [--border 0|1] [--mask ..]]
 //            [--transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG [--pivot X,Y,Z] [--op ..]
 //             [--material K] [--mask x0,y0,z0,x1,y1,z1]]
 //            [--mesh FILE.ply [--solid] [--material K] [--op set|fill|paint|clear] [--box x0,y0,z0,x1,y1,z1]]
@@ -81,6 +82,11 @@
 // --morph-round dilate|erode|open|close|shell:R2 [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]: round morphology
 //   (Octree::morph_round) with the Euclidean ball of SQUARED radius R2 (1..4096); new voxels get --material or inherit their
 //   nearest voxel's; --border 1: the outside of the grid is solid.  Applied after --morph; prints the new cell count.
+// --smooth R2[:ITER] [--threshold Q16] [--smooth-mode both|add|remove] [--material K] [--border 0|1] [--mask x0,y0,z0,x1,y1,z1]: the
+//   smooth brush (Octree::smooth): ITER (default 1) steps of the ball-density threshold filter with the ball of SQUARED radius R2
+//   (1..225); a voxel holds after a step when more than half of the ball around it is occupied, or with --threshold at least
+//   Q16 / 65536 of it; add / remove only fill dents / shave bumps; new voxels get --material or inherit their nearest voxel's;
+//   --border 1 leaves the outside of the grid out of the vote.  Applied after --morph-round; prints the new cell count.
 // --transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG [--pivot X,Y,Z] [--op set|fill|paint|clear]
 //   [--material K] [--mask x0,y0,z0,x1,y1,z1]: move, turn (K quarter turns about AXIS 0 / 1 / 2), mirror, scale or rotate (DEG
 //   degrees about the axis AX,AY,AZ) the tree's voxels, those inside the --mask box only, about the voxel corner --pivot (default
@@ -133,6 +139,7 @@ int main(int argc, char **argv) {
   std::string morph_name;
   int round_op = -1, round_r2 = 0, round_border = 0;
   std::string round_name;
+  int smooth_r2 = 0, smooth_iter = 1, smooth_threshold = 0, smooth_mode = TDT_SMOOTH_BOTH;
   std::string xform_kind;
   double xform_arg[4] = {0, 0, 0, 0};
   std::vector<int32_t> pivot;
@@ -237,6 +244,15 @@ int main(int argc, char **argv) {
       if (!good) { std::fprintf(stderr, "--transform translate:DX,DY,DZ|turn:AXIS,K|mirror:AXIS|scale:NUM/DEN|rotate:AX,AY,AZ,DEG\n"); return 2; }
     }
     else if (a == "--pivot") { int32_t v[3]; if (std::sscanf(next(), "%d,%d,%d", v, v + 1, v + 2) != 3) { std::fprintf(stderr, "--pivot X,Y,Z\n"); return 2; } pivot.assign(v, v + 3); }
+    else if (a == "--smooth") {
+      if (std::sscanf(next(), "%d:%d", &smooth_r2, &smooth_iter) < 1 || smooth_r2 < 1) { std::fprintf(stderr, "--smooth R2[:ITER]\n"); return 2; }
+    }
+    else if (a == "--threshold") smooth_threshold = std::atoi(next());
+    else if (a == "--smooth-mode") {
+      const std::string v = next();
+      if (v == "both") smooth_mode = TDT_SMOOTH_BOTH; else if (v == "add") smooth_mode = TDT_SMOOTH_ADD; else if (v == "remove") smooth_mode = TDT_SMOOTH_REMOVE;
+      else { std::fprintf(stderr, "--smooth-mode both|add|remove\n"); return 2; }
+    }
     else if (a == "--border") { round_border = std::atoi(next()); if (round_border != 0 && round_border != 1) { std::fprintf(stderr, "--border 0|1\n"); return 2; } }
     else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
@@ -519,6 +535,20 @@ int main(int argc, char **argv) {
         regions.push_back(r);
       }
       std::printf("morph-round %s:%d border %d cells %u\n", round_name.c_str(), round_r2, round_border, octree.morph_round(ctx, q, regions));
+    }
+    if (smooth_r2 > 0) {
+      tdt_smooth q{};
+      q.radius2 = smooth_r2; q.iterations = smooth_iter; q.threshold = smooth_threshold; q.mode = smooth_mode;
+      q.material = material_given ? material : -1; q.border = round_border;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      std::printf("smooth %d:%d threshold %d mode %d border %d cells %u\n", smooth_r2, smooth_iter, smooth_threshold, smooth_mode, round_border,
+                  octree.smooth(ctx, q, regions));
     }
     if (!xform_kind.empty()) {
       const int32_t half = 1 << (ints[0] - 1);

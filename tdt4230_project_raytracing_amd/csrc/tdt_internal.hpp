@@ -13,7 +13,8 @@
 // guide-keyed upsampling of a frame traced at reduced resolution; tdt_adaptive.hip: the sampling controller that turns per-pixel
 // variance into the masks of tdt_dispatch_accumulate_masked; tdt_select.hip: screen-space selection, where the two halves meet:
 // voxel-id images, overlays of a voxel list and the voxels of a rectangle; tdt_screen.hip: through-selection, the tree's voxels
-// projected into a view and tested against a rectangle, a polygon or a mask.  The host helpers
+// projected into a view and tested against a rectangle, a polygon or a mask; tdt_smooth.hip: voxel smoothing, a ball-density
+// threshold filter and the density field, on the bit volume too.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).

@@ -188,6 +188,21 @@ class Round(ctypes.Structure):
 
 assert ctypes.sizeof(Round) == 16
 
+# voxel smoothing (include/tdt_rt.h): modes and struct tdt_smooth
+SMOOTH_BOTH, SMOOTH_ADD, SMOOTH_REMOVE = 0, 1, 2
+SMOOTH_DOMAIN_CAP = 1 << 28
+
+
+class Smooth(ctypes.Structure):
+    """struct tdt_smooth: radius2 1..225 (the squared radius of the ball), iterations 1..16, threshold 0 (majority) or a Q16
+    fraction 1..65536 of the support, mode SMOOTH_*, material -1 (inherit the nearest voxel's) or 0..253, border 0 / 1 (outside
+    the grid empty / left out of the vote)."""
+    _fields_ = [("radius2", ctypes.c_int32), ("iterations", ctypes.c_int32), ("threshold", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("material", ctypes.c_int32), ("border", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Smooth) == 24
+
 
 # affine transforms of voxel selections (include/tdt_rt.h): struct tdt_xform
 XFORM_ONE = 65536
@@ -448,6 +463,11 @@ SYMBOLS = [
     ("tdt_octree_extract_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_distance_field", _I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                                        _P, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_ball_size", ctypes.c_int32, [ctypes.c_int32]),
+    ("tdt_octree_smooth", _I, [_P, ctypes.POINTER(Smooth), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_smooth", _I, [_P, ctypes.POINTER(Smooth), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_density_field", _I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, _P, _S,
+                                      ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_extract_transform", _I, [_P, ctypes.POINTER(Xform), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_transform", _I, [_P, ctypes.POINTER(Xform), _I, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_debug_xform_bricks", _I, [_P, ctypes.POINTER(ctypes.c_uint32)]),
@@ -490,6 +510,13 @@ def lib():
             f.argtypes = args
         _lib = L
     return _lib
+
+
+def ball_size(radius2):
+    """tdt_ball_size: the number of lattice points d with |d|^2 <= radius2, for 1..4096; -1 otherwise.  Host arithmetic: no device."""
+    if isinstance(radius2, bool) or int(radius2) != radius2 or not -2**31 <= int(radius2) <= 2**31 - 1:
+        raise ValueError(f"radius2 must be an int32, not {radius2!r}")
+    return int(lib().tdt_ball_size(int(radius2)))
 
 
 class TdtError(RuntimeError):
@@ -883,6 +910,50 @@ class Context:
         self.check(lib().tdt_octree_distance_field(self.h, box3[0], box3[1], max_d2, border, field.ctypes.data,
                                                    near.ctypes.data if nearest else None, field.size, ctypes.byref(n)))
         return (field, near) if nearest else field
+
+    @classmethod
+    def _smooth(cls, radius2, iterations, threshold, mode, material, border):
+        """struct tdt_smooth (threshold None: majority; material None: inherit).  The ranges themselves are the library's to check."""
+        threshold = 0 if threshold is None else threshold
+        material = -1 if material is None else material
+        return Smooth(cls._int32("radius2", radius2), cls._int32("iterations", iterations), cls._int32("threshold", threshold),
+                      cls._int32("mode", mode), cls._int32("material", material), cls._int32("border", border, allow_bool=True))
+
+    def octree_smooth(self, radius2, iterations=1, threshold=None, mode=SMOOTH_BOTH, material=None, border=0, regions=()):
+        """tdt_octree_smooth: `iterations` (1..16) steps of the ball-density threshold filter on the bound tree, rebuilt in place.
+        A step keeps (SMOOTH_BOTH), adds (SMOOTH_ADD) or removes (SMOOTH_REMOVE) by the test "the ball of squared radius `radius2`
+        (1..225) around the voxel holds more than half of its support" (threshold None) or "at least threshold / 65536 of it"
+        (1..65536); new voxels inherit the material of their nearest voxel (None) or get `material` 0..253; border 1 leaves the
+        outside of the grid out of the vote; regions: one Region or a sequence limits what a step may change (none, as the C
+        call's n_regions = 0: no mask).  Returns the canonical tree's cell count."""
+        s = self._smooth(radius2, iterations, threshold, mode, material, border)
+        arr, k = _regions(() if regions is None else regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_smooth(self.h, ctypes.byref(s), arr, k, ctypes.byref(n)), n)
+        return int(n.value)
+
+    def octree_extract_smooth(self, radius2, iterations=1, threshold=None, mode=SMOOTH_BOTH, material=None, border=0, regions=()):
+        """tdt_octree_extract_smooth: what octree_smooth would leave, as an (n, 4) int32 list {x, y, z, material + 1},
+        Morton-sorted; the tree is untouched.  Counts first, fills second: the filter runs twice."""
+        s = self._smooth(radius2, iterations, threshold, mode, material, border)
+        arr, k = _regions(() if regions is None else regions)
+        return self._list(lib().tdt_octree_extract_smooth, ctypes.byref(s), arr, k)
+
+    def octree_density_field(self, lo, hi, radius2, support=False):
+        """tdt_octree_density_field: how many voxels of the bound tree the ball of squared radius `radius2` (1..225) around each
+        voxel of the inclusive box lo..hi holds, as an (ez, ey, ex) int32 array.  support: also an array of the same shape with the
+        number of ball points inside the grid.  The tree is untouched."""
+        box3 = self._box3(lo, hi)
+        radius2 = self._int32("radius2", radius2)
+        n = ctypes.c_size_t(0)
+        self.check(lib().tdt_octree_density_field(self.h, box3[0], box3[1], radius2, None, None, 0, ctypes.byref(n)))
+        ex, ey, ez = (int(box3[1][a]) - int(box3[0][a]) + 1 for a in range(3))
+        density = np.zeros((ez, ey, ex), np.int32)
+        sup = np.zeros((ez, ey, ex), np.int32) if support else None
+        assert density.size == n.value
+        self.check(lib().tdt_octree_density_field(self.h, box3[0], box3[1], radius2, density.ctypes.data,
+                                                  sup.ctypes.data if support else None, density.size, ctypes.byref(n)))
+        return (density, sup) if support else density
 
     @classmethod
     def _xform(cls, xf):

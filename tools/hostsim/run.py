@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A bit-volume unit (csrc/tdt_fill.hip, tdt_distance.hip, tdt_xform.hip or tdt_geodesic.hip) and the layers under it
+"""A bit-volume unit (csrc/tdt_fill.hip, tdt_distance.hip, tdt_xform.hip, tdt_geodesic.hip or tdt_smooth.hip) and the layers under it
 (csrc/tdt_bitvol.hip, bitvol_device.hpp; the capped tree list of csrc/tdt_voxlist.hip) — kernels and host code, unchanged — compiled for the CPU and run against a brute-force
 model, under AddressSanitizer and UBSan.  No GPU, no HIP: hip/hip_runtime.h here stands in for the constructs the units use (a
 block is 256 real threads behind a pthread barrier, blocks run one after another, hipMalloc is malloc), device_scan.hpp for the
@@ -20,6 +20,10 @@ because every block costs 256 threads:
               {5,1,1}, {7,0,2}, a material match, a mask, max_cost 0 and cuts, seeds off the grid and off the medium, no seeds,
               an empty mask, the empty tree, a serpentine corridor that needs more than one batch of passes, a corridor across a
               word boundary; each compares the field, the list, the list the edit form hands on and the canonical path
+    smooth    a brute force over every offset of the ball: random grids at depth 3 and 4 under majority and Q16 thresholds, the
+              three modes, both borders, fixed and inherited materials, a box + sphere mask and up to three iterations; radius2
+              225 on a grid smaller than the ball; a tied pair and a bar across the words of a row at depth 6; a full grid, an
+              empty one and a single voxel; the density field with its support.  The edit form's list is what it hands the builder
 
 A stand-alone program: nothing of it is loaded into python or linked into libtdtrt.so.
 
@@ -33,7 +37,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "tdt4230_project_raytracing_amd", "csrc")
-UNITS = ("fill", "distance", "xform", "geodesic")
+UNITS = ("fill", "distance", "xform", "geodesic", "smooth")
 
 
 def main():
