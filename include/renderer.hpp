@@ -393,6 +393,58 @@ class Octree {
     if (n_cells) *n_cells = n;
     return true;
   }
+  // NEW: a brush pulled along a path (tdt_octree_edit_stroke): op (TDT_REGION_*) over the voxels within `radius` of the segments
+  // between `points_xyz` (voxel coordinates, on or off the grid) — a TDT_SHAPE_SPHERE nib sweeps capsules, a TDT_SHAPE_BOX nib of
+  // half-width `radius` swept cubes.  `segments` empty and polyline = true: the polyline of the points (one point: a dab);
+  // otherwise pairs of point indices (i == j: a dab).  material 0..253 for every segment or, with `materials`, material + 1 per
+  // segment (the highest covering segment wins).  The list never leaves the device; returns the number of cells.
+  uint32_t stroke(const Context &ctx, int op, const std::vector<int32_t> &points_xyz, int shape, int radius, int32_t material,
+                  const std::vector<uint32_t> &segments = {}, bool polyline = true, const std::vector<int32_t> &materials = {}) const {
+    static const uint32_t none[2] = {0, 0};
+    const tdt_stroke s = stroke_of(points_xyz, shape, radius, material, segments, polyline, materials, none);
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_stroke(ctx.raw(), op, &s, &n));
+    return n;
+  }
+  // NEW: the tree's voxels that stroke covers, {x, y, z, material + 1} with the tree's own materials, in Morton order
+  // (tdt_octree_extract_stroke): the undo record of a CLEAR or PAINT stroke (edit_voxels(TDT_REGION_SET, it) puts them back)
+  std::vector<int32_t> extract_stroke(const Context &ctx, const std::vector<int32_t> &points_xyz, int shape, int radius,
+                                      const std::vector<uint32_t> &segments = {}, bool polyline = true) const {
+    static const uint32_t none[2] = {0, 0};
+    const tdt_stroke s = stroke_of(points_xyz, shape, radius, 0, segments, polyline, {}, none);
+    size_t n = 0;
+    ctx.check(tdt_octree_extract_stroke(ctx.raw(), &s, nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_stroke(ctx.raw(), &s, v.data(), n, &n));
+    return v;
+  }
+  // NEW: a brush dragged over pixels: one batched pick of all of them (tdt_pick_pixels, sample 0), every hit turned into the grid
+  // voxel in front of the face (SET / FILL) or behind it (PAINT / CLEAR) (tdt_pick_grid_voxel), consecutive hits joined by
+  // segments, a miss breaking the stroke and a hit between two misses left as a dab; then stroke() of those points
+  // (tdt_octree_edit_stroke).  Returns the number of cells; *points_xyz receives the points used.  No hit: the empty stroke.
+  uint32_t stroke(const ComputeShader &raytracer, const std::vector<std::array<int32_t, 2>> &pixels, int shape, int radius, int op,
+                  int32_t material, std::vector<int32_t> *points_xyz = nullptr) const {
+    const std::vector<tdt_ray_hit> hits = raytracer.pick(pixels, 0);
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    const int place = op == TDT_REGION_SET || op == TDT_REGION_FILL ? 1 : 0;
+    std::vector<int32_t> pts;
+    std::vector<uint32_t> seg;
+    std::vector<char> joined;
+    bool prev = false;
+    for (const tdt_ray_hit &h : hits) {
+      int32_t c[3];
+      if (tdt_pick_grid_voxel(&h, floats, ints, place, c) != 0) { prev = false; continue; }   // miss / stale record / outside
+      const uint32_t i = (uint32_t)(pts.size() / 3);
+      pts.insert(pts.end(), c, c + 3);
+      joined.push_back(0);
+      if (prev) { seg.push_back(i - 1); seg.push_back(i); joined[i - 1] = joined[i] = 1; }
+      prev = true;
+    }
+    for (uint32_t i = 0; i < joined.size(); i++) if (!joined[i]) { seg.push_back(i); seg.push_back(i); }
+    if (points_xyz) *points_xyz = pts;
+    return stroke(raytracer.context(), op, pts, shape, radius, material, seg, false);
+  }
   // NEW: connected components of the bound tree (tdt_octree_components): the table, numbered in the Morton order of each
   // component's first voxel; labels (may be null) receive the component of every voxel of extract's list.  A count query costs
   // a whole labelling, so this labels once: labels sized by a walk (tdt_octree_extract's count), the table by `capacity`; only a
@@ -692,6 +744,17 @@ class Octree {
     return true;
   }
  private:
+  // the tdt_stroke of stroke() / extract_stroke(); an explicit empty segment list still points somewhere (NULL means the polyline)
+  static tdt_stroke stroke_of(const std::vector<int32_t> &points_xyz, int shape, int radius, int32_t material, const std::vector<uint32_t> &segments,
+                              bool polyline, const std::vector<int32_t> &materials, const uint32_t *none) {
+    tdt_stroke s{};
+    s.points = points_xyz.empty() ? nullptr : points_xyz.data();
+    s.segments = !segments.empty() ? segments.data() : polyline ? nullptr : none;
+    s.materials = materials.empty() ? nullptr : materials.data();
+    s.n_points = (uint32_t)(points_xyz.size() / 3); s.n_segments = (uint32_t)(segments.size() / 2);
+    s.shape = shape; s.radius = radius; s.material = material;
+    return s;
+  }
   Vector3f min_point_{};
   float scale_ = 1, block_distance_ = 0;
   int max_depth_ = 0, cell_count_ = 0, active_cell_count_ = 0, max_traversal_iter_ = 0;

@@ -970,6 +970,57 @@ _Static_assert(sizeof(tdt_mesh) == 40, "tdt_mesh is 40 bytes");
 int tdt_voxelize_triangles(tdt_ctx *ctx, const tdt_mesh *mesh, int depth, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
 int tdt_octree_edit_triangles(tdt_ctx *ctx, int op, const tdt_mesh *mesh, uint32_t *n_cells);
 
+/* ---- stroke brushes ---------------------------------------------------------------------------------------------------------
+ * Pull a brush along a path.  A stroke is a set of segments between points given in voxel coordinates (on or off the grid,
+ * |coordinate| <= TDT_STROKE_COORD_MAX), swept by a nib of `radius` 0..TDT_STROKE_RADIUS_MAX.  Coverage is defined on the grid
+ * alone and decided in exact integers: voxel p of [0, 2^depth)^3 is covered by segment (a, b) when some point q of the closed
+ * segment is within `radius` of p — TDT_SHAPE_SPHERE in the Euclidean metric, |p - q|_2 <= r (a capsule), TDT_SHAPE_BOX in the
+ * Chebyshev metric, max_k |p_k - q_k| <= r (a swept cube).  A dab (a == b) with SPHERE is exactly the TDT_SHAPE_SPHERE of
+ * tdt_region, with BOX exactly the box [a - r, a + r]; radius 0 covers only the lattice points lying on the segment; the set
+ * of (a, b) is the set of (b, a).
+ *   SPHERE, with d = b - a, w = p - a, L2 = d . d, t = w . d:  t <= 0: |w|^2 <= r^2;  t >= L2: |p - b|^2 <= r^2;  otherwise
+ *     (|w|^2 - r^2) L2 <= t^2.
+ *   BOX: the slab test of the segment against the cube [p - r, p + r], the ends of the parameter's intervals compared by
+ *     cross-multiplication; an axis with d_k = 0 bounds no parameter but must satisfy |w_k| <= r.
+ * segments == NULL (n_segments must be 0): the polyline 0-1, 1-2, ... of the points, one point being a single dab; otherwise
+ * n_segments x {i, j} point indices (i == j: a dab; n_segments == 0: nothing).  Segment s carries materials[s] = material + 1 in
+ * 1..254 (materials == NULL: `material` + 1 for all, material 0..253); a voxel covered by several segments takes the material of
+ * the one with the highest index — the builder's last-duplicate-wins rule over (segment, voxel) pairs in segment order.
+ * tdt_voxelize_stroke needs no bound tree (depth 1..10) and returns the covered voxels {x, y, z, material + 1}, Morton-sorted
+ * and unique, by tdt_octree_extract's rules (voxels_xyzm == NULL only counts; capacity < the count: TDT_ERR_INVALID_VALUE with
+ * *n_voxels set and nothing written; a multi-device context answers from device_ids[0]).
+ * tdt_octree_edit_stroke is tdt_octree_edit_voxels(op, that list at the max_depth of slot 7) — same op table, install rule,
+ * *n_cells on a misfit, every replica of a multi-device context edited and a failure leaving all of them unchanged — without
+ * the list ever leaving the device.  tdt_octree_extract_stroke is V (the bound tree's voxels) intersected with that list, with
+ * V's own materials, by tdt_octree_extract_region's rules: the undo record to take before a CLEAR or PAINT stroke, and the copy
+ * tool.  An empty stroke (n_points == 0) is legal: the empty list, and the edit installs the compacted tree.
+ * Limits: the 8^3-voxel tiles inside the grid-clipped bounding boxes of the segments grown by the radius, summed over the
+ * stroke, and the covered (segment, voxel) pairs must each be <= 2^26 (TDT_REGION_BRUSH_CAP); n_points and n_segments <= 2^20.
+ * Errors, nothing written: NULL stroke, NULL arrays with a count above 0, n_points == 0 with segments, segments == NULL with
+ * n_segments != 0, a point index >= n_points, a coordinate, radius, material, shape, depth, op or pad out of range, a limit
+ * exceeded: TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound (edit and extract forms): TDT_ERR_INCOMPLETE.  Ordered after work queued
+ * on the context's stream; synchronous. */
+#define TDT_STROKE_COORD_MAX 8192
+#define TDT_STROKE_RADIUS_MAX 2048
+typedef struct tdt_stroke {
+  const int32_t *points;       /* n_points x {x, y, z}, voxel coordinates */
+  const uint32_t *segments;    /* n_segments x {i, j} point indices, or NULL: the polyline of the points */
+  const int32_t *materials;    /* per segment, material + 1, or NULL */
+  uint32_t n_points, n_segments;
+  int32_t shape;               /* TDT_SHAPE_SPHERE: round nib; TDT_SHAPE_BOX: cube nib of half-width radius */
+  int32_t radius;              /* 0..TDT_STROKE_RADIUS_MAX */
+  int32_t material;            /* used when materials == NULL: 0..253 */
+  int32_t pad;                 /* 0 */
+} tdt_stroke;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_stroke) == 48, "tdt_stroke is 48 bytes");
+#else
+_Static_assert(sizeof(tdt_stroke) == 48, "tdt_stroke is 48 bytes");
+#endif
+int tdt_voxelize_stroke(tdt_ctx *ctx, const tdt_stroke *stroke, int depth, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+int tdt_octree_edit_stroke(tdt_ctx *ctx, int op, const tdt_stroke *stroke, uint32_t *n_cells);
+int tdt_octree_extract_stroke(tdt_ctx *ctx, const tdt_stroke *stroke, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+
 /* ---- enclosed space ---------------------------------------------------------------------------------------------------------
  * Fill what is sealed off: the cavities of a tree, the inside of a watertight mesh.  Let G = [0, 2^depth)^3 and W, a subset of
  * G, a wall set.  Two EMPTY voxels (G \ W) are neighbours under connectivity 6 when they share a face, under connectivity 26

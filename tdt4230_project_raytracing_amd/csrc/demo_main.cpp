@@ -18,6 +18,7 @@
 //            [--adaptive TOL [--batch K]] [--preview] [--select-rect X0,Y0,X1,Y1 [--op ..] [--material K]]
 //            [--select-through X0,Y0,X1,Y1 | --lasso X,Y;X,Y;... [--window] [--only-material K] [--max-distance D]
 //             [--op paint|clear --material K] [--preview]]
+//            [--stroke X,Y;X,Y;... --brush sphere:R|box:R [--op set|fill|paint|clear] [--material K]]
 //            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -60,6 +61,10 @@
 //   voxels of its material only with --match-material) or through the air (empty: from the voxel in front of it), by face steps
 //   (6, the default), face / edge / corner steps of cost 1 (26) or the chamfer weights 3 / 4 / 5 (345), inside the --mask box
 //   only — is applied with `op` in material K (solid: default the voxel's own).  Prints the pick and the new cell count.
+// --stroke X,Y;X,Y;... --brush sphere:R|box:R [--op set|fill|paint|clear] [--material N]: the brush dragged over the pixels
+//   (Octree::stroke): every pixel is picked, each hit gives the grid voxel in front of the face (set, the default, / fill) or
+//   behind it (paint / clear), consecutive hits are joined by capsules (sphere) or swept cubes (box) of radius R, a miss breaks
+//   the stroke.  Applied after the --pick edits and before --select-rect.  Prints the points used and the new cell count.
 // --preview: with --box, --pick --brush or --pick --flood, the edit is not applied: the tree's voxels it would touch are
 //   extracted (tdt_octree_extract_region / tdt_octree_extract_connected) and drawn over the finished frame
 //   (ComputeShader::dispatch_voxel_ids with place 0, sample 0; Texture::overlay: fill 1, .6, 0, .35, edge 1, .6, 0, 1 of width 1).
@@ -152,12 +157,18 @@ int main(int argc, char **argv) {
   bool preview = false;
   std::vector<int32_t> select_rect;
   std::vector<int32_t> through_rect, lasso;                                              // --select-through / --lasso
+  std::vector<int32_t> stroke_px;                                                         // --stroke
   bool through_window = false, op_given = false;
   int only_material = -1;
   float max_distance = INFINITY;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
+    auto pixel_list = [](const char *t, std::vector<int32_t> &xy) {                        // X,Y;X,Y;... ; false: something else is left
+      int x, y, used;
+      while (std::sscanf(t, "%d,%d%n", &x, &y, &used) == 2) { xy.push_back(x); xy.push_back(y); t += used; if (*t == ';') t++; else break; }
+      return *t == 0;
+    };
     if (a == "--size") { if (std::sscanf(next(), "%dx%d", &W, &H) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; } }
     else if (a == "--spp") spp = std::atoi(next());
     else if (a == "--bounce") bounce = std::atoi(next());
@@ -268,10 +279,10 @@ int main(int argc, char **argv) {
     else if (a == "--select-rect") { int32_t v[4]; if (std::sscanf(next(), "%d,%d,%d,%d", v, v + 1, v + 2, v + 3) != 4) { std::fprintf(stderr, "--select-rect X0,Y0,X1,Y1\n"); return 2; } select_rect.assign(v, v + 4); }
     else if (a == "--select-through") { int32_t v[4]; if (std::sscanf(next(), "%d,%d,%d,%d", v, v + 1, v + 2, v + 3) != 4) { std::fprintf(stderr, "--select-through X0,Y0,X1,Y1\n"); return 2; } through_rect.assign(v, v + 4); }
     else if (a == "--lasso") {
-      const char *t = next();
-      int x, y, used;
-      while (std::sscanf(t, "%d,%d%n", &x, &y, &used) == 2) { lasso.push_back(x); lasso.push_back(y); t += used; if (*t == ';') t++; else break; }
-      if (*t || lasso.size() < 6 || lasso.size() > 2 * TDT_SCREEN_MAX_VERTICES) { std::fprintf(stderr, "--lasso X,Y;X,Y;... (3..256 vertices)\n"); return 2; }
+      if (!pixel_list(next(), lasso) || lasso.size() < 6 || lasso.size() > 2 * TDT_SCREEN_MAX_VERTICES) { std::fprintf(stderr, "--lasso X,Y;X,Y;... (3..256 vertices)\n"); return 2; }
+    }
+    else if (a == "--stroke") {
+      if (!pixel_list(next(), stroke_px) || stroke_px.empty() || stroke_px.size() > 2 * 4096) { std::fprintf(stderr, "--stroke X,Y;X,Y;... (1..4096 pixels)\n"); return 2; }
     }
     else if (a == "--window") through_window = true;
     else if (a == "--only-material") { only_material = std::atoi(next()); if (only_material < 0 || only_material > 253) { std::fprintf(stderr, "--only-material 0..253\n"); return 2; } }
@@ -283,6 +294,7 @@ int main(int argc, char **argv) {
   if (!through && (through_window || only_material >= 0 || max_distance != INFINITY)) { std::fprintf(stderr, "--window, --only-material and --max-distance need --select-through or --lasso\n"); return 2; }
   if (through && op_given && op != TDT_REGION_PAINT && op != TDT_REGION_CLEAR) { std::fprintf(stderr, "--select-through / --lasso take --op paint|clear\n"); return 2; }
   if (through && op_given && preview) { std::fprintf(stderr, "--select-through / --lasso: --preview shows the list, --op applies it; not both\n"); return 2; }
+  if (!stroke_px.empty() && (brush_shape < 0 || pick_x >= 0 || preview)) { std::fprintf(stderr, "--stroke needs --brush sphere:R|box:R and does not combine with --pick or --preview\n"); return 2; }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
   if (adaptive >= 0.0f && (temporal > 0 || upsample > 0)) { std::fprintf(stderr, "--adaptive does not combine with --temporal or --upsample\n"); return 2; }
   if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
@@ -481,6 +493,16 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g iterations %d point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d edit %s\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.iterations, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1],
                   h.normal[2], h.fresh_record, edited ? (place ? "place" : "remove") : "none");
+    }
+    if (!stroke_px.empty()) {                                                             // NEW: a brush dragged over the pixels
+      std::vector<std::array<int32_t, 2>> px(stroke_px.size() / 2);
+      for (size_t k = 0; k < px.size(); k++) px[k] = {stroke_px[2 * k], stroke_px[2 * k + 1]};
+      std::vector<int32_t> pts;
+      static const char *op_names[4] = {"set", "fill", "paint", "clear"};
+      const uint32_t cells = octree.stroke(raytrace_program, px, brush_shape, brush_size, op, material, &pts);
+      std::printf("stroke pixels %zu points %zu:", px.size(), pts.size() / 3);
+      for (size_t k = 0; k < pts.size(); k += 3) std::printf(" %d,%d,%d", pts[k], pts[k + 1], pts[k + 2]);
+      std::printf(" op %s cells %u\n", op_names[op], cells);
     }
     if (!select_rect.empty()) {                                                           // NEW: marquee: `op` over what the rectangle shows
       const Texture ids = Texture::new_2d(ctx, camera.render_texture.width(), camera.render_texture.height(), false);

@@ -14,7 +14,8 @@
 // variance into the masks of tdt_dispatch_accumulate_masked; tdt_select.hip: screen-space selection, where the two halves meet:
 // voxel-id images, overlays of a voxel list and the voxels of a rectangle; tdt_screen.hip: through-selection, the tree's voxels
 // projected into a view and tested against a rectangle, a polygon or a mask; tdt_smooth.hip: voxel smoothing, a ball-density
-// threshold filter and the density field, on the bit volume too.  The host helpers
+// threshold filter and the density field, on the bit volume too; tdt_stroke.hip: stroke brushes, capsule and swept-box polylines
+// voxelised like a mesh.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
@@ -292,6 +293,9 @@ struct VoxelSource {
 };
 // tdt_octree_edit_voxels(op, the source's list) on every replica (the caller has checked op)
 int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells);
+// the voxels of device_ids[0]'s tree that the source's list (at the tree's max_depth) holds, with the tree's materials, into host
+// memory by tdt_octree_extract_region's rules (tdt_stroke.hip)
+int region_intersect_source(tdt_ctx *ctx, VoxelSource &src, int32_t *host_out, size_t capacity, size_t *n_out);
 // the source's list on device_ids[0] (depth: what its run() is given; no tree need be bound) into host memory, by
 // tdt_octree_extract's rules
 inline int region_extract_source(tdt_ctx *ctx, VoxelSource &src, int depth, int32_t *host_out, size_t capacity, size_t *n_out) {

@@ -288,6 +288,12 @@ int region_edit_source(tdt_ctx *ctx, int op, VoxelSource &src, uint32_t *n_cells
   return region_edit(ctx, R, n_cells);
 }
 
+int region_intersect_source(tdt_ctx *ctx, VoxelSource &src, int32_t *host_out, size_t capacity, size_t *n_out) {
+  Request R;
+  R.op = kOpIntersect; R.list = true; R.source = &src;
+  return region_one(ctx, first_member(ctx), R, nullptr, host_out, capacity, n_out);
+}
+
 int region_extract_selected(tdt_ctx *ctx, VoxelSelect &sel, int32_t *host_out, size_t capacity, size_t *n_out) {
   Request R;
   R.op = kOpIntersect; R.select = &sel;

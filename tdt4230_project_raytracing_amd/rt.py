@@ -265,6 +265,70 @@ def _mesh(vertices, triangles, materials, material):
     return mesh, (v, t, m)
 
 
+# stroke brushes (include/tdt_rt.h): the limits of a stroke's points and radius, and struct tdt_stroke
+STROKE_COORD_MAX, STROKE_RADIUS_MAX = 8192, 2048
+
+
+class Stroke(ctypes.Structure):
+    """struct tdt_stroke: points n_points x {x, y, z} int32 voxel coordinates, segments n_segments x {i, j} uint32 point indices or
+    NULL (the polyline of the points), materials per segment (material + 1) int32 or NULL (then `material` 0..253 for every
+    segment), shape SHAPE_SPHERE (round nib) / SHAPE_BOX (cube nib of half-width radius), radius 0..STROKE_RADIUS_MAX, pad 0."""
+    _fields_ = [("points", ctypes.c_void_p), ("segments", ctypes.c_void_p), ("materials", ctypes.c_void_p),
+                ("n_points", ctypes.c_uint32), ("n_segments", ctypes.c_uint32), ("shape", ctypes.c_int32), ("radius", ctypes.c_int32),
+                ("material", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Stroke) == 48
+
+
+def _stroke(points, radius, segments=None, materials=None, material=0, shape=SHAPE_SPHERE, depth=None, op=None):
+    """(struct tdt_stroke, the arrays it points into) from (n, 3) voxel coordinates, the nib's radius, None (the polyline of the
+    points) or (m, 2) point indices, None or per-segment material + 1, the material used without them, and the nib's shape; depth
+    / op: those of the call, when it takes them.  What ctypes would wrap or truncate silently is refused, and every range the
+    header lists under its errors is checked here as the library checks it (ValueError), so a bad stroke fails before any
+    device work; the two 2^26 limits, which depend on the grid, stay the library's."""
+    p = _exact_ints(points, np.int32, "points")
+    if p.size == 0:
+        p = p.reshape(0, 3)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points must be an (n, 3) array")
+    g = None
+    if segments is not None:
+        g = _exact_ints(segments, np.uint32, "segments")
+        if g.size == 0:
+            g = g.reshape(0, 2)
+        if g.ndim != 2 or g.shape[1] != 2:
+            raise ValueError("segments must be an (m, 2) array")
+    n_seg = len(g) if g is not None else (len(p) - 1 if len(p) > 1 else len(p))
+    m = None
+    if materials is not None:
+        m = _exact_ints(materials, np.int32, "materials").reshape(-1)
+        if len(m) != n_seg:
+            raise ValueError(f"{len(m)} materials for {n_seg} segments")
+    for name, v, lo, hi in (("radius", radius, 0, STROKE_RADIUS_MAX), ("material", material, 0, 253), ("shape", shape, SHAPE_BOX, SHAPE_SPHERE),
+                            ("depth", depth, 1, 10), ("op", op, REGION_SET, REGION_CLEAR)):
+        if v is None and name in ("depth", "op"):
+            continue
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, not {v!r}")
+        if not lo <= int(v) <= hi and not (name == "material" and m is not None and -2**31 <= int(v) <= 2**31 - 1):
+            raise ValueError(f"{name} must be {lo}..{hi}, not {v!r}")
+    if len(p) > 1 << 20 or n_seg > 1 << 20:
+        raise ValueError("a stroke takes at most 2^20 points and 2^20 segments")
+    if p.size and int(np.abs(p.astype(np.int64)).max()) > STROKE_COORD_MAX:
+        raise ValueError(f"a point coordinate beyond +-{STROKE_COORD_MAX}")
+    if g is not None and g.size and int(g.max()) >= len(p):
+        raise ValueError(f"a segment names point {int(g.max())} of {len(p)}")
+    if m is not None and m.size and not (1 <= int(m.min()) and int(m.max()) <= 254):
+        raise ValueError("materials (material + 1) must be 1..254")
+    n_list = len(g) if g is not None else 0
+    if g is not None and len(g) == 0:
+        g = np.zeros((1, 2), np.uint32)                # an explicit empty list still needs an address: NULL means the polyline
+    stroke = Stroke(p.ctypes.data if len(p) else None, g.ctypes.data if g is not None else None,
+                    m.ctypes.data if m is not None and len(m) else None, len(p), n_list, int(shape), int(radius), int(material), 0)
+    return stroke, (p, g, m)
+
+
 class Adapt(ctypes.Structure):
     """struct tdt_adapt: the relative error of the mean luminance at which a pixel stops, the brightness floor that error is
     measured against, and the fewest / most samples a pixel receives."""
@@ -453,6 +517,9 @@ SYMBOLS = [
     ("tdt_octree_extract_morph", _I, [_P, ctypes.POINTER(Morph), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_voxelize_triangles", _I, [_P, ctypes.POINTER(Mesh), _I, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_edit_triangles", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_voxelize_stroke", _I, [_P, ctypes.POINTER(Stroke), _I, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_stroke", _I, [_P, _I, ctypes.POINTER(Stroke), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_octree_extract_stroke", _I, [_P, ctypes.POINTER(Stroke), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_extract_enclosed", _I, [_P, ctypes.POINTER(Fill), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_fill_enclosed", _I, [_P, ctypes.POINTER(Fill), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_voxelize_triangles_solid", _I, [_P, ctypes.POINTER(Mesh), _I, ctypes.POINTER(Fill), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
@@ -780,6 +847,34 @@ class Context:
         self._check_edit(lib().tdt_octree_edit_triangles(self.h, int(op), ctypes.byref(mesh), ctypes.byref(n)), n)
         del keep
         return int(n.value)
+
+    def voxelize_stroke(self, points, radius, depth, segments=None, materials=None, material=0, shape=SHAPE_SPHERE):
+        """tdt_voxelize_stroke: the voxels of the grid [0, 2^depth)^3 within `radius` of the stroke's segments — Euclidean for
+        SHAPE_SPHERE, Chebyshev for SHAPE_BOX — as an (n, 4) int32 list {x, y, z, material + 1}, Morton-sorted; points (n, 3)
+        voxel coordinates on or off the grid, segments None (the polyline of the points; one point: a dab) or (m, 2) point
+        indices, materials None or material + 1 per segment (the highest covering segment wins).  Needs no bound tree.  Counts
+        first, fills second: two sweeps."""
+        stroke, keep = _stroke(points, radius, segments, materials, material, shape, depth=depth)
+        out = self._list(lib().tdt_voxelize_stroke, ctypes.byref(stroke), int(depth))
+        del keep
+        return out
+
+    def octree_edit_stroke(self, op, points, radius, segments=None, materials=None, material=0, shape=SHAPE_SPHERE):
+        """tdt_octree_edit_stroke: octree_edit_voxels(op, voxelize_stroke(..., max_depth of slot 7)) without the list leaving the
+        device; returns the canonical tree's cell count."""
+        stroke, keep = _stroke(points, radius, segments, materials, material, shape, op=op)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_stroke(self.h, int(op), ctypes.byref(stroke), ctypes.byref(n)), n)
+        del keep
+        return int(n.value)
+
+    def octree_extract_stroke(self, points, radius, segments=None, shape=SHAPE_SPHERE):
+        """tdt_octree_extract_stroke: the bound tree's voxels the stroke covers, with the tree's materials, (n, 4) int32,
+        Morton-sorted: the undo record of a CLEAR or PAINT stroke (octree_edit_voxels(REGION_SET, it) puts them back)."""
+        stroke, keep = _stroke(points, radius, segments, None, 0, shape)
+        out = self._list(lib().tdt_octree_extract_stroke, ctypes.byref(stroke))
+        del keep
+        return out
 
     @staticmethod
     def _fill(connectivity, material):
@@ -1876,6 +1971,33 @@ class Renderer:
     def pick(self, xy, sample=0, return_rays=False):
         """ComputeShader.pick with this renderer's camera: what is under each pixel."""
         return self.shader.pick(xy, sample, return_rays)
+
+    def stroke(self, pixels, radius, op, material=0, shape=SHAPE_SPHERE, sample=0):
+        """A brush dragged over the pixels (n, 2) of this renderer's camera: one batched pick of all of them, each hit turned into
+        the grid voxel in front of the face (REGION_SET / REGION_FILL) or behind it (REGION_PAINT / REGION_CLEAR)
+        (host.pick_grid_voxel), consecutive hits joined by segments, a miss breaking the stroke and a hit between two misses
+        left as a dab; then Context.octree_edit_stroke of those points and segments.  Returns (points, cells): the (k, 3) int32
+        points used and the canonical tree's cell count.  No hit at all: the empty stroke, which installs the compacted tree."""
+        from . import host
+        hits = self.pick(pixels, sample)
+        place = 1 if op in (REGION_SET, REGION_FILL) else 0
+        uniforms = (self.vbos[6].read(np.float32), self.vbos[7].read(np.int32))   # slots 6 / 7 as the device holds them
+        points, segments, prev = [], [], None
+        for h in hits:
+            try:
+                v = host.pick_grid_voxel(h, uniforms, place)
+            except ValueError:                             # a miss, a stale record or a point outside the octree
+                prev = None
+                continue
+            points.append(v)
+            if prev is not None:
+                segments.append((prev, len(points) - 1))
+            prev = len(points) - 1
+        joined = {i for g in segments for i in g}
+        segments += [(i, i) for i in range(len(points)) if i not in joined]
+        pts = np.asarray(points, np.int32).reshape(-1, 3)
+        seg = np.asarray(segments, np.uint32).reshape(-1, 2)
+        return pts, self.ctx.octree_edit_stroke(op, pts, radius, segments=seg, material=material, shape=shape)
 
     def compact(self):
         """Context.octree_compact on this renderer's scene: the number of cells the canonical tree takes."""
