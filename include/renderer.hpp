@@ -445,6 +445,72 @@ class Octree {
     if (points_xyz) *points_xyz = pts;
     return stroke(raytracer.context(), op, pts, shape, radius, material, seg, false);
   }
+  // NEW: the tree's exposed faces labelled into coplanar face regions (tdt_octree_face_regions): the table, numbered in the order
+  // of each region's first face; faces / labels (may be null) receive the 1 x 1 quads of extract_surface(merge = 0) under the same
+  // mask and the region of each.  Labels once where it can, as components() does: the arrays are sized by `capacity`, and only a
+  // tree with more faces or regions is labelled again, into arrays of the sizes the first call reported.
+  std::vector<tdt_face_region> face_regions(const Context &ctx, int connectivity, int match, const std::vector<tdt_region> &mask = {},
+                                            std::vector<tdt_quad> *faces = nullptr, std::vector<uint32_t> *labels = nullptr,
+                                            size_t capacity = 4096) const {
+    size_t nf = 0, nr = 0;
+    std::vector<tdt_face_region> table(capacity ? capacity : 1);
+    size_t fcap = (faces || labels) ? (capacity ? capacity : 1) : 0;
+    auto run = [&]() {
+      if (faces) faces->assign(fcap, tdt_quad{});
+      if (labels) labels->assign(fcap, 0u);
+      return tdt_octree_face_regions(ctx.raw(), connectivity, match, mask.empty() ? nullptr : mask.data(), mask.size(),
+                                     faces ? faces->data() : nullptr, labels ? labels->data() : nullptr, fcap, &nf, table.data(), table.size(), &nr);
+    };
+    int rc = run();
+    if (rc == TDT_ERR_INVALID_VALUE && (nr > table.size() || (fcap && nf > fcap))) {
+      table.resize(nr);
+      if (fcap) fcap = nf;
+      rc = run();
+    }
+    ctx.check(rc);
+    table.resize(nr);
+    if (faces) faces->resize(nf);
+    if (labels) labels->resize(nf);
+    return table;
+  }
+  // NEW: the face regions under the seeds {x, y, z, f} swept by the signed distance of `opt` (tdt_octree_extract_faces), as a
+  // voxel list {x, y, z, material + 1} in Morton order — TDT_FACES_COLUMNS: the columns themselves (the preview; what
+  // Texture::overlay takes); TDT_FACES_TREE: the tree's voxels they cover, with the tree's materials (the undo record of a push,
+  // a paint or a SET pull: edit_voxels(TDT_REGION_SET, it) puts them back)
+  std::vector<int32_t> extract_faces(const Context &ctx, const tdt_faces &opt, const std::vector<int32_t> &seeds_xyzf, int what = TDT_FACES_COLUMNS,
+                                     const std::vector<tdt_region> &mask = {}) const {
+    const int32_t *s = seeds_xyzf.empty() ? nullptr : seeds_xyzf.data();
+    const tdt_region *r = mask.empty() ? nullptr : mask.data();
+    size_t n = 0;
+    ctx.check(tdt_octree_extract_faces(ctx.raw(), &opt, s, seeds_xyzf.size() / 4, r, mask.size(), what, nullptr, 0, &n));
+    std::vector<int32_t> v(4 * n);
+    if (n) ctx.check(tdt_octree_extract_faces(ctx.raw(), &opt, s, seeds_xyzf.size() / 4, r, mask.size(), what, v.data(), n, &n));
+    return v;
+  }
+  // NEW: op over those columns without the list leaving the device (tdt_octree_edit_faces): pull (TDT_REGION_FILL / SET, distance
+  // > 0), push (TDT_REGION_CLEAR, distance < 0), paint a face (TDT_REGION_PAINT, distance -1).  Returns the number of cells.
+  uint32_t extrude(const Context &ctx, int op, const tdt_faces &opt, const std::vector<int32_t> &seeds_xyzf,
+                   const std::vector<tdt_region> &mask = {}) const {
+    uint32_t n = 0;
+    ctx.check(tdt_octree_edit_faces(ctx.raw(), op, &opt, seeds_xyzf.empty() ? nullptr : seeds_xyzf.data(), seeds_xyzf.size() / 4,
+                                    mask.empty() ? nullptr : mask.data(), mask.size(), &n));
+    return n;
+  }
+  // NEW: the face under the cursor: pick pixel (x, y) of the raytracer's camera (sample 0), turn the hit into the seed {x, y, z, f}
+  // (tdt_pick_face) and extrude() the face region that holds it.  Returns whether an edit ran (a miss, a stale record or a hit
+  // outside the octree: none); seed (may be null) receives the four ints, *n_cells the size.
+  bool extrude(const ComputeShader &raytracer, int x, int y, int op, const tdt_faces &opt, const std::vector<tdt_region> &mask = {},
+               int32_t *seed = nullptr, uint32_t *n_cells = nullptr) const {
+    const tdt_ray_hit h = raytracer.pick({{{x, y}}}, 0)[0];
+    const float floats[7] = {min_point_[0], min_point_[1], min_point_[2], 0.0f, scale_, 1.0f / scale_, 1.0f / (float)cell_count_};   // :44-50
+    const int32_t ints[3] = {max_depth_, max_traversal_iter_, cell_count_};
+    int32_t s[4];
+    if (tdt_pick_face(&h, floats, ints, s) != 0) return false;
+    if (seed) for (int a = 0; a < 4; a++) seed[a] = s[a];
+    const uint32_t n = extrude(raytracer.context(), op, opt, std::vector<int32_t>(s, s + 4), mask);
+    if (n_cells) *n_cells = n;
+    return true;
+  }
   // NEW: connected components of the bound tree (tdt_octree_components): the table, numbered in the Morton order of each
   // component's first voxel; labels (may be null) receive the component of every voxel of extract's list.  A count query costs
   // a whole labelling, so this labels once: labels sized by a walk (tdt_octree_extract's count), the table by `capacity`; only a

@@ -248,6 +248,12 @@ int tdt_pick_edit_delta(const tdt_ray_hit *hit, const float octree_floats[7], co
  * in front of the hit face (place = 1) or just behind it (place = 0).  How a click becomes a brush centre for
  * tdt_octree_edit_region.  Same errors as tdt_pick_edit_delta. */
 int tdt_pick_grid_voxel(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int place, int32_t out[3]);
+/* The face under the cursor as a seed of the face tools (tdt_octree_edit_faces, include/tdt_rt.h): out[0..2] =
+ * tdt_pick_grid_voxel(place = 0), the voxel behind the hit face; out[3] = the face index 0..5 (-x, +x, -y, +y, -z, +z) of the hit
+ * normal, which is oriented against the ray and axis-aligned: the component with |n| == 1 gives the axis a, its sign s, and
+ * out[3] = 2 a + s.  Same errors as tdt_pick_grid_voxel, and TDT_ERR_INVALID_VALUE for a normal that is not a signed unit axis
+ * vector. */
+int tdt_pick_face(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -1119,6 +1119,88 @@ _Static_assert(sizeof(tdt_quad) == 32, "tdt_quad is 32 bytes");
 int tdt_octree_extract_surface(tdt_ctx *ctx, const tdt_surface *opt, const tdt_region *regions, size_t n_regions, tdt_quad *quads,
                                size_t capacity, size_t *n_quads);
 
+/* ---- face tools -------------------------------------------------------------------------------------------------------------
+ * Act on a FACE of the model: the connected coplanar patch under the cursor is pulled out, pushed in or painted.  V, G, the face
+ * numbering f = 0..5, a = f >> 1, s = f & 1, u = (a + 1) % 3, v = (a + 2) % 3, w = p[a] and "voxel p has an EXPOSED face f" are
+ * those of the surface extraction above; n_f is the outward unit normal of direction f.  All arithmetic is in integers and every
+ * result is canonical, so results compare bit for bit.
+ *   Face list: F = the exposed faces in the order of tdt_octree_extract_surface with merge = 0, by_material = 1 — by face, then
+ *     w, then u, then v — each carrying its voxel's material + 1.  With n_regions > 0 only the faces of voxels inside the union of
+ *     the shapes are in F: the mask CONFINES a region (geodesic's convention); exposure is always evaluated on the whole tree.
+ *   Adjacency: two faces of F with the same f and the same w are adjacent under connectivity 4 when they differ by 1 in exactly
+ *     one of u, v; under connectivity 8 when they differ by at most 1 in each of u, v and are not equal.  Faces of different
+ *     direction are never adjacent — not even the -x face at w and the +x face at w - 1, which lie in one geometric plane — and
+ *     nothing wraps around the grid.  With TDT_MATCH_MATERIAL only faces of equal carried material are adjacent, with
+ *     TDT_MATCH_ANY any two.
+ *   Face region: a maximal connected set; regions are numbered 0, 1, .. in the order of their first face in F.
+ *   Seeds: n_seeds quadruples {x, y, z, f}; a seed selects the region that holds face f of voxel (x, y, z).  A seed off the grid,
+ *     on an empty voxel, on a face that is not exposed or on a face outside the mask selects nothing; duplicates are allowed;
+ *     f outside 0..5 is an error.
+ *   Columns: for a selected face (p, f) and the signed `distance` d, |d| <= TDT_FACES_DISTANCE_MAX: d > 0: the voxels p + k n_f,
+ *     k = 1..d; d < 0: the voxels p - k n_f, k = 0..|d| - 1 (the owner and what lies behind it); d = 0: nothing.  Columns are
+ *     clipped to G.  With block = 1 a column ends early: for d > 0 before its first voxel that is in V (it stops at an obstacle),
+ *     for d < 0 before its first voxel that is NOT in V (it carves only the contiguous solid run).  With block = 0 it runs its
+ *     full clipped length.
+ *   Material: a column voxel carries material + 1 for material 0..253; with material = -1 its face's carried material, so an
+ *     extrusion continues the wall's colours.
+ *   The column list: the (voxel, material) pairs of all selected faces, taken in the order of F, then k, reduced by the
+ *     builder's rule that of duplicates the last one wins; Morton-sorted and unique.  Two columns of one region never overlap;
+ *     columns of different seeded regions can (opposite walls of a slot pulled towards each other, one direction at different
+ *     w), and the last-wins rule decides.
+ *   Stories: pull = TDT_REGION_FILL or SET with d > 0; push = TDT_REGION_CLEAR with d < 0; paint a face = TDT_REGION_PAINT with
+ *     d = -1; "until it hits something" = block = 1 with a large |d|.
+ * tdt_octree_face_regions returns F as 1 x 1 tdt_quads — byte for byte what tdt_octree_extract_surface with merge = 0,
+ * by_material = 1 and the same mask returns — the label of each face and the region table, by tdt_octree_components' rules: a
+ * NULL array only counts; a capacity below its count: TDT_ERR_INVALID_VALUE with the counts set and nothing written.  It only
+ * reads; a multi-device context answers from device_ids[0].
+ * tdt_octree_extract_faces lists, by tdt_octree_extract's rules, TDT_FACES_COLUMNS: the column list (the preview, and what
+ * tdt_image_overlay takes); TDT_FACES_TREE: V intersected with the column list, with V's own materials (the undo record before a
+ * push, a paint or a SET pull).
+ * tdt_octree_edit_faces is tdt_octree_edit_voxels(op, the column list) without the list leaving the device: all four ops, the
+ * install rule, *n_cells on a misfit, every replica edited and a failure leaving all replicas unchanged exactly as for
+ * tdt_octree_edit_stroke.  With n_seeds == 0 or distance == 0 it installs the compacted tree.
+ * Limits: |V|, the faces of any one direction and the (face, voxel) pairs of the columns each <= 2^26 (TDT_REGION_BRUSH_CAP);
+ * n_seeds <= 2^20.
+ * Errors, nothing written: a NULL struct, NULL seeds or regions with a count above 0, connectivity other than 4 or 8, match,
+ * block or what out of range, distance or material out of range, non-zero pad, a seed f outside 0..5, a bad shape or op, a LEAF
+ * value >= 254, a limit exceeded, a result larger than the buffer: TDT_ERR_INVALID_VALUE; slot 0 or 7 unbound:
+ * TDT_ERR_INCOMPLETE.  Ordered after work queued on the context's stream; synchronous. */
+#define TDT_FACES_DISTANCE_MAX 1023
+enum { TDT_FACES_COLUMNS = 0, TDT_FACES_TREE = 1 };
+typedef struct tdt_faces {
+  int32_t connectivity;        /* 4 or 8 */
+  int32_t match;               /* TDT_MATCH_ANY / TDT_MATCH_MATERIAL */
+  int32_t distance;            /* -1023..1023 */
+  int32_t block;               /* 0 / 1 */
+  int32_t material;            /* -1 inherit, 0..253 */
+  int32_t pad;                 /* 0 */
+} tdt_faces;
+typedef struct tdt_face_region {
+  uint32_t first;              /* index in F of its first face */
+  uint32_t faces;              /* its size */
+  int32_t face, w;             /* direction and the voxels' own coordinate along the axis */
+  int32_t lo[2], hi[2];        /* (u, v) bounding box, inclusive */
+  int32_t material;            /* carried material of its first face */
+  int32_t pad;
+} tdt_face_region;
+#ifdef __cplusplus
+static_assert(sizeof(tdt_faces) == 24, "tdt_faces is 24 bytes");
+static_assert(sizeof(tdt_face_region) == 40, "tdt_face_region is 40 bytes");
+#else
+_Static_assert(sizeof(tdt_faces) == 24, "tdt_faces is 24 bytes");
+_Static_assert(sizeof(tdt_face_region) == 40, "tdt_face_region is 40 bytes");
+#endif
+int tdt_octree_face_regions(tdt_ctx *ctx, int connectivity, int match, const tdt_region *regions, size_t n_regions, tdt_quad *faces,
+                            uint32_t *labels, size_t faces_capacity, size_t *n_faces, tdt_face_region *table, size_t capacity,
+                            size_t *n_face_regions);
+int tdt_octree_extract_faces(tdt_ctx *ctx, const tdt_faces *faces, const int32_t *seeds_xyzf, size_t n_seeds, const tdt_region *regions,
+                             size_t n_regions, int what, int32_t *voxels_xyzm, size_t capacity, size_t *n_voxels);
+int tdt_octree_edit_faces(tdt_ctx *ctx, int op, const tdt_faces *faces, const int32_t *seeds_xyzf, size_t n_seeds,
+                          const tdt_region *regions, size_t n_regions, uint32_t *n_cells);
+/* the labelling's hook stage with (on = 1, the default) or without (0) the in-wave pre-merge of runs along v; both label alike.
+ * Measurement only (tools/faces_time.py). */
+int tdt_debug_faces_premerge(tdt_ctx *ctx, int on);
+
 /* ---- exact Euclidean distance ----------------------------------------------------------------------------------------------
  * Round grow, shrink, open, close and hollow, and a distance field.  V = what tdt_octree_extract returns, over the grid
  * G = [0, N)^3, N = 2^max_depth.  For a voxel q of G and a set S, d2(q, S) = min over p in S of |q - p|^2, in integers; nothing

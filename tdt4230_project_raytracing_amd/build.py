@@ -47,9 +47,9 @@ DEVICE_UNITS = ("tdt_rt.hip", "tdt_multi.hip", "tdt_build.hip", "tdt_edit.hip", 
                 "tdt_region.hip", "tdt_connect.hip", "tdt_morph.hip", "tdt_mesh.hip", "tdt_fill.hip", "tdt_surface.hip",
                 "tdt_distance.hip", "tdt_bitvol.hip", "tdt_xform.hip", "tdt_geodesic.hip", "tdt_voxlist.hip", "tdt_denoise.hip",
                 "tdt_reproject.hip", "tdt_variance.hip", "tdt_upsample.hip", "tdt_adaptive.hip", "tdt_select.hip",
-                "tdt_screen.hip", "tdt_smooth.hip", "tdt_stroke.hip")
+                "tdt_screen.hip", "tdt_smooth.hip", "tdt_stroke.hip", "tdt_faces.hip")
 DEVICE_HEADERS = ("trace_device.hpp", "trace_params.h", "tdt_internal.hpp", "device_scan.hpp", "region_device.hpp", "bitvol_device.hpp",
-                  "query_device.hpp", "denoise_device.hpp", "reproject_device.hpp")
+                  "query_device.hpp", "denoise_device.hpp", "reproject_device.hpp", "surface_device.hpp", "unionfind_device.hpp")
 
 
 def build_device(force=False, extra_flags=(), out=None):

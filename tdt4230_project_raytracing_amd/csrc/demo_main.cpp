@@ -19,6 +19,7 @@
 //            [--select-through X0,Y0,X1,Y1 | --lasso X,Y;X,Y;... [--window] [--only-material K] [--max-distance D]
 //             [--op paint|clear --material K] [--preview]]
 //            [--stroke X,Y;X,Y;... --brush sphere:R|box:R [--op set|fill|paint|clear] [--material K]]
+//            [--pick X,Y --extrude D [--conn 4|8] [--match-material] [--block 0|1] [--op ..] [--material K] [--mask ..]]
 //            [--out frame.pfm] [--png frame.png]
 //
 // Defaults are the reference's: 1280x720 window (main.rs:26), camera.ron's spp 4 / max_bounce 6 / controller rates.
@@ -65,6 +66,12 @@
 //   (Octree::stroke): every pixel is picked, each hit gives the grid voxel in front of the face (set, the default, / fill) or
 //   behind it (paint / clear), consecutive hits are joined by capsules (sphere) or swept cubes (box) of radius R, a miss breaks
 //   the stroke.  Applied after the --pick edits and before --select-rect.  Prints the points used and the new cell count.
+// --pick X,Y --extrude D [--conn 4|8] [--match-material] [--block 0|1] [--op set|fill|paint|clear] [--material K] [--mask x0,y0,z0,x1,y1,z1]:
+//   the face tools (Octree::extrude): the connected coplanar patch of exposed faces under the pixel (4- or 8-connected inside its
+//   plane, of any material or with --match-material of the picked face's only, confined to the --mask box) swept by D voxels along
+//   its normal: D > 0 pulls (--op fill or set), D < 0 pushes (--op clear) or, with -1, paints (--op paint); --block 1 stops a pull
+//   at an obstacle and a push at the air behind; new voxels get --material or continue the wall's own.  Prints the seed and the
+//   new cell count.
 // --preview: with --box, --pick --brush or --pick --flood, the edit is not applied: the tree's voxels it would touch are
 //   extracted (tdt_octree_extract_region / tdt_octree_extract_connected) and drawn over the finished frame
 //   (ComputeShader::dispatch_voxel_ids with place 0, sample 0; Texture::overlay: fill 1, .6, 0, .35, edge 1, .6, 0, 1 of width 1).
@@ -158,6 +165,8 @@ int main(int argc, char **argv) {
   std::vector<int32_t> select_rect;
   std::vector<int32_t> through_rect, lasso;                                              // --select-through / --lasso
   std::vector<int32_t> stroke_px;                                                         // --stroke
+  int extrude = 0, extrude_block = 0;                                                     // --extrude D, --block 0|1
+  bool extrude_given = false, conn_given = false;
   bool through_window = false, op_given = false;
   int only_material = -1;
   float max_distance = INFINITY;
@@ -265,7 +274,9 @@ int main(int argc, char **argv) {
       else { std::fprintf(stderr, "--smooth-mode both|add|remove\n"); return 2; }
     }
     else if (a == "--border") { round_border = std::atoi(next()); if (round_border != 0 && round_border != 1) { std::fprintf(stderr, "--border 0|1\n"); return 2; } }
-    else if (a == "--conn") { morph_conn = std::atoi(next()); if (morph_conn != 6 && morph_conn != 26) { std::fprintf(stderr, "--conn 6|26\n"); return 2; } }
+    else if (a == "--conn") { morph_conn = std::atoi(next()); conn_given = true; if (morph_conn != 6 && morph_conn != 26 && morph_conn != 4 && morph_conn != 8) { std::fprintf(stderr, "--conn 6|26 (with --extrude: 4|8)\n"); return 2; } }
+    else if (a == "--extrude") { extrude = std::atoi(next()); extrude_given = true; if (extrude < -TDT_FACES_DISTANCE_MAX || extrude > TDT_FACES_DISTANCE_MAX) { std::fprintf(stderr, "--extrude D, -1023..1023\n"); return 2; } }
+    else if (a == "--block") { extrude_block = std::atoi(next()); if (extrude_block != 0 && extrude_block != 1) { std::fprintf(stderr, "--block 0|1\n"); return 2; } }
     else if (a == "--mask") { int32_t v[6]; if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5) != 6) { std::fprintf(stderr, "--mask x0,y0,z0,x1,y1,z1\n"); return 2; } mask.assign(v, v + 6); }
     else if (a == "--cells") { pad_cells = std::atoll(next()); if (pad_cells < 0) { std::fprintf(stderr, "--cells N\n"); return 2; } }
     else if (a == "--mesh") mesh_path = next();
@@ -295,6 +306,10 @@ int main(int argc, char **argv) {
   if (through && op_given && op != TDT_REGION_PAINT && op != TDT_REGION_CLEAR) { std::fprintf(stderr, "--select-through / --lasso take --op paint|clear\n"); return 2; }
   if (through && op_given && preview) { std::fprintf(stderr, "--select-through / --lasso: --preview shows the list, --op applies it; not both\n"); return 2; }
   if (!stroke_px.empty() && (brush_shape < 0 || pick_x >= 0 || preview)) { std::fprintf(stderr, "--stroke needs --brush sphere:R|box:R and does not combine with --pick or --preview\n"); return 2; }
+  if (extrude_given && (pick_x < 0 || reach_cost >= 0 || flood_op >= 0 || brush_shape >= 0 || preview)) { std::fprintf(stderr, "--extrude needs --pick X,Y and does not combine with --reach, --flood, --brush or --preview\n"); return 2; }
+  if (!conn_given && extrude_given) morph_conn = 4;
+  if (extrude_given != (morph_conn == 4 || morph_conn == 8)) { std::fprintf(stderr, "--conn 6|26 (with --extrude: 4|8)\n"); return 2; }
+  if (extrude_block && !extrude_given) { std::fprintf(stderr, "--block needs --extrude D\n"); return 2; }
   if (variance > 0.0f && denoise == 0) { std::fprintf(stderr, "--variance needs --denoise N\n"); return 2; }
   if (adaptive >= 0.0f && (temporal > 0 || upsample > 0)) { std::fprintf(stderr, "--adaptive does not combine with --temporal or --upsample\n"); return 2; }
   if (upsample > 0 && temporal > 0) { std::fprintf(stderr, "--upsample does not combine with --temporal\n"); return 2; }
@@ -471,6 +486,23 @@ int main(int argc, char **argv) {
       std::printf("pick %d,%d status %d material %u t %.9g point %.9g,%.9g,%.9g normal %g,%g,%g fresh %d reach %d steps %d medium %s %s cells %u\n",
                   pick_x, pick_y, h.status, h.material, h.t, h.point[0], h.point[1], h.point[2], h.normal[0], h.normal[1], h.normal[2], h.fresh_record,
                   reach_cost, reach_steps, reach_medium == TDT_MEDIUM_SOLID ? "solid" : "empty", edited ? "applied" : "none", cells);
+    } else if (pick_x >= 0 && extrude_given) {                                           // the face under the pixel pulled, pushed or painted
+      tdt_faces f{};
+      f.connectivity = morph_conn; f.match = reach_match ? TDT_MATCH_MATERIAL : TDT_MATCH_ANY; f.distance = extrude; f.block = extrude_block;
+      f.material = material_given ? material : -1;
+      std::vector<tdt_region> regions;
+      if (!mask.empty()) {
+        tdt_region r{};
+        r.shape = TDT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) { r.a[a] = mask[a]; r.b[a] = mask[3 + a]; }
+        regions.push_back(r);
+      }
+      int32_t seed[4] = {-1, -1, -1, 0};
+      uint32_t cells = 0;
+      static const char *op_names[4] = {"set", "fill", "paint", "clear"};
+      const bool edited = octree.extrude(raytrace_program, pick_x, pick_y, op, f, regions, seed, &cells);
+      if (edited) std::printf("extrude seed %d,%d,%d face %d distance %d op %s cells %u\n", seed[0], seed[1], seed[2], seed[3], extrude, op_names[op], cells);
+      else std::printf("extrude pick %d,%d none\n", pick_x, pick_y);
     } else if (pick_x >= 0 && flood_op >= 0) {                                           // a flood click at the pixel
       tdt_ray_hit h;
       uint32_t cells = 0;

@@ -712,4 +712,22 @@ int tdt_pick_grid_voxel(const tdt_ray_hit *hit, const float octree_floats[7], co
   return 0;
 }
 
+// the voxel behind the hit face and the face's direction: a seed of the face tools
+int tdt_pick_face(const tdt_ray_hit *hit, const float octree_floats[7], const int32_t octree_ints[3], int32_t out[4]) {
+  if (!out) { g_err = "null argument"; return TDT_ERR_INVALID_VALUE; }
+  double k[3];
+  if (const int rc = pick_cell(hit, octree_floats, octree_ints, 0, k)) return rc;
+  int face = -1, zeros = 0;
+  for (int a = 0; a < 3; a++) {
+    if (hit->normal[a] == 0.0f) zeros++;
+    else if (hit->normal[a] == 1.0f) face = 2 * a + 1;
+    else if (hit->normal[a] == -1.0f) face = 2 * a;
+  }
+  if (face < 0 || zeros != 2) { g_err = "the hit normal is not a signed unit axis vector"; return TDT_ERR_INVALID_VALUE; }
+  for (int a = 0; a < 3; a++) out[a] = (int32_t)k[a];
+  out[3] = face;
+  g_err.clear();
+  return 0;
+}
+
 }  // extern "C"

@@ -5,10 +5,8 @@
 //   hook     one lane per voxel; for each neighbour offset of a fixed half of the set (3 of 6, 13 of 26: the offsets that
 //            are lexicographically positive, so each unordered pair is handled once) the neighbour's key, a galloping search
 //            from the lane's own index (Morton neighbours are mostly near), and, when found and the match rule allows it, a
-//            union.  Lock-free union-find: the larger root is hung under the smaller one by atomicCAS, so the final root of
-//            every component is its lowest index whatever the schedule.  Parent words are read with agent-scope relaxed
-//            atomic loads (a plain load may be served by the CU's non-coherent L1 and see a stale root) and path halving
-//            writes them with agent-scope atomic stores.
+//            union.  Lock-free union-find (unionfind_device.hpp, shared with tdt_faces.hip): the larger root is hung under the
+//            smaller one by atomicCAS, so the final root of every component is its lowest index whatever the schedule.
 //   flatten  a separate launch: root(i), a root flag, exclusive_scan_u32 over the flags -> dense canonical numbers (the
 //            Morton order of each component's first voxel).  ONE host synchronisation reads the component count.
 //   table    one lane per voxel: its label; labels come in long runs (V is Morton-sorted), so each run of equal labels inside
@@ -26,35 +24,9 @@
 #include "device_scan.hpp"
 #include "region_device.hpp"
 #include "tdt_internal.hpp"
+#include "unionfind_device.hpp"
 
 namespace tdt {
-
-__device__ __forceinline__ uint32_t uf_load(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x, halving the path on the way (every parent word is an ancestor with a lower index, so any value a racing
-// store leaves there is still one)
-__device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t px = uf_load(parent + x);
-    if (px == x) return x;
-    const uint32_t gx = uf_load(parent + px);
-    if (gx == px) return px;
-    __hip_atomic_store(parent + x, gx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = gx;
-  }
-}
-
-__device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }     // hang the larger root under the smaller one
-    if (atomicCAS(parent + a, a, b) == a) return;
-  }
-}
 
 __global__ __launch_bounds__(256) void connect_init_kernel(const int4 *v, uint32_t n, uint32_t *keys, uint32_t *parent) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -105,12 +77,6 @@ __global__ __launch_bounds__(256) void connect_table_init_kernel(tdt_component *
   e.hi[0] = e.hi[1] = e.hi[2] = INT_MIN;
   e.material = 0; e.pad = 0;
   tab[c] = e;
-}
-
-// the lane of the first lane of this lane's run (heads: one bit per lane that starts a run; lane 0 always does)
-__device__ __forceinline__ uint32_t run_head(unsigned long long heads, uint32_t lane) {
-  const unsigned long long upto = lane == 63u ? ~0ull : ((2ull << lane) - 1ull);
-  return 63u - (uint32_t)__clzll(heads & upto);
 }
 
 // label[i]: root in, dense label out (each lane reads and writes only its own word); the table by run-aggregated atomics
@@ -194,6 +160,10 @@ __global__ __launch_bounds__(256) void connect_select_kernel(const tdt_component
   selected[c] = (sel != (invert != 0)) ? 1u : 0u;
 }
 
+void connect_flatten(hipStream_t st, uint32_t *parent, uint32_t n, uint32_t *root, uint32_t *flag) {
+  hipLaunchKernelGGL(connect_flatten_kernel, dim3(blocks_of((size_t)n + 1)), dim3(256), 0, st, parent, n, root, flag);
+}
+
 namespace {
 
 const char *kNoMemory = "out of device memory in the component labelling";
@@ -213,7 +183,7 @@ int label_voxels(tdt_ctx *front, tdt_ctx *ctx, const int4 *v, uint32_t nv, int d
     hipLaunchKernelGGL(connect_hook_kernel<6>, dim3(blocks_of(nv)), dim3(256), 0, st, v, (const uint32_t *)keys, nv, depth, match, parent);
   else
     hipLaunchKernelGGL(connect_hook_kernel<26>, dim3(blocks_of(nv)), dim3(256), 0, st, v, (const uint32_t *)keys, nv, depth, match, parent);
-  hipLaunchKernelGGL(connect_flatten_kernel, dim3(blocks_of((size_t)nv + 1)), dim3(256), 0, st, parent, nv, label, flag);
+  connect_flatten(st, parent, nv, label, flag);
   TDT_HIP(front, exclusive_scan_u32(st, flag, flag, nv + 1u, fscr));
   uint32_t nc = 0;
   if (int rc = read_word(front, st, flag + nv, &nc)) return rc;   // the component count

@@ -15,7 +15,8 @@
 // voxel-id images, overlays of a voxel list and the voxels of a rectangle; tdt_screen.hip: through-selection, the tree's voxels
 // projected into a view and tested against a rectangle, a polygon or a mask; tdt_smooth.hip: voxel smoothing, a ball-density
 // threshold filter and the density field, on the bit volume too; tdt_stroke.hip: stroke brushes, capsule and swept-box polylines
-// voxelised like a mesh.  The host helpers
+// voxelised like a mesh; tdt_faces.hip: face tools, the exposed faces (surface_device.hpp, the one face list of tdt_surface.hip)
+// labelled into coplanar face regions (unionfind_device.hpp, the union-find of tdt_connect.hip) and swept into columns.  The host helpers
 // around a call that every editing unit repeated are inline here: first_member, edit_replicas, read_word, rebuild_install, list_to_host, region_extract_source;
 // and so is the host frame of an image call: device_image, camera_program, overlap, image_grid, images_of_context, images_fit, run_passes.
 // Nothing here is part of the C ABI (include/tdt_rt.h).
@@ -85,6 +86,7 @@ struct tdt_ctx {
   uint64_t screen_counts[4] = {0, 0, 0, 0};            // tdt_debug_screen_counts: of the last through-selection that returned TDT_OK (tdt_screen.hip)
   uint32_t fill_passes = 0;      // tdt_debug_fill_passes: flood passes of the last enclosed-space call that changed the volume (tdt_fill.hip)
   uint32_t xform_bricks[2] = {0, 0};   // tdt_debug_xform_bricks: the last transform's bricks in the domain / kept for the count and emit passes (tdt_xform.hip)
+  int faces_premerge = 1;        // tdt_debug_faces_premerge: the face labelling's hook stage pre-merges runs inside a wave (tdt_faces.hip)
   uint32_t geodesic_passes = 0;  // tdt_debug_geodesic_passes: relaxation passes of the last geodesic call that changed the volume (tdt_geodesic.hip)
   std::vector<tdt_buffer *> buffers;
   std::vector<tdt_image *> images;

@@ -21,6 +21,9 @@
 //   quads    one lane per quad reads its first run and its length and writes the 32-byte tdt_quad with two 16-byte stores.
 //            Segments are in face order and each is sorted by (w, u0, v0): the array is the result as it stands.
 //
+// The first three stages — walk, keys, probe, scan, emit, sort — are surface_face_list (surface_device.hpp): the ONE definition of the face
+// list, which tdt_faces.hip labels into face regions; surface_unit_quads is the last stage over a merge = 0 list for that unit.
+//
 // Host synchronisations per call: tree_voxels' own, then 1 (merge = 0) or 3 (merge = 1) for the lengths above, then the copy of
 // the quads.  The six directions share every launch except the sorts; whether fusing the sorts too (a 64-bit key) or running
 // six independent passes would be faster is NOT measured.  Measured (tools/surface_time.py): on large trees the walk
@@ -36,24 +39,10 @@
 
 #include "device_scan.hpp"
 #include "region_device.hpp"
+#include "surface_device.hpp"
 #include "tdt_internal.hpp"
 
 namespace tdt {
-
-struct SurfaceSegs { uint32_t at[7]; };                 // segment f = [at[f], at[f + 1]) of an array of at[6] items
-
-__device__ __forceinline__ int surface_seg_of(const SurfaceSegs &s, uint32_t j) {
-  int f = 0;
-#pragma unroll
-  for (int t = 1; t < 6; t++) f += j >= s.at[t] ? 1 : 0;
-  return f;
-}
-__device__ __forceinline__ uint32_t surface_seg_start(const SurfaceSegs &s, uint32_t j) {   // at[surface_seg_of(j)], without indexing
-  uint32_t lo = s.at[0];
-#pragma unroll
-  for (int t = 1; t < 6; t++) lo = j >= s.at[t] ? s.at[t] : lo;
-  return lo;
-}
 
 // mask[i]: bit f = face f of voxel i is exposed and the voxel is inside the union of the shapes; cnt[f * (n + 1) + i] = that bit,
 // cnt[f * (n + 1) + n] = 0
@@ -212,43 +201,14 @@ struct Pass {
 int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch &S, const int4 **out, uint32_t *n_out) {
   *out = nullptr; *n_out = 0;
   hipStream_t st = ctx->stream;
-  int4 *v = nullptr;
-  uint32_t nv = 0;
-  int depth = 0;
-  if (int rc = tree_voxels_capped(front, ctx, S, &v, &nv, &depth)) return rc;
-  if (nv == 0) return TDT_OK;
-  // ---- probe: the faces, numbered direction by direction ----
-  const size_t stride = (size_t)nv + 1, n_cnt = 6 * stride;                // < 2^32: nv <= 2^26
-  uint32_t *keys = S.get<uint32_t>(nv), *mask = S.get<uint32_t>(nv), *cnt = S.get<uint32_t>(n_cnt), *scr = S.get<uint32_t>(scan_scratch_words(n_cnt));
-  uint32_t *d_bounds = S.get<uint32_t>(7);
-  RegionShape *d_shapes = nullptr;
-  if (!keys || !mask || !cnt || !scr || !d_bounds) return fail(front, TDT_ERR_HIP, kNoMemory);
-  const uint32_t n_shapes = (uint32_t)R.shapes.size();
-  if (int rc = upload_shapes(front, st, S, R.shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
-  voxlist_keys(st, v, nv, keys);
-  hipLaunchKernelGGL(surface_probe_kernel, dim3(blocks_of(stride)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)keys, nv, depth,
-                     (const RegionShape *)d_shapes, n_shapes, mask, cnt);
-  TDT_HIP(front, exclusive_scan_u32(st, cnt, cnt, (uint32_t)n_cnt, scr));
-  Pass P{front, st, d_bounds};
-  SurfaceSegs idx, faces;
-  for (int f = 0; f < 6; f++) idx.at[f] = (uint32_t)(f * stride);
-  idx.at[6] = (uint32_t)(n_cnt - 1);                                       // the last direction's closing 0: the total
-  if (int rc = P.read_bounds(cnt, idx, faces)) return rc;
-  const uint32_t nf = faces.at[6];
-  for (int f = 0; f < 6; f++)
-    if (faces.at[f + 1] - faces.at[f] > kVoxelListCap)
-      return fail(front, TDT_ERR_INVALID_VALUE, "direction " + std::to_string(f) + " has " + std::to_string(faces.at[f + 1] - faces.at[f]) +
-                                                    " exposed faces (more than 2^26)");
+  // ---- probe, emit, sort: the faces, numbered direction by direction ----
+  SurfaceFaces L;
+  if (int rc = surface_face_list(front, ctx, R.shapes, R.s.by_material, R.s.merge ? 0 : 1, S, L)) return rc;
+  const uint32_t nf = L.nf;
   if (nf == 0) return TDT_OK;
-  // ---- emit, sort ----
-  uint32_t largest = 0;
-  for (int f = 0; f < 6; f++) largest = std::max(largest, faces.at[f + 1] - faces.at[f]);
-  uint32_t *fk = S.get<uint32_t>(nf), *fv = S.get<uint32_t>(nf), *fk_alt = S.get<uint32_t>(nf), *fv_alt = S.get<uint32_t>(nf);
-  P.hist = S.get<uint32_t>(sort_hist_words(largest)); P.hscr = S.get<uint32_t>(sort_scratch_words(largest));
-  if (!fk || !fv || !fk_alt || !fv_alt || !P.hist || !P.hscr) return fail(front, TDT_ERR_HIP, kNoMemory);
-  hipLaunchKernelGGL(surface_emit_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)mask, (const uint32_t *)cnt, nv,
-                     R.s.by_material, R.s.merge ? 0 : 1, fk, fv);
-  if (int rc = P.sort_segments(fk, fv, fk_alt, fv_alt, faces)) return rc;
+  Pass P{front, st, L.d_bounds, L.hist, L.hscr};
+  const SurfaceSegs &faces = L.segs;
+  uint32_t *fk = L.fk, *fv = L.fv, *fk_alt = L.fk_alt, *fv_alt = L.fv_alt;
   const uint32_t *qk = fk, *qv = fv, *q_start = nullptr;                   // what the quads are written from
   SurfaceSegs q_segs = faces;
   uint32_t nq = nf;
@@ -283,6 +243,58 @@ int surface_quads(tdt_ctx *front, tdt_ctx *ctx, const Request &R, DeviceScratch 
 }
 
 }  // namespace
+
+int surface_face_list(tdt_ctx *front, tdt_ctx *ctx, const std::vector<RegionShape> &shapes, int by_material, int stacked, DeviceScratch &S,
+                      SurfaceFaces &L) {
+  L = SurfaceFaces{};
+  hipStream_t st = ctx->stream;
+  if (int rc = tree_voxels_capped(front, ctx, S, &L.v, &L.nv, &L.depth)) return rc;
+  const uint32_t nv = L.nv;
+  if (nv == 0) return TDT_OK;
+  int4 *v = L.v;
+  // ---- probe: the faces, numbered direction by direction ----
+  const size_t stride = (size_t)nv + 1, n_cnt = 6 * stride;                // < 2^32: nv <= 2^26
+  uint32_t *keys = S.get<uint32_t>(nv), *mask = S.get<uint32_t>(nv), *cnt = S.get<uint32_t>(n_cnt), *scr = S.get<uint32_t>(scan_scratch_words(n_cnt));
+  uint32_t *d_bounds = S.get<uint32_t>(7);
+  RegionShape *d_shapes = nullptr;
+  if (!keys || !mask || !cnt || !scr || !d_bounds) return fail(front, TDT_ERR_HIP, kNoMemory);
+  L.keys = keys; L.d_bounds = d_bounds;
+  const uint32_t n_shapes = (uint32_t)shapes.size();
+  if (int rc = upload_shapes(front, st, S, shapes.data(), n_shapes, kNoMemory, &d_shapes)) return rc;
+  voxlist_keys(st, v, nv, keys);
+  hipLaunchKernelGGL(surface_probe_kernel, dim3(blocks_of(stride)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)keys, nv, L.depth,
+                     (const RegionShape *)d_shapes, n_shapes, mask, cnt);
+  TDT_HIP(front, exclusive_scan_u32(st, cnt, cnt, (uint32_t)n_cnt, scr));
+  Pass P{front, st, d_bounds};
+  SurfaceSegs idx, faces;
+  for (int f = 0; f < 6; f++) idx.at[f] = (uint32_t)(f * stride);
+  idx.at[6] = (uint32_t)(n_cnt - 1);                                       // the last direction's closing 0: the total
+  if (int rc = P.read_bounds(cnt, idx, faces)) return rc;
+  const uint32_t nf = faces.at[6];
+  for (int f = 0; f < 6; f++)
+    if (faces.at[f + 1] - faces.at[f] > kVoxelListCap)
+      return fail(front, TDT_ERR_INVALID_VALUE, "direction " + std::to_string(f) + " has " + std::to_string(faces.at[f + 1] - faces.at[f]) +
+                                                    " exposed faces (more than 2^26)");
+  L.segs = faces; L.nf = nf;
+  if (nf == 0) return TDT_OK;
+  // ---- emit, sort ----
+  uint32_t largest = 0;
+  for (int f = 0; f < 6; f++) largest = std::max(largest, faces.at[f + 1] - faces.at[f]);
+  uint32_t *fk = S.get<uint32_t>(nf), *fv = S.get<uint32_t>(nf), *fk_alt = S.get<uint32_t>(nf), *fv_alt = S.get<uint32_t>(nf);
+  P.hist = S.get<uint32_t>(sort_hist_words(largest)); P.hscr = S.get<uint32_t>(sort_scratch_words(largest));
+  if (!fk || !fv || !fk_alt || !fv_alt || !P.hist || !P.hscr) return fail(front, TDT_ERR_HIP, kNoMemory);
+  hipLaunchKernelGGL(surface_emit_kernel, dim3(blocks_of(nv)), dim3(256), 0, st, (const int4 *)v, (const uint32_t *)mask, (const uint32_t *)cnt, nv,
+                     by_material, stacked, fk, fv);
+  if (int rc = P.sort_segments(fk, fv, fk_alt, fv_alt, faces)) return rc;
+  TDT_HIP(front, hipGetLastError());
+  L.fk = fk; L.fv = fv; L.fk_alt = fk_alt; L.fv_alt = fv_alt; L.hist = P.hist; L.hscr = P.hscr;
+  return TDT_OK;
+}
+
+void surface_unit_quads(hipStream_t st, const uint32_t *fk, const uint32_t *fv, uint32_t n, const SurfaceSegs &segs, int4 *quads) {
+  hipLaunchKernelGGL(surface_quads_kernel, dim3(blocks_of(n)), dim3(256), 0, st, fk, fv, (const uint32_t *)nullptr, n, segs, quads);
+}
+
 }  // namespace tdt
 
 extern "C" {

@@ -305,6 +305,25 @@ def pick_grid_voxel(hit, scene, place):
     return out
 
 
+def pick_face(hit, scene):
+    """tdt_pick_face: (4,) int32 {x, y, z, f} — the grid voxel behind the face `hit` found (pick_grid_voxel with place = 0) and the
+    face's direction 0..5 (-x, +x, -y, +y, -z, +z) from the hit normal: a seed for rt.Context.octree_edit_faces.  Raises
+    ValueError when the hit cannot be edited at or its normal is not a signed unit axis vector."""
+    L = lib()
+    L.tdt_pick_face.argtypes = [ctypes.c_void_p] * 4
+    rec = np.ascontiguousarray(np.asarray(hit).reshape(-1)[:1])
+    if rec.dtype.itemsize != 64:
+        raise TypeError("hit must be a tdt_ray_hit record (rt.RAY_HIT_DTYPE)")
+    floats, ints = (scene.blobs[6], scene.blobs[7]) if isinstance(scene, Scene) else scene
+    of = np.ascontiguousarray(np.asarray(floats).view(np.float32).reshape(-1)[:7], np.float32)
+    oi = np.ascontiguousarray(np.asarray(ints).view(np.int32).reshape(-1)[:3], np.int32)
+    out = np.zeros(4, np.int32)
+    rc = L.tdt_pick_face(rec.ctypes.data, of.ctypes.data, oi.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"[{rc:#x}] " + L.tdt_host_last_error().decode())
+    return out
+
+
 def scene_with_cell_count(scene, cell_count, zero_tail_nodes=0):
     """The same tree as a host with other conventions uploads it: Octree::init_global_buffers writes floats[6] = 1.0 / cell_count as
     f32 and ints[2] = cell_count (octree.rs:49, 79) — the reference's main.rs passes 100000 — and a pre-allocated cells buffer ends in

@@ -329,6 +329,62 @@ def _stroke(points, radius, segments=None, materials=None, material=0, shape=SHA
     return stroke, (p, g, m)
 
 
+# face tools (include/tdt_rt.h): struct tdt_faces, struct tdt_face_region, the distance limit and what extract_faces lists
+FACES_DISTANCE_MAX = 1023
+FACES_COLUMNS, FACES_TREE = 0, 1
+
+
+class Faces(ctypes.Structure):
+    """struct tdt_faces: connectivity 4 / 8 of the exposed faces inside a plane, match MATCH_*, the signed distance
+    -FACES_DISTANCE_MAX..FACES_DISTANCE_MAX (> 0 pulls, < 0 pushes), block 0 / 1 (stop at an obstacle / at the air behind),
+    material -1 (inherit the face's) or 0..253, pad 0."""
+    _fields_ = [("connectivity", ctypes.c_int32), ("match", ctypes.c_int32), ("distance", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("material", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class FaceRegion(ctypes.Structure):
+    """struct tdt_face_region: the index in F of its first face, its size, its direction 0..5 and the voxels' own coordinate along
+    the axis, the inclusive (u, v) bounding box, the carried material (material + 1) of its first face."""
+    _fields_ = [("first", ctypes.c_uint32), ("faces", ctypes.c_uint32), ("face", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("lo", ctypes.c_int32 * 2), ("hi", ctypes.c_int32 * 2), ("material", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+FACE_REGION_DTYPE = np.dtype([("first", "<u4"), ("faces", "<u4"), ("face", "<i4"), ("w", "<i4"), ("lo", "<i4", (2,)), ("hi", "<i4", (2,)),
+                              ("material", "<i4"), ("pad", "<i4")])
+assert ctypes.sizeof(Faces) == 24 and ctypes.sizeof(FaceRegion) == 40 == FACE_REGION_DTYPE.itemsize
+
+
+def _faces(seeds, distance, connectivity=4, match=MATCH_MATERIAL, block=False, material=-1, what=None, op=None):
+    """(struct tdt_faces, the contiguous (n, 4) int32 seed array {x, y, z, f}) for the face tools; what / op: those of the call,
+    when it takes them.  What ctypes would wrap or truncate silently is refused, and every range the header lists under its errors
+    is checked here as the library checks it (ValueError), so a bad call fails before any device work; the 2^26 limits, which
+    depend on the tree, stay the library's.  block takes True / False; everything else must be an integer."""
+    s = _exact_ints(seeds, np.int32, "seeds")
+    if s.size == 0:
+        s = s.reshape(0, 4)
+    if s.ndim == 1 and s.size == 4:
+        s = s.reshape(1, 4)
+    if s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("seeds must be an (n, 4) array of {x, y, z, f}")
+    if len(s) > 1 << 20:
+        raise ValueError("the face tools take at most 2^20 seeds")
+    if len(s) and not (0 <= int(s[:, 3].min()) and int(s[:, 3].max()) <= 5):
+        raise ValueError("a seed's face must be 0..5")
+    if isinstance(block, (bool, np.bool_)):
+        block = int(block)
+    for name, v, allowed in (("connectivity", connectivity, (4, 8)), ("match", match, (MATCH_ANY, MATCH_MATERIAL)),
+                             ("distance", distance, range(-FACES_DISTANCE_MAX, FACES_DISTANCE_MAX + 1)), ("block", block, (0, 1)),
+                             ("material", material, range(-1, 254)), ("what", what, (FACES_COLUMNS, FACES_TREE)),
+                             ("op", op, range(REGION_SET, REGION_CLEAR + 1))):
+        if v is None and name in ("what", "op"):
+            continue
+        if isinstance(v, (bool, np.bool_)) or v is None or int(v) != v:
+            raise ValueError(f"{name} must be an integer, not {v!r}")
+        if int(v) not in allowed:
+            raise ValueError(f"{name} must be one of {allowed!r}, not {v!r}")
+    return Faces(int(connectivity), int(match), int(distance), int(block), int(material), 0), np.ascontiguousarray(s)
+
+
 class Adapt(ctypes.Structure):
     """struct tdt_adapt: the relative error of the mean luminance at which a pixel stops, the brightness floor that error is
     measured against, and the fewest / most samples a pixel receives."""
@@ -526,6 +582,10 @@ SYMBOLS = [
     ("tdt_octree_edit_triangles_solid", _I, [_P, _I, ctypes.POINTER(Mesh), ctypes.POINTER(Fill), ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_debug_fill_passes", _I, [_P]),
     ("tdt_octree_extract_surface", _I, [_P, ctypes.POINTER(Surface), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_face_regions", _I, [_P, _I, _I, _P, _S, _P, _P, _S, ctypes.POINTER(ctypes.c_size_t), _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_extract_faces", _I, [_P, ctypes.POINTER(Faces), _P, _S, _P, _S, _I, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tdt_octree_edit_faces", _I, [_P, _I, ctypes.POINTER(Faces), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tdt_debug_faces_premerge", _I, [_P, _I]),
     ("tdt_octree_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, ctypes.POINTER(ctypes.c_uint32)]),
     ("tdt_octree_extract_morph_round", _I, [_P, ctypes.POINTER(Round), _P, _S, _P, _S, ctypes.POINTER(ctypes.c_size_t)]),
     ("tdt_octree_distance_field", _I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
@@ -944,6 +1004,57 @@ class Context:
         s = self._surface(merge, by_material)
         arr, k = _touch_regions(regions)
         return self._list(lib().tdt_octree_extract_surface, ctypes.byref(s), arr, k, width=8)
+
+    def octree_face_regions(self, connectivity=4, match=MATCH_MATERIAL, regions=None, capacity=4096):
+        """tdt_octree_face_regions: (faces, labels, table) of the bound tree's exposed faces — faces the (n, 8) int32 tdt_quad rows
+        of octree_extract_surface(merge=False) under the same mask, labels (n,) uint32 the face region of each, table a
+        FACE_REGION_DTYPE array numbered in the order of each region's first face.  connectivity 4 / 8 inside a plane; match
+        MATCH_*; regions confine the regions (None: no mask; an empty list: an empty mask).  Labels once where it can, as
+        octree_components does: the arrays are sized by `capacity`, and only a tree with more faces or regions is labelled a
+        second time, into arrays of the sizes the first call reported."""
+        _faces(np.zeros((0, 4), np.int32), 0, connectivity, match)
+        arr, k = _touch_regions(regions)
+        nf, nr = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        cap = max(int(capacity), 1)
+        faces, labels, table = np.zeros((cap, 8), np.int32), np.zeros(cap, np.uint32), np.zeros(cap, FACE_REGION_DTYPE)
+
+        def run():
+            return lib().tdt_octree_face_regions(self.h, int(connectivity), int(match), arr, k, faces.ctypes.data, labels.ctypes.data, len(labels),
+                                                 ctypes.byref(nf), table.ctypes.data, len(table), ctypes.byref(nr))
+
+        rc = run()
+        if rc == ERR_INVALID_VALUE and (nf.value > len(labels) or nr.value > len(table)):
+            faces, labels = np.zeros((max(nf.value, 1), 8), np.int32), np.zeros(max(nf.value, 1), np.uint32)
+            table = np.zeros(max(nr.value, 1), FACE_REGION_DTYPE)
+            rc = run()
+        self.check(rc)
+        return faces[: nf.value].copy(), labels[: nf.value].copy(), table[: nr.value].copy()
+
+    def octree_extract_faces(self, seeds, distance, what=FACES_COLUMNS, connectivity=4, match=MATCH_MATERIAL, block=False, material=-1,
+                             regions=None):
+        """tdt_octree_extract_faces: for the face regions under `seeds` ((n, 4) int32 {x, y, z, f}; host.pick_face makes one from a
+        pick) swept by the signed `distance`, FACES_COLUMNS: the column list {x, y, z, material + 1} (the preview, what
+        Texture.overlay takes); FACES_TREE: the bound tree's voxels the columns cover, with the tree's materials (the undo record
+        before a push, a paint or a SET pull).  (n, 4) int32, Morton-sorted.  Counts first, fills second: two sweeps."""
+        f, s = _faces(seeds, distance, connectivity, match, block, material, what=what)
+        arr, k = _touch_regions(regions)
+        return self._list(lib().tdt_octree_extract_faces, ctypes.byref(f), s.ctypes.data if len(s) else None, len(s), arr, k, int(what))
+
+    def octree_edit_faces(self, op, seeds, distance, connectivity=4, match=MATCH_MATERIAL, block=False, material=-1, regions=None):
+        """tdt_octree_edit_faces: octree_edit_voxels(op, octree_extract_faces(..., FACES_COLUMNS)) without the list leaving the
+        device: pull (REGION_FILL / REGION_SET, distance > 0), push (REGION_CLEAR, distance < 0), paint a face (REGION_PAINT,
+        distance -1); returns the canonical tree's cell count.  No seed or distance 0 installs the compacted tree."""
+        f, s = _faces(seeds, distance, connectivity, match, block, material, op=op)
+        arr, k = _touch_regions(regions)
+        n = ctypes.c_uint32(0)
+        self._check_edit(lib().tdt_octree_edit_faces(self.h, int(op), ctypes.byref(f), s.ctypes.data if len(s) else None, len(s), arr, k,
+                                                     ctypes.byref(n)), n)
+        return int(n.value)
+
+    def debug_faces_premerge(self, on):
+        """tdt_debug_faces_premerge: the face labelling's hook stage with (True, the default) or without the in-wave pre-merge of
+        runs; both label alike.  Measurement only."""
+        self.check(lib().tdt_debug_faces_premerge(self.h, 1 if on else 0))
 
     @staticmethod
     def _int32(name, v, allow_bool=False):
@@ -1998,6 +2109,19 @@ class Renderer:
         pts = np.asarray(points, np.int32).reshape(-1, 3)
         seg = np.asarray(segments, np.uint32).reshape(-1, 2)
         return pts, self.ctx.octree_edit_stroke(op, pts, radius, segments=seg, material=material, shape=shape)
+
+    def extrude(self, pixel, distance, op, material=-1, connectivity=4, match=MATCH_MATERIAL, block=False, sample=0):
+        """The face under `pixel` = (x, y) of this renderer's camera pulled out, pushed in or painted: one pick, the hit turned
+        into the seed {x, y, z, f} (host.pick_face), then Context.octree_edit_faces of the face region that holds it swept by the
+        signed `distance` — REGION_FILL / REGION_SET with distance > 0 pulls, REGION_CLEAR with distance < 0 pushes,
+        REGION_PAINT with distance -1 paints.  Returns (seed, cells): the (4,) int32 seed and the canonical tree's cell count.  A
+        pixel that hits nothing raises ValueError."""
+        from . import host
+        _faces(np.zeros((0, 4), np.int32), distance, connectivity, match, block, material, op=op)
+        hit = self.pick([pixel], sample)[0]
+        uniforms = (self.vbos[6].read(np.float32), self.vbos[7].read(np.int32))   # slots 6 / 7 as the device holds them
+        seed = host.pick_face(hit, uniforms)                                      # a miss, a stale record: ValueError
+        return seed, self.ctx.octree_edit_faces(op, seed.reshape(1, 4), distance, connectivity, match, block, material)
 
     def compact(self):
         """Context.octree_compact on this renderer's scene: the number of cells the canonical tree takes."""
